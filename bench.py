@@ -14,6 +14,9 @@ one process per GPU, rendezvous on 127.0.0.1) before anything touches a GPU, rel
 non-zero if a rank fails or fewer than N GPUs are visible.  Launched under torchrun it is one rank of the job.
 
 Rank 0 prints ONE JSON line.  `value` = frames of all ranks / max-over-ranks wall time of exactly K steps (PCIe inclusive).
+The timed loop runs exactly K steps after max(W, --streams) warm-up steps (--repeats R: R such windows back to back, the median counts).
+--dump-outputs DIR then writes the detections the last timed step returned as DIR/<name>.npy (frames and weights are
+procedural and seeded: the same arguments give the same inputs, so two builds can be compared output for output).
 At N = 1 the same run also measures and reports, in that line:
   resident        the same steps with the frames already in HBM and the records left there (the kernels alone; r01-r03's `value`)
   roofline        dominant kernel, HIP events around every launch on the launch stream (serial passes)
@@ -36,10 +39,8 @@ import time
 # RCCL between processes on this driver stack needs dmabuf IPC (already exported on the pool's boxes; kept here so a
 # bare environment behaves the same)
 os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-# HIP maps its streams onto GPU_MAX_HW_QUEUES hardware queues (default 4), and two streams that share a queue run one after
-# the other: the PCIe-inclusive variant's copy stream was the fifth stream of the process, so two of its three batches in
-# flight serialised (profiles/r03c_pcie_inclusive.txt: 4.9 k against 6.3 k frames/s).  Read by the runtime at start-up.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
+# The number of hardware queues HIP maps this process's streams onto (GPU_MAX_HW_QUEUES) is left to the environment: a
+# card's queues are shared by every process on it.  The line records what was in effect (`gpu_max_hw_queues`).
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(ROOT, "pytorch-yolov3_amd"))
@@ -49,7 +50,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 HEAVY_OBJ_BIAS = -6.9          # objectness bias of the procedural weights that leaves ~4000 candidates / frame at threshold 0.05
-PEAK_TFLOPS = {"bf16": 2500.0, "fp16": 2500.0, "float32": 157.3}   # /opt/skills/guides/MI355X_MICROARCH.md (dense MFMA; F16 = BF16 rate)
+PEAK_TFLOPS = {"bf16": 2500.0, "fp16": 2500.0, "float32": 157.3}   # MI355X dense MFMA peaks (F16 = BF16 rate)
 MODEL_FLOPS_PER_FRAME = {("yolov3", 608): 140.692e9, ("yolov3-tiny", 416): 5.565e9, ("yolov3-spp", 608): 141.449e9}
 TRAFFIC_FILE = os.path.join(ROOT, "profiles", "r06_traffic.json")
 
@@ -68,9 +69,12 @@ def parse_args(argv=None):
     ap.add_argument("--kmax", type=int, default=512, help="detection records per frame in the gather")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-baseline-child", action="store_true", help="(internal) run only the CPU baseline and print its JSON object")
-    ap.add_argument("--repeats", type=int, default=5,
-                    help="timed windows of --steps steps each, back to back; value / ms_per_step = the MEDIAN window, the line "
-                         "carries min / median / max (`repeats`)")
+    ap.add_argument("--repeats", type=int, default=1,
+                    help="timed windows of --steps steps each, back to back (default 1: exactly --steps timed steps); value / "
+                         "ms_per_step = the MEDIAN window, the line carries min / median / max (`repeats`)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the detections the last timed step returned (what "
+                         "Pipeline.results hands a caller) as DIR/<name>.npy, float32 / float64 (dump_outputs)")
     ap.add_argument("--no-extras", action="store_true",
                     help="skip pcie_inclusive / other_configs / bf16_agreement (A/B runs, profiling)")
     ap.add_argument("--cpu-budget", type=float, default=30.0, help="seconds of CPU-baseline work (bounded sample)")
@@ -501,14 +505,16 @@ def plumbing_main(args, backend):
     rec = torch.from_numpy(pack_records_host(dets, args.kmax))
     for _ in range(args.warmup):
         all_gather_records(rec, world)
+    # gloo's own barrier: dist.barrier() asks for the machine's accelerator first, which starts the GPU runtime in every rank
+    # of this no-GPU mode
     windows = []                              # R windows of exactly K steps, each between barriers; max over ranks; the median counts
     for _ in range(max(1, args.repeats)):
-        dist.barrier()
+        dist.monitored_barrier()
         t0 = time.perf_counter()
         for _ in range(args.steps):
             out = all_gather_records(rec, world)
         host_enqueue = time.perf_counter() - t0
-        dist.barrier()
+        dist.monitored_barrier()
         t = torch.tensor([time.perf_counter() - t0], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         windows.append((float(t.item()), host_enqueue))
@@ -529,7 +535,7 @@ def plumbing_main(args, backend):
                           "frames_gathered_per_step": int(counts_of(out).shape[0]), "per_rank": stats,
                           "config": {"global_batch": total, "frames_per_gpu": [frames_per_rank(args, r, world) for r in range(world)],
                                      "parallelism": "dp%d" % world}}), flush=True)
-    dist.barrier()
+    dist.monitored_barrier()
     dist.destroy_process_group()
     return 0
 
@@ -711,6 +717,55 @@ class Workload(object):
                "all_kernels_ms_per_step": round(report["plan_ms"], 4),
                "all_kernels_ms_per_step_event_bracket": round(report["plan_ms_bracket"], 4)}
         return out
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def last_step_detections(wl, resident):
+    """Per-frame ``[tlbr int64 (K, 4), prob float32 (K,), cls int64 (K,)]`` of the last timed step, as a caller of the timed
+    path receives them: ``Pipeline.results`` of its ticket (under a process group that is a collective -- every rank calls
+    it -- and the frames of all ranks come back in rank order).  With --resident the records stayed on the device: the
+    detector of that ticket is read instead (this rank's frames)."""
+    last = wl.pipe._n - 1
+    if not resident:
+        return wl.pipe.results(last)
+    torch.cuda.synchronize(wl.dev)
+    with torch.cuda.device(wl.dev):
+        return wl.pipe.dets[last % wl.pipe.max_open].fetch()
+
+
+def dump_outputs(out_dir, dets, limit=DUMP_LIMIT_BYTES):
+    """Write per-frame detections as flat arrays in the caller's order (frame by frame, within a frame as returned):
+      frame.npy (N,) float64            frame index of every detection
+      boxes_tlbr.npy (N, 4) float64     integer pixel corners x1, y1, x2, y2
+      scores.npy (N,) float32
+      classes.npy (N,) float64
+      count_per_frame.npy (F,) float64
+    Beyond ``limit`` bytes in all, a fixed, seeded sample of the detections is written instead, and sample_index.npy holds
+    their positions in the full list.  Returns {name: shape}."""
+    counts = np.array([len(d[1]) for d in dets], dtype=np.int64)
+    arrays = {
+        "frame": np.repeat(np.arange(len(dets)), counts).astype(np.float64),
+        "boxes_tlbr": np.concatenate([np.asarray(d[0], dtype=np.int64).reshape(-1, 4) for d in dets]).astype(np.float64),
+        "scores": np.concatenate([np.asarray(d[1], dtype=np.float32).reshape(-1) for d in dets]),
+        "classes": np.concatenate([np.asarray(d[2], dtype=np.int64).reshape(-1) for d in dets]).astype(np.float64),
+    }
+    n = int(counts.sum())
+    per_detection = sum(a.itemsize * (a.size // max(1, n)) for a in arrays.values()) + 8     # + its sample_index entry
+    cap = max(0, (limit - 4096 - 8 * len(dets)) // per_detection)      # 4096: the six .npy headers
+    os.makedirs(out_dir, exist_ok=True)
+    stale = os.path.join(out_dir, "sample_index.npy")
+    if n > cap:
+        idx = np.sort(np.random.default_rng(0).choice(n, size=cap, replace=False))
+        arrays = {name: a[idx] for name, a in arrays.items()}
+        arrays["sample_index"] = idx.astype(np.float64)
+    elif os.path.exists(stale):
+        os.remove(stale)
+    arrays["count_per_frame"] = counts.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
 
 
 def lib_sha256():
@@ -1206,6 +1261,11 @@ def main(argv=None):
     t_timed0 = time.perf_counter()
     elapsed = wl.timed(args.steps, args.warmup, distributed, resident=args.resident, repeats=args.repeats)
     phases["warmup_and_timed_s"] = round(time.perf_counter() - t_timed0, 1)
+    dumped = None
+    if args.dump_outputs:            # before anything else runs on the pipeline; every rank takes part (results() may gather)
+        dets = last_step_detections(wl, args.resident)
+        if rank == 0:
+            dumped = dump_outputs(args.dump_outputs, dets)
     windows_ms = sorted(w / args.steps * 1e3 for w in wl.windows_s)
     kept = wl.kept_per_frame()
     gathered = [placement]
@@ -1257,8 +1317,8 @@ def main(argv=None):
                        "collective": ("1 x all_gather_into_tensor(%d x %d x 8 int32 records) per step, side stream" % (
                            b, args.kmax)) if distributed else "none"},
             "use_graph": bool(use_graph),
-            # hardware queues the HIP runtime maps this rank's five streams onto (yolov3/_hip.py sets 8 before HIP initialises;
-            # `certain` is False when the runtime was up before the package was imported: then probably its default of 4)
+            # hardware queues the HIP runtime maps this rank's five streams onto (the environment's setting, else the runtime's
+            # default; yolov3/_hip.py: hw_queues)
             "gpu_max_hw_queues": {"value": _hip.hw_queues()[0], "certain": _hip.hw_queues()[1]},
             # a library other than the in-tree product build (Y3_HIP_LIB: stamps / experiment variants) or a debug knob:
             # the line then is a diagnostic, not a result
@@ -1272,6 +1332,9 @@ def main(argv=None):
             "lib_sha256": lib_sha256()[:16],
             "device_code_sha256": (device_code_sha256() or "")[:16],
         }
+        if dumped is not None:
+            line["dump_outputs"] = {"dir": os.path.abspath(args.dump_outputs), "arrays": dumped,
+                                    "what": "detections of the last timed step (Pipeline.results of its ticket)"}
         if flops_frame:
             line["end_to_end_tflops"] = round(fps * flops_frame / 1e12, 2)
             line["end_to_end_frac_of_peak"] = round(fps * flops_frame / 1e12 / (PEAK_TFLOPS[args.dtype] * world), 4)
@@ -1290,8 +1353,8 @@ def main(argv=None):
             "value": round(my_frames * args.steps / e2, 2), "unit": "frames/s", "ms_per_step": round(e2 / args.steps * 1e3, 4),
             "what": "same pipeline, frames resident in HBM and records left on the device (rounds 1-3 reported this as `value`); "
                     "the headline adds, inside every step, y3_copy_bytes on a copy stream (8 workgroups read the pinned frames over "
-                    "PCIe into one of six device buffers) and 4 workgroups writing the records back; GPU_MAX_HW_QUEUES=8 so that "
-                    "the copy stream does not share a hardware queue with a compute stream"}
+                    "PCIe into one of six device buffers) and 4 workgroups writing the records back (`gpu_max_hw_queues`: "
+                    "whether the copy stream has a hardware queue of its own)"}
         # ---- the other single-GPU configurations of BASELINE.json (parity cases; each with its own roofline) -----
         others = []
         for model, dim, batch, dtype in (("yolov3-tiny", 416, 8, "float32"), ("yolov3-spp", 608, 16, "bf16"),

@@ -26,7 +26,7 @@ from .dist import DetectionGather, all_gather_records, regather_if_truncated, un
 from .inference import Detector
 
 
-# HIP deals streams onto its hardware queues (GPU_MAX_HW_QUEUES, 8 here) in creation order and two streams on one queue run one
+# HIP deals streams onto its hardware queues (GPU_MAX_HW_QUEUES) in creation order and two streams on one queue run one
 # after the other, so streams are a per-device resource: every Pipeline of a device uses the SAME compute / copy / gather
 # streams (a second Pipeline with four streams of its own cost the first one 15 % -- and yolov3-tiny, whose kernels are short,
 # 20 %: profiles/r04m_pipeline_depth.txt).  Pipelines that are active at the same time then share streams: still correct
@@ -74,8 +74,8 @@ class Pipeline(object):
         nq, sure = _hip.hw_queues()
         if in_flight > 1 and (nq < in_flight + 2 or not sure):
             warnings.warn("yolov3.Pipeline: {} batches in flight + a copy stream (+ a gather stream) want GPU_MAX_HW_QUEUES >= {}, "
-                          "but the HIP runtime {} {} hardware queues (it reads the variable when it initialises: import yolov3 -- or "
-                          "set GPU_MAX_HW_QUEUES=8 -- before the first torch.cuda call); streams that share a queue run one after "
+                          "but the HIP runtime {} {} hardware queues (it reads the variable from the environment when it "
+                          "initialises); streams that share a queue run one after "
                           "the other (measured: 4.9 k instead of 6.3 k frames/s)".format(
                               in_flight, in_flight + 2, "has" if sure else "was probably initialised with", nq), RuntimeWarning)
         self.copy_blocks = int(copy_blocks)

@@ -42,9 +42,9 @@ def golden_params(model, obj_bias=GOLDEN_OBJ_BIAS):
 
 
 def golden_weights_path(model, tmp_path=None, obj_bias=GOLDEN_OBJ_BIAS):
-    """Write (once per machine) the Darknet-format file the golden run loaded, so tests exercise
+    """Write (once per machine and user) the Darknet-format file the golden run loaded, so tests exercise
     the ordinary ``load_weights`` path."""
-    cache = os.path.join(os.environ.get("TMPDIR", "/tmp"), "y3_golden_weights")
+    cache = os.path.join(os.environ.get("TMPDIR", "/tmp"), "y3_golden_weights_%d" % os.getuid())
     os.makedirs(cache, exist_ok=True)
     tag = "" if obj_bias == GOLDEN_OBJ_BIAS else "_ob%g" % obj_bias
     path = os.path.join(cache, "%s_seed%d%s.weights" % (model, GOLDEN_SEED, tag))

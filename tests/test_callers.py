@@ -146,15 +146,32 @@ def test_video_loop_over_a_frame_directory_and_cli(tmp_path):
     assert len(os.listdir(out_dir)) == len(names_sorted)
 
 
+def _check_dump(dump, d, n_frames):
+    """The arrays `bench.py --dump-outputs` wrote: the detections of one batch, as the JSON line lists them.  Returns the
+    number of detections."""
+    arrays = {name: np.load(os.path.join(dump, name + ".npy")) for name in d["dump_outputs"]["arrays"]}
+    assert {name: list(a.shape) for name, a in arrays.items()} == d["dump_outputs"]["arrays"]
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+    counts = arrays["count_per_frame"]
+    assert counts.shape == (n_frames,) and counts.sum() == len(arrays["frame"]) and "sample_index" not in arrays
+    assert (np.diff(arrays["frame"]) >= 0).all() and (np.bincount(arrays["frame"].astype(int), minlength=n_frames) == counts).all()
+    n = int(counts.sum())
+    assert arrays["boxes_tlbr"].shape == (n, 4) and arrays["scores"].shape == arrays["classes"].shape == (n,)
+    assert ((arrays["scores"] >= 0.05) & (arrays["scores"] <= 1)).all() and (arrays["classes"] == np.round(arrays["classes"])).all()
+    return n
+
+
 @pytest.mark.gpu
-def test_bench_prints_one_contract_json_line():
+def test_bench_prints_one_contract_json_line(tmp_path):
     """bench.py's output contract (one JSON line with the driver's keys plus roofline / cpu_baseline objects), on a
     small workload so the test stays short."""
     import subprocess
     import sys
     from golden_util import ROOT
+    dump = str(tmp_path / "dump")
     proc = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--model", "yolov3-tiny", "--dim", "416",
-                           "--batch", "2", "--steps", "3", "--warmup", "1", "--cpu-budget", "4"],
+                           "--batch", "2", "--steps", "3", "--warmup", "1", "--cpu-budget", "4", "--repeats", "5",
+                           "--dump-outputs", dump],
                           capture_output=True, text=True, timeout=900)
     assert proc.returncode == 0, proc.stderr[-2000:]
     lines = [l for l in proc.stdout.splitlines() if l.startswith("{")]
@@ -200,21 +217,28 @@ def test_bench_prints_one_contract_json_line():
     assert "child process" in c["process"] and len(c["pinned_cpus"]) == c["cores"] and len(c["loadavg_before"]) == 3
     assert d["phases_s"]["total_s"] > 0 and "cpu_baseline_s" in d["phases_s"]
     assert d["per_rank"]["placement"][0]["cpus"] >= 1
+    # --dump-outputs: the detections of the last timed step, as Pipeline.results returned them
+    _check_dump(dump, d, 2)
 
 
 @pytest.mark.gpu
-def test_bench_resident_variant_runs():
+def test_bench_resident_variant_runs(tmp_path):
     """`bench.py --resident` (frames already in HBM, records left there: kernel A/B runs): runs and says in
-    config.workload that it is not the headline configuration."""
+    config.workload that it is not the headline configuration.  By default --steps is the number of timed steps (one
+    window); --dump-outputs reads the last step's detections from the device."""
     import subprocess
     import sys
     from golden_util import ROOT
+    dump = str(tmp_path / "dump")
     proc = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--model", "yolov3-tiny", "--dim", "416",
-                           "--batch", "2", "--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--resident"],
+                           "--batch", "2", "--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--resident",
+                           "--obj-bias", "-5", "--dump-outputs", dump],
                           capture_output=True, text=True, timeout=600)
     assert proc.returncode == 0, proc.stderr[-2000:]
     d = json.loads([l for l in proc.stdout.splitlines() if l.startswith("{")][0])
     assert d["value"] > 0 and "NOT the headline" in d["config"]["workload"] and "resident" not in d
+    assert d["steps"] == 5 and d["repeats"]["windows"] == 1
+    assert _check_dump(dump, d, 2) > 0           # objectness bias -5: a few hundred candidates per frame
 
 
 @pytest.mark.gpu

@@ -38,7 +38,7 @@ def _worker(rank, world, port, n_frames, kmax, q):
     assert counts_of(all_rec).shape == (n_frames,)
     out = unpack_records(all_rec)
     q.put((rank, [(d[0].tolist(), d[1].tolist(), d[2].tolist(), d[3].tolist(), d[4]) for d in out]))
-    dist.barrier()
+    dist.monitored_barrier()          # (dist.barrier() would start the GPU runtime in every worker)
     dist.destroy_process_group()
 
 
@@ -120,7 +120,7 @@ def _ragged_worker(rank, world, port, n_frames, kmax, q):
     full = regather_if_truncated(first, kmax, repack, world)
     out = unpack_records(full)
     q.put((rank, calls, [(d[0].tolist(), d[1].tolist(), d[2].tolist(), d[3].tolist(), d[4]) for d in out]))
-    dist.barrier()
+    dist.monitored_barrier()          # (dist.barrier() would start the GPU runtime in every worker)
     dist.destroy_process_group()
 
 
@@ -180,7 +180,7 @@ def test_bench_self_launch_starts_n_ranks(world):
     """The driver runs `python bench.py --gpus N ...` without torchrun: the parent process must start N ranks itself
     (torch.distributed.run), relay rank 0's one JSON line and propagate failures.  Exercised here with the
     plumbing-only mode (Y3_BENCH_PLUMBING=gloo: no GPU work, the same shard / gather / timing skeleton over gloo)."""
-    r = _run_bench(["--gpus", str(world), "--steps", "3", "--warmup", "1", "--batch", "16", "--no-cpu-baseline"],
+    r = _run_bench(["--gpus", str(world), "--steps", "3", "--warmup", "1", "--batch", "16", "--no-cpu-baseline", "--repeats", "5"],
                    {"Y3_BENCH_PLUMBING": "gloo"})
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -211,3 +211,35 @@ def test_product_never_imports_the_oracle():
             with open(os.path.join(pkg, name)) as fh:
                 src = fh.read()
             assert "oracle" not in src.replace("no CPU or PyTorch fallback", ""), name
+
+
+def test_bench_dump_outputs_flattens_detections_and_samples_past_the_limit(tmp_path):
+    """`bench.py --dump-outputs`: the per-frame detections a caller receives, flattened in the caller's order into float32 /
+    float64 arrays; past the size limit a fixed, seeded sample (the same in every run) with the positions it took."""
+    import importlib.util
+    env = dict(os.environ)
+    spec = importlib.util.spec_from_file_location("y3_bench", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    os.environ.clear()
+    os.environ.update(env)                   # (bench.py sets defaults for the processes it starts)
+    rng = np.random.default_rng(5)
+    dets = [[rng.integers(-5, 600, (k, 4)), rng.random(k).astype(np.float32), rng.integers(0, 80, k)] for k in (3, 0, 7)]
+    flat = [np.concatenate([d[i] for d in dets]) for i in range(3)]
+    shapes = bench.dump_outputs(str(tmp_path / "all"), dets)
+    assert shapes == {"frame": [10], "boxes_tlbr": [10, 4], "scores": [10], "classes": [10], "count_per_frame": [3]}
+    got = {n: np.load(str(tmp_path / "all" / (n + ".npy"))) for n in shapes}
+    assert got["scores"].dtype == np.float32 and all(got[n].dtype == np.float64 for n in shapes if n != "scores")
+    assert got["frame"].tolist() == [0] * 3 + [2] * 7 and got["count_per_frame"].tolist() == [3, 0, 7]
+    assert (got["boxes_tlbr"] == flat[0]).all() and (got["scores"] == flat[1]).all() and (got["classes"] == flat[2]).all()
+    limit = 4096 + 8 * 3 + 60 * 4            # room for four detections
+    for sub in ("a", "b"):
+        shapes = bench.dump_outputs(str(tmp_path / sub), dets, limit=limit)
+        assert shapes["scores"] == [4] and shapes["sample_index"] == [4] and shapes["count_per_frame"] == [3]
+        assert sum(os.path.getsize(str(tmp_path / sub / f)) for f in os.listdir(str(tmp_path / sub))) <= limit
+    idx = np.load(str(tmp_path / "a" / "sample_index.npy"))
+    assert (idx == np.load(str(tmp_path / "b" / "sample_index.npy"))).all() and (np.diff(idx) > 0).all()
+    assert (np.load(str(tmp_path / "a" / "scores.npy")) == flat[1][idx.astype(int)]).all()
+    # a later run under the limit into the same directory leaves no stale sample index behind
+    bench.dump_outputs(str(tmp_path / "a"), dets)
+    assert not os.path.exists(str(tmp_path / "a" / "sample_index.npy"))
