@@ -36,7 +36,7 @@ typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 
 // diagnostic builds only (y3_set_tuning("debug", v)): 0 in the product
 int y3_debug_flags();
-// CU count of the current device (api.hip); the launchers' grid-size heuristics scale with it
+// CU count of the current device (api.hip); the choosers' grid-size heuristics scale with it
 int y3_device_cus();
 
 // thread-local error string shared by all translation units
@@ -334,79 +334,76 @@ __device__ __forceinline__ unsigned long long y3_now_real() {
 #define Y3_COARSE(slot) Y3_STAMP(slot)
 #endif
 
-// launchers implemented in the .hip files; each fills *kernel_name with a static string
-// force_version / force_ns / force_bm: 0 = the "igemm_version" / "igemm_ns" / "igemm_bm" knobs
-int y3_launch_conv_igemm(const y3_op &op, const void *d_in, const void *d_zero, hipStream_t s,
-                         const char **kernel_name, bool dry_run, int force_version = 0, int force_ns = 0,
-                         int force_bm = 0);
-int y3_launch_conv_small(const y3_op &op, const void *d_in, hipStream_t s, const char **kernel_name,
-                         bool dry_run);
-int y3_launch_conv_direct(const y3_op &op, const void *d_in, hipStream_t s, const char **kernel_name,
-                          bool dry_run);
+// ---- plan steps ----------------------------------------------------------------------------------------------------------
+// What one step of a plan (a single op, or a fused group led by its first op) launches: decided once, when the plan is created,
+// from the op(s) and the plan's options (api.hip: choose_conv and the choosers below); the launcher only launches what it records.
+enum class y3_fuse : uint8_t {
+  none,         // one op
+  into_prev,    // nothing: launched by an earlier step
+  stem_pair,    // MFMA stem conv + the 3x3 stride-2 conv after it (conv_fused.hip)
+  resblock,     // 64-32-64 residual block (conv_fused.hip)
+  block,        // 1x1 -> 128 channels + 3x3 (+ shortcut), bottleneck tensor in LDS (conv_block.hip)
+  head_decode,  // detection-head conv + YOLO decode (conv_igemm.hip, conv_1x1.hip)
+  spp,          // SPP pyramid: the op and the next two, pools 5 / 9 / 13 of one tensor (layers.hip)
+};
+struct y3_step;
+// ops: the step's op(s); d_in: the input of ops[0] (the plan input where it reads that)
+typedef int (*y3_launcher)(const y3_op *ops, const y3_step &st, const void *d_in, const void *d_zero, hipStream_t s);
+struct y3_step {
+  y3_fuse fuse = y3_fuse::none;
+  y3_launcher launch = nullptr;
+  const char *name = "";
+  // variant parameters, each launcher reading its own: implicit GEMM version / pipeline stages / pixel x channel tile; the halo
+  // kernel's pixel tile (192 / 256); the 1x1-dw and head-dw tile height (bm); the weights-resident channel tile (bn); dw48 waves
+  // per workgroup; decode lanes per box; block-fused tile; pipelined (or phase-by-phase) stem pair
+  int version = 0, ns = 0, bm = 0, bn = 0, waves = 0, lanes = 0, tw = 0, th = 0;
+  bool pipelined = false;
+  bool frag = false;              // reads the fragment-order copy of ops[0]'s weights (y3_conv_halo_dw_make_weights) ...
+  const void *frag_w = nullptr;   // ... this one (never null at launch)
+};
+
+// choosers implemented in the .hip files: fill the step (launcher, kernel name, variant) or return an error for a shape the
+// kernel family cannot take
+int y3_choose_conv_igemm(const y3_op &op, const y3_options &o, y3_step &st, int force_version = 0, int force_ns = 0,
+                         int force_bm = 0);   // force_*: 0 = the options' igemm_version / igemm_ns / igemm_bm
+int y3_choose_conv_small(const y3_op &op, y3_step &st);
+int y3_choose_conv_direct(const y3_op &op, y3_step &st);
 bool y3_conv_stem_mfma_supported(const y3_op &op);
-int y3_launch_conv_stem_mfma(const y3_op &op, const void *d_in, hipStream_t s, const char **kernel_name,
-                             bool dry_run);
-int y3_launch_maxpool(const y3_op &op, const void *d_in, hipStream_t s, const char **kernel_name,
-                      bool dry_run);
-// SPP pyramid: three stride-1 max-pools (5 / 9 / 13) of one tensor in one launch (layers.hip)
-bool y3_maxpool_spp_supported(const y3_op &a, const y3_op &b, const y3_op &c);
-int y3_launch_maxpool_spp(const y3_op &a, const y3_op &b, const y3_op &c, hipStream_t s, const char **kernel_name,
-                          bool dry_run);
-int y3_launch_upsample(const y3_op &op, const void *d_in, hipStream_t s, const char **kernel_name,
-                       bool dry_run);
-int y3_launch_add(const y3_op &op, const void *d_in, hipStream_t s, const char **kernel_name,
-                  bool dry_run);
-int y3_launch_copy(const y3_op &op, const void *d_in, hipStream_t s, const char **kernel_name,
-                   bool dry_run);
-int y3_launch_yolo(const y3_op &op, const void *d_in, hipStream_t s, const char **kernel_name,
-                   bool dry_run);
+int y3_choose_conv_stem_mfma(const y3_op &op, y3_step &st);
+int y3_choose_layer(const y3_op &op, y3_step &st);   // max-pool, upsample, add, copy (layers.hip)
+int y3_choose_yolo(const y3_op &op, const y3_options &o, y3_step &st);
+// Fused groups: true (and the step filled) when the kernel takes the group
+bool y3_choose_maxpool_spp(const y3_op &a, const y3_op &b, const y3_op &c, y3_step &st);
 // first two layers of Darknet-53 as one kernel (conv_fused.hip); op1 must read only op0's output
-bool y3_conv_fused_stem_s2_supported(const y3_op &op0, const y3_op &op1);
-int y3_launch_conv_fused_stem_s2(const y3_op &op0, const y3_op &op1, const void *d_in, hipStream_t s,
-                                 const char **kernel_name, bool dry_run);
-bool y3_conv_fused_resblock_supported(const y3_op &op0, const y3_op &op1);
-int y3_launch_conv_fused_resblock(const y3_op &op0, const y3_op &op1, hipStream_t s, const char **kernel_name,
-                                  bool dry_run);
-// 1x1 (-> 128 channels) + 3x3 (+ shortcut) in one kernel, bottleneck tensor in LDS (conv_block.hip)
-bool y3_conv_block_fused_supported(const y3_op &op0, const y3_op &op1);
-int y3_launch_conv_block_fused(const y3_op &op0, const y3_op &op1, hipStream_t s, const char **kernel_name, bool dry_run);
+bool y3_choose_conv_fused_stem_s2(const y3_op &op0, const y3_op &op1, const y3_options &o, y3_step &st);
+bool y3_choose_conv_fused_resblock(const y3_op &op0, const y3_op &op1, const y3_options &o, y3_step &st);
+bool y3_choose_conv_block_fused(const y3_op &op0, const y3_op &op1, const y3_options &o, y3_step &st);
 // detection head: 1x1 conv + YOLO decode in one launch (conv_igemm.hip: the tiled form and the choice between the two; conv_1x1.hip:
-// the direct-weights form, which reads the fragment-order copy of the head conv's weights: `frag_w`, nullptr = made per launch)
-bool y3_conv_head_decode_supported(const y3_op &op0, const y3_op &op1);
-int y3_launch_conv_head_decode(const y3_op &op0, const y3_op &op1, const void *d_zero, hipStream_t s,
-                               const char **kernel_name, bool dry_run, const void *frag_w = nullptr);
-bool y3_conv_head_dw_fits(const y3_op &op0);
-int y3_launch_conv_head_decode_dw(const y3_op &op0, const y3_op &op1, const void *d_zero, hipStream_t s, const char **kernel_name,
-                                  bool dry_run, const void *frag_w);
-// halo-reuse 3x3 kernel (conv_halo.hip): whether it can take this conv, and its launcher
+// the direct-weights form, which reads the fragment-order copy of the head conv's weights)
+bool y3_choose_conv_head_decode(const y3_op &op0, const y3_op &op1, const y3_options &o, y3_step &st);
+bool y3_conv_head_dw_fits(const y3_op &op0, const y3_options &o);
+void y3_choose_conv_head_decode_dw(const y3_op &op0, const y3_options &o, y3_step &st);
+// halo-reuse 3x3 kernel (conv_halo.hip): whether it can take this conv, and its chooser
 bool y3_conv_halo_ws_fits(const y3_op &op);
 bool y3_conv_halo_dw_fits(const y3_op &op);
-bool y3_conv_halo_dw_pays(const y3_op &op);
+bool y3_conv_halo_dw_pays(const y3_op &op, const y3_options &o);
 size_t y3_conv_halo_dw_weight_bytes(const y3_op &op);
 int y3_conv_halo_dw_make_weights(const y3_op &op, void *dst, hipStream_t s);
-int y3_launch_conv_halo_dw(const y3_op &op, const void *d_in, const void *d_zero, hipStream_t s,
-                           const char **kernel_name, bool dry_run, const void *frag_w);
-int y3_launch_conv_halo(const y3_op &op, const void *d_in, const void *d_zero, hipStream_t s,
-                        const char **kernel_name, bool dry_run);
+int y3_choose_conv_halo_dw(const y3_op &op, y3_step &st);
+int y3_choose_conv_halo(const y3_op &op, const y3_options &o, y3_step &st);
 // 1x1 conv with LDS-resident weights, persistent workgroups (conv_1x1.hip)
 bool y3_conv1x1_wres_supported(const y3_op &op);
 bool y3_conv1x1_wres_pays(const y3_op &op);
-int y3_launch_conv1x1_wres(const y3_op &op, const void *d_in, const void *d_zero, hipStream_t s, const char **kernel_name,
-                           bool dry_run);
+int y3_choose_conv1x1_wres(const y3_op &op, y3_step &st);
 // direct-weights 1x1 kernel for the short-K bottleneck layers on small maps (conv_1x1.hip; fragment-order weights)
 bool y3_conv1x1_dw_pays(const y3_op &op);
-int y3_launch_conv1x1_dw(const y3_op &op, const void *d_in, const void *d_zero, hipStream_t s, const char **kernel_name,
-                         bool dry_run, const void *frag_w);
+int y3_choose_conv1x1_dw(const y3_op &op, y3_step &st);
 // small-grid direct-weights kernel, 1x1 and 3x3 (conv_dw48.hip; fragment-order weights): 48-pixel x 32..256-channel tiles
-bool y3_conv_dw48_fits(const y3_op &op);
-bool y3_conv_dw48_fits_wide(const y3_op &op);
-int y3_launch_conv_dw48(const y3_op &op, const void *d_in, const void *d_zero, hipStream_t s, const char **kernel_name,
-                        bool dry_run, const void *frag_w);
+bool y3_conv_dw48_fits(const y3_op &op, const y3_options &o);
+bool y3_conv_dw48_fits_wide(const y3_op &op, const y3_options &o);
+int y3_choose_conv_dw48(const y3_op &op, const y3_options &o, y3_step &st);
 // 2-D patch form of the halo kernel for rows wider than 128 pixels (conv_halo.hip)
 bool y3_conv_patch_fits(const y3_op &op);
-int y3_launch_conv_patch(const y3_op &op, const void *d_in, const void *d_zero, hipStream_t s,
-                         const char **kernel_name, bool dry_run);
-// options of the plan being created / run on this thread (api.hip), else the process defaults (y3_set_tuning)
-const y3_options &y3_opt();
+int y3_choose_conv_patch(const y3_op &op, y3_step &st);
 // true when the MFMA implicit-GEMM kernel can take this conv
 bool y3_conv_igemm_supported(const y3_op &op);

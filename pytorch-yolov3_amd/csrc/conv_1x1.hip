@@ -418,8 +418,8 @@ int dw1x1_bm(const y3_op &op) {
 // 1 = 48 (measured at batch 16 / one frame, us per launch: 19^2 x 1024 13.8 / 10.9, 38^2 x 512 16.0 / 8.0, 76^2 x 256 32.9 / 6.7; 96-pixel
 // tiles 13.8 (48: does not fit) / 15.8 / 38.1 and -- / 10.7 / 8.9; the tiled kernel 27.7 / 20.2 / 39.3 and 21.3 / 14.6 / 10.4:
 // profiles/r06_head_dw.txt), 2 = never (the tiled kernel, A/B), 3 / 4 = 48 / 96 wherever the shape allows (A/B, tests)
-int dw_head_bm(const y3_op &op) {
-  const int mode = y3_opt().fuse_head;
+int dw_head_bm(const y3_op &op, const y3_options &o) {
+  const int mode = o.fuse_head;
   if (mode == 0 || mode == 2) return 0;
   if (op.kind != Y3_OP_CONV || !y3_is16(op.dtype) || op.ksize != 1 || op.stride != 1 || op.pad != 0 || !(op.flags & Y3_F_OUT_F32)) return 0;
   if (op.flags & (Y3_F_LEAKY | Y3_F_RESIDUAL | Y3_F_IN_NCHW_F32 | Y3_F_IN_NHWC_U8BGR | Y3_F_PLAN_INPUT)) return 0;
@@ -438,28 +438,12 @@ int wres_bn(const y3_op &op) {
   return 0;
 }
 
-}  // namespace
-
-// the layers the direct-weights 1x1 kernel takes: 16-bit, no shortcut, Cout a multiple of 256, Cin 256 .. 1024, and a map x
-// batch that gives (nearly) every CU exactly one tile
-bool y3_conv1x1_dw_pays(const y3_op &op) { return dw1x1_bm(op) != 0; }
-
-int y3_launch_conv1x1_dw(const y3_op &op, const void *d_in, const void *d_zero, hipStream_t s, const char **kernel_name,
-                         bool dry_run, const void *frag_w) {
-  const int bm = dw1x1_bm(op);
-  Y3_REQUIRE(bm != 0, "conv block %d: not a shape for the direct-weights 1x1 kernel", op.block_idx);
-  *kernel_name = bm == 96 ? Y3_KNAME(op.dtype, "conv1x1_dw_", "_96x256") : Y3_KNAME(op.dtype, "conv1x1_dw_", "_48x256");
-  if (dry_run) return Y3_OK;
-  void *tmp = nullptr;
-  if (!frag_w) {                                      // single-op calls without a shared copy: made here, stream-ordered
-    Y3_HIP_CHECK(hipMallocAsync(&tmp, y3_conv_halo_dw_weight_bytes(op), s));
-    const int rc = y3_conv_halo_dw_make_weights(op, tmp, s);
-    if (rc != Y3_OK) { (void)hipFreeAsync(tmp, s); return rc; }
-    frag_w = tmp;
-  }
+int launch_conv1x1_dw(const y3_op *ops, const y3_step &st, const void *d_in, const void *d_zero, hipStream_t s) {
+  const y3_op &op = ops[0];
+  const int bm = st.bm;
   DwArgs a;
   a.in = static_cast<const char *>(d_in);
-  a.wgt = static_cast<const char *>(frag_w);
+  a.wgt = static_cast<const char *>(st.frag_w);
   a.scale = op.d_scale; a.bias = op.d_bias;
   a.out = static_cast<char *>(op.d_out);
   a.zero = static_cast<const char *>(d_zero);
@@ -468,7 +452,7 @@ int y3_launch_conv1x1_dw(const y3_op &op, const void *d_in, const void *d_zero, 
   a.n_tiles = op.out_c / 256;
   a.flags = op.flags;
   const int nkt = op.in_c / 64;
-  const int rc = y3_by_dtype16(op.dtype, [&](auto tag) {
+  return y3_by_dtype16(op.dtype, [&](auto tag) {
     typedef decltype(tag) T;
     static Y3DeviceOnce once;
     {
@@ -494,30 +478,14 @@ int y3_launch_conv1x1_dw(const y3_op &op, const void *d_in, const void *d_zero, 
     Y3_HIP_CHECK(hipGetLastError());
     return Y3_OK;
   });
-  if (tmp) (void)hipFreeAsync(tmp, s);
-  return rc;
 }
 
-// detection-head conv + YOLO decode on the direct-weights 1x1 kernel (op0: the head conv, op1: the Y3_OP_YOLO op reading it; the pair
-// has passed y3_conv_head_decode_supported)
-bool y3_conv_head_dw_fits(const y3_op &op0) { return dw_head_bm(op0) != 0; }
-
-int y3_launch_conv_head_decode_dw(const y3_op &op0, const y3_op &op1, const void *d_zero, hipStream_t s, const char **kernel_name,
-                                  bool dry_run, const void *frag_w) {
-  const int bm = dw_head_bm(op0);
-  Y3_REQUIRE(bm != 0, "conv block %d: not a shape for the direct-weights head kernel", op0.block_idx);
-  *kernel_name = bm == 96 ? Y3_KNAME(op0.dtype, "conv_head_decode_dw_", "_96x256") : Y3_KNAME(op0.dtype, "conv_head_decode_dw_", "_48x256");
-  if (dry_run) return Y3_OK;
-  void *tmp = nullptr;
-  if (!frag_w) {                                      // callers without a shared copy: made here, stream-ordered
-    Y3_HIP_CHECK(hipMallocAsync(&tmp, y3_conv_halo_dw_weight_bytes(op0), s));
-    const int rc = y3_conv_halo_dw_make_weights(op0, tmp, s);
-    if (rc != Y3_OK) { (void)hipFreeAsync(tmp, s); return rc; }
-    frag_w = tmp;
-  }
+int launch_head_decode_dw(const y3_op *ops, const y3_step &st, const void *, const void *d_zero, hipStream_t s) {
+  const y3_op &op0 = ops[0], &op1 = ops[1];
+  const int bm = st.bm;
   DwArgs a;
   a.in = static_cast<const char *>(op0.d_in);
-  a.wgt = static_cast<const char *>(frag_w);
+  a.wgt = static_cast<const char *>(st.frag_w);
   a.scale = op0.d_scale; a.bias = op0.d_bias;
   a.out = nullptr;
   a.zero = static_cast<const char *>(d_zero);
@@ -534,7 +502,7 @@ int y3_launch_conv_head_decode_dw(const y3_op &op0, const y3_op &op1, const void
   a.y_net_w = op1.net_w; a.y_net_h = op1.net_h;
   for (int i = 0; i < 8; ++i) { a.y_aw[i] = op1.anchor_w[i]; a.y_ah[i] = op1.anchor_h[i]; }
   const int nkt = op0.in_c / 64;
-  const int rc = y3_by_dtype16(op0.dtype, [&](auto tag) {
+  return y3_by_dtype16(op0.dtype, [&](auto tag) {
     typedef decltype(tag) T;
     static Y3DeviceOnce once;
     {
@@ -559,35 +527,11 @@ int y3_launch_conv_head_decode_dw(const y3_op &op0, const y3_op &op1, const void
     Y3_HIP_CHECK(hipGetLastError());
     return Y3_OK;
   });
-  if (tmp) (void)hipFreeAsync(tmp, s);
-  return rc;
 }
 
-// 1x1 stride-1 bf16 conv without shortcut operand whose weight panel fits LDS
-bool y3_conv1x1_wres_supported(const y3_op &op) {
-  if (op.kind != Y3_OP_CONV || !y3_is16(op.dtype) || op.ksize != 1 || op.stride != 1 || op.pad != 0) return false;
-  if (op.flags & (Y3_F_RESIDUAL | Y3_F_OUT_F32 | Y3_F_IN_NCHW_F32 | Y3_F_IN_NHWC_U8BGR | Y3_F_PLAN_INPUT)) return false;
-  if (op.in_c % 64 != 0 || op.in_c < 128 || op.in_ld % 8 != 0 || op.out_ld % 8 != 0 || op.k_ld < op.in_c) return false;
-  if (((uintptr_t)op.d_in | (uintptr_t)op.d_out) % 16 != 0) return false;
-  return wres_bn(op) != 0;
-}
-
-// ... where it measured faster than the tiled kernels (profiles/r02h_convbench_1x1.txt, batch 16): ONE channel tile (every
-// workgroup streams the activations once: 256 -> 128 at 76^2 14.3 against 18.9 us, 128 -> 64 at 152^2 23.3 against 28.9 us
-// = 6.1 TB/s) on a map large enough to keep every CU streaming at least two pixel tiles.  With several channel tiles
-// (512 -> 256 at 38^2 as 4 x 64 channels, 384 -> 128 as 2 x 64) every tile's workgroups re-read the activations and the
-// 64 x 32 wave tiles feed the matrix pipe worse: 17.9 against 14.2 us, 26.1 against 23.9 us.
-bool y3_conv1x1_wres_pays(const y3_op &op) {
-  const int bn = wres_bn(op);
-  return bn != 0 && op.out_c == bn && (long long)y3_ceil_div(op.batch * op.in_h * op.in_w, 128) >= 512;
-}
-
-int y3_launch_conv1x1_wres(const y3_op &op, const void *d_in, const void *d_zero, hipStream_t s, const char **kernel_name,
-                           bool dry_run) {
-  Y3_REQUIRE(y3_conv1x1_wres_supported(op), "conv block %d: not a shape for the weights-resident 1x1 kernel", op.block_idx);
-  const int bn = wres_bn(op);
-  *kernel_name = bn == 128 ? Y3_KNAME(op.dtype, "conv1x1_wres_", "_128x128") : Y3_KNAME(op.dtype, "conv1x1_wres_", "_128x64");
-  if (dry_run) return Y3_OK;
+int launch_conv1x1_wres(const y3_op *ops, const y3_step &st, const void *d_in, const void *d_zero, hipStream_t s) {
+  const y3_op &op = ops[0];
+  const int bn = st.bn;
   WresArgs a;
   a.in = static_cast<const char *>(d_in);
   a.wgt = static_cast<const char *>(op.d_weight);
@@ -626,4 +570,57 @@ int y3_launch_conv1x1_wres(const y3_op &op, const void *d_in, const void *d_zero
     Y3_HIP_CHECK(hipGetLastError());
     return Y3_OK;
   });
+}
+
+}  // namespace
+
+// the layers the direct-weights 1x1 kernel takes: 16-bit, no shortcut, Cout a multiple of 256, Cin 256 .. 1024, and a map x
+// batch that gives (nearly) every CU exactly one tile
+bool y3_conv1x1_dw_pays(const y3_op &op) { return dw1x1_bm(op) != 0; }
+
+int y3_choose_conv1x1_dw(const y3_op &op, y3_step &st) {
+  st.bm = dw1x1_bm(op);
+  Y3_REQUIRE(st.bm != 0, "conv block %d: not a shape for the direct-weights 1x1 kernel", op.block_idx);
+  st.launch = launch_conv1x1_dw;
+  st.name = st.bm == 96 ? Y3_KNAME(op.dtype, "conv1x1_dw_", "_96x256") : Y3_KNAME(op.dtype, "conv1x1_dw_", "_48x256");
+  st.frag = true;
+  return Y3_OK;
+}
+
+// detection-head conv + YOLO decode on the direct-weights 1x1 kernel (op0: the head conv, op1: the Y3_OP_YOLO op reading it; the pair
+// has passed the checks of y3_choose_conv_head_decode)
+bool y3_conv_head_dw_fits(const y3_op &op0, const y3_options &o) { return dw_head_bm(op0, o) != 0; }
+
+void y3_choose_conv_head_decode_dw(const y3_op &op0, const y3_options &o, y3_step &st) {
+  st.bm = dw_head_bm(op0, o);
+  st.launch = launch_head_decode_dw;
+  st.name = st.bm == 96 ? Y3_KNAME(op0.dtype, "conv_head_decode_dw_", "_96x256") : Y3_KNAME(op0.dtype, "conv_head_decode_dw_", "_48x256");
+  st.frag = true;
+}
+
+// 1x1 stride-1 bf16 conv without shortcut operand whose weight panel fits LDS
+bool y3_conv1x1_wres_supported(const y3_op &op) {
+  if (op.kind != Y3_OP_CONV || !y3_is16(op.dtype) || op.ksize != 1 || op.stride != 1 || op.pad != 0) return false;
+  if (op.flags & (Y3_F_RESIDUAL | Y3_F_OUT_F32 | Y3_F_IN_NCHW_F32 | Y3_F_IN_NHWC_U8BGR | Y3_F_PLAN_INPUT)) return false;
+  if (op.in_c % 64 != 0 || op.in_c < 128 || op.in_ld % 8 != 0 || op.out_ld % 8 != 0 || op.k_ld < op.in_c) return false;
+  if (((uintptr_t)op.d_in | (uintptr_t)op.d_out) % 16 != 0) return false;
+  return wres_bn(op) != 0;
+}
+
+// ... where it measured faster than the tiled kernels (profiles/r02h_convbench_1x1.txt, batch 16): ONE channel tile (every
+// workgroup streams the activations once: 256 -> 128 at 76^2 14.3 against 18.9 us, 128 -> 64 at 152^2 23.3 against 28.9 us
+// = 6.1 TB/s) on a map large enough to keep every CU streaming at least two pixel tiles.  With several channel tiles
+// (512 -> 256 at 38^2 as 4 x 64 channels, 384 -> 128 as 2 x 64) every tile's workgroups re-read the activations and the
+// 64 x 32 wave tiles feed the matrix pipe worse: 17.9 against 14.2 us, 26.1 against 23.9 us.
+bool y3_conv1x1_wres_pays(const y3_op &op) {
+  const int bn = wres_bn(op);
+  return bn != 0 && op.out_c == bn && (long long)y3_ceil_div(op.batch * op.in_h * op.in_w, 128) >= 512;
+}
+
+int y3_choose_conv1x1_wres(const y3_op &op, y3_step &st) {
+  Y3_REQUIRE(y3_conv1x1_wres_supported(op), "conv block %d: not a shape for the weights-resident 1x1 kernel", op.block_idx);
+  st.bn = wres_bn(op);
+  st.launch = launch_conv1x1_wres;
+  st.name = st.bn == 128 ? Y3_KNAME(op.dtype, "conv1x1_wres_", "_128x128") : Y3_KNAME(op.dtype, "conv1x1_wres_", "_128x64");
+  return Y3_OK;
 }

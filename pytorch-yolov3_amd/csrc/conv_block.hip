@@ -431,12 +431,47 @@ bool choose_tile(int H, int W, int batch, int n_cu, int &TW, int &TH, double &ef
   return true;
 }
 
+int launch_block_fused(const y3_op *ops, const y3_step &st, const void *, const void *, hipStream_t s) {
+  const y3_op &op0 = ops[0], &op1 = ops[1];
+  BlockArgs a;
+  a.x = static_cast<const char *>(op0.d_in);
+  a.H = op0.in_h; a.W = op0.in_w; a.x_ld = op0.in_ld; a.ns = op0.in_c / 64;
+  a.w1 = static_cast<const char *>(op0.d_weight); a.k_ld1 = op0.k_ld; a.sc1 = op0.d_scale; a.bi1 = op0.d_bias;
+  a.w3 = static_cast<const char *>(op1.d_weight); a.k_ld3 = op1.k_ld; a.sc3 = op1.d_scale; a.bi3 = op1.d_bias;
+  a.out = static_cast<char *>(op1.d_out); a.out_ld = op1.out_ld; a.npass = op1.out_c / 128;
+  a.res = (op1.flags & Y3_F_RESIDUAL) ? 1 : 0;
+  a.leaky1 = (op0.flags & Y3_F_LEAKY) ? 1 : 0;
+  a.leaky3 = (op1.flags & Y3_F_LEAKY) ? 1 : 0;
+  a.TW = st.tw;
+  a.TH = st.th;
+  return y3_by_dtype16(op0.dtype, [&](auto tag) {
+    typedef decltype(tag) T;
+    static Y3DeviceOnce once;
+    {
+      const int rc = once.run([]() -> int {
+        Y3_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(conv_block_fused_kernel<T>),
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, kBlockLds));
+        return Y3_OK;
+      });
+      if (rc != Y3_OK) return rc;
+    }
+    a.tiles_x = y3_ceil_div(a.W, a.TW);
+    a.tiles_y = y3_ceil_div(a.H, a.TH);
+    a.inv_pw = (65536u + (uint32_t)(a.TW + 2) - 1u) / (uint32_t)(a.TW + 2);
+    a.inv_tw = (65536u + (uint32_t)a.TW - 1u) / (uint32_t)a.TW;
+    const int grid = a.tiles_x * a.tiles_y * op0.batch;
+    Y3_LAUNCH(conv_block_fused_kernel<T>, dim3(grid), dim3(kNT), kBlockLds, s, a);
+    Y3_HIP_CHECK(hipGetLastError());
+    return Y3_OK;
+  });
+}
+
 }  // namespace
 
 // op0: 1x1 conv Cin -> 128 whose output only op1 reads; op1: 3x3 stride-1 conv 128 -> Cout, optionally with the shortcut
 // operand == op0's input.  fuse_block: 0 never [default], 1 where the rectangles fill the chip, 2 wherever supported.
-bool y3_conv_block_fused_supported(const y3_op &op0, const y3_op &op1) {
-  const int mode = y3_opt().fuse_block;
+bool y3_choose_conv_block_fused(const y3_op &op0, const y3_op &op1, const y3_options &o, y3_step &st) {
+  const int mode = o.fuse_block;
   if (!mode) return false;
   if (op0.kind != Y3_OP_CONV || op1.kind != Y3_OP_CONV || !y3_is16(op0.dtype) || op1.dtype != op0.dtype) return false;
   if (op0.ksize != 1 || op0.stride != 1 || op0.in_c % 64 != 0 || op0.in_c < 192 || op0.out_c != 128) return false;
@@ -465,45 +500,12 @@ bool y3_conv_block_fused_supported(const y3_op &op0, const y3_op &op1) {
   if ((long long)op1.cout_pad * op1.k_ld * 2 >= (1ll << 31) || (long long)op0.cout_pad * op0.k_ld * 2 >= (1ll << 31)) return false;
   int tw, th;
   double eff;
-  if (!choose_tile(op0.in_h, op0.in_w, op0.batch, y3_device_cus(), tw, th, eff)) return false;
-  return mode >= 2 || eff >= 0.7;
-}
-
-int y3_launch_conv_block_fused(const y3_op &op0, const y3_op &op1, hipStream_t s, const char **kernel_name, bool dry_run) {
-  *kernel_name = Y3_KNAME(op0.dtype, "conv_block_fused_", "_x128");
-  if (dry_run) return Y3_OK;
-  BlockArgs a;
-  a.x = static_cast<const char *>(op0.d_in);
-  a.H = op0.in_h; a.W = op0.in_w; a.x_ld = op0.in_ld; a.ns = op0.in_c / 64;
-  a.w1 = static_cast<const char *>(op0.d_weight); a.k_ld1 = op0.k_ld; a.sc1 = op0.d_scale; a.bi1 = op0.d_bias;
-  a.w3 = static_cast<const char *>(op1.d_weight); a.k_ld3 = op1.k_ld; a.sc3 = op1.d_scale; a.bi3 = op1.d_bias;
-  a.out = static_cast<char *>(op1.d_out); a.out_ld = op1.out_ld; a.npass = op1.out_c / 128;
-  a.res = (op1.flags & Y3_F_RESIDUAL) ? 1 : 0;
-  a.leaky1 = (op0.flags & Y3_F_LEAKY) ? 1 : 0;
-  a.leaky3 = (op1.flags & Y3_F_LEAKY) ? 1 : 0;
-  return y3_by_dtype16(op0.dtype, [&](auto tag) {
-    typedef decltype(tag) T;
-    static Y3DeviceOnce once;
-    int n_cu = 0;
-    {
-      const int rc = once.run([]() -> int {
-        Y3_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(conv_block_fused_kernel<T>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, kBlockLds));
-        return Y3_OK;
-      }, &n_cu);
-      if (rc != Y3_OK) return rc;
-    }
-    double eff;
-    Y3_REQUIRE(choose_tile(a.H, a.W, op0.batch, n_cu, a.TW, a.TH, eff), "conv block %d: no tile shape", op0.block_idx);
-    a.tiles_x = y3_ceil_div(a.W, a.TW);
-    a.tiles_y = y3_ceil_div(a.H, a.TH);
-    a.inv_pw = (65536u + (uint32_t)(a.TW + 2) - 1u) / (uint32_t)(a.TW + 2);
-    a.inv_tw = (65536u + (uint32_t)a.TW - 1u) / (uint32_t)a.TW;
-    const int grid = a.tiles_x * a.tiles_y * op0.batch;
-    Y3_LAUNCH(conv_block_fused_kernel<T>, dim3(grid), dim3(kNT), kBlockLds, s, a);
-    Y3_HIP_CHECK(hipGetLastError());
-    return Y3_OK;
-  });
+  if (!choose_tile(op0.in_h, op0.in_w, op0.batch, y3_device_cus(), tw, th, eff) || (mode < 2 && eff < 0.7)) return false;
+  st.tw = tw;
+  st.th = th;
+  st.launch = launch_block_fused;
+  st.name = Y3_KNAME(op0.dtype, "conv_block_fused_", "_x128");
+  return true;
 }
 
 Y3_STAMP_READER(y3_debug_stamps_block)

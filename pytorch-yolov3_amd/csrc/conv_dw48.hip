@@ -368,37 +368,19 @@ int dw48_waves(const y3_op &op, int grid) {
   return op.out_c >= 128 && op.out_c == 32 * widest && tiles <= 8ll * n_cu ? widest : 0;
 }
 
-int dw48_waves_for(const y3_op &op) {
-  const unsigned am = (unsigned)y3_opt().auto_mask;
+int dw48_waves_for(const y3_op &op, const y3_options &o) {
+  const unsigned am = (unsigned)o.auto_mask;
   if (am & Y3_AM_SMALL_DW_ALWAYS) return dw48_waves(op, 2);
   const int nw = dw48_waves(op, 0);
   return nw || !(am & Y3_AM_SMALL_DW_WIDE) ? nw : dw48_waves(op, 1);
 }
 
-}  // namespace
-
-// one round of workgroups (or any grid under Y3_AM_SMALL_DW_ALWAYS)
-bool y3_conv_dw48_fits(const y3_op &op) { return dw48_waves(op, ((unsigned)y3_opt().auto_mask & Y3_AM_SMALL_DW_ALWAYS) ? 2 : 0) != 0; }
-// ... or a grid a little over one round (Y3_AM_SMALL_DW_WIDE): asked after the kernels that win on such grids where they apply
-bool y3_conv_dw48_fits_wide(const y3_op &op) { return ((unsigned)y3_opt().auto_mask & Y3_AM_SMALL_DW_WIDE) && dw48_waves(op, 1) != 0; }
-
-int y3_launch_conv_dw48(const y3_op &op, const void *d_in, const void *d_zero, hipStream_t s, const char **kernel_name,
-                        bool dry_run, const void *frag_w) {
-  const int nw = dw48_waves_for(op);
-  Y3_REQUIRE(nw != 0, "conv block %d: not a shape for the small-grid direct-weights kernel", op.block_idx);
-  *kernel_name = op.ksize == 3 ? (op.stride == 2 ? Y3_KNAME(op.dtype, "conv_dw48_k3s2_", "") : Y3_KNAME(op.dtype, "conv_dw48_k3_", ""))
-                               : Y3_KNAME(op.dtype, "conv_dw48_k1_", "");
-  if (dry_run) return Y3_OK;
-  void *tmp = nullptr;
-  if (!frag_w) {                                      // single-op calls without a shared copy: made here, stream-ordered
-    Y3_HIP_CHECK(hipMallocAsync(&tmp, y3_conv_halo_dw_weight_bytes(op), s));
-    const int rc = y3_conv_halo_dw_make_weights(op, tmp, s);
-    if (rc != Y3_OK) { (void)hipFreeAsync(tmp, s); return rc; }
-    frag_w = tmp;
-  }
+int launch_dw48(const y3_op *ops, const y3_step &step, const void *d_in, const void *d_zero, hipStream_t s) {
+  const y3_op &op = ops[0];
+  const int nw = step.waves;
   Dw48Args a;
   a.in = static_cast<const char *>(d_in);
-  a.wgt = static_cast<const char *>(frag_w);
+  a.wgt = static_cast<const char *>(step.frag_w);
   a.scale = op.d_scale; a.bias = op.d_bias;
   a.res = static_cast<const char *>(op.d_res);
   a.out = static_cast<char *>(op.d_out);
@@ -420,7 +402,7 @@ int y3_launch_conv_dw48(const y3_op &op, const void *d_in, const void *d_zero, h
   const size_t lds = (size_t)(a.hr + 1) * sh.cin_img * 2 + 1024;   // (+ the tail of the last 1-KiB piece)
   const dim3 grid(y3_ceil_div(a.M, 48) * a.n_ctiles), block(Y3_DW48_HELPERS ? 512 : 64 * nw);
   const int ks = op.ksize, st = op.stride, nh = sh.nh;
-  const int rc = y3_by_dtype16(op.dtype, [&](auto tag) {
+  return y3_by_dtype16(op.dtype, [&](auto tag) {
     typedef decltype(tag) T;
     static Y3DeviceOnce once;
     {
@@ -452,6 +434,21 @@ int y3_launch_conv_dw48(const y3_op &op, const void *d_in, const void *d_zero, h
     Y3_HIP_CHECK(hipGetLastError());
     return Y3_OK;
   });
-  if (tmp) (void)hipFreeAsync(tmp, s);
-  return rc;
+}
+
+}  // namespace
+
+// one round of workgroups (or any grid under Y3_AM_SMALL_DW_ALWAYS)
+bool y3_conv_dw48_fits(const y3_op &op, const y3_options &o) { return dw48_waves(op, ((unsigned)o.auto_mask & Y3_AM_SMALL_DW_ALWAYS) ? 2 : 0) != 0; }
+// ... or a grid a little over one round (Y3_AM_SMALL_DW_WIDE): asked after the kernels that win on such grids where they apply
+bool y3_conv_dw48_fits_wide(const y3_op &op, const y3_options &o) { return ((unsigned)o.auto_mask & Y3_AM_SMALL_DW_WIDE) && dw48_waves(op, 1) != 0; }
+
+int y3_choose_conv_dw48(const y3_op &op, const y3_options &o, y3_step &st) {
+  st.waves = dw48_waves_for(op, o);
+  Y3_REQUIRE(st.waves != 0, "conv block %d: not a shape for the small-grid direct-weights kernel", op.block_idx);
+  st.launch = launch_dw48;
+  st.name = op.ksize == 3 ? (op.stride == 2 ? Y3_KNAME(op.dtype, "conv_dw48_k3s2_", "") : Y3_KNAME(op.dtype, "conv_dw48_k3_", ""))
+                          : Y3_KNAME(op.dtype, "conv_dw48_k1_", "");
+  st.frag = true;
+  return Y3_OK;
 }

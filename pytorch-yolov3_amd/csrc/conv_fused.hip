@@ -920,9 +920,12 @@ __global__ __launch_bounds__(kThreads) void conv_resblock_fused_kernel(ResArgs<T
 }  // namespace
 
 
+static int launch_stem_s2(const y3_op *ops, const y3_step &st, const void *d_in, const void *, hipStream_t s);
+static int launch_resblock(const y3_op *ops, const y3_step &, const void *, const void *, hipStream_t s);
+
 // op0: the MFMA stem conv (uint8 frames, 3 -> 32, bf16 out); op1: 3x3 stride-2 conv 32 -> 64 reading ONLY op0's output
-bool y3_conv_fused_stem_s2_supported(const y3_op &op0, const y3_op &op1) {
-  if (!y3_opt().fuse_stem) return false;
+bool y3_choose_conv_fused_stem_s2(const y3_op &op0, const y3_op &op1, const y3_options &o, y3_step &st) {
+  if (!o.fuse_stem) return false;
   if (!y3_conv_stem_mfma_supported(op0) || op0.out_c != 32 || (op0.flags & Y3_F_RESIDUAL)) return false;
   if (!(op0.flags & Y3_F_LEAKY) || !(op1.flags & Y3_F_LEAKY)) return false;   // the kernel hard-wires LeakyReLU(0.1)
   if (op1.kind != Y3_OP_CONV || op1.dtype != op0.dtype || op1.ksize != 3 || op1.stride != 2 || op1.pad != 1) return false;
@@ -931,13 +934,14 @@ bool y3_conv_fused_stem_s2_supported(const y3_op &op0, const y3_op &op1) {
   if (op1.d_in != op0.d_out || op1.in_h != op0.out_h || op1.in_w != op0.out_w || op1.batch != op0.batch) return false;
   if (op1.k_ld < 288 || op1.cout_pad < 64) return false;
   if (op1.out_h != (op1.in_h + 2 - 3) / 2 + 1 || op1.out_w != (op1.in_w + 2 - 3) / 2 + 1) return false;
+  st.launch = launch_stem_s2;
+  st.name = op0.dtype == Y3_F16 ? "conv_stem_s2_fused_u8_f16" : "conv_stem_s2_fused_u8_bf16";
+  st.pipelined = o.fuse_stem != 2;                      // fuse_stem 2: the phase-by-phase kernel (A/B)
   return true;
 }
 
-int y3_launch_conv_fused_stem_s2(const y3_op &op0, const y3_op &op1, const void *d_in, hipStream_t s,
-                                 const char **kernel_name, bool dry_run) {
-  *kernel_name = op0.dtype == Y3_F16 ? "conv_stem_s2_fused_u8_f16" : "conv_stem_s2_fused_u8_bf16";
-  if (dry_run) return Y3_OK;
+static int launch_stem_s2(const y3_op *ops, const y3_step &st, const void *d_in, const void *, hipStream_t s) {
+  const y3_op &op0 = ops[0], &op1 = ops[1];
   return y3_by_dtype16(op0.dtype, [&](auto tag) {
     typedef decltype(tag) T;
     FusedArgs<T> a;
@@ -963,7 +967,7 @@ int y3_launch_conv_fused_stem_s2(const y3_op &op0, const y3_op &op1, const void 
       }, &n_cu);
       if (rc != Y3_OK) return rc;
     }
-    const bool pipelined = y3_opt().fuse_stem != 2;                      // fuse_stem 2: the phase-by-phase kernel (A/B)
+    const bool pipelined = st.pipelined;
     a.tiles_x = y3_ceil_div(a.Wo, pipelined ? kPX : kTO);
     a.tiles_y = y3_ceil_div(a.Ho, pipelined ? kPY : kTO);
     a.n_tiles = a.tiles_x * a.tiles_y * a.batch;
@@ -977,8 +981,8 @@ int y3_launch_conv_fused_stem_s2(const y3_op &op0, const y3_op &op1, const void 
 
 // op0: 1x1 conv 64 -> 32 whose output only op1 reads; op1: 3x3 stride-1 conv 32 -> 64 with the shortcut operand == op0's
 // input (one Darknet-53 residual block, bf16, LeakyReLU on both)
-bool y3_conv_fused_resblock_supported(const y3_op &op0, const y3_op &op1) {
-  if (!y3_opt().fuse_stem) return false;
+bool y3_choose_conv_fused_resblock(const y3_op &op0, const y3_op &op1, const y3_options &o, y3_step &st) {
+  if (!o.fuse_stem) return false;
   if (op0.kind != Y3_OP_CONV || op1.kind != Y3_OP_CONV || !y3_is16(op0.dtype) || op1.dtype != op0.dtype) return false;
   if (op0.ksize != 1 || op0.stride != 1 || op0.in_c != 64 || op0.out_c != 32) return false;
   if (op1.ksize != 3 || op1.stride != 1 || op1.pad != 1 || op1.in_c != 32 || op1.out_c != 64) return false;
@@ -990,13 +994,13 @@ bool y3_conv_fused_resblock_supported(const y3_op &op0, const y3_op &op1) {
   if (op0.out_h != op0.in_h || op0.out_w != op0.in_w || op1.out_h != op1.in_h || op1.out_w != op1.in_w) return false;
   if (op0.in_ld % 8 != 0 || op1.out_ld % 8 != 0 || op0.in_ld < 64 || op1.out_ld < 64) return false;
   if (op0.k_ld < 64 || op1.k_ld < 288 || op0.cout_pad < 32 || op1.cout_pad < 64) return false;
+  st.launch = launch_resblock;
+  st.name = Y3_KNAME(op0.dtype, "conv_resblock_fused_", "_64_32_64");
   return true;
 }
 
-int y3_launch_conv_fused_resblock(const y3_op &op0, const y3_op &op1, hipStream_t s, const char **kernel_name,
-                                  bool dry_run) {
-  *kernel_name = Y3_KNAME(op0.dtype, "conv_resblock_fused_", "_64_32_64");
-  if (dry_run) return Y3_OK;
+static int launch_resblock(const y3_op *ops, const y3_step &, const void *, const void *, hipStream_t s) {
+  const y3_op &op0 = ops[0], &op1 = ops[1];
   return y3_by_dtype16(op0.dtype, [&](auto tag) {
     typedef decltype(tag) T;
     ResArgs<T> a;

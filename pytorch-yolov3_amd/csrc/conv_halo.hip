@@ -1266,8 +1266,8 @@ void fast_div(uint32_t d, uint32_t &mul, uint32_t &sh) {
 // their own streams (bench.py) the idle CUs of a short last round are filled by the other batches' kernels anyway and
 // what counts is CU time, which smaller tiles raise (the ~11 k cycles per tile are paid 248 instead of 184 times):
 // 2.3 % fewer frames/s end to end.  Such callers set Y3_AM_HALO_TILE256 (256-pixel tiles only) in their plan options.
-static int halo_tile_fragments(int M, int n_tiles, int nchunks, int n_cu) {
-  if ((unsigned)y3_opt().auto_mask & Y3_AM_HALO_TILE256) return 4;
+static int halo_tile_fragments(int M, int n_tiles, int nchunks, int n_cu, const y3_options &o) {
+  if ((unsigned)o.auto_mask & Y3_AM_HALO_TILE256) return 4;
   double best = 0;
   int best_mi = 4;
   for (int mi = 4; mi >= 3; --mi) {
@@ -1280,10 +1280,9 @@ static int halo_tile_fragments(int M, int n_tiles, int nchunks, int n_cu) {
 }
 
 template <typename T>
-int launch_halo_ws(const HaloArgs &a0, hipStream_t s) {
+int launch_halo_ws(const HaloArgs &a0, int mi, hipStream_t s) {
   HaloArgs a = a0;
   static Y3DeviceOnce once;
-  int n_cu = 256;
   {
     const int rc = once.run([]() -> int {
       Y3_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(conv_halo_ws_kernel<T, 3, 4>),
@@ -1295,10 +1294,9 @@ int launch_halo_ws(const HaloArgs &a0, hipStream_t s) {
       Y3_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(conv_halo_ws_kernel<T, 4, 3>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
       return Y3_OK;
-    }, &n_cu);
+    });
     if (rc != Y3_OK) return rc;
   }
-  const int mi = halo_tile_fragments(a.M, a.n_tiles, a.nchunks, n_cu);
   const int bm = 64 * mi;
   const int hr = bm + 2 * a.W + 2;
   a.hr = hr;
@@ -1474,13 +1472,13 @@ bool y3_conv_halo_dw_fits(const y3_op &op) {
 // batch 16: 256 -> 512 at 38^2 is 364 tiles of 256 x 128 in two rounds against 242 of 192 x 256 in one: 58.5 -> 49.5 us,
 // 930 -> 1100 TFLOP/s per launch (profiles/r05s_halo_dw.txt).  Layers with fewer than four channel chunks stay on the
 // wave-specialised kernel (76^2: its shorter prologue / epilogue wins), and so does everything the model puts within 7 %.
-bool y3_conv_halo_dw_pays(const y3_op &op) {
+bool y3_conv_halo_dw_pays(const y3_op &op, const y3_options &o) {
   if (!y3_conv_halo_dw_fits(op)) return false;
   const int es = y3_elem_size(op.dtype);
   const int nchunks = op.in_c / (128 / es), n_cu = y3_device_cus();
   if (nchunks < 4) return false;
   const int M = op.batch * op.in_h * op.in_w;
-  const int mi = halo_tile_fragments(M, op.out_c / 128, nchunks, n_cu);
+  const int mi = halo_tile_fragments(M, op.out_c / 128, nchunks, n_cu, o);
   const long long t_ws = (long long)y3_ceil_div(M, 64 * mi) * (op.out_c / 128), t_dw = (long long)y3_ceil_div(M, DW_BM) * (op.out_c / 256);
   const double c_ws = (double)((t_ws + n_cu - 1) / n_cu) * (nchunks * 9.0 * (256.0 * mi + 300.0) + 13000.0);
   const double c_dw = (double)((t_dw + n_cu - 1) / n_cu) * (nchunks * 9.0 * 1920.0 + 17000.0);
@@ -1498,22 +1496,11 @@ int y3_conv_halo_dw_make_weights(const y3_op &op, void *dst, hipStream_t s) {
   return Y3_OK;
 }
 
-// `frag_w`: the plan's fragment-order copy of the weights; nullptr (single-op calls, unit tests): made here, stream-ordered
-int y3_launch_conv_halo_dw(const y3_op &op, const void *d_in, const void *d_zero, hipStream_t s,
-                           const char **kernel_name, bool dry_run, const void *frag_w) {
-  Y3_REQUIRE(y3_conv_halo_dw_fits(op), "conv block %d: shape not supported by the direct-weights halo kernel", op.block_idx);
-  *kernel_name = Y3_KNAME(op.dtype, "conv_halo_dw_", "_192x256");
-  if (dry_run) return Y3_OK;
-  void *tmp = nullptr;
-  if (!frag_w) {
-    Y3_HIP_CHECK(hipMallocAsync(&tmp, y3_conv_halo_dw_weight_bytes(op), s));
-    const int rc = y3_conv_halo_dw_make_weights(op, tmp, s);
-    if (rc != Y3_OK) { (void)hipFreeAsync(tmp, s); return rc; }
-    frag_w = tmp;
-  }
+static int launch_conv_halo_dw(const y3_op *ops, const y3_step &st, const void *d_in, const void *d_zero, hipStream_t s) {
+  const y3_op &op = ops[0];
   HaloArgs a;
   a.in = static_cast<const char *>(d_in);
-  a.wgt = static_cast<const char *>(frag_w);
+  a.wgt = static_cast<const char *>(st.frag_w);
   a.scale = op.d_scale; a.bias = op.d_bias;
   a.res = static_cast<const char *>(op.d_res);
   a.out = static_cast<char *>(op.d_out);
@@ -1530,15 +1517,16 @@ int y3_launch_conv_halo_dw(const y3_op &op, const void *d_in, const void *d_zero
   fast_div((uint32_t)a.HW, a.mul_hw, a.sh_hw);
   fast_div((uint32_t)a.W, a.mul_w, a.sh_w);
   a.flags = op.flags;
-  int rc = Y3_OK;
-  if ((long long)op.batch * a.HW >= (1ll << 31)) {
-    y3_set_error("conv block %d: too many pixels for the 32-bit tile index", op.block_idx);
-    rc = Y3_ERR_INVALID;
-  } else {
-    rc = y3_by_dtype16(op.dtype, [&](auto tag) { return launch_halo_dw<decltype(tag)>(a, s); });
-  }
-  if (tmp) (void)hipFreeAsync(tmp, s);
-  return rc;
+  return y3_by_dtype16(op.dtype, [&](auto tag) { return launch_halo_dw<decltype(tag)>(a, s); });
+}
+
+int y3_choose_conv_halo_dw(const y3_op &op, y3_step &st) {
+  Y3_REQUIRE(y3_conv_halo_dw_fits(op), "conv block %d: shape not supported by the direct-weights halo kernel", op.block_idx);
+  Y3_REQUIRE((long long)op.batch * op.in_h * op.in_w < (1ll << 31), "conv block %d: too many pixels for the 32-bit tile index", op.block_idx);
+  st.launch = launch_conv_halo_dw;
+  st.name = Y3_KNAME(op.dtype, "conv_halo_dw_", "_192x256");
+  st.frag = true;
+  return Y3_OK;
 }
 
 // 2-D patch kernel: same layer class, any number (>= 1) of channel chunks, any row width
@@ -1552,12 +1540,9 @@ bool y3_conv_patch_fits(const y3_op &op) {
   return op.k_ld >= 9 * op.in_c;
 }
 
-int y3_launch_conv_patch(const y3_op &op, const void *d_in, const void *d_zero, hipStream_t s,
-                         const char **kernel_name, bool dry_run) {
+static int launch_conv_patch(const y3_op *ops, const y3_step &, const void *d_in, const void *d_zero, hipStream_t s) {
+  const y3_op &op = ops[0];
   const int es = y3_elem_size(op.dtype);
-  Y3_REQUIRE(y3_conv_patch_fits(op), "conv block %d: shape not supported by the patch kernel", op.block_idx);
-  *kernel_name = Y3_KNAME(op.dtype, "conv_patch_wsp_", "_8x32x128");
-  if (dry_run) return Y3_OK;
   HaloArgs a;
   a.in = static_cast<const char *>(d_in);
   a.wgt = static_cast<const char *>(op.d_weight);
@@ -1579,14 +1564,16 @@ int y3_launch_conv_patch(const y3_op &op, const void *d_in, const void *d_zero, 
   return y3_by_dtype(op.dtype, [&](auto tag) { return launch_patch_wsp<decltype(tag)>(a, s); });
 }
 
-int y3_launch_conv_halo(const y3_op &op, const void *d_in, const void *d_zero, hipStream_t s,
-                        const char **kernel_name, bool dry_run) {
+int y3_choose_conv_patch(const y3_op &op, y3_step &st) {
+  Y3_REQUIRE(y3_conv_patch_fits(op), "conv block %d: shape not supported by the patch kernel", op.block_idx);
+  st.launch = launch_conv_patch;
+  st.name = Y3_KNAME(op.dtype, "conv_patch_wsp_", "_8x32x128");
+  return Y3_OK;
+}
+
+static int launch_conv_halo(const y3_op *ops, const y3_step &st, const void *d_in, const void *d_zero, hipStream_t s) {
+  const y3_op &op = ops[0];
   const int es = y3_elem_size(op.dtype);
-  Y3_REQUIRE(y3_conv_halo_ws_fits(op), "conv block %d: shape not supported by the halo kernel", op.block_idx);
-  const int mi = halo_tile_fragments(op.batch * op.in_h * op.in_w, op.out_c / 128, op.in_c / (128 / es), y3_device_cus());
-  if (mi == 3) *kernel_name = Y3_KNAME(op.dtype, "conv_halo_ws_", "_192x128");
-  else *kernel_name = Y3_KNAME(op.dtype, "conv_halo_ws_", "_256x128");
-  if (dry_run) return Y3_OK;
   HaloArgs a;
   a.in = static_cast<const char *>(d_in);
   a.wgt = static_cast<const char *>(op.d_weight);
@@ -1606,8 +1593,18 @@ int y3_launch_conv_halo(const y3_op &op, const void *d_in, const void *d_zero, h
   fast_div((uint32_t)a.HW, a.mul_hw, a.sh_hw);
   fast_div((uint32_t)a.W, a.mul_w, a.sh_w);
   a.flags = op.flags | (y3_debug_flags() ? 0x40000000u : 0u);
-  Y3_REQUIRE((long long)op.batch * a.HW < (1ll << 31), "conv block %d: too many pixels for the 32-bit tile index", op.block_idx);
-  return y3_by_dtype(op.dtype, [&](auto tag) { return launch_halo_ws<decltype(tag)>(a, s); });
+  return y3_by_dtype(op.dtype, [&](auto tag) { return launch_halo_ws<decltype(tag)>(a, st.bm / 64, s); });
+}
+
+int y3_choose_conv_halo(const y3_op &op, const y3_options &o, y3_step &st) {
+  const int es = y3_elem_size(op.dtype);
+  Y3_REQUIRE(y3_conv_halo_ws_fits(op), "conv block %d: shape not supported by the halo kernel", op.block_idx);
+  Y3_REQUIRE((long long)op.batch * op.in_h * op.in_w < (1ll << 31), "conv block %d: too many pixels for the 32-bit tile index", op.block_idx);
+  const int mi = halo_tile_fragments(op.batch * op.in_h * op.in_w, op.out_c / 128, op.in_c / (128 / es), y3_device_cus(), o);
+  st.launch = launch_conv_halo;
+  st.bm = 64 * mi;
+  st.name = mi == 3 ? Y3_KNAME(op.dtype, "conv_halo_ws_", "_192x128") : Y3_KNAME(op.dtype, "conv_halo_ws_", "_256x128");
+  return Y3_OK;
 }
 
 Y3_STAMP_READER(y3_debug_stamps_halo)

@@ -956,15 +956,18 @@ static void igemm_fast_div(uint32_t d, uint32_t &mul, uint32_t &sh) {
   mul = (uint32_t)((((uint64_t)1 << 32) * (((uint64_t)1 << sh) - d)) / d + 1);
 }
 
-int y3_launch_conv_igemm(const y3_op &op, const void *d_in, const void *d_zero, hipStream_t s,
-                         const char **kernel_name, bool dry_run, int force_version, int force_ns, int force_bm) {
-  const int version = force_version ? force_version : y3_opt().igemm_version;
-  const int ns = force_ns ? force_ns : y3_opt().igemm_ns;
-  const int bm_knob = force_bm ? force_bm : y3_opt().igemm_bm;
-  Y3_REQUIRE(y3_conv_igemm_supported(op), "conv block %d: shape not supported by the igemm kernel",
-             op.block_idx);
-  const int es = y3_elem_size(op.dtype);
-  const int bke = 128 / es;
+// K-tiling mode: 0 one tap per tile, 2 several whole taps per tile, 1 per-chunk taps; and the number of K-tiles
+static int igemm_ktiles(const y3_op &op, int &kmode) {
+  const int bke = 128 / y3_elem_size(op.dtype);
+  kmode = op.in_c % bke == 0 ? 0 : (bke % op.in_c == 0 ? 2 : 1);
+  if (kmode == 0) return op.ksize * op.ksize * (op.in_c / bke);
+  if (kmode == 2) return y3_ceil_div(op.ksize * op.ksize, bke / op.in_c);
+  return y3_ceil_div(op.ksize * op.ksize * op.in_c, bke);
+}
+
+static int launch_conv_igemm(const y3_op *ops, const y3_step &st, const void *d_in, const void *d_zero, hipStream_t s) {
+  const y3_op &op = ops[0];
+  const int bke = 128 / y3_elem_size(op.dtype);
   IgemmArgs a;
   a.in = static_cast<const char *>(d_in);
   a.wgt = static_cast<const char *>(op.d_weight);
@@ -980,16 +983,10 @@ int y3_launch_conv_igemm(const y3_op &op, const void *d_in, const void *d_zero, 
   a.M = op.batch * a.HoWo;
   a.k_ld = op.k_ld;
   a.K = op.ksize * op.ksize * op.in_c;
-  // K-tiling mode: 0 one tap per tile, 2 several whole taps per tile, 1 per-chunk taps
-  int kmode = 1;
-  if (op.in_c % bke == 0) kmode = 0;
-  else if (bke % op.in_c == 0) kmode = 2;
+  int kmode;
+  a.n_ktiles = igemm_ktiles(op, kmode);
   a.ktiles_per_tap = kmode == 0 ? op.in_c / bke : 0;
   a.n_taps = op.ksize * op.ksize;
-  if (kmode == 0) a.n_ktiles = op.ksize * op.ksize * a.ktiles_per_tap;
-  else if (kmode == 2) a.n_ktiles = y3_ceil_div(op.ksize * op.ksize, bke / op.in_c);
-  else a.n_ktiles = y3_ceil_div(a.K, bke);
-  Y3_REQUIRE(a.n_ktiles * bke <= op.k_ld, "conv block %d: k_ld %d too small for %d K-tiles", op.block_idx, op.k_ld, a.n_ktiles);
   a.m_tiles = a.n_tiles = 0;
   // Each XCD gets one contiguous run of tile ids (y3_xcd_remap) and has its own L2.  Channel tiles innermost: the run covers a
   // few pixel tiles x ALL channel tiles, so every XCD fetches the whole weight matrix and 1/8 of the activations; pixel
@@ -998,75 +995,84 @@ int y3_launch_conv_igemm(const y3_op &op, const void *d_in, const void *d_zero, 
   // launch for 16 MB algorithmic before this, profiles/r03_traffic.json).  Placement only: results do not change.
   a.n_major = (double)op.out_c * a.K > (double)op.batch * op.in_h * op.in_w * op.in_c ? 1 : 0;
   a.flags = op.flags | (y3_debug_flags() ? 0x40000000u : 0u) | (y3_debug_flags() == 2 ? 0x80000000u : 0u);
-  Y3_REQUIRE((long long)op.batch * a.HoWo < (1ll << 31), "conv block %d: too many output pixels for the 32-bit tile index", op.block_idx);
   igemm_fast_div((uint32_t)a.HoWo, a.mul_hw, a.sh_hw);
   igemm_fast_div((uint32_t)a.Wo, a.mul_w, a.sh_w);
+  const int dt = op.dtype, bm = st.bm, bn = st.bn, ns = st.ns;
+  if (st.version == 1) {
+    const bool generic = kmode != 0;
+    if (generic) a.n_ktiles = y3_ceil_div(a.K, bke);
+    if (bn == 128) return y3_by_dtype(dt, [&](auto tag) { return launch_cfg<decltype(tag), 128, 128, 2, 2>(a, generic, s); });
+    if (bn == 64) return y3_by_dtype(dt, [&](auto tag) { return launch_cfg<decltype(tag), 128, 64, 2, 2>(a, generic, s); });
+    return y3_by_dtype(dt, [&](auto tag) { return launch_cfg<decltype(tag), 128, 32, 4, 1>(a, generic, s); });
+  }
+  if (st.version == 3) {
+    if (bm == 64) return y3_by_dtype16(dt, [&](auto tag) { return launch_cfg3<decltype(tag), 64, 128, 1, 4>(a, kmode, ns, s); });
+    return y3_by_dtype(dt, [&](auto tag) { return launch_cfg3<decltype(tag), 128, 128, 2, 2>(a, kmode, ns, s); });
+  }
+  if (bm == 96) return y3_by_dtype(dt, [&](auto tag) { return launch_cfg2<decltype(tag), 96, 64, 2, 2>(a, kmode, s); });
+  if (bn == 128) return y3_by_dtype(dt, [&](auto tag) { return launch_cfg2<decltype(tag), 128, 128, 2, 2>(a, kmode, s); });
+  if (bn == 64) return y3_by_dtype(dt, [&](auto tag) { return launch_cfg2<decltype(tag), 128, 64, 2, 2>(a, kmode, s); });
+  return y3_by_dtype(dt, [&](auto tag) { return launch_cfg2<decltype(tag), 128, 32, 4, 1>(a, kmode, s); });
+}
 
+int y3_choose_conv_igemm(const y3_op &op, const y3_options &o, y3_step &st, int force_version, int force_ns, int force_bm) {
+  const int version = force_version ? force_version : o.igemm_version;
+  const int ns = force_ns ? force_ns : o.igemm_ns;
+  const int bm_knob = force_bm ? force_bm : o.igemm_bm;
+  Y3_REQUIRE(y3_conv_igemm_supported(op), "conv block %d: shape not supported by the igemm kernel",
+             op.block_idx);
+  int kmode;
+  const int n_ktiles = igemm_ktiles(op, kmode), M = op.batch * op.out_h * op.out_w;
+  Y3_REQUIRE(n_ktiles * (128 / y3_elem_size(op.dtype)) <= op.k_ld, "conv block %d: k_ld %d too small for %d K-tiles", op.block_idx, op.k_ld, n_ktiles);
+  Y3_REQUIRE((long long)op.batch * op.out_h * op.out_w < (1ll << 31), "conv block %d: too many output pixels for the 32-bit tile index", op.block_idx);
   const int dt = op.dtype;
   const bool bf = y3_is16(dt);                   // a 16-bit storage mode (bf16 / IEEE half): same tiles, same selection
+  st.launch = launch_conv_igemm;
+  st.ns = ns;
+  st.bm = 128;
   // channel-tile width follows Cout so narrow layers do not multiply zero padding ...
   int bn = op.out_c > 64 ? 128 : (op.out_c > 32 ? 64 : 32);
   // ... and shrinks while the grid would leave most CUs without a workgroup (small maps / small batches: 13^2 x 8 frames
   // of yolov3-tiny has 11 pixel tiles; 128-channel tiles of its 512 -> 1024 layer are 88 workgroups on 256 CUs, two per
   // CU resident).  Narrower tiles re-read the (small) activation tile more often and keep the weight bytes per FLOP.
-  if (version == 2 && !(op.flags & Y3_F_OUT_F32) && !((unsigned)y3_opt().auto_mask & Y3_AM_NO_BN_SHRINK)) {
-    const long long m_tiles = y3_ceil_div(a.M, 128);
+  if (version == 2 && !(op.flags & Y3_F_OUT_F32) && !((unsigned)o.auto_mask & Y3_AM_NO_BN_SHRINK)) {
+    const long long m_tiles = y3_ceil_div(M, 128);
     while (bn > 32 && m_tiles * y3_ceil_div(op.out_c, bn) < y3_device_cus()) bn >>= 1;   // 362 / 368 workgroups at 128 measured faster than twice as many at 64
   }
+  st.bn = bn;
   // float32-output (detection head) convs: the direct epilogue of v1 measured faster
   if (version == 1 || (version == 2 && bf && (op.flags & Y3_F_OUT_F32))) {
-    const bool generic = kmode != 0;
-    if (generic) a.n_ktiles = y3_ceil_div(a.K, bke);
-    if (bn == 128) {
-      *kernel_name = Y3_KNAME(dt, "conv_igemm_", "_128x128");
-      if (dry_run) return Y3_OK;
-      return y3_by_dtype(dt, [&](auto tag) { return launch_cfg<decltype(tag), 128, 128, 2, 2>(a, generic, s); });
-    } else if (bn == 64) {
-      *kernel_name = Y3_KNAME(dt, "conv_igemm_", "_128x64");
-      if (dry_run) return Y3_OK;
-      return y3_by_dtype(dt, [&](auto tag) { return launch_cfg<decltype(tag), 128, 64, 2, 2>(a, generic, s); });
-    }
-    *kernel_name = Y3_KNAME(dt, "conv_igemm_", "_128x32");
-    if (dry_run) return Y3_OK;
-    return y3_by_dtype(dt, [&](auto tag) { return launch_cfg<decltype(tag), 128, 32, 4, 1>(a, generic, s); });
-  }
-  if (version == 3 && bn == 128 && bm_knob == 64 && bf && !(op.flags & Y3_F_OUT_F32)) {
-    *kernel_name = Y3_KNAME(dt, "conv_igemm3_", "_64x128");   // 64-pixel tiles: twice the workgroups, two per CU at 3 stages
-    if (dry_run) return Y3_OK;
-    return y3_by_dtype16(dt, [&](auto tag) { return launch_cfg3<decltype(tag), 64, 128, 1, 4>(a, kmode, ns, s); });
+    st.version = 1;
+    st.name = bn == 128 ? Y3_KNAME(dt, "conv_igemm_", "_128x128")
+                        : (bn == 64 ? Y3_KNAME(dt, "conv_igemm_", "_128x64") : Y3_KNAME(dt, "conv_igemm_", "_128x32"));
+    return Y3_OK;
   }
   if (version == 3 && bn == 128 && !(op.flags & Y3_F_OUT_F32)) {
-    *kernel_name = Y3_KNAME(dt, "conv_igemm3_", "_128x128");
-    if (dry_run) return Y3_OK;
-    return y3_by_dtype(dt, [&](auto tag) { return launch_cfg3<decltype(tag), 128, 128, 2, 2>(a, kmode, ns, s); });
+    st.version = 3;
+    st.bm = bm_knob == 64 && bf ? 64 : 128;   // 64-pixel tiles: twice the workgroups, two per CU at 3 stages
+    st.name = st.bm == 64 ? Y3_KNAME(dt, "conv_igemm3_", "_64x128") : Y3_KNAME(dt, "conv_igemm3_", "_128x128");
+    return Y3_OK;
   }
+  st.version = 2;
   // 96 x 64 tiles where they fit the chip in ONE round of equal workgroups and the tile above does not: yolov3-tiny's big
   // float32 layers at batch 8 are 352 / 344 tiles of 128 x 32 on 256 CUs (the CUs that get two take twice as long: 39 % of
   // the float32 MFMA peak) against 240 / 228 of 96 x 64, with twice the weight bytes reused per pixel fragment.  Same K order,
   // same bits.  igemm_bm = 96 forces them (A/B), igemm_bm = 128 forbids them.
   if (version == 2 && !(op.flags & Y3_F_OUT_F32) && op.out_c % 64 == 0 && bm_knob != 128 && bm_knob != 64) {
     const int n_cu = y3_device_cus();
-    const long long t96 = (long long)y3_ceil_div(a.M, 96) * (op.out_c / 64);
-    const long long tcur = (long long)y3_ceil_div(a.M, 128) * y3_ceil_div(op.out_c, bn);
-    const bool pays = t96 <= n_cu && t96 * 4 >= n_cu * 3 && tcur > n_cu && tcur < 2 * n_cu && a.n_ktiles >= 32;
+    const long long t96 = (long long)y3_ceil_div(M, 96) * (op.out_c / 64);
+    const long long tcur = (long long)y3_ceil_div(M, 128) * y3_ceil_div(op.out_c, bn);
+    const bool pays = t96 <= n_cu && t96 * 4 >= n_cu * 3 && tcur > n_cu && tcur < 2 * n_cu && n_ktiles >= 32;
     if (bm_knob == 96 || pays) {
-      *kernel_name = Y3_KNAME(dt, "conv_igemm2_", "_96x64");
-      if (dry_run) return Y3_OK;
-      return y3_by_dtype(dt, [&](auto tag) { return launch_cfg2<decltype(tag), 96, 64, 2, 2>(a, kmode, s); });
+      st.bm = 96;
+      st.bn = 64;
+      st.name = Y3_KNAME(dt, "conv_igemm2_", "_96x64");
+      return Y3_OK;
     }
   }
-  if (bn == 128) {
-    *kernel_name = Y3_KNAME(dt, "conv_igemm2_", "_128x128");
-    if (dry_run) return Y3_OK;
-    return y3_by_dtype(dt, [&](auto tag) { return launch_cfg2<decltype(tag), 128, 128, 2, 2>(a, kmode, s); });
-  } else if (bn == 64) {
-    *kernel_name = Y3_KNAME(dt, "conv_igemm2_", "_128x64");
-    if (dry_run) return Y3_OK;
-    return y3_by_dtype(dt, [&](auto tag) { return launch_cfg2<decltype(tag), 128, 64, 2, 2>(a, kmode, s); });
-  }
-  *kernel_name = Y3_KNAME(dt, "conv_igemm2_", "_128x32");
-  if (dry_run) return Y3_OK;
-  return y3_by_dtype(dt, [&](auto tag) { return launch_cfg2<decltype(tag), 128, 32, 4, 1>(a, kmode, s); });
+  st.name = bn == 128 ? Y3_KNAME(dt, "conv_igemm2_", "_128x128")
+                      : (bn == 64 ? Y3_KNAME(dt, "conv_igemm2_", "_128x64") : Y3_KNAME(dt, "conv_igemm2_", "_128x32"));
+  return Y3_OK;
 }
 
 Y3_STAMP_READER(y3_debug_stamps_igemm)
@@ -1075,25 +1081,30 @@ Y3_STAMP_READER(y3_debug_stamps_igemm)
 // op0: the head conv as the plan holds it (Y3_F_OUT_F32, Cout = anchors * attributes <= 256); op1: the Y3_OP_YOLO op
 // reading it.  16-bit networks (bf16 / fp16) only: the float32 parity path keeps the two kernels (sequential class loop).
 
-bool y3_conv_head_decode_supported(const y3_op &op0, const y3_op &op1) {
-  if (!y3_opt().fuse_head) return false;
+static int launch_head_decode(const y3_op *ops, const y3_step &, const void *, const void *d_zero, hipStream_t s);
+
+bool y3_choose_conv_head_decode(const y3_op &op0, const y3_op &op1, const y3_options &o, y3_step &st) {
+  if (!o.fuse_head) return false;
   if (op0.kind != Y3_OP_CONV || op1.kind != Y3_OP_YOLO || !y3_is16(op0.dtype)) return false;
   if (op0.ksize != 1 || op0.stride != 1 || !(op0.flags & Y3_F_OUT_F32)) return false;
   if (op0.flags & (Y3_F_LEAKY | Y3_F_RESIDUAL | Y3_F_IN_NCHW_F32 | Y3_F_IN_NHWC_U8BGR | Y3_F_PLAN_INPUT)) return false;
   if (!y3_conv_igemm_supported(op0) || op0.in_c % 64 != 0 || op0.out_c > 256 || op0.cout_pad < 256) return false;
   if (op1.d_in != op0.d_out || op1.in_ld != op0.out_ld || op1.in_h != op0.out_h || op1.in_w != op0.out_w) return false;
   if (op1.batch != op0.batch || op1.n_anchor < 1 || op1.n_anchor > 8 || op1.n_attr <= 5) return false;
-  if (op1.n_anchor * op1.n_attr != op0.out_c) return false;
-  return op1.d_bbox && op1.d_prob && op1.d_cls;
-}
-
-int y3_launch_conv_head_decode(const y3_op &op0, const y3_op &op1, const void *d_zero, hipStream_t s,
-                               const char **kernel_name, bool dry_run, const void *frag_w) {
+  if (op1.n_anchor * op1.n_attr != op0.out_c || !op1.d_bbox || !op1.d_prob || !op1.d_cls) return false;
   // the direct-weights form (conv_1x1.hip) wherever its shape constraints hold: nothing in its K loop waits on a barrier or a cold
   // load; this tiled form (one K-step of prefetch) keeps the other shapes
-  if (y3_conv_head_dw_fits(op0)) return y3_launch_conv_head_decode_dw(op0, op1, d_zero, s, kernel_name, dry_run, frag_w ? frag_w : op0.d_weight_frag);
-  *kernel_name = Y3_KNAME(op0.dtype, "conv_head_decode_", "_64x256");
-  if (dry_run) return Y3_OK;
+  if (y3_conv_head_dw_fits(op0, o)) {
+    y3_choose_conv_head_decode_dw(op0, o, st);
+  } else {
+    st.launch = launch_head_decode;
+    st.name = Y3_KNAME(op0.dtype, "conv_head_decode_", "_64x256");
+  }
+  return true;
+}
+
+static int launch_head_decode(const y3_op *ops, const y3_step &, const void *, const void *d_zero, hipStream_t s) {
+  const y3_op &op0 = ops[0], &op1 = ops[1];
   IgemmArgs a;
   a.in = static_cast<const char *>(op0.d_in);
   a.wgt = static_cast<const char *>(op0.d_weight);

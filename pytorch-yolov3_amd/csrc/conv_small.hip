@@ -264,14 +264,8 @@ __global__ __launch_bounds__(256) void conv_direct_kernel(DirectArgs p) {
 
 }  // namespace
 
-int y3_launch_conv_small(const y3_op &op, const void *d_in, hipStream_t s, const char **kernel_name,
-                         bool dry_run) {
-  Y3_REQUIRE(op.in_c == 3 && op.ksize == 3, "conv block %d: stem kernel needs Cin=3, 3x3", op.block_idx);
-  Y3_REQUIRE(op.flags & (Y3_F_IN_NCHW_F32 | Y3_F_IN_NHWC_U8BGR),
-             "conv block %d: stem kernel reads the network input only", op.block_idx);
-  Y3_REQUIRE(op.cout_pad % 8 == 0 && op.cout_pad >= op.out_c && op.cout_pad <= 256,
-             "conv block %d: bad cout_pad %d", op.block_idx, op.cout_pad);
-  Y3_REQUIRE(!(op.flags & Y3_F_RESIDUAL), "conv block %d: stem kernel has no residual input", op.block_idx);
+static int launch_conv_small(const y3_op *ops, const y3_step &, const void *d_in, const void *, hipStream_t s) {
+  const y3_op &op = ops[0];
   SmallArgs a;
   a.in = d_in;
   a.wgt = static_cast<const float *>(op.d_weight);
@@ -285,8 +279,6 @@ int y3_launch_conv_small(const y3_op &op, const void *d_in, hipStream_t s, const
   a.flags = op.flags;
   const bool u8 = op.flags & Y3_F_IN_NHWC_U8BGR;
   const int odt = (op.flags & Y3_F_OUT_F32) ? Y3_F32 : op.dtype;   // element type of the output
-  *kernel_name = u8 ? Y3_KNAME(odt, "conv_stem3x3_u8_", "") : Y3_KNAME(odt, "conv_stem3x3_nchw_", "");
-  if (dry_run) return Y3_OK;
   const dim3 grid(y3_ceil_div(a.M, 256)), block(256);
   const size_t lds = ((size_t)27 * op.cout_pad + 256) * sizeof(float);
   return y3_by_dtype(odt, [&](auto tag) {
@@ -297,17 +289,27 @@ int y3_launch_conv_small(const y3_op &op, const void *d_in, hipStream_t s, const
   });
 }
 
+int y3_choose_conv_small(const y3_op &op, y3_step &st) {
+  Y3_REQUIRE(op.in_c == 3 && op.ksize == 3, "conv block %d: stem kernel needs Cin=3, 3x3", op.block_idx);
+  Y3_REQUIRE(op.flags & (Y3_F_IN_NCHW_F32 | Y3_F_IN_NHWC_U8BGR),
+             "conv block %d: stem kernel reads the network input only", op.block_idx);
+  Y3_REQUIRE(op.cout_pad % 8 == 0 && op.cout_pad >= op.out_c && op.cout_pad <= 256,
+             "conv block %d: bad cout_pad %d", op.block_idx, op.cout_pad);
+  Y3_REQUIRE(!(op.flags & Y3_F_RESIDUAL), "conv block %d: stem kernel has no residual input", op.block_idx);
+  const int odt = (op.flags & Y3_F_OUT_F32) ? Y3_F32 : op.dtype;
+  st.launch = launch_conv_small;
+  st.name = (op.flags & Y3_F_IN_NHWC_U8BGR) ? Y3_KNAME(odt, "conv_stem3x3_u8_", "") : Y3_KNAME(odt, "conv_stem3x3_nchw_", "");
+  return Y3_OK;
+}
+
 // MFMA stem: needs weights in its own layout (bf16 [32][32], see yolov3/darknet.py) -> separate conv path (3)
 bool y3_conv_stem_mfma_supported(const y3_op &op) {
   return (op.flags & Y3_F_IN_NHWC_U8BGR) && !(op.flags & (Y3_F_OUT_F32 | Y3_F_RESIDUAL)) && y3_is16(op.dtype) &&
          op.in_c == 3 && op.ksize == 3 && op.stride == 1 && op.pad == 1 && op.out_c <= 32 && op.out_ld % 4 == 0;
 }
 
-int y3_launch_conv_stem_mfma(const y3_op &op, const void *d_in, hipStream_t s, const char **kernel_name,
-                             bool dry_run) {
-  Y3_REQUIRE(y3_conv_stem_mfma_supported(op), "conv block %d: not a shape for the MFMA stem", op.block_idx);
-  *kernel_name = op.dtype == Y3_F16 ? "conv_stem_mfma_u8_f16" : "conv_stem_mfma_u8_bf16";
-  if (dry_run) return Y3_OK;
+static int launch_conv_stem_mfma(const y3_op *ops, const y3_step &, const void *d_in, const void *, hipStream_t s) {
+  const y3_op &op = ops[0];
   return y3_by_dtype16(op.dtype, [&](auto tag) {
     typedef decltype(tag) T;
     StemMfmaArgs<T> a;
@@ -325,8 +327,15 @@ int y3_launch_conv_stem_mfma(const y3_op &op, const void *d_in, hipStream_t s, c
   });
 }
 
-int y3_launch_conv_direct(const y3_op &op, const void *d_in, hipStream_t s, const char **kernel_name,
-                          bool dry_run) {
+int y3_choose_conv_stem_mfma(const y3_op &op, y3_step &st) {
+  Y3_REQUIRE(y3_conv_stem_mfma_supported(op), "conv block %d: not a shape for the MFMA stem", op.block_idx);
+  st.launch = launch_conv_stem_mfma;
+  st.name = op.dtype == Y3_F16 ? "conv_stem_mfma_u8_f16" : "conv_stem_mfma_u8_bf16";
+  return Y3_OK;
+}
+
+static int launch_conv_direct(const y3_op *ops, const y3_step &, const void *d_in, const void *, hipStream_t s) {
+  const y3_op &op = ops[0];
   DirectArgs a;
   a.in = d_in; a.wgt = op.d_weight; a.scale = op.d_scale; a.bias = op.d_bias; a.res = op.d_res;
   a.out = op.d_out;
@@ -335,13 +344,17 @@ int y3_launch_conv_direct(const y3_op &op, const void *d_in, hipStream_t s, cons
   a.ks = op.ksize; a.stride = op.stride; a.pad = op.pad; a.k_ld = op.k_ld;
   a.total = (long long)op.batch * op.out_h * op.out_w * op.out_c;
   a.flags = op.flags;
-  Y3_REQUIRE(op.k_ld >= op.ksize * op.ksize * op.in_c, "conv block %d: k_ld too small", op.block_idx);
-  *kernel_name = Y3_KNAME(op.dtype, "conv_direct_", "");
-  if (dry_run) return Y3_OK;
   const dim3 grid((unsigned)((a.total + 255) / 256)), block(256);
   return y3_by_dtype(op.dtype, [&](auto tag) {
     Y3_LAUNCH(conv_direct_kernel<decltype(tag)>, grid, block, 0, s, a);
     Y3_HIP_CHECK(hipGetLastError());
     return Y3_OK;
   });
+}
+
+int y3_choose_conv_direct(const y3_op &op, y3_step &st) {
+  Y3_REQUIRE(op.k_ld >= op.ksize * op.ksize * op.in_c, "conv block %d: k_ld too small", op.block_idx);
+  st.launch = launch_conv_direct;
+  st.name = Y3_KNAME(op.dtype, "conv_direct_", "");
+  return Y3_OK;
 }

@@ -153,7 +153,9 @@ void launch_one(Which w, const LayerArgs &a, hipStream_t s) {
   }
 }
 
-int launch_layer(Which w, const y3_op &op, const void *d_in, hipStream_t s, bool dry_run) {
+int launch_layer(const y3_op *ops, const y3_step &, const void *d_in, const void *, hipStream_t s) {
+  const y3_op &op = ops[0];
+  const Which w = op.kind == Y3_OP_MAXPOOL ? MAXPOOL : op.kind == Y3_OP_UPSAMPLE ? UPSAMPLE : op.kind == Y3_OP_ADD ? ADD : COPY;
   LayerArgs a;
   a.in = d_in;
   a.in2 = op.d_res;
@@ -162,14 +164,12 @@ int launch_layer(Which w, const y3_op &op, const void *d_in, hipStream_t s, bool
   a.Ho = op.out_h; a.Wo = op.out_w; a.out_ld = op.out_ld;
   a.k = op.ksize; a.stride = op.stride;
   a.zero_pad = (op.ksize > 1 && op.stride == 1) ? 1 : 0;
-  Y3_REQUIRE(op.in_c == op.out_c, "block %d: channel count changes in a pool/upsample/add/copy op", op.block_idx);
   const int es = y3_elem_size(op.dtype);
   const int vec = 16 / es;
   bool wide = op.in_c % vec == 0 && op.in_ld % vec == 0 && op.out_ld % vec == 0 &&
               ((uintptr_t)d_in % 16 == 0) && ((uintptr_t)op.d_out % 16 == 0);
   if (w == ADD) wide = wide && op.res_ld % vec == 0 && ((uintptr_t)op.d_res % 16 == 0);
   a.total = (long long)op.batch * op.out_h * op.out_w * (wide ? op.in_c / vec : op.in_c);
-  if (dry_run) return Y3_OK;
   return y3_by_dtype(op.dtype, [&](auto tag) {
     typedef decltype(tag) T;
     if (wide) launch_one<T, 16 / sizeof(T)>(w, a, s); else launch_one<T, 1>(w, a, s);
@@ -180,37 +180,34 @@ int launch_layer(Which w, const y3_op &op, const void *d_in, hipStream_t s, bool
 
 }  // namespace
 
-int y3_launch_maxpool(const y3_op &op, const void *d_in, hipStream_t s, const char **kernel_name,
-                      bool dry_run) {
-  Y3_REQUIRE(op.ksize >= 1 && op.stride >= 1, "maxpool block %d: bad size/stride", op.block_idx);
-  if (op.stride == 1) {
-    Y3_REQUIRE(op.out_h == op.in_h && op.out_w == op.in_w, "maxpool block %d: stride-1 keeps H,W", op.block_idx);
-  } else {
-    Y3_REQUIRE(op.out_h == (op.in_h - op.ksize) / op.stride + 1 && op.out_w == (op.in_w - op.ksize) / op.stride + 1,
-               "maxpool block %d: output size mismatch", op.block_idx);
+int y3_choose_layer(const y3_op &op, y3_step &st) {
+  Y3_REQUIRE(op.in_c == op.out_c, "block %d: channel count changes in a pool/upsample/add/copy op", op.block_idx);
+  st.launch = launch_layer;
+  switch (op.kind) {
+    case Y3_OP_MAXPOOL:
+      Y3_REQUIRE(op.ksize >= 1 && op.stride >= 1, "maxpool block %d: bad size/stride", op.block_idx);
+      if (op.stride == 1) {
+        Y3_REQUIRE(op.out_h == op.in_h && op.out_w == op.in_w, "maxpool block %d: stride-1 keeps H,W", op.block_idx);
+      } else {
+        Y3_REQUIRE(op.out_h == (op.in_h - op.ksize) / op.stride + 1 && op.out_w == (op.in_w - op.ksize) / op.stride + 1,
+                   "maxpool block %d: output size mismatch", op.block_idx);
+      }
+      st.name = Y3_KNAME(op.dtype, "maxpool_", "");
+      return Y3_OK;
+    case Y3_OP_UPSAMPLE:
+      Y3_REQUIRE(op.stride >= 1 && op.out_h == op.in_h * op.stride && op.out_w == op.in_w * op.stride,
+                 "upsample block %d: output size mismatch", op.block_idx);
+      st.name = Y3_KNAME(op.dtype, "upsample_", "");
+      return Y3_OK;
+    case Y3_OP_ADD:
+      Y3_REQUIRE(op.out_h == op.in_h && op.out_w == op.in_w, "add block %d: size mismatch", op.block_idx);
+      st.name = Y3_KNAME(op.dtype, "add_", "");
+      return Y3_OK;
+    default:
+      Y3_REQUIRE(op.out_h == op.in_h && op.out_w == op.in_w, "copy block %d: size mismatch", op.block_idx);
+      st.name = Y3_KNAME(op.dtype, "copy_", "");
+      return Y3_OK;
   }
-  *kernel_name = Y3_KNAME(op.dtype, "maxpool_", "");
-  return launch_layer(MAXPOOL, op, d_in, s, dry_run);
-}
-
-int y3_launch_upsample(const y3_op &op, const void *d_in, hipStream_t s, const char **kernel_name,
-                       bool dry_run) {
-  Y3_REQUIRE(op.stride >= 1 && op.out_h == op.in_h * op.stride && op.out_w == op.in_w * op.stride,
-             "upsample block %d: output size mismatch", op.block_idx);
-  *kernel_name = Y3_KNAME(op.dtype, "upsample_", "");
-  return launch_layer(UPSAMPLE, op, d_in, s, dry_run);
-}
-
-int y3_launch_add(const y3_op &op, const void *d_in, hipStream_t s, const char **kernel_name, bool dry_run) {
-  Y3_REQUIRE(op.out_h == op.in_h && op.out_w == op.in_w, "add block %d: size mismatch", op.block_idx);
-  *kernel_name = Y3_KNAME(op.dtype, "add_", "");
-  return launch_layer(ADD, op, d_in, s, dry_run);
-}
-
-int y3_launch_copy(const y3_op &op, const void *d_in, hipStream_t s, const char **kernel_name, bool dry_run) {
-  Y3_REQUIRE(op.out_h == op.in_h && op.out_w == op.in_w, "copy block %d: size mismatch", op.block_idx);
-  *kernel_name = Y3_KNAME(op.dtype, "copy_", "");
-  return launch_layer(COPY, op, d_in, s, dry_run);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -316,9 +313,11 @@ size_t spp_lds_bytes(const y3_op &op) { return (size_t)(op.in_h + 12) * (op.in_w
 
 }  // namespace
 
-// ops[0..2]: three consecutive max-pool ops of a plan.  True when they form the SPP pyramid this kernel computes:
-// sizes {5, 9, 13} in any order, stride 1, the same input view, 32-byte channel groups, and the image fits LDS.
-bool y3_maxpool_spp_supported(const y3_op &a, const y3_op &b, const y3_op &c) {
+static int launch_maxpool_spp(const y3_op *ops, const y3_step &, const void *, const void *, hipStream_t s);
+
+// three consecutive max-pool ops of a plan.  True when they form the SPP pyramid this kernel computes: sizes {5, 9, 13} in
+// any order, stride 1, the same input view, 32-byte channel groups, and the image fits LDS.
+bool y3_choose_maxpool_spp(const y3_op &a, const y3_op &b, const y3_op &c, y3_step &st) {
   const y3_op *o[3] = {&a, &b, &c};
   int seen = 0;
   for (const y3_op *q : o) {
@@ -332,14 +331,15 @@ bool y3_maxpool_spp_supported(const y3_op &a, const y3_op &b, const y3_op &c) {
       return false;
     if (q->out_h != q->in_h || q->out_w != q->in_w || q->out_c != q->in_c) return false;
   }
-  return seen == 7 && spp_lds_bytes(a) <= 64 * 1024;
+  if (seen != 7 || spp_lds_bytes(a) > 64 * 1024) return false;
+  st.launch = launch_maxpool_spp;
+  st.name = Y3_KNAME(a.dtype, "maxpool_spp_pyramid_", "");
+  return true;
 }
 
-int y3_launch_maxpool_spp(const y3_op &a, const y3_op &b, const y3_op &c, hipStream_t s, const char **kernel_name,
-                          bool dry_run) {
-  *kernel_name = Y3_KNAME(a.dtype, "maxpool_spp_pyramid_", "");
-  if (dry_run) return Y3_OK;
-  const y3_op *o[3] = {&a, &b, &c};
+static int launch_maxpool_spp(const y3_op *ops, const y3_step &, const void *, const void *, hipStream_t s) {
+  const y3_op &a = ops[0];
+  const y3_op *o[3] = {&ops[0], &ops[1], &ops[2]};
   SppArgs p;
   p.in = static_cast<const char *>(a.d_in);
   p.H = a.in_h; p.W = a.in_w; p.in_ld = a.in_ld;

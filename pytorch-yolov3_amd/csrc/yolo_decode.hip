@@ -119,12 +119,8 @@ __global__ __launch_bounds__(LANES == 1 ? 256 : 384) void yolo_decode_kernel(Yol
 }  // namespace
 
 
-int y3_launch_yolo(const y3_op &op, const void *d_in, hipStream_t s, const char **kernel_name,
-                   bool dry_run) {
-  Y3_REQUIRE(op.n_anchor >= 1 && op.n_anchor <= 8, "yolo block %d: 1..8 anchors per head", op.block_idx);
-  Y3_REQUIRE(op.n_attr > 5 && op.n_anchor * op.n_attr <= op.in_ld, "yolo block %d: bad attribute count", op.block_idx);
-  Y3_REQUIRE(dry_run || (op.d_bbox && op.d_prob && op.d_cls), "yolo block %d: missing output pointers", op.block_idx);
-  Y3_REQUIRE(op.in_ld % 4 == 0 && op.in_ld <= 1024, "yolo block %d: pixel stride must be a multiple of 4 floats (<= 1024)", op.block_idx);
+static int launch_yolo(const y3_op *ops, const y3_step &st, const void *d_in, const void *, hipStream_t s) {
+  const y3_op &op = ops[0];
   YoloArgs a;
   a.in = static_cast<const float *>(d_in);
   a.bbox = op.d_bbox;
@@ -136,14 +132,22 @@ int y3_launch_yolo(const y3_op &op, const void *d_in, hipStream_t s, const char 
   a.net_w = op.net_w; a.net_h = op.net_h;
   for (int i = 0; i < 8; ++i) { a.aw[i] = op.anchor_w[i]; a.ah[i] = op.anchor_h[i]; }
   a.total = (long long)op.batch * op.in_h * op.in_w * op.n_anchor;
-  *kernel_name = "yolo_decode_f32";
-  if (dry_run) return Y3_OK;
   const long long npix = (long long)op.batch * op.in_h * op.in_w;
   const size_t lds = (size_t)kPix * (op.in_ld + 1) * sizeof(float);
   const dim3 grid((unsigned)((npix + kPix - 1) / kPix));
-  // bf16 networks (throughput mode) take the four-lanes-per-box form; float32 networks keep the sequential class loop
-  if (y3_is16(op.dtype) && y3_opt().decode_lanes != 1) Y3_LAUNCH(yolo_decode_kernel<4>, grid, dim3(384), lds, s, a);
+  if (st.lanes == 4) Y3_LAUNCH(yolo_decode_kernel<4>, grid, dim3(384), lds, s, a);
   else Y3_LAUNCH(yolo_decode_kernel<1>, grid, dim3(256), lds, s, a);
   Y3_HIP_CHECK(hipGetLastError());
+  return Y3_OK;
+}
+
+int y3_choose_yolo(const y3_op &op, const y3_options &o, y3_step &st) {
+  Y3_REQUIRE(op.n_anchor >= 1 && op.n_anchor <= 8, "yolo block %d: 1..8 anchors per head", op.block_idx);
+  Y3_REQUIRE(op.n_attr > 5 && op.n_anchor * op.n_attr <= op.in_ld, "yolo block %d: bad attribute count", op.block_idx);
+  Y3_REQUIRE(op.in_ld % 4 == 0 && op.in_ld <= 1024, "yolo block %d: pixel stride must be a multiple of 4 floats (<= 1024)", op.block_idx);
+  st.launch = launch_yolo;
+  st.name = "yolo_decode_f32";
+  // bf16 networks (throughput mode) take the four-lanes-per-box form; float32 networks keep the sequential class loop
+  st.lanes = y3_is16(op.dtype) && o.decode_lanes != 1 ? 4 : 1;
   return Y3_OK;
 }

@@ -1353,6 +1353,33 @@ def test_plan_options_are_per_plan():
     assert float((o_plain["class_prob"] - o_dflt["class_prob"]).abs().median()) < 2e-3
 
 
+def test_plan_options_choose_fragment_weight_kernels():
+    """A plan's own options decide which convs read fragment-order weights, also where the process defaults would not pick
+    those kernels: a small-grid direct-weights kernel wherever it fits (Y3_AM_SMALL_DW_ALWAYS) at batch 16, and 96-pixel head
+    tiles (fuse_head 4) while y3_set_tuning has fuse_head 0.  Both compile, run other kernels than the defaults, and give the
+    same bits (every MFMA conv kernel sums in the same K order)."""
+    from yolov3 import _hip
+    lib = _hip.lib()
+    frames = synth_frames(5, 16, 608, 608)
+    dflt = _net("yolov3", dtype="bf16")
+    o_dflt = {k: v.clone() for k, v in dflt.forward_frames(frames).items()}
+    names_dflt = [r["kernel"] for r in dflt.plan_report()]
+    small = _net("yolov3", dtype="bf16", options={"auto_mask": _hip.AM_DEFAULT | _hip.AM_SMALL_DW_ALWAYS})
+    o_small = {k: v.clone() for k, v in small.forward_frames(frames).items()}
+    assert [r["kernel"] for r in small.plan_report()] != names_dflt
+    try:
+        _hip.check(lib.y3_set_tuning(b"fuse_head", 0))
+        head = _net("yolov3", dtype="bf16", options={"fuse_head": 4})
+        o_head = {k: v.clone() for k, v in head.forward_frames(frames).items()}
+    finally:
+        lib.y3_set_tuning(b"fuse_head", DEFAULT_KNOBS["fuse_head"])
+    names_head = [r["kernel"] for r in head.plan_report()]
+    assert names_head != names_dflt and any(k.startswith("conv_head_decode_dw_") and k.endswith("_96x256") for k in names_head)
+    for k in o_dflt:
+        assert torch.equal(o_small[k], o_dflt[k]), k
+        assert torch.equal(o_head[k], o_dflt[k]), k
+
+
 @pytest.mark.parametrize("dtype,dim,batch", [("bf16", 608, 2), ("float32", 416, 1), ("bf16", 320, 3), ("fp16", 416, 2)])
 def test_spp_pyramid_kernel_is_bit_identical_to_three_pools(dtype, dim, batch):
     """yolov3-spp's three stride-1 max-pools (5 / 9 / 13, zero pad right / bottom) as ONE LDS-staged cascade launch
