@@ -63,6 +63,9 @@ extern "C" {
 #define Y3_F_PLAN_INPUT 32u    /* d_in is supplied at y3_plan_run time                  */
 #define Y3_F_FUSE_NEXT 64u     /* plan hint: this conv's output is read by the NEXT op only, so the executor may run
                                   both as one kernel (stem + stride-2 conv) and never materialise d_out      */
+#define Y3_F_MISH 128u         /* mish, x * tanh(softplus(x)), after scale/bias instead of LeakyReLU (YOLOv4's backbone);
+                                  exclusive with Y3_F_LEAKY; Y3_F_RESIDUAL still adds after it.  Kernels that do not
+                                  implement it decline the op; y3_capabilities() reports Y3_CAP_MISH             */
 
 /*
  * One unit of work.  POD, 8-byte aligned, zero-initialise unused fields.
@@ -100,7 +103,9 @@ typedef struct y3_op {
   float *d_prob;                  /* (B, rows_total)                                       */
   int64_t *d_cls;                 /* (B, rows_total)                                       */
   int32_t block_idx;              /* Darknet block this op implements (diagnostics)        */
-  int32_t reserved;
+  /* Y3_OP_YOLO: Darknet's [yolo] scale_x_y s, box centre = (sigmoid(t) * s - (s - 1) / 2 + cell) / grid; 0 means 1 (the
+   * YOLOv3 decode, bit for bit).  Was `int32_t reserved` (always 0) before Y3_CAP_SCALE_X_Y.                          */
+  float scale_x_y;
   /* ABI 6: the conv's weights in MFMA-fragment order (y3_conv_make_fragment_weights), y3_conv_fragment_weight_bytes() bytes,
    * for the layers the direct-weights strip kernel takes; shared by every plan of the network.  NULL: a plan that needs the
    * copy makes a private one (see the conventions above).                                                              */
@@ -176,6 +181,12 @@ typedef struct y3_options {
 
 /* library / device ------------------------------------------------------------------- */
 int y3_abi_version(void);
+/* what this build computes beyond ABI 6 as first released (the version number and y3_op's size stay put: every addition
+ * keeps zero-initialised callers working).  Callers check it before they rely on a feature, so that a stale library is
+ * refused instead of running, say, mish as linear.                                                                   */
+#define Y3_CAP_MISH 1u         /* Y3_F_MISH on conv ops                      */
+#define Y3_CAP_SCALE_X_Y 2u    /* y3_op.scale_x_y on YOLO ops                */
+uint32_t y3_capabilities(void);
 const char *y3_last_error(void);
 /* number of visible HIP devices whose arch is gfx950 (0 on a CPU-only machine) */
 int y3_device_count(void);

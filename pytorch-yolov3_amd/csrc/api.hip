@@ -79,6 +79,8 @@ int conv_path(const y3_op &op) {
 // The conv chooser: what a conv op runs under options `o`.  The rules are asked in this order and are not independent (the
 // SMALL_DW_WIDE 1x1 rule, for one, is asked only after the weights-resident kernel's).
 int choose_conv(const y3_op &op, const y3_options &o, y3_step &st) {
+  Y3_REQUIRE(!((op.flags & Y3_F_MISH) && (op.flags & Y3_F_LEAKY)), "conv block %d: Y3_F_MISH and Y3_F_LEAKY are exclusive",
+             op.block_idx);
   Y3_REQUIRE(op.out_h == (op.in_h + 2 * op.pad - op.ksize) / op.stride + 1 &&
                  op.out_w == (op.in_w + 2 * op.pad - op.ksize) / op.stride + 1,
              "conv block %d: output size mismatch", op.block_idx);
@@ -155,6 +157,16 @@ int choose_op(const y3_op &op, const y3_options &o, y3_step &st) {
   return Y3_ERR_INVALID;
 }
 
+// Every single-op conv kernel computes the op's activation code (common.h: y3_act); the fused conv groups hard-wire
+// LeakyReLU and their choosers decline mish ops.  Checked once more per step, so that a chooser that forgot would be an
+// error here and never a conv run as linear or leaky.
+int check_activation(const y3_op *ops, int n, const y3_step &st) {
+  for (int k = 0; k < n; ++k)
+    Y3_REQUIRE(!(ops[k].kind == Y3_OP_CONV && (ops[k].flags & Y3_F_MISH)) || st.fuse == y3_fuse::none,
+               "conv block %d: mish op given to %s, which does not compute mish", ops[k].block_idx, st.name);
+  return Y3_OK;
+}
+
 // the pointers an op launched on its own reads and writes; `in` is the plan input where the op reads that
 int check_pointers(const y3_op &op, const void *in) {
   Y3_REQUIRE(in != nullptr, "op for block %d has no input pointer", op.block_idx);
@@ -223,6 +235,8 @@ int make_private_fragment_weights(y3_plan *p) {
 extern "C" {
 
 int y3_abi_version(void) { return Y3_ABI_VERSION; }
+
+uint32_t y3_capabilities(void) { return Y3_CAP_MISH | Y3_CAP_SCALE_X_Y; }
 
 const char *y3_last_error(void) { return g_err; }
 
@@ -300,11 +314,12 @@ int y3_plan_create_ex(const y3_op *ops, int n_ops, const void *d_zero, const y3_
     } else {
       rc = choose_op(q[i], o, st);
     }
+    const int absorbed = st.fuse == y3_fuse::none ? 0 : (st.fuse == y3_fuse::spp ? 2 : 1);
+    if (rc == Y3_OK) rc = check_activation(q + i, absorbed + 1, st);
     if (rc != Y3_OK) {
       y3_plan_destroy(p);
       return rc;
     }
-    const int absorbed = st.fuse == y3_fuse::none ? 0 : (st.fuse == y3_fuse::spp ? 2 : 1);
     for (int k = 1; k <= absorbed; ++k) p->steps[i + k].fuse = y3_fuse::into_prev;
     // a kernel that reads its weights in MFMA-fragment order: the caller's shared copy (y3_op.d_weight_frag, ABI 6), or --
     // callers that pass none -- a private copy that the plan makes below and frees when it is destroyed

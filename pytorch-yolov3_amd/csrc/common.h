@@ -221,7 +221,7 @@ __device__ __forceinline__ u32x2 y3_pack4(float a, float b, float c, float d) {
   return __builtin_bit_cast(u32x2, o);
 }
 
-// Conv epilogue arithmetic for eight consecutive output channels: acc * scale + bias, then LeakyReLU(0.1).  Written
+// Conv epilogue arithmetic for eight consecutive output channels: acc * scale + bias, then the activation.  Written
 // on 2-wide vectors so that hipcc emits v_pk_fma_f32 / v_pk_mul_f32, and with v_max_f32 spelled out: max(v, 0.1 v) is
 // v > 0 ? v : 0.1 v bit for bit (both operands carry v's sign), one instruction instead of compare + select, and fmaxf
 // would add a canonicalising v_max per value.  The epilogues are VALU-bound (MI355X: 4 cycles per instruction and
@@ -231,11 +231,37 @@ __device__ __forceinline__ float y3_vmax(float a, float b) {
   asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
   return r;
 }
-// `leaky` is a run-time flag of the layer: a slope of 1 makes max(v, slope * v) the identity without a branch (phi
-// copies of all eight values otherwise)
-__device__ __forceinline__ void y3_bn_leaky8(float (&v)[8], const f32x4 &lo, const f32x4 &hi, const f32x4 &sc_lo,
-                                             const f32x4 &sc_hi, const f32x4 &bi_lo, const f32x4 &bi_hi, bool leaky) {
-  const float slope = leaky ? Y3_LEAKY_SLOPE : 1.0f;
+// Activation of a conv op, from its flags: a run-time value of the layer (uniform across the grid, so the branches on it
+// below are scalar branches, and the leaky / linear arithmetic is the same instruction sequence as before mish existed)
+enum : int { Y3_ACT_LINEAR = 0, Y3_ACT_LEAKY = 1, Y3_ACT_MISH = 2 };
+__host__ __device__ __forceinline__ int y3_act(uint32_t flags) {
+  return (flags & Y3_F_MISH) ? Y3_ACT_MISH : ((flags & Y3_F_LEAKY) ? Y3_ACT_LEAKY : Y3_ACT_LINEAR);
+}
+// mish(x) = x tanh(softplus(x)) = x t / (t + 2) with n = e^x, t = n (n + 2) = (1 + n)^2 - 1: one v_exp_f32, one v_rcp_f32,
+// a few FMAs.  Above 20 the ratio is 1 in float32 (mish(x) == x there), and from about 44 on t overflows and the ratio
+// would be inf / inf: x is returned instead.
+__device__ __forceinline__ float y3_mish(float x) {
+  const float n = __expf(x);
+  const float t = n * (n + 2.0f);
+  const float y = x * t * __builtin_amdgcn_rcpf(t + 2.0f);
+  return x > 20.0f ? x : y;
+}
+// one value: the scalar epilogues (float32 kernels, stem kernels)
+__device__ __forceinline__ float y3_act1(float t, int act) {
+  if (act == Y3_ACT_MISH) return y3_mish(t);
+  return act == Y3_ACT_LEAKY ? (t > 0.f ? t : Y3_LEAKY_SLOPE * t) : t;
+}
+// eight values, activation `act` (Y3_ACT_*).  Leaky / linear: a slope of 1 makes max(v, slope * v) the identity without a
+// branch (phi copies of all eight values otherwise).  Mish runs the linear form and then, behind one scalar branch per eight
+// values, replaces each value in place: the leaky / linear path keeps its instruction sequence and nothing of the mish
+// arithmetic is live across it.
+__device__ __forceinline__ void y3_mish8(float (&v)[8]) {
+#pragma unroll
+  for (int i = 0; i < 8; ++i) v[i] = y3_mish(v[i]);
+}
+__device__ __forceinline__ void y3_bn_act8(float (&v)[8], const f32x4 &lo, const f32x4 &hi, const f32x4 &sc_lo,
+                                           const f32x4 &sc_hi, const f32x4 &bi_lo, const f32x4 &bi_hi, int act) {
+  const float slope = act == Y3_ACT_LEAKY ? Y3_LEAKY_SLOPE : 1.0f;
   f32x2 t[4];
   t[0] = f32x2{lo[0], lo[1]} * f32x2{sc_lo[0], sc_lo[1]} + f32x2{bi_lo[0], bi_lo[1]};
   t[1] = f32x2{lo[2], lo[3]} * f32x2{sc_lo[2], sc_lo[3]} + f32x2{bi_lo[2], bi_lo[3]};
@@ -247,6 +273,7 @@ __device__ __forceinline__ void y3_bn_leaky8(float (&v)[8], const f32x4 &lo, con
     v[2 * i] = y3_vmax(t[i][0], s[0]);
     v[2 * i + 1] = y3_vmax(t[i][1], s[1]);
   }
+  if (act == Y3_ACT_MISH) y3_mish8(v);
 }
 
 // Diagnostic build only (-DY3_STAMPS, `make stamps`): per-workgroup phase timing with s_memtime.

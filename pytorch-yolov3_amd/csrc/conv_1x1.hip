@@ -126,8 +126,7 @@ __global__ __launch_bounds__(512, 2) void conv1x1_wres_kernel(WresArgs p) {
   // ---------------- MFMA waves ----------------
   const int wm = wave >> 1, wn = wave & 1;
   const int fr = lane & 15, fq = lane >> 4;
-  const bool leaky = p.flags & Y3_F_LEAKY;
-  const float slope = leaky ? Y3_LEAKY_SLOPE : 1.0f;
+  const int act = y3_act(p.flags);
   f32x4 sc[NI], bi[NI];
 #pragma unroll
   for (int ni = 0; ni < NI; ++ni) {
@@ -170,24 +169,14 @@ __global__ __launch_bounds__(512, 2) void conv1x1_wres_kernel(WresArgs p) {
           for (int ni = 0; ni < NI; ++ni)
             acc[mi][ni] = y3_mfma16<T>(wf[g][ni], xf[g][mi], acc[mi][ni]);
     }
-    // ---- epilogue: scale / bias / LeakyReLU in registers (the arithmetic of y3_bn_leaky8), bf16, park, write out
+    // ---- epilogue: scale / bias / activation in registers (y3_bn_act8), bf16, park, write out
 #pragma unroll
     for (int mi = 0; mi < MI; ++mi) {
       const int pl = wm * 64 + mi * 16 + fr;
 #pragma unroll
       for (int k = 0; k < NI / 2; ++k) {
         float o[8];
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-          const int ni = 2 * k + h;
-          const f32x2 t0 = f32x2{acc[mi][ni][0], acc[mi][ni][1]} * f32x2{sc[ni][0], sc[ni][1]} + f32x2{bi[ni][0], bi[ni][1]};
-          const f32x2 t1 = f32x2{acc[mi][ni][2], acc[mi][ni][3]} * f32x2{sc[ni][2], sc[ni][3]} + f32x2{bi[ni][2], bi[ni][3]};
-          const f32x2 s0 = t0 * slope, s1 = t1 * slope;
-          o[4 * h + 0] = y3_vmax(t0[0], s0[0]);
-          o[4 * h + 1] = y3_vmax(t0[1], s0[1]);
-          o[4 * h + 2] = y3_vmax(t1[0], s1[0]);
-          o[4 * h + 3] = y3_vmax(t1[1], s1[1]);
-        }
+        y3_bn_act8(o, acc[mi][2 * k], acc[mi][2 * k + 1], sc[2 * k], sc[2 * k + 1], bi[2 * k], bi[2 * k + 1], act);
         const int oc = wn * (TN / 8) + k * 4 + fq;                       // 16-byte chunk of the pixel's row
         *reinterpret_cast<u32x4 *>(sP + pl * (BN * 2) + ((oc ^ (pl & (OCT - 1))) << 4)) = y3_pack8<T>(o);
       }
@@ -237,7 +226,7 @@ struct DwArgs {
   float *y_bbox, *y_prob;
   long long *y_cls;
   int y_anchors, y_attr, y_row_offset, y_rows_total;
-  float y_net_w, y_net_h, y_aw[8], y_ah[8];
+  float y_net_w, y_net_h, y_sxy, y_aw[8], y_ah[8];
 };
 
 template <int V>
@@ -387,12 +376,12 @@ __global__ __launch_bounds__(512, 2) void conv1x1_dw_kernel(DwArgs p) {
   }
   const f32x4 sc_lo = *reinterpret_cast<const f32x4 *>(p.scale + co), sc_hi = *reinterpret_cast<const f32x4 *>(p.scale + co + 4);
   const f32x4 bi_lo = *reinterpret_cast<const f32x4 *>(p.bias + co), bi_hi = *reinterpret_cast<const f32x4 *>(p.bias + co + 4);
-  const bool leaky = p.flags & Y3_F_LEAKY;
+  const int act = y3_act(p.flags);
 #pragma unroll
   for (int mi = 0; mi < MI; ++mi) {
     const int m = m0 + mi * 16 + fr;
     float v[8];
-    y3_bn_leaky8(v, acc[mi][0], acc[mi][1], sc_lo, sc_hi, bi_lo, bi_hi, leaky);
+    y3_bn_act8(v, acc[mi][0], acc[mi][1], sc_lo, sc_hi, bi_lo, bi_hi, act);
     if (m < p.M) *reinterpret_cast<u32x4 *>(p.out + ((long long)m * p.out_ld + co) * 2) = y3_pack8<T>(v);
   }
 }
@@ -422,7 +411,7 @@ int dw_head_bm(const y3_op &op, const y3_options &o) {
   const int mode = o.fuse_head;
   if (mode == 0 || mode == 2) return 0;
   if (op.kind != Y3_OP_CONV || !y3_is16(op.dtype) || op.ksize != 1 || op.stride != 1 || op.pad != 0 || !(op.flags & Y3_F_OUT_F32)) return 0;
-  if (op.flags & (Y3_F_LEAKY | Y3_F_RESIDUAL | Y3_F_IN_NCHW_F32 | Y3_F_IN_NHWC_U8BGR | Y3_F_PLAN_INPUT)) return 0;
+  if (op.flags & (Y3_F_LEAKY | Y3_F_MISH | Y3_F_RESIDUAL | Y3_F_IN_NCHW_F32 | Y3_F_IN_NHWC_U8BGR | Y3_F_PLAN_INPUT)) return 0;
   if (op.out_c > 256 || op.cout_pad < 256 || op.cout_pad % 32 != 0 || op.in_ld % 8 != 0 || op.k_ld % 32 != 0 || op.k_ld < op.in_c) return 0;
   const int nkt = op.in_c / 64;
   if (op.in_c % 128 != 0 || !(nkt == 4 || nkt == 8 || nkt == 16)) return 0;
@@ -500,6 +489,7 @@ int launch_head_decode_dw(const y3_op *ops, const y3_step &st, const void *, con
   a.y_anchors = op1.n_anchor; a.y_attr = op1.n_attr;
   a.y_row_offset = op1.row_offset; a.y_rows_total = op1.rows_total;
   a.y_net_w = op1.net_w; a.y_net_h = op1.net_h;
+  a.y_sxy = y3_op_scale_xy(op1);
   for (int i = 0; i < 8; ++i) { a.y_aw[i] = op1.anchor_w[i]; a.y_ah[i] = op1.anchor_h[i]; }
   const int nkt = op0.in_c / 64;
   return y3_by_dtype16(op0.dtype, [&](auto tag) {

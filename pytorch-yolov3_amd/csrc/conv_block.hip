@@ -231,7 +231,7 @@ __global__ __launch_bounds__(kNT) void conv_block_fused_kernel(BlockArgs p) {
 #pragma unroll
       for (int mi = 0; mi < kMA; ++mi) {
         float v[8];
-        y3_bn_leaky8(v, acc[mi][2 * k], acc[mi][2 * k + 1], sl, sh, bl, bh, p.leaky1 != 0);
+        y3_bn_act8(v, acc[mi][2 * k], acc[mi][2 * k + 1], sl, sh, bl, bh, p.leaky1 ? Y3_ACT_LEAKY : Y3_ACT_LINEAR);
         u32x4 ov = y3_pack8<T>(v);
         if (!((inside >> mi) & 1u)) ov = u32x4{0u, 0u, 0u, 0u};   // the 3x3's zero padding
         *reinterpret_cast<u32x4 *>(smem + (midw[mi] ^ (k * 64))) = ov;
@@ -385,7 +385,7 @@ __global__ __launch_bounds__(kNT) void conv_block_fused_kernel(BlockArgs p) {
 #pragma unroll
           for (int mi = 0; mi < kMB; ++mi) {
             float v[8];
-            y3_bn_leaky8(v, acc[mi][2 * k], acc[mi][2 * k + 1], sl, sh, bl, bh, p.leaky3 != 0);
+            y3_bn_act8(v, acc[mi][2 * k], acc[mi][2 * k + 1], sl, sh, bl, bh, p.leaky3 ? Y3_ACT_LEAKY : Y3_ACT_LINEAR);
             if constexpr (RES) y3_add8<T>(v, rv[k][mi]);
             if ((stored >> mi) & 1u) *reinterpret_cast<u32x4 *>(p.out + lane32((uint32_t)(pxo[mi] * p.out_ld + ch0) * 2u)) = y3_pack8<T>(v);
           }
@@ -478,6 +478,8 @@ bool y3_choose_conv_block_fused(const y3_op &op0, const y3_op &op1, const y3_opt
   if (op1.ksize != 3 || op1.stride != 1 || op1.pad != 1 || op1.in_c != 128 || op1.out_c % 128 != 0) return false;
   const uint32_t bad = Y3_F_OUT_F32 | Y3_F_IN_NCHW_F32 | Y3_F_IN_NHWC_U8BGR | Y3_F_PLAN_INPUT;
   if ((op0.flags & (bad | Y3_F_RESIDUAL)) || (op1.flags & bad)) return false;
+  // the kernel knows LeakyReLU and linear only (its leaky1 / leaky3 map every other op to linear): no mish
+  if ((op0.flags | op1.flags) & Y3_F_MISH) return false;
   if (op1.d_in != op0.d_out || op1.in_ld != op0.out_ld) return false;
   // z must not overlap x: a workgroup writes its rectangle of z while its neighbours still read those pixels of x as their
   // one-pixel border (phase A), and nothing orders workgroups of different rounds / streams.  The arena planner frees x after

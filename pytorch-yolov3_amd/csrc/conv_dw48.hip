@@ -279,7 +279,7 @@ __global__ __launch_bounds__(512) void conv_dw48_kernel(Dw48Args p) {
   const int co = n0 + fq * 8;
   const f32x4 sc_lo = *reinterpret_cast<const f32x4 *>(p.scale + co), sc_hi = *reinterpret_cast<const f32x4 *>(p.scale + co + 4);
   const f32x4 bi_lo = *reinterpret_cast<const f32x4 *>(p.bias + co), bi_hi = *reinterpret_cast<const f32x4 *>(p.bias + co + 4);
-  const bool leaky = p.flags & Y3_F_LEAKY;
+  const int act = y3_act(p.flags);
   const bool has_res = p.flags & Y3_F_RESIDUAL;
   u32x4 resv[MI];
   if (has_res) {
@@ -293,7 +293,7 @@ __global__ __launch_bounds__(512) void conv_dw48_kernel(Dw48Args p) {
   for (int mi = 0; mi < MI; ++mi) {
     const int m = m0 + mi * 16 + fr;
     float v[8];
-    y3_bn_leaky8(v, acc[mi][0], acc[mi][1], sc_lo, sc_hi, bi_lo, bi_hi, leaky);
+    y3_bn_act8(v, acc[mi][0], acc[mi][1], sc_lo, sc_hi, bi_lo, bi_hi, act);
     if (has_res) y3_add8<T>(v, resv[mi]);
     if (m < p.M) *reinterpret_cast<u32x4 *>(p.out + ((long long)m * p.out_ld + co) * 2) = y3_pack8<T>(v);
   }

@@ -898,7 +898,7 @@ __global__ __launch_bounds__(kThreads) void conv_resblock_fused_kernel(ResArgs<T
         const int pp = (oyl + 1) * kRP + fr + 1;                          // this output pixel inside the patch
         const u32x4 xr = *reinterpret_cast<const u32x4 *>(xt + pp * 128 + (((k * 4 + fq) ^ (pp & 7)) << 4));
         float v[8];
-        y3_bn_leaky8(v, acc[mi][2 * k], acc[mi][2 * k + 1], s3[0], s3[1], b3[0], b3[1], true);   // packed arithmetic
+        y3_bn_act8(v, acc[mi][2 * k], acc[mi][2 * k + 1], s3[0], s3[1], b3[0], b3[1], Y3_ACT_LEAKY);   // packed arithmetic
         y3_add8<T>(v, xr);
         const int px = oyl * kRT + fr;
         *reinterpret_cast<u32x4 *>(yt + px * 128 + (((k * 4 + fq) ^ (px & 7)) << 4)) = y3_pack8<T>(v);
@@ -928,6 +928,7 @@ bool y3_choose_conv_fused_stem_s2(const y3_op &op0, const y3_op &op1, const y3_o
   if (!o.fuse_stem) return false;
   if (!y3_conv_stem_mfma_supported(op0) || op0.out_c != 32 || (op0.flags & Y3_F_RESIDUAL)) return false;
   if (!(op0.flags & Y3_F_LEAKY) || !(op1.flags & Y3_F_LEAKY)) return false;   // the kernel hard-wires LeakyReLU(0.1)
+  if ((op0.flags | op1.flags) & Y3_F_MISH) return false;
   if (op1.kind != Y3_OP_CONV || op1.dtype != op0.dtype || op1.ksize != 3 || op1.stride != 2 || op1.pad != 1) return false;
   if (op1.in_c != 32 || op1.out_c != 64 || op1.out_ld % 8 != 0 || op1.out_ld < 64) return false;
   if (op1.flags & (Y3_F_RESIDUAL | Y3_F_OUT_F32 | Y3_F_IN_NCHW_F32 | Y3_F_IN_NHWC_U8BGR | Y3_F_PLAN_INPUT)) return false;
@@ -988,7 +989,8 @@ bool y3_choose_conv_fused_resblock(const y3_op &op0, const y3_op &op1, const y3_
   if (op1.ksize != 3 || op1.stride != 1 || op1.pad != 1 || op1.in_c != 32 || op1.out_c != 64) return false;
   const uint32_t bad = Y3_F_OUT_F32 | Y3_F_IN_NCHW_F32 | Y3_F_IN_NHWC_U8BGR | Y3_F_PLAN_INPUT;
   if ((op0.flags & (bad | Y3_F_RESIDUAL)) || (op1.flags & bad)) return false;
-  if (!(op0.flags & Y3_F_LEAKY) || !(op1.flags & Y3_F_LEAKY) || !(op1.flags & Y3_F_RESIDUAL)) return false;
+  if (!(op0.flags & Y3_F_LEAKY) || !(op1.flags & Y3_F_LEAKY) || !(op1.flags & Y3_F_RESIDUAL)) return false;   // LeakyReLU only
+  if ((op0.flags | op1.flags) & Y3_F_MISH) return false;
   if (op1.d_in != op0.d_out || op1.d_res != op0.d_in || op1.res_ld != op0.in_ld) return false;
   if (op0.in_h != op1.in_h || op0.in_w != op1.in_w || op0.batch != op1.batch) return false;
   if (op0.out_h != op0.in_h || op0.out_w != op0.in_w || op1.out_h != op1.in_h || op1.out_w != op1.in_w) return false;

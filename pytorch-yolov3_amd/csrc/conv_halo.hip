@@ -516,7 +516,7 @@ __global__ __launch_bounds__(768, 3) void conv_halo_ws_kernel(HaloArgs p) {
   constexpr int RPP = NT / 16;                       // pixel rows written per pass of the workgroup (48)
   constexpr int WR = (BM + RPP - 1) / RPP;           // 6 passes at 256 pixels (the last one: rows 240 .. 255, the first 256 lanes), 4 at 192
   float *sC = reinterpret_cast<float *>(smem);
-  const bool leaky = p.flags & Y3_F_LEAKY;
+  const int act = y3_act(p.flags);
   const bool has_res = p.flags & Y3_F_RESIDUAL;
   const int oc_mine = tid & 15;
   const int co = n0 + oc_mine * 8;
@@ -564,7 +564,7 @@ __global__ __launch_bounds__(768, 3) void conv_halo_ws_kernel(HaloArgs p) {
     const f32x4 lo = *reinterpret_cast<const f32x4 *>(sC + pl * BN + (((2 * oc_mine) ^ (pl & SWZ)) << 2));
     const f32x4 hi = *reinterpret_cast<const f32x4 *>(sC + pl * BN + (((2 * oc_mine + 1) ^ (pl & SWZ)) << 2));
     float v[8];
-    y3_bn_leaky8(v, lo, hi, sc_lo, sc_hi, bi_lo, bi_hi, leaky);
+    y3_bn_act8(v, lo, hi, sc_lo, sc_hi, bi_lo, bi_hi, act);
     if (has_res) {
       if constexpr (sizeof(T) == 2) {
         y3_add8<T>(v, resv[j]);
@@ -720,7 +720,7 @@ __global__ __launch_bounds__(768, 3) void conv_patch_wsp_kernel(HaloArgs p, int 
   const int b_lane_row = wn * 64 + fr;
   const int b_off0 = b_lane_row * 128 + (((0 + fq) ^ (b_lane_row & 7)) << 4);
   const int b_off1 = b_lane_row * 128 + (((4 + fq) ^ (b_lane_row & 7)) << 4);
-  const bool leaky = p.flags & Y3_F_LEAKY;
+  const int act = y3_act(p.flags);
   const bool has_res = p.flags & Y3_F_RESIDUAL;
   int ring = 0, gchunk = 0;
   for (int tile = tile0; tile < n_tiles_total; tile += grid) {
@@ -858,7 +858,7 @@ __global__ __launch_bounds__(768, 3) void conv_patch_wsp_kernel(HaloArgs p, int 
         const f32x4 lo = *reinterpret_cast<const f32x4 *>(sC + pl * 64 + (((2 * oc) ^ pl) << 2));
         const f32x4 hi = *reinterpret_cast<const f32x4 *>(sC + pl * 64 + (((2 * oc + 1) ^ pl) << 2));
         float v[8];
-        y3_bn_leaky8(v, lo, hi, sc_lo, sc_hi, bi_lo, bi_hi, leaky);
+        y3_bn_act8(v, lo, hi, sc_lo, sc_hi, bi_lo, bi_hi, act);
         if (oy < p.H && ox < p.W) {
           if (has_res) {
             if constexpr (sizeof(T) == 2) {
@@ -1126,7 +1126,7 @@ __global__ __launch_bounds__(512, 2) void conv_halo_dw_kernel(HaloArgs p) {
   dw_wait_vm<0>(wf[1]);
   dw_wait_vm<0>(wf[2]);
 
-  const bool leaky = p.flags & Y3_F_LEAKY;
+  const int act = y3_act(p.flags);
   const bool has_res = p.flags & Y3_F_RESIDUAL;
 #if Y3_DW_EPI != 0
   // ---- epilogue in registers (Y3_DW_EPI 1 / 2).  The weight rows were laid out with y3_pair_perm: after both fragments of a
@@ -1162,7 +1162,7 @@ __global__ __launch_bounds__(512, 2) void conv_halo_dw_kernel(HaloArgs p) {
       for (int mi = 0; mi < MI; ++mi) {
         const int m = mrow + mi * 16;
         float v[8];
-        y3_bn_leaky8(v, acc[mi][2 * pr], acc[mi][2 * pr + 1], sc_lo, sc_hi, bi_lo, bi_hi, leaky);
+        y3_bn_act8(v, acc[mi][2 * pr], acc[mi][2 * pr + 1], sc_lo, sc_hi, bi_lo, bi_hi, act);
         if (has_res) y3_add8<T>(v, resv[pr][mi]);
         const u32x4 o = y3_pack8<T>(v);
 #if Y3_DW_EPI == 1
@@ -1239,7 +1239,7 @@ __global__ __launch_bounds__(512, 2) void conv_halo_dw_kernel(HaloArgs p) {
       const f32x4 lo = *reinterpret_cast<const f32x4 *>(sC + pl * 128 + (((2 * oc_mine) ^ (pl & SWZ)) << 2));
       const f32x4 hi = *reinterpret_cast<const f32x4 *>(sC + pl * 128 + (((2 * oc_mine + 1) ^ (pl & SWZ)) << 2));
       float v[8];
-      y3_bn_leaky8(v, lo, hi, sc_lo[h], sc_hi[h], bi_lo[h], bi_hi[h], leaky);
+      y3_bn_act8(v, lo, hi, sc_lo[h], sc_hi[h], bi_lo[h], bi_hi[h], act);
       if (has_res) y3_add8<T>(v, resv[h][j]);
       T *op = reinterpret_cast<T *>(p.out) + (long long)m * p.out_ld + co;
       *reinterpret_cast<u32x4 *>(op) = y3_pack8<T>(v);

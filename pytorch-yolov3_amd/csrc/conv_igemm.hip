@@ -48,7 +48,7 @@ struct IgemmArgs {
   float *y_bbox, *y_prob;
   long long *y_cls;
   int y_anchors, y_attr, y_row_offset, y_rows_total;
-  float y_net_w, y_net_h, y_aw[8], y_ah[8];
+  float y_net_w, y_net_h, y_sxy, y_aw[8], y_ah[8];
 };
 
 template <typename T>
@@ -228,7 +228,7 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(IgemmArgs p) {
   }
 
   // ---- epilogue: lane holds channels co..co+3 (registers) of pixel m (lane&15) -------------
-  const bool leaky = p.flags & Y3_F_LEAKY;
+  const int act = y3_act(p.flags);
   const bool has_res = p.flags & Y3_F_RESIDUAL;
   const bool out_f32 = (p.flags & Y3_F_OUT_F32) || sizeof(T) == 4;
 #pragma unroll
@@ -246,7 +246,7 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(IgemmArgs p) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         float t = acc[mi][ni][r] * sc[r] + bi[r];
-        if (leaky) t = t > 0.f ? t : Y3_LEAKY_SLOPE * t;
+        t = y3_act1(t, act);
         v[r] = t;
       }
       if (has_res) {
@@ -503,7 +503,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N) void conv_igemm2_kernel(Ige
   constexpr int CPR = BN / 4;  // 16-byte chunks per tile row
   constexpr int SWZ = (CPR < 16 ? CPR : 16) - 1;
   float *sC = reinterpret_cast<float *>(smem);
-  const bool leaky = p.flags & Y3_F_LEAKY;
+  const int act = y3_act(p.flags);
   const bool out_f32 = (p.flags & Y3_F_OUT_F32) || sizeof(T) == 4;
   const int nvalid = p.Cout - co < 8 ? p.Cout - co : 8;   // <= 0: this thread's channels are padding
 #pragma unroll
@@ -548,7 +548,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N) void conv_igemm2_kernel(Ige
       const f32x4 lo = *reinterpret_cast<const f32x4 *>(sC + pl * BN + (((2 * oc_mine) ^ (pl & SWZ)) << 2));
       const f32x4 hi = *reinterpret_cast<const f32x4 *>(sC + pl * BN + (((2 * oc_mine + 1) ^ (pl & SWZ)) << 2));
       float v[8];
-      y3_bn_leaky8(v, lo, hi, sc_lo, sc_hi, bi_lo, bi_hi, leaky);
+      y3_bn_act8(v, lo, hi, sc_lo, sc_hi, bi_lo, bi_hi, act);
       if (has_res) {
         if (res_fast) {
           if constexpr (sizeof(T) == 2) y3_add8<T>(v, resv[h * WR + j]);
@@ -822,7 +822,7 @@ void conv_igemm3_kernel(IgemmArgs p) {
   constexpr int CPR = BN / 4;
   constexpr int SWZ = (CPR < 16 ? CPR : 16) - 1;
   float *sC = reinterpret_cast<float *>(smem);
-  const bool leaky = p.flags & Y3_F_LEAKY;
+  const int act = y3_act(p.flags);
   const bool out_f32 = (p.flags & Y3_F_OUT_F32) || sizeof(T) == 4;
   const int nvalid = p.Cout - co < 8 ? p.Cout - co : 8;
   if (!loader) {
@@ -846,7 +846,7 @@ void conv_igemm3_kernel(IgemmArgs p) {
     const f32x4 lo = *reinterpret_cast<const f32x4 *>(sC + pl * BN + (((2 * oc_mine) ^ (pl & SWZ)) << 2));
     const f32x4 hi = *reinterpret_cast<const f32x4 *>(sC + pl * BN + (((2 * oc_mine + 1) ^ (pl & SWZ)) << 2));
     float v[8];
-    y3_bn_leaky8(v, lo, hi, sc_lo, sc_hi, bi_lo, bi_hi, leaky);
+    y3_bn_act8(v, lo, hi, sc_lo, sc_hi, bi_lo, bi_hi, act);
     if (has_res) {
       if (res_fast) {
         if constexpr (sizeof(T) == 2) y3_add8<T>(v, resv[j]);
@@ -1087,7 +1087,7 @@ bool y3_choose_conv_head_decode(const y3_op &op0, const y3_op &op1, const y3_opt
   if (!o.fuse_head) return false;
   if (op0.kind != Y3_OP_CONV || op1.kind != Y3_OP_YOLO || !y3_is16(op0.dtype)) return false;
   if (op0.ksize != 1 || op0.stride != 1 || !(op0.flags & Y3_F_OUT_F32)) return false;
-  if (op0.flags & (Y3_F_LEAKY | Y3_F_RESIDUAL | Y3_F_IN_NCHW_F32 | Y3_F_IN_NHWC_U8BGR | Y3_F_PLAN_INPUT)) return false;
+  if (op0.flags & (Y3_F_LEAKY | Y3_F_MISH | Y3_F_RESIDUAL | Y3_F_IN_NCHW_F32 | Y3_F_IN_NHWC_U8BGR | Y3_F_PLAN_INPUT)) return false;
   if (!y3_conv_igemm_supported(op0) || op0.in_c % 64 != 0 || op0.out_c > 256 || op0.cout_pad < 256) return false;
   if (op1.d_in != op0.d_out || op1.in_ld != op0.out_ld || op1.in_h != op0.out_h || op1.in_w != op0.out_w) return false;
   if (op1.batch != op0.batch || op1.n_anchor < 1 || op1.n_anchor > 8 || op1.n_attr <= 5) return false;
@@ -1130,6 +1130,7 @@ static int launch_head_decode(const y3_op *ops, const y3_step &, const void *, c
   a.y_anchors = op1.n_anchor; a.y_attr = op1.n_attr;
   a.y_row_offset = op1.row_offset; a.y_rows_total = op1.rows_total;
   a.y_net_w = op1.net_w; a.y_net_h = op1.net_h;
+  a.y_sxy = y3_op_scale_xy(op1);
   for (int i = 0; i < 8; ++i) { a.y_aw[i] = op1.anchor_w[i]; a.y_ah[i] = op1.anchor_h[i]; }
   // 64 pixels x all 255 channels per workgroup: 80 KiB of LDS (two operand stages; the padded logit tile of 64 x 260 floats
   // is parked in them), so two workgroups share a CU and one's decode runs under the other's loads (128-pixel tiles, one

@@ -62,7 +62,7 @@ __global__ __launch_bounds__(256) void conv_stem3x3_kernel(SmallArgs p) {
       for (int c = 0; c < 3; ++c)
         x[(ky * 3 + kx) * 3 + c] = ok ? load_input<MODE>(p.in, lut, b, c, iy, ix, p.H, p.W) : 0.f;
     }
-  const bool leaky = p.flags & Y3_F_LEAKY;
+  const int act = y3_act(p.flags);
   TO *orow = reinterpret_cast<TO *>(p.out) + (long long)m * p.out_ld;
   for (int co = 0; co < p.Cout; co += 8) {
     float acc[8];
@@ -83,9 +83,10 @@ __global__ __launch_bounds__(256) void conv_stem3x3_kernel(SmallArgs p) {
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       float t = acc[j] * p.scale[co + j] + p.bias[co + j];
-      if (leaky) t = t > 0.f ? t : Y3_LEAKY_SLOPE * t;
+      if (act == Y3_ACT_LEAKY) t = t > 0.f ? t : Y3_LEAKY_SLOPE * t;
       v[j] = t;
     }
+    if (act == Y3_ACT_MISH) y3_mish8(v);
     if (nvalid == 8 && (p.out_ld % 8) == 0) {
       if constexpr (sizeof(TO) == 2) {
         *reinterpret_cast<u32x4 *>(orow + co) = y3_pack8<TO>(v);
@@ -163,7 +164,7 @@ __global__ __launch_bounds__(256) void conv_stem_mfma_kernel(StemMfmaArgs<T> p) 
     sc[ni] = *reinterpret_cast<const f32x4 *>(p.scale + ni * 16 + cq);
     bi[ni] = *reinterpret_cast<const f32x4 *>(p.bias + ni * 16 + cq);
   }
-  const bool leaky = p.flags & Y3_F_LEAKY;
+  const int act = y3_act(p.flags);
   __syncthreads();
 
   // ---- each wave: 2 pixel rows x 2 groups of 16 pixels ------------------------------------------------
@@ -192,7 +193,7 @@ __global__ __launch_bounds__(256) void conv_stem_mfma_kernel(StemMfmaArgs<T> p) 
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             float t = a[r] * sc[ni][r] + bi[ni][r];
-            if (leaky) t = t > 0.f ? t : Y3_LEAKY_SLOPE * t;
+            t = y3_act1(t, act);
             v[r] = t;
           }
           if (co + 4 <= p.Cout) {
@@ -254,7 +255,7 @@ __global__ __launch_bounds__(256) void conv_direct_kernel(DirectArgs p) {
     }
   }
   float v = acc * p.scale[co] + p.bias[co];
-  if (p.flags & Y3_F_LEAKY) v = v > 0.f ? v : Y3_LEAKY_SLOPE * v;
+  v = y3_act1(v, y3_act(p.flags));
   if (p.flags & Y3_F_RESIDUAL) v += y3_to_float<T>(static_cast<const T *>(p.res)[m * p.res_ld + co]);
   if ((p.flags & Y3_F_OUT_F32) || sizeof(T) == 4)
     static_cast<float *>(p.out)[m * p.out_ld + co] = v;

@@ -29,14 +29,24 @@ __device__ __forceinline__ float y3_quad_from3(float v) {
   return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xFF, 0xF, 0xF, true));
 }
 
+// Darknet's [yolo] scale_x_y s stretches the sigmoid of the centre offsets: sig * s - (s - 1) / 2, computed as
+// t = sig * s + (-0.5 (s - 1)) with every operation rounded on its own.  s == 1 (YOLOv3) gives sig itself, bit for bit:
+// sig * 1 is exact and adding -0 changes nothing.
+__device__ __forceinline__ float y3_scale_xy(float sig, float s) {
+#pragma clang fp contract(off)
+  return sig * s + (-0.5f * (s - 1.0f));
+}
+// y3_op.scale_x_y as the kernels take it: 0 (a caller that zero-initialises the op) means 1
+static inline float y3_op_scale_xy(const y3_op &op) { return op.scale_x_y == 0.0f ? 1.0f : op.scale_x_y; }
+
 // t_: the box's n_attr logits (LDS).  Called by all four lanes of the box together (EXEC must hold whole quads).
 // cell_*: grid column / row of the box's cell; grid_*: grid size; anchor_*: the box's anchor (pixels); net_*: the network
-// input size the anchors refer to.  (Scalars by value: selecting between members of a struct in memory by lane turns
+// input size the anchors refer to; sxy: the head's scale_x_y.  (Scalars by value: selecting between members of a struct in memory by lane turns
 // into an indexed load from scratch memory.)
 // comp: this lane's box component (sub 0: bx, 1: by, 2: bw, 3: bh); score / cls are valid on the lane with sub == 2.
 __device__ __forceinline__ void y3_decode_box4(const float *t_, int n_attr, int sub, float cell_x, float cell_y, float grid_w,
                                                float grid_h, float anchor_w, float anchor_h, float net_w, float net_h,
-                                               float &comp, float &score, int &cls) {
+                                               float sxy, float &comp, float &score, int &cls) {
 #pragma clang fp contract(off)
   constexpr float kLog2e = 1.44269504088896340736f;
   const int ncls = n_attr - 5;
@@ -94,7 +104,7 @@ __device__ __forceinline__ void y3_decode_box4(const float *t_, int n_attr, int 
       best_c = oc;
     }
   }
-  // box component of this lane: sub 0 / 1: (sigmoid(t) + cell) / grid;  sub 2 / 3: exp(t) * anchor / net
+  // box component of this lane: sub 0 / 1: (sigmoid(t) * s - (s - 1) / 2 + cell) / grid;  sub 2 / 3: exp(t) * anchor / net
   const bool is_xy = (sub & 2) == 0, second = (sub & 1) != 0;
   const float tk = t_[sub];
   const float e = expf(is_xy ? -tk : tk);
@@ -103,7 +113,7 @@ __device__ __forceinline__ void y3_decode_box4(const float *t_, int n_attr, int 
   const float anchor = second ? anchor_h : anchor_w;
   const float grid = second ? grid_h : grid_w;
   const float net = second ? net_h : net_w;
-  const float num = is_xy ? sig + cell : e * anchor;
+  const float num = is_xy ? y3_scale_xy(sig, sxy) + cell : e * anchor;
   const float den = is_xy ? grid : net;
   comp = num / den;
   // sub 2: objectness = sigmoid(t4);  sub 3: best / sum;  score = (best / sum) * objectness on sub 2
@@ -135,7 +145,7 @@ __device__ __forceinline__ void y3_head_decode_rows(const Args &p, const float *
     float comp, score;
     int best_c;
     y3_decode_box4(sL + pl * LD + a * p.y_attr, p.y_attr, sub, (float)x, (float)y, (float)p.Wo, (float)p.Ho, p.y_aw[a],
-                   p.y_ah[a], p.y_net_w, p.y_net_h, comp, score, best_c);
+                   p.y_ah[a], p.y_net_w, p.y_net_h, p.y_sxy, comp, score, best_c);
     if (!live) continue;
     const long long row = (long long)b * p.y_rows_total + p.y_row_offset + (long long)a * p.HoWo + (long long)y * p.Wo + x;
     p.y_bbox[row * 4 + sub] = comp;

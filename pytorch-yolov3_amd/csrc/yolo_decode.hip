@@ -7,8 +7,9 @@
 //
 // Input : float32 head-conv output, NHWC (B, h, w, ld), channel = anchor * n_attr + attr
 //         (the reference reshapes (B, A*n_attr, h, w) -> (B, A, n_attr, h, w), darknet.py:68).
+// sxy(v) = v * s - (s - 1) / 2 with the head's scale_x_y s (decode_core.h: y3_scale_xy; s = 1 for YOLOv3).
 // Output: row = row_offset + a*h*w + y*w + x   (darknet.py:118-120, heads in cfg order)
-//   bbox[row] = ((sigmoid(tx)+x)/w, (sigmoid(ty)+y)/h, exp(tw)*Aw/net_w, exp(th)*Ah/net_h)
+//   bbox[row] = ((sxy(sigmoid(tx))+x)/w, (sxy(sigmoid(ty))+y)/h, exp(tw)*Aw/net_w, exp(th)*Ah/net_h)
 //   prob[row] = max_c softmax(tc)_c * sigmoid(to)       cls[row] = argmax (first on ties), int64
 // Built with -ffp-contract=off: each operation rounds like the reference's separate torch ops.
 #include "common.h"
@@ -22,7 +23,7 @@ struct YoloArgs {
   float *prob;
   long long *cls;
   int B, h, w, ld, n_anchor, n_attr, row_offset, rows_total;
-  float net_w, net_h;
+  float net_w, net_h, sxy;       // sxy: scale_x_y (1 for YOLOv3)
   float aw[8], ah[8];
   long long total;
 };
@@ -77,8 +78,8 @@ __global__ __launch_bounds__(LANES == 1 ? 256 : 384) void yolo_decode_kernel(Yol
       // bf16 networks: decode_core.h (shared with the fused head kernel)
       float comp, score;
       int best_c;
-      y3_decode_box4(t_, p.n_attr, sub, (float)x, (float)y, (float)p.w, (float)p.h, p.aw[a], p.ah[a], p.net_w, p.net_h, comp,
-                     score, best_c);
+      y3_decode_box4(t_, p.n_attr, sub, (float)x, (float)y, (float)p.w, (float)p.h, p.aw[a], p.ah[a], p.net_w, p.net_h, p.sxy,
+                     comp, score, best_c);
       if (!live) continue;
       const long long row = (long long)b * p.rows_total + p.row_offset + (long long)a * p.h * p.w + (long long)y * p.w + x;
       p.bbox[row * 4 + sub] = comp;
@@ -102,8 +103,8 @@ __global__ __launch_bounds__(LANES == 1 ? 256 : 384) void yolo_decode_kernel(Yol
       }
     }
     if (!live) continue;
-    const float bx = (sigmoidf_ref(t_[0]) + (float)x) / (float)p.w;
-    const float by = (sigmoidf_ref(t_[1]) + (float)y) / (float)p.h;
+    const float bx = (y3_scale_xy(sigmoidf_ref(t_[0]), p.sxy) + (float)x) / (float)p.w;
+    const float by = (y3_scale_xy(sigmoidf_ref(t_[1]), p.sxy) + (float)y) / (float)p.h;
     const float bw = (expf(t_[2]) * p.aw[a]) / p.net_w;
     const float bh = (expf(t_[3]) * p.ah[a]) / p.net_h;
     const float obj = sigmoidf_ref(t_[4]);
@@ -130,6 +131,7 @@ static int launch_yolo(const y3_op *ops, const y3_step &st, const void *d_in, co
   a.n_anchor = op.n_anchor; a.n_attr = op.n_attr;
   a.row_offset = op.row_offset; a.rows_total = op.rows_total;
   a.net_w = op.net_w; a.net_h = op.net_h;
+  a.sxy = y3_op_scale_xy(op);
   for (int i = 0; i < 8; ++i) { a.aw[i] = op.anchor_w[i]; a.ah[i] = op.anchor_h[i]; }
   a.total = (long long)op.batch * op.in_h * op.in_w * op.n_anchor;
   const long long npix = (long long)op.batch * op.in_h * op.in_w;

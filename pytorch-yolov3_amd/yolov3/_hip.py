@@ -34,6 +34,9 @@ LIB_PATH = os.environ.get("Y3_HIP_LIB") or os.path.join(_HERE, "..", "lib", "lib
 Y3_F32, Y3_BF16, Y3_F16, Y3_F64 = 0, 1, 2, 3
 OP_CONV, OP_MAXPOOL, OP_UPSAMPLE, OP_ADD, OP_COPY, OP_YOLO = 1, 2, 3, 4, 5, 6
 F_LEAKY, F_RESIDUAL, F_OUT_F32, F_IN_NCHW_F32, F_IN_NHWC_U8BGR, F_PLAN_INPUT, F_FUSE_NEXT = 1, 2, 4, 8, 16, 32, 64
+F_MISH = 128
+# y3_capabilities() bits: what the loaded library computes beyond ABI 6 as first released
+CAP_MISH, CAP_SCALE_X_Y = 1, 2
 PATH_IGEMM, PATH_STEM, PATH_DIRECT, PATH_STEM_MFMA = 0, 1, 2, 3
 
 
@@ -53,7 +56,7 @@ class Y3Op(ctypes.Structure):
         ("row_offset", ctypes.c_int32), ("rows_total", ctypes.c_int32),
         ("net_w", ctypes.c_float), ("net_h", ctypes.c_float),
         ("d_bbox", ctypes.c_void_p), ("d_prob", ctypes.c_void_p), ("d_cls", ctypes.c_void_p),
-        ("block_idx", ctypes.c_int32), ("reserved", ctypes.c_int32),
+        ("block_idx", ctypes.c_int32), ("scale_x_y", ctypes.c_float),
         ("d_weight_frag", ctypes.c_void_p),
     ]
 
@@ -85,6 +88,7 @@ _lib = None
 # name -> (restype, argtypes); every symbol include/yolov3_hip.h declares
 PROTOTYPES = {
     "y3_abi_version": (ctypes.c_int, []),
+    "y3_capabilities": (ctypes.c_uint32, []),
     "y3_last_error": (ctypes.c_char_p, []),
     "y3_device_count": (ctypes.c_int, []),
     "y3_plan_create": (ctypes.c_int, [ctypes.POINTER(Y3Op), ctypes.c_int, ctypes.c_void_p,
@@ -131,6 +135,10 @@ PROTOTYPES = {
 }
 
 
+# symbols a library of ABI 6 built before they were added lacks: asked for through capabilities()
+_OPTIONAL = ("y3_capabilities",)
+
+
 class HipLibraryError(RuntimeError):
     pass
 
@@ -151,6 +159,8 @@ def lib():
     except OSError as exc:
         raise HipLibraryError("cannot load {}: {}".format(path, exc))
     for name, (restype, argtypes) in PROTOTYPES.items():
+        if name in _OPTIONAL and not hasattr(handle, name):
+            continue
         fn = getattr(handle, name)
         fn.restype = restype
         fn.argtypes = argtypes
@@ -159,6 +169,22 @@ def lib():
             handle.y3_abi_version(), ABI_VERSION))
     _lib = handle
     return _lib
+
+
+def capabilities():
+    """CAP_* bits of the loaded library (0 from a library older than y3_capabilities)."""
+    handle = lib()
+    return int(handle.y3_capabilities()) if hasattr(handle, "y3_capabilities") else 0
+
+
+def require_capabilities(needs, what):
+    """Refuse a plan that needs a computation the loaded library does not report: a stale library would run mish as
+    linear and ignore scale_x_y."""
+    missing = needs & ~capabilities()
+    if missing:
+        names = [n for n, b in (("mish", CAP_MISH), ("scale_x_y", CAP_SCALE_X_Y)) if missing & b]
+        raise HipLibraryError("{}: the loaded libyolov3_hip.so cannot compute {} (rebuild: make -C pytorch-yolov3_amd/csrc)"
+                              .format(what, ", ".join(names)))
 
 
 def options(**overrides):

@@ -20,7 +20,7 @@ import torch
 
 from . import _hip
 from .cfgparse import parse_config
-from .plan import build_plan
+from .plan import build_plan, check_blocks
 from .weights import conv_layout, read_darknet_weights
 
 BN_EPS = np.float32(1e-5)
@@ -125,6 +125,7 @@ class Darknet(object):
             elif blk["type"] == "shortcut":
                 self.blocks_to_cache.add(i - 1)
                 self.blocks_to_cache.add(i + blk["from"])
+        check_blocks(self.blocks)       # what the kernels cannot compute is refused here, not run with other semantics
         self._out_channels, self._convs = conv_layout(self.blocks, self.net_info)
         if self.blocks and self.blocks[0]["type"] != "convolutional":
             raise ValueError("the first block must be [convolutional] (it reads the network input)")
@@ -315,6 +316,7 @@ class Darknet(object):
             return base + desc["offsets"][t.buf] + t.off * elem
 
         ops = (_hip.Y3Op * len(desc["ops"]))()
+        needs = 0                            # library capabilities (y3_capabilities) the plan relies on
         for n, od in enumerate(desc["ops"]):
             op = ops[n]
             kind = od["kind"]
@@ -344,6 +346,9 @@ class Darknet(object):
                 op.ksize, op.stride, op.pad = od["ksize"], od["stride"], od["pad"]
                 if od["leaky"]:
                     op.flags |= _hip.F_LEAKY
+                if od.get("mish"):
+                    op.flags |= _hip.F_MISH
+                    needs |= _hip.CAP_MISH
                 if od.get("fuse_next"):
                     op.flags |= _hip.F_FUSE_NEXT
                 if res is not None:
@@ -385,8 +390,12 @@ class Darknet(object):
                     op.anchor_h[a] = float(ah)
                 op.row_offset, op.rows_total = od["row_offset"], od["rows_total"]
                 op.net_w, op.net_h = float(self.net_info["width"]), float(self.net_info["height"])
+                if "scale_x_y" in od:
+                    op.scale_x_y = od["scale_x_y"]
+                    needs |= _hip.CAP_SCALE_X_Y
             else:
                 raise AssertionError(kind)
+        _hip.require_capabilities(needs, self.config_fpath)
         cp.ops = ops
         cp.n_ops = len(desc["ops"])
         cp.desc = desc

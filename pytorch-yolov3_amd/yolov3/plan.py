@@ -38,9 +38,51 @@ class Tensor(object):
             self.buf, self.off, self.ld, self.c, self.h, self.w, " f32" if self.f32 else "")
 
 
+ACTIVATIONS = ("leaky", "linear", "mish")
+
+
+def route_groups(blk):
+    """(groups, group_id) of a [route] block: Darknet's grouped route takes channel group `group_id` of `groups` equal
+    parts of its input (yolov4-tiny's CSP blocks)."""
+    return int(blk.get("groups", 1)), int(blk.get("group_id", 0))
+
+
+def check_blocks(blocks):
+    """Refuse, naming the block, what the kernels cannot compute: any of it would otherwise run with different semantics
+    and return wrong boxes without an error."""
+    for i, blk in enumerate(blocks):
+        kind = blk["type"]
+        if kind == "convolutional":
+            act = blk.get("activation")
+            if act not in ACTIVATIONS:
+                raise ValueError("conv block {}: activation {!r} is not supported (only {})".format(
+                    i, act, ", ".join(ACTIVATIONS)))
+            if int(blk.get("groups", 1)) != 1:
+                raise ValueError("conv block {}: grouped convolution (groups={}) is not supported".format(i, blk["groups"]))
+            if int(blk.get("dilation", 1)) != 1:
+                raise ValueError("conv block {}: dilated convolution (dilation={}) is not supported".format(
+                    i, blk["dilation"]))
+        elif kind == "route":
+            groups, gid = route_groups(blk)
+            if groups != 1 and len(blk["layers"]) != 1:
+                raise ValueError("route block {}: groups={} is supported on single-layer routes only".format(i, groups))
+            if groups < 1 or not 0 <= gid < groups:
+                raise ValueError("route block {}: group_id={} out of range for groups={}".format(i, gid, groups))
+        elif kind == "yolo":
+            if int(blk.get("new_coords", 0)) != 0:
+                raise ValueError("yolo block {}: new_coords=1 is not supported".format(i))
+        elif kind == "shortcut":
+            if "weights_type" in blk:
+                raise ValueError("shortcut block {}: weighted shortcuts (weights_type) are not supported".format(i))
+            if blk.get("activation", "linear") != "linear":
+                raise ValueError("shortcut block {}: activation {!r} is not supported (linear only)".format(
+                    i, blk["activation"]))
+
+
 def infer_shapes(blocks, net_info, height, width):
     """(C,H,W) of every block output for an input of size (height,width); conv arithmetic
     as torch.nn.Conv2d / MaxPool2d / Upsample compute it."""
+    check_blocks(blocks)
     shapes = []
     c, h, w = net_info["channels"], height, width
     for i, blk in enumerate(blocks):
@@ -63,6 +105,10 @@ def infer_shapes(blocks, net_info, height, width):
             if any((s_[1], s_[2]) != (srcs[0][1], srcs[0][2]) for s_ in srcs):
                 raise ValueError("route block {} joins tensors of different sizes: {}".format(i, srcs))
             c, h, w = sum(s_[0] for s_ in srcs), srcs[0][1], srcs[0][2]
+            groups = route_groups(blk)[0]
+            if c % groups:
+                raise ValueError("route block {}: {} channels do not split into {} groups".format(i, c, groups))
+            c //= groups
         elif kind == "shortcut":
             a, b = shapes[i - 1], shapes[i + blk["from"]]
             if a != b:
@@ -118,7 +164,7 @@ def build_plan(blocks, net_info, batch, height, width, elem_size, reuse=True, fu
     # ---- concat placement ------------------------------------------------------------------
     def resolve(j):
         """follow single-source routes down to the block that really produces the data"""
-        while kinds[j] == "route" and len(blocks[j]["layers"]) == 1:
+        while kinds[j] == "route" and len(blocks[j]["layers"]) == 1 and route_groups(blocks[j])[0] == 1:
             j = blocks[j]["layers"][0]
         return j
 
@@ -188,7 +234,7 @@ def build_plan(blocks, net_info, batch, height, width, elem_size, reuse=True, fu
             if i in conv_fused:
                 sc = conv_fused[i]
                 res = tensor_of[sc + blocks[sc]["from"]]
-            ops.append(dict(kind="conv", block=i, inp=prev_tensor(i), out=out, res=res, ksize=k, stride=s,
+            op = dict(kind="conv", block=i, inp=prev_tensor(i), out=out, res=res, ksize=k, stride=s,
                             pad=(k - 1) // 2 if "pad" in blk else 0, leaky=blk["activation"] == "leaky",
                             slot=conv_slot, bn=bool(blk.get("batch_normalize", 0)), net_input=(i == 0),
                             # hint for the executor: the next op is a conv and the ONLY reader of this conv's
@@ -196,7 +242,10 @@ def build_plan(blocks, net_info, batch, height, width, elem_size, reuse=True, fu
                             # conv, 1x1 + 3x3 of a residual block); needs arena reuse semantics, i.e. not the
                             # keep-every-tensor debugging mode.  Whether a fused kernel exists is the executor's call.
                             fuse_next=bool(fuse and i not in conv_fused and i + 1 < n and
-                                           kinds[i + 1] == "convolutional" and readers[i] == [(i + 1, "in")])))
+                                           kinds[i + 1] == "convolutional" and readers[i] == [(i + 1, "in")]))
+            if blk["activation"] == "mish":
+                op["mish"] = True
+            ops.append(op)
             conv_slot += 1
             if i in conv_fused:
                 tensor_of[i] = None                # never materialised
@@ -216,8 +265,22 @@ def build_plan(blocks, net_info, batch, height, width, elem_size, reuse=True, fu
                 ops.append(dict(kind="add", block=i, inp=tensor_of[i - 1], res=tensor_of[i + blk["from"]], out=out))
                 tensor_of[i] = out
         elif kind == "route":
-            if len(blk["layers"]) == 1:
+            groups, gid = route_groups(blk)
+            if len(blk["layers"]) == 1 and groups == 1:
                 tensor_of[i] = tensor_of[blk["layers"][0]]
+            elif len(blk["layers"]) == 1:
+                # grouped route: channel group `gid` of the source, an alias at the same pixel stride (no copy) unless
+                # the slice breaks the channel-slice granularity
+                src = tensor_of[blk["layers"][0]]
+                c = src.c // groups
+                off = src.off + gid * c
+                if off % CH_ALIGN == 0 and c % CH_ALIGN == 0:
+                    tensor_of[i] = Tensor(src.buf, off, src.ld, c, src.h, src.w, src.f32)
+                else:
+                    out = own_tensor(i)
+                    ops.append(dict(kind="copy", block=i, inp=Tensor(src.buf, off, src.ld, c, src.h, src.w, src.f32),
+                                    out=out))
+                    tensor_of[i] = out
             else:
                 for j, dst in copies[i]:
                     ops.append(dict(kind="copy", block=i, inp=tensor_of[j], out=dst))
@@ -228,8 +291,11 @@ def build_plan(blocks, net_info, batch, height, width, elem_size, reuse=True, fu
             if c % na != 0 or c // na <= 5:
                 raise ValueError("yolo block {}: {} channels do not split into {} anchors".format(i, c, na))
             anchors = [blk["anchors"][m] for m in mask_of(blk)]
-            ops.append(dict(kind="yolo", block=i, inp=src, anchors=anchors, n_attr=c // na,
-                            row_offset=row_offset, rows_total=rows_total))
+            op = dict(kind="yolo", block=i, inp=src, anchors=anchors, n_attr=c // na,
+                      row_offset=row_offset, rows_total=rows_total)
+            if float(blk.get("scale_x_y", 1)) != 1.0:
+                op["scale_x_y"] = float(blk["scale_x_y"])     # Darknet's centre stretch (default 1: the YOLOv3 decode)
+            ops.append(op)
             row_offset += na * h * w
             tensor_of[i] = src
         if tensor_of[i] is None and kind != "convolutional":

@@ -44,6 +44,8 @@ def conv_layout(blocks, net_info):
             ))
         elif kind == "route":
             cur = sum(out_ch[j if j >= 0 else i + j] for j in blk["layers"])
+            # a grouped route (groups=G group_id=g) passes one of G equal channel groups on
+            cur //= int(blk.get("groups", 1))
         elif kind == "shortcut":
             if cur != out_ch[i + blk["from"]]:
                 raise AssertionError(
