@@ -6,6 +6,7 @@
 #include <stdio.h>
 
 #include <mutex>
+#include <type_traits>
 
 #include "yolov3_hip.h"
 
@@ -80,26 +81,41 @@ Y3KernelTimer *y3_kernel_timer();
     }                                                                                                                \
   } while (0)
 
-// One-time set-up per DEVICE (dynamic-LDS function attributes are per device; so is the CU count a persistent grid is
-// sized by), safe to call from several host threads.
-struct Y3DeviceOnce {
-  std::mutex mu;
-  bool done[32] = {};
-  int n_cu[32] = {};
-  template <typename F>
-  int run(F &&setup, int *cu_out = nullptr) {
+// Launches one kernel instance through Y3_LAUNCH and checks the launch.  Dynamic LDS over 64 KiB needs the instance's limit
+// raised first; the attribute is per device, so it is set on the instance's first such launch on each device (one lock and
+// state per instance: the statics of this template).  Launches within 64 KiB take no lock.
+template <auto Kernel, typename... A>
+int y3_launch(dim3 grid, dim3 block, size_t lds, hipStream_t s, const A &...args) {
+  if (lds > 64 * 1024) {
+    static std::mutex mu;
+    static bool done[32];
     int dev = 0;
     Y3_HIP_CHECK(hipGetDevice(&dev));
     Y3_REQUIRE(dev >= 0 && dev < 32, "device index %d out of range", dev);
     std::lock_guard<std::mutex> lock(mu);
     if (!done[dev]) {
-      const int rc = setup();
-      if (rc != Y3_OK) return rc;
-      Y3_HIP_CHECK(hipDeviceGetAttribute(&n_cu[dev], hipDeviceAttributeMultiprocessorCount, dev));
+      Y3_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       160 * 1024));
       done[dev] = true;
     }
-    if (cu_out) *cu_out = n_cu[dev];
-    return Y3_OK;
+  }
+  Y3_LAUNCH(Kernel, grid, block, lds, s, args...);
+  Y3_HIP_CHECK(hipGetLastError());
+  return Y3_OK;
+}
+
+// The instantiated values of one template parameter of a kernel family: the chooser asks has(v), the launcher pick(v, f),
+// which returns f(std::integral_constant<int, V>{}) for the listed V == v, and fails for any other v.  The instances are
+// emitted into the code object in list order (bench.device_code_sha256 sees the order): reordering a list moves kernels.
+template <int... V>
+struct y3_ints {
+  static constexpr bool has(int v) { return ((v == V) || ...); }
+  template <typename F>
+  static int pick(int v, F &&f) {
+    int rc = Y3_OK;
+    if ((... || (v == V && ((rc = f(std::integral_constant<int, V>{})), true)))) return rc;
+    y3_set_error("no kernel instance for template value %d", v);
+    return Y3_ERR_INVALID;
   }
 };
 

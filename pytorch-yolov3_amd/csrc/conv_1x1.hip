@@ -17,6 +17,7 @@
 // Geometry: BM = 128 pixels, BN = 128 (K <= 256) or 64 (K <= 512) channels, 4 MFMA waves (2 x 2, wave tile 64 x BN/2)
 // + 4 loader waves, LDS = K*BN*2 (weights) + 128*BN*2 (park) + 4 x 16 KiB (ring) <= 160 KiB, one workgroup per CU.
 // Workgroup b owns channel tile b % n_tiles and the pixel tiles (b / n_tiles) + j * (grid / n_tiles).
+#include <type_traits>
 #include <utility>
 
 #include "common.h"
@@ -223,11 +224,9 @@ struct DwArgs {
   // detection-head form (HEAD = true): the YOLO decode of yolo_decode.hip runs on the workgroup's logit tile (see y3_head_decode_rows)
   int Ho, Wo, HoWo;
   uint32_t mul_hw, sh_hw, mul_w, sh_w;   // n / d == (umulhi(n, mul) + n) >> sh  (d = HoWo, Wo)
-  float *y_bbox, *y_prob;
-  long long *y_cls;
-  int y_anchors, y_attr, y_row_offset, y_rows_total;
-  float y_net_w, y_net_h, y_sxy, y_aw[8], y_ah[8];
+  Y3DecodeArgs dec;
 };
+static_assert(offsetof(DwArgs, dec) == 104 && sizeof(DwArgs) == 224, "kernel argument layout");
 
 template <int V>
 struct StepC { static constexpr int value = V; };
@@ -386,20 +385,26 @@ __global__ __launch_bounds__(512, 2) void conv1x1_dw_kernel(DwArgs p) {
   }
 }
 
+// Instantiated K-steps (nkt = Cin / 64) of the direct-weights kernel per tile height BM (96 / 48): the tile of BM pixels x all
+// of Cin lives in LDS, so 96-pixel tiles stop short of the 48-pixel ones; the plain 1x1 form, the detection-head form
+using DwBm = y3_ints<96, 48>;
+template <int BM> using Dw1Nkt = std::conditional_t<BM == 96, y3_ints<4, 6, 8, 12>, y3_ints<4, 6, 8, 12, 16>>;
+template <int BM> using DwHeadNkt = std::conditional_t<BM == 96, y3_ints<4, 8>, y3_ints<4, 8, 16>>;
+
 // tile height of the direct-weights 1x1 kernel for this op (96 / 48), or 0 when it does not take it
 int dw1x1_bm(const y3_op &op) {
   if (op.kind != Y3_OP_CONV || !y3_is16(op.dtype) || op.ksize != 1 || op.stride != 1 || op.pad != 0) return 0;
   if (op.flags & (Y3_F_RESIDUAL | Y3_F_OUT_F32 | Y3_F_IN_NCHW_F32 | Y3_F_IN_NHWC_U8BGR | Y3_F_PLAN_INPUT)) return 0;
   if (op.out_c % 256 != 0 || op.in_ld % 8 != 0 || op.out_ld % 8 != 0 || op.k_ld % 32 != 0 || op.k_ld < op.in_c || op.cout_pad % 32 != 0) return 0;
   const int nkt = op.in_c / 64;
-  if (op.in_c % 128 != 0 || !(nkt == 4 || nkt == 6 || nkt == 8 || nkt == 12 || nkt == 16)) return 0;
+  if (op.in_c % 128 != 0) return 0;
   const int M = op.batch * op.in_h * op.in_w, n_cu = y3_device_cus(), nt = op.out_c / 256;
   // one round of workgroups: 96-pixel tiles where they already give every CU (nearly) one, else 48-pixel tiles -- down to a
   // quarter of the CUs (512 -> 256 at 19^2 x 16 frames: 121 tiles, 5.8 against 8.1-8.9 us on the implicit GEMMs, whose eight
   // K-steps each wait out an L2 round trip whatever the grid; 38^2 x 8 frames 6.6 against 8.7-11.2: profiles/r06_conv1x1_dw.txt); smaller grids (one frame at a time) stay on the tiled kernels
   const long long t96 = (long long)y3_ceil_div(M, 96) * nt, t48 = (long long)y3_ceil_div(M, 48) * nt;
-  if (op.in_c * 2 * 96 <= 144 * 1024 && t96 <= n_cu && 4 * t96 >= 3 * n_cu) return 96;
-  if (op.in_c * 2 * 48 <= 144 * 1024 && t48 <= n_cu && 4 * t48 >= n_cu) return 48;
+  if (Dw1Nkt<96>::has(nkt) && op.in_c * 2 * 96 <= 144 * 1024 && t96 <= n_cu && 4 * t96 >= 3 * n_cu) return 96;
+  if (Dw1Nkt<48>::has(nkt) && op.in_c * 2 * 48 <= 144 * 1024 && t48 <= n_cu && 4 * t48 >= n_cu) return 48;
   return 0;
 }
 
@@ -414,12 +419,13 @@ int dw_head_bm(const y3_op &op, const y3_options &o) {
   if (op.flags & (Y3_F_LEAKY | Y3_F_MISH | Y3_F_RESIDUAL | Y3_F_IN_NCHW_F32 | Y3_F_IN_NHWC_U8BGR | Y3_F_PLAN_INPUT)) return 0;
   if (op.out_c > 256 || op.cout_pad < 256 || op.cout_pad % 32 != 0 || op.in_ld % 8 != 0 || op.k_ld % 32 != 0 || op.k_ld < op.in_c) return 0;
   const int nkt = op.in_c / 64;
-  if (op.in_c % 128 != 0 || !(nkt == 4 || nkt == 8 || nkt == 16)) return 0;
+  if (op.in_c % 128 != 0 || !DwHeadNkt<48>::has(nkt)) return 0;
   const long long M = (long long)op.batch * op.in_h * op.in_w;
   if (M >= (1ll << 31)) return 0;
-  const bool fits96 = nkt <= 8;                       // 96 pixels x 1024 channels would be 192 KiB
-  return mode == 4 && fits96 ? 96 : 48;
+  return mode == 4 && DwHeadNkt<96>::has(nkt) ? 96 : 48;   // (96 pixels x 1024 channels would be 192 KiB)
 }
+
+using WresBn = y3_ints<128, 64>;   // channel tiles of the weights-resident kernel
 
 int wres_bn(const y3_op &op) {
   if (op.in_c <= 256 && op.out_c % 128 == 0) return 128;
@@ -443,29 +449,13 @@ int launch_conv1x1_dw(const y3_op *ops, const y3_step &st, const void *d_in, con
   const int nkt = op.in_c / 64;
   return y3_by_dtype16(op.dtype, [&](auto tag) {
     typedef decltype(tag) T;
-    static Y3DeviceOnce once;
-    {
-      const int rc1 = once.run([]() -> int {
-#define Y3_DW1_ATTR(BM_, NKT_) Y3_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(conv1x1_dw_kernel<T, BM_, NKT_>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024))
-        Y3_DW1_ATTR(96, 4); Y3_DW1_ATTR(96, 6); Y3_DW1_ATTR(96, 8); Y3_DW1_ATTR(96, 12);
-        Y3_DW1_ATTR(48, 4); Y3_DW1_ATTR(48, 6); Y3_DW1_ATTR(48, 8); Y3_DW1_ATTR(48, 12); Y3_DW1_ATTR(48, 16);
-#undef Y3_DW1_ATTR
-        return Y3_OK;
-      });
-      if (rc1 != Y3_OK) return rc1;
-    }
     const size_t lds = (size_t)bm * op.in_c * 2;
     const dim3 grid(y3_ceil_div(a.M, bm) * a.n_tiles);
-#define Y3_DW1_GO(BM_, NKT_) Y3_LAUNCH((conv1x1_dw_kernel<T, BM_, NKT_>), grid, dim3(512), lds, s, a)
-    if (bm == 96) {
-      if (nkt == 4) Y3_DW1_GO(96, 4); else if (nkt == 6) Y3_DW1_GO(96, 6); else if (nkt == 8) Y3_DW1_GO(96, 8); else Y3_DW1_GO(96, 12);
-    } else {
-      if (nkt == 4) Y3_DW1_GO(48, 4); else if (nkt == 6) Y3_DW1_GO(48, 6); else if (nkt == 8) Y3_DW1_GO(48, 8);
-      else if (nkt == 12) Y3_DW1_GO(48, 12); else Y3_DW1_GO(48, 16);
-    }
-#undef Y3_DW1_GO
-    Y3_HIP_CHECK(hipGetLastError());
-    return Y3_OK;
+    return DwBm::pick(bm, [&](auto m) {
+      return Dw1Nkt<m.value>::pick(nkt, [&](auto k) {
+        return y3_launch<conv1x1_dw_kernel<T, m.value, k.value>>(grid, dim3(512), lds, s, a);
+      });
+    });
   });
 }
 
@@ -485,37 +475,18 @@ int launch_head_decode_dw(const y3_op *ops, const y3_step &st, const void *, con
   a.flags = op0.flags;
   y3_fast_div((uint32_t)a.HoWo, a.mul_hw, a.sh_hw);
   y3_fast_div((uint32_t)a.Wo, a.mul_w, a.sh_w);
-  a.y_bbox = op1.d_bbox; a.y_prob = op1.d_prob; a.y_cls = reinterpret_cast<long long *>(op1.d_cls);
-  a.y_anchors = op1.n_anchor; a.y_attr = op1.n_attr;
-  a.y_row_offset = op1.row_offset; a.y_rows_total = op1.rows_total;
-  a.y_net_w = op1.net_w; a.y_net_h = op1.net_h;
-  a.y_sxy = y3_op_scale_xy(op1);
-  for (int i = 0; i < 8; ++i) { a.y_aw[i] = op1.anchor_w[i]; a.y_ah[i] = op1.anchor_h[i]; }
+  a.dec = y3_decode_args(op1);
   const int nkt = op0.in_c / 64;
   return y3_by_dtype16(op0.dtype, [&](auto tag) {
     typedef decltype(tag) T;
-    static Y3DeviceOnce once;
-    {
-      const int rc1 = once.run([]() -> int {
-#define Y3_DWH_ATTR(BM_, NKT_) Y3_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(conv1x1_dw_kernel<T, BM_, NKT_, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024))
-        Y3_DWH_ATTR(96, 4); Y3_DWH_ATTR(96, 8); Y3_DWH_ATTR(48, 4); Y3_DWH_ATTR(48, 8); Y3_DWH_ATTR(48, 16);
-#undef Y3_DWH_ATTR
-        return Y3_OK;
-      });
-      if (rc1 != Y3_OK) return rc1;
-    }
     const size_t tile = (size_t)bm * op0.in_c * 2, logits = (size_t)bm * 260 * 4;
     const size_t lds = tile > logits ? tile : logits;
     const dim3 grid(y3_ceil_div(a.M, bm));
-#define Y3_DWH_GO(BM_, NKT_) Y3_LAUNCH((conv1x1_dw_kernel<T, BM_, NKT_, true>), grid, dim3(512), lds, s, a)
-    if (bm == 96) {
-      if (nkt == 4) Y3_DWH_GO(96, 4); else Y3_DWH_GO(96, 8);
-    } else {
-      if (nkt == 4) Y3_DWH_GO(48, 4); else if (nkt == 8) Y3_DWH_GO(48, 8); else Y3_DWH_GO(48, 16);
-    }
-#undef Y3_DWH_GO
-    Y3_HIP_CHECK(hipGetLastError());
-    return Y3_OK;
+    return DwBm::pick(bm, [&](auto m) {
+      return DwHeadNkt<m.value>::pick(nkt, [&](auto k) {
+        return y3_launch<conv1x1_dw_kernel<T, m.value, k.value, true>>(grid, dim3(512), lds, s, a);
+      });
+    });
   });
 }
 
@@ -536,29 +507,15 @@ int launch_conv1x1_wres(const y3_op *ops, const y3_step &st, const void *d_in, c
   a.flags = op.flags;
   return y3_by_dtype16(op.dtype, [&](auto tag) {
     typedef decltype(tag) T;
-    static Y3DeviceOnce once;
-    int n_cu = 0;
-    {
-      const int rc = once.run([]() -> int {
-        Y3_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(conv1x1_wres_kernel<T, 128>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        Y3_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(conv1x1_wres_kernel<T, 64>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        return Y3_OK;
-      }, &n_cu);
-      if (rc != Y3_OK) return rc;
-    }
     const size_t lds = (size_t)a.n_kt * bn * 128 + (size_t)128 * bn * 2 + (size_t)4 * 128 * 128;
     Y3_REQUIRE(lds <= 160 * 1024, "conv block %d: weight panel does not fit LDS", op.block_idx);
     // one workgroup per CU, a whole number of them per channel tile (at least one each: more channel tiles than CUs just
     // means more than one workgroup per CU in turn)
+    const int n_cu = y3_device_cus();
     int grid = a.n_tiles > n_cu ? a.n_tiles : n_cu - n_cu % a.n_tiles;
     const long long tiles = (long long)a.m_tiles * a.n_tiles;
     if (grid > tiles) grid = (int)tiles;
-    if (bn == 128) Y3_LAUNCH((conv1x1_wres_kernel<T, 128>), dim3(grid), dim3(512), lds, s, a);
-    else Y3_LAUNCH((conv1x1_wres_kernel<T, 64>), dim3(grid), dim3(512), lds, s, a);
-    Y3_HIP_CHECK(hipGetLastError());
-    return Y3_OK;
+    return WresBn::pick(bn, [&](auto n) { return y3_launch<conv1x1_wres_kernel<T, n.value>>(dim3(grid), dim3(512), lds, s, a); });
   });
 }
 

@@ -446,23 +446,12 @@ int launch_block_fused(const y3_op *ops, const y3_step &st, const void *, const 
   a.TH = st.th;
   return y3_by_dtype16(op0.dtype, [&](auto tag) {
     typedef decltype(tag) T;
-    static Y3DeviceOnce once;
-    {
-      const int rc = once.run([]() -> int {
-        Y3_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(conv_block_fused_kernel<T>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, kBlockLds));
-        return Y3_OK;
-      });
-      if (rc != Y3_OK) return rc;
-    }
     a.tiles_x = y3_ceil_div(a.W, a.TW);
     a.tiles_y = y3_ceil_div(a.H, a.TH);
     a.inv_pw = (65536u + (uint32_t)(a.TW + 2) - 1u) / (uint32_t)(a.TW + 2);
     a.inv_tw = (65536u + (uint32_t)a.TW - 1u) / (uint32_t)a.TW;
     const int grid = a.tiles_x * a.tiles_y * op0.batch;
-    Y3_LAUNCH(conv_block_fused_kernel<T>, dim3(grid), dim3(kNT), kBlockLds, s, a);
-    Y3_HIP_CHECK(hipGetLastError());
-    return Y3_OK;
+    return y3_launch<conv_block_fused_kernel<T>>(dim3(grid), dim3(kNT), kBlockLds, s, a);
   });
 }
 

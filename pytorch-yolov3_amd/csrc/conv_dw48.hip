@@ -299,12 +299,11 @@ __global__ __launch_bounds__(512) void conv_dw48_kernel(Dw48Args p) {
   }
 }
 
-void dw48_fast_div(uint32_t d, uint32_t &mul, uint32_t &sh) {
-  if (d <= 1) { mul = 0; sh = 0; return; }
-  sh = 0;
-  while ((1u << sh) < d) ++sh;
-  mul = (uint32_t)((((uint64_t)1 << 32) * (((uint64_t)1 << sh) - d)) / d + 1);
-}
+// Instantiated K-steps per halo image (nkt = 64-channel pieces), per form: 3x3, 1x1, 3x3 stride 2 (one image, two images)
+using Dw48NktK3 = y3_ints<2, 4, 8>;
+using Dw48NktK1 = y3_ints<2, 4, 6, 8, 12, 16>;
+using Dw48NktS2 = y3_ints<1, 2, 4>;
+using Dw48NktS2Halves = y3_ints<2, 4>;
 
 // Shape of the halo image(s) for an op: rows that hold pixels, channels per image, images (NH); rows = 0: not a shape of this kernel
 struct Dw48Shape { int rows, cin_img, nh; };
@@ -326,8 +325,7 @@ Dw48Shape dw48_shape(const y3_op &op) {
   if (k3s2 && (long long)(sh.rows + 1) * sh.cin_img * 2 + 1024 > 160 * 1024 && sh.cin_img % 256 == 0) { sh.cin_img /= 2; sh.nh = 2; }
   if ((long long)(sh.rows + 1) * sh.cin_img * 2 + 1024 > 160 * 1024) return z;
   const int nkt = sh.cin_img / 64;
-  const bool inst = k1 ? (nkt == 2 || nkt == 4 || nkt == 6 || nkt == 8 || nkt == 12 || nkt == 16)
-                       : (k3 ? (nkt == 2 || nkt == 4 || nkt == 8) : (nkt == 1 || nkt == 2 || nkt == 4));
+  const bool inst = k1 ? Dw48NktK1::has(nkt) : (k3 ? Dw48NktK3::has(nkt) : (sh.nh == 1 ? Dw48NktS2::has(nkt) : Dw48NktS2Halves::has(nkt)));
   if (!inst) return z;
   if ((long long)op.batch * op.out_h * op.out_w >= (1ll << 31)) return z;
   return sh;
@@ -395,44 +393,21 @@ int launch_dw48(const y3_op *ops, const y3_step &step, const void *d_in, const v
   a.m_inner = (double)op.ksize * op.ksize * op.in_c * op.out_c > (double)op.batch * op.in_h * op.in_w * op.in_c;   // weights outweigh the activations
   const Dw48Shape sh = dw48_shape(op);
   a.hr = sh.rows;
-  dw48_fast_div((uint32_t)a.HW, a.mul_hw, a.sh_hw);
-  dw48_fast_div((uint32_t)a.W, a.mul_w, a.sh_w);
+  y3_fast_div((uint32_t)a.HW, a.mul_hw, a.sh_hw);
+  y3_fast_div((uint32_t)a.W, a.mul_w, a.sh_w);
   a.flags = op.flags;
   const int nkt = sh.cin_img / 64;
   const size_t lds = (size_t)(a.hr + 1) * sh.cin_img * 2 + 1024;   // (+ the tail of the last 1-KiB piece)
   const dim3 grid(y3_ceil_div(a.M, 48) * a.n_ctiles), block(Y3_DW48_HELPERS ? 512 : 64 * nw);
-  const int ks = op.ksize, st = op.stride, nh = sh.nh;
   return y3_by_dtype16(op.dtype, [&](auto tag) {
     typedef decltype(tag) T;
-    static Y3DeviceOnce once;
-    {
-      const int rc1 = once.run([]() -> int {
-#define Y3_DW48_ATTR(KS_, NKT_) Y3_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(conv_dw48_kernel<T, KS_, NKT_>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024))
-        Y3_DW48_ATTR(3, 2); Y3_DW48_ATTR(3, 4); Y3_DW48_ATTR(3, 8);
-        Y3_DW48_ATTR(1, 2); Y3_DW48_ATTR(1, 4); Y3_DW48_ATTR(1, 6); Y3_DW48_ATTR(1, 8); Y3_DW48_ATTR(1, 12); Y3_DW48_ATTR(1, 16);
-#undef Y3_DW48_ATTR
-#define Y3_DW48_ATTR2(NKT_, NH_) Y3_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(conv_dw48_kernel<T, 3, NKT_, 2, NH_>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024))
-        Y3_DW48_ATTR2(1, 1); Y3_DW48_ATTR2(2, 1); Y3_DW48_ATTR2(4, 1); Y3_DW48_ATTR2(2, 2); Y3_DW48_ATTR2(4, 2);
-#undef Y3_DW48_ATTR2
-        return Y3_OK;
-      });
-      if (rc1 != Y3_OK) return rc1;
-    }
-#define Y3_DW48_GO(KS_, NKT_) Y3_LAUNCH((conv_dw48_kernel<T, KS_, NKT_>), grid, block, lds, s, a)
-    if (ks == 3 && st == 2) {
-#define Y3_DW48_GO2(NKT_, NH_) Y3_LAUNCH((conv_dw48_kernel<T, 3, NKT_, 2, NH_>), grid, block, lds, s, a)
-      if (nkt == 1) Y3_DW48_GO2(1, 1); else if (nkt == 2 && nh == 1) Y3_DW48_GO2(2, 1); else if (nkt == 4 && nh == 1) Y3_DW48_GO2(4, 1);
-      else if (nkt == 2) Y3_DW48_GO2(2, 2); else Y3_DW48_GO2(4, 2);
-#undef Y3_DW48_GO2
-    } else if (ks == 3) {
-      if (nkt == 2) Y3_DW48_GO(3, 2); else if (nkt == 4) Y3_DW48_GO(3, 4); else Y3_DW48_GO(3, 8);
-    } else {
-      if (nkt == 2) Y3_DW48_GO(1, 2); else if (nkt == 4) Y3_DW48_GO(1, 4); else if (nkt == 6) Y3_DW48_GO(1, 6);
-      else if (nkt == 8) Y3_DW48_GO(1, 8); else if (nkt == 12) Y3_DW48_GO(1, 12); else Y3_DW48_GO(1, 16);
-    }
-#undef Y3_DW48_GO
-    Y3_HIP_CHECK(hipGetLastError());
-    return Y3_OK;
+    if (op.ksize == 3 && op.stride == 1)
+      return Dw48NktK3::pick(nkt, [&](auto k) { return y3_launch<conv_dw48_kernel<T, 3, k.value>>(grid, block, lds, s, a); });
+    if (op.ksize == 1)
+      return Dw48NktK1::pick(nkt, [&](auto k) { return y3_launch<conv_dw48_kernel<T, 1, k.value>>(grid, block, lds, s, a); });
+    if (sh.nh == 1)
+      return Dw48NktS2::pick(nkt, [&](auto k) { return y3_launch<conv_dw48_kernel<T, 3, k.value, 2, 1>>(grid, block, lds, s, a); });
+    return Dw48NktS2Halves::pick(nkt, [&](auto k) { return y3_launch<conv_dw48_kernel<T, 3, k.value, 2, 2>>(grid, block, lds, s, a); });
   });
 }
 

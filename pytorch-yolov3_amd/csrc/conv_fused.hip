@@ -956,27 +956,13 @@ static int launch_stem_s2(const y3_op *ops, const y3_step &st, const void *d_in,
     a.out = static_cast<T *>(op1.d_out);
     a.out_ld = op1.out_ld; a.Ho = op1.out_h; a.Wo = op1.out_w;
     a.dbg = 0;
-    static Y3DeviceOnce once;                          // (one per element type: the lambda is instantiated per T)
-    int n_cu = 0;
-    {
-      const int rc = once.run([]() -> int {
-        Y3_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(conv_stem_s2_fused_kernel<T>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, kLds));
-        Y3_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(conv_stem_s2_ws_kernel<T, 4>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, kPLds));
-        return Y3_OK;
-      }, &n_cu);
-      if (rc != Y3_OK) return rc;
-    }
     const bool pipelined = st.pipelined;
     a.tiles_x = y3_ceil_div(a.Wo, pipelined ? kPX : kTO);
     a.tiles_y = y3_ceil_div(a.Ho, pipelined ? kPY : kTO);
     a.n_tiles = a.tiles_x * a.tiles_y * a.batch;
-    const int grid = a.n_tiles < n_cu ? a.n_tiles : n_cu;
-    if (pipelined) Y3_LAUNCH((conv_stem_s2_ws_kernel<T, 4>), dim3(grid), dim3(1024), kPLds, s, a);
-    else Y3_LAUNCH(conv_stem_s2_fused_kernel<T>, dim3(grid), dim3(kThreads), kLds, s, a);
-    Y3_HIP_CHECK(hipGetLastError());
-    return Y3_OK;
+    const int n_cu = y3_device_cus(), grid = a.n_tiles < n_cu ? a.n_tiles : n_cu;
+    if (!pipelined) return y3_launch<conv_stem_s2_fused_kernel<T>>(dim3(grid), dim3(kThreads), kLds, s, a);
+    return y3_launch<conv_stem_s2_ws_kernel<T, 4>>(dim3(grid), dim3(1024), kPLds, s, a);
   });
 }
 
@@ -1015,20 +1001,8 @@ static int launch_resblock(const y3_op *ops, const y3_step &, const void *, cons
     a.tiles_x = y3_ceil_div(a.W, kRT);
     a.tiles_y = y3_ceil_div(a.H, kRT);
     a.n_tiles = a.tiles_x * a.tiles_y * a.batch;
-    static Y3DeviceOnce once;
-    int n_cu = 0;
-    {
-      const int rc = once.run([]() -> int {
-        Y3_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(conv_resblock_fused_kernel<T>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, kRLds));
-        return Y3_OK;
-      }, &n_cu);
-      if (rc != Y3_OK) return rc;
-    }
-    const int grid = a.n_tiles < n_cu ? a.n_tiles : n_cu;
-    Y3_LAUNCH(conv_resblock_fused_kernel<T>, dim3(grid), dim3(kThreads), kRLds, s, a);
-    Y3_HIP_CHECK(hipGetLastError());
-    return Y3_OK;
+    const int n_cu = y3_device_cus(), grid = a.n_tiles < n_cu ? a.n_tiles : n_cu;
+    return y3_launch<conv_resblock_fused_kernel<T>>(dim3(grid), dim3(kThreads), kRLds, s, a);
   });
 }
 

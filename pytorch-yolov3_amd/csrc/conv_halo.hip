@@ -42,7 +42,7 @@ struct HaloArgs {
   int k_ld;
   int nchunks;         // Cin / BKE
   int n_tiles;
-  int ngrp_w, m_tiles; // strip kernel's tile order: channel tiles in groups of ngrp_w, pixel tiles inside a group (see launch_halo_ws)
+  int ngrp_w, m_tiles; // strip kernel's tile order: channel tiles in groups of ngrp_w, pixel tiles inside a group (see halo_tile_groups)
   int hr;              // halo rows that hold pixels (256 + 2W + 2); strip kernel: row `hr` of each buffer is all zero
   int hr_pad;          // halo rows, padded to a multiple of the loader's rows-per-pass
   int na;              // loader passes per halo (= glds per thread per halo)
@@ -1249,12 +1249,47 @@ __global__ __launch_bounds__(512, 2) void conv_halo_dw_kernel(HaloArgs p) {
 #endif
 }
 
-// n / d == (umulhi(n, mul) + n) >> sh for 0 <= n < 2^31 (round-up method, d >= 1)
-void fast_div(uint32_t d, uint32_t &mul, uint32_t &sh) {
-  if (d <= 1) { mul = 0; sh = 0; return; }
-  sh = 0;
-  while ((1u << sh) < d) ++sh;
-  mul = (uint32_t)((((uint64_t)1 << 32) * (((uint64_t)1 << sh) - d)) / d + 1);
+// HaloArgs of a 3x3 stride-1 conv with `wgt` as its weights and tile_n output channels per tile: all but the tile geometry,
+// which each launcher sets
+HaloArgs halo_args(const y3_op &op, const void *wgt, const void *d_in, const void *d_zero, int tile_n) {
+  HaloArgs a;
+  a.in = static_cast<const char *>(d_in);
+  a.wgt = static_cast<const char *>(wgt);
+  a.scale = op.d_scale; a.bias = op.d_bias;
+  a.res = static_cast<const char *>(op.d_res);
+  a.out = static_cast<char *>(op.d_out);
+  a.zero = static_cast<const char *>(d_zero);
+  a.H = op.in_h; a.W = op.in_w; a.Cin = op.in_c; a.in_ld = op.in_ld;
+  a.Cout = op.out_c; a.out_ld = op.out_ld; a.res_ld = op.res_ld;
+  a.HW = op.in_h * op.in_w;
+  a.M = op.batch * a.HW;
+  a.k_ld = op.k_ld;
+  a.nchunks = op.in_c / (128 / y3_elem_size(op.dtype));
+  a.n_tiles = op.out_c / tile_n;
+  a.hr = a.hr_pad = a.na = a.a_bytes = 0;
+  a.ngrp_w = a.n_tiles; a.m_tiles = 0;
+  y3_fast_div((uint32_t)a.HW, a.mul_hw, a.sh_hw);
+  y3_fast_div((uint32_t)a.W, a.mul_w, a.sh_w);
+  a.flags = op.flags;
+  return a;
+}
+
+// Tile order and HBM traffic of the strip kernels: the ngrp_w for a.  Each XCD (own L2) gets one contiguous run of tile ids.
+// With all channel tiles innermost (ngrp_w = n_tiles) a run covers a few pixel tiles x ALL weight panels: every XCD fetches
+// the whole weight matrix -- fine while the input outweighs it (76^2, 38^2), 75 MB of extra fetches per launch at 19^2
+// (9.4 MB of weights, 5.9 MB of input).  With channel tiles in pn groups the XCDs split into pn sets of 8 / pn, each set
+// owning one group's panels and all pixels: extra fetches ~ pn x input + (8 / pn) x weights; pick the pn (1, 2, 4, 8 dividing
+// n_tiles) that minimises it.  Placement only: results and per-tile time do not change.
+int halo_tile_groups(const HaloArgs &a) {
+  const double in_b = (double)a.M * a.Cin, w_b = 9.0 * a.Cin * a.Cout;
+  int best = 1;
+  double best_cost = 0;
+  for (int pn = 1; pn <= 8; pn <<= 1) {
+    if (a.n_tiles % pn) break;
+    const double cost = pn * in_b + (8.0 / pn) * w_b;
+    if (pn == 1 || cost < 0.9 * best_cost) { best = pn; best_cost = cost; }
+  }
+  return a.n_tiles / best;
 }
 
 // 192-pixel tiles (MI = 3) when they finish sooner than 256-pixel tiles: rounds of workgroups (one per CU) x per-tile
@@ -1279,70 +1314,6 @@ static int halo_tile_fragments(int M, int n_tiles, int nchunks, int n_cu, const 
   return best_mi;
 }
 
-template <typename T>
-int launch_halo_ws(const HaloArgs &a0, int mi, hipStream_t s) {
-  HaloArgs a = a0;
-  static Y3DeviceOnce once;
-  {
-    const int rc = once.run([]() -> int {
-      Y3_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(conv_halo_ws_kernel<T, 3, 4>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      Y3_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(conv_halo_ws_kernel<T, 4, 4>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      Y3_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(conv_halo_ws_kernel<T, 3, 3>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      Y3_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(conv_halo_ws_kernel<T, 4, 3>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      return Y3_OK;
-    });
-    if (rc != Y3_OK) return rc;
-  }
-  const int bm = 64 * mi;
-  const int hr = bm + 2 * a.W + 2;
-  a.hr = hr;
-  a.na = y3_ceil_div(hr + 2, 32);                     // + the two zero rows (hr is even: rows hr, hr + 1 = one 256-byte bank row)
-  a.hr_pad = a.na * 32;
-  a.a_bytes = a.hr_pad * 128;
-  // the next chunk's halo goes out two passes per K-step and must be older than the last loads allowed in flight
-  int nsb = 0;
-  size_t lds = 0;
-  for (int c = 4; c >= 3; --c) {
-    if (a.na > (c == 4 ? 12 : 14)) continue;   // all real halo slices out by tap 5 (4 slots) / 6 (3 slots)
-    lds = (size_t)c * 128 * 128 + (size_t)2 * a.a_bytes;
-    if (lds < (size_t)bm * 128 * 4) lds = (size_t)bm * 128 * 4;
-    if (lds <= 160 * 1024) { nsb = c; break; }
-  }
-  Y3_REQUIRE(nsb != 0, "wave-specialised halo kernel: row width %d does not fit", a.W);
-  a.m_tiles = y3_ceil_div(a.M, bm);
-  // Tile order and HBM traffic.  Each XCD (own L2) gets one contiguous run of tile ids.  With all channel tiles innermost
-  // (ngrp_w = n_tiles) a run covers a few pixel tiles x ALL weight panels: every XCD fetches the whole weight matrix -- fine
-  // while the input outweighs it (76^2, 38^2), 75 MB of extra fetches per launch at 19^2 (9.4 MB of weights, 5.9 MB of
-  // input).  With channel tiles in pn groups the XCDs split into pn sets of 8 / pn, each set owning one group's panels and
-  // all pixels: extra fetches ~ pn x input + (8 / pn) x weights; pick the pn (1, 2, 4, 8 dividing n_tiles) that minimises
-  // it.  Placement only: results and per-tile time do not change.
-  {
-    const double in_b = (double)a.M * a.Cin, w_b = 9.0 * a.Cin * a.Cout;
-    int best = 1;
-    double best_cost = 0;
-    for (int pn = 1; pn <= 8; pn <<= 1) {
-      if (a.n_tiles % pn) break;
-      const double cost = pn * in_b + (8.0 / pn) * w_b;
-      if (pn == 1 || cost < 0.9 * best_cost) { best = pn; best_cost = cost; }
-    }
-    a.ngrp_w = a.n_tiles / best;
-  }
-  const dim3 grid(a.m_tiles * a.n_tiles);
-  if (mi == 3) {
-    if (nsb == 4) Y3_LAUNCH((conv_halo_ws_kernel<T, 4, 3>), grid, dim3(768), lds, s, a);
-    else Y3_LAUNCH((conv_halo_ws_kernel<T, 3, 3>), grid, dim3(768), lds, s, a);
-  } else {
-    if (nsb == 4) Y3_LAUNCH((conv_halo_ws_kernel<T, 4, 4>), grid, dim3(768), lds, s, a);
-    else Y3_LAUNCH((conv_halo_ws_kernel<T, 3, 4>), grid, dim3(768), lds, s, a);
-  }
-  Y3_HIP_CHECK(hipGetLastError());
-  return Y3_OK;
-}
-
 // [Cout_pad][k_ld] 16-bit weights -> fragment order: 1-KiB blocks of 16 channels x 32 K-elements, lane l = fq * 16 + fr of a
 // wave holds channel fr, K-elements [8 fq, 8 fq + 8) of the block at l * 16 (the MFMA operand layout of y3_mfma16's first
 // operand); block (cb, kb) at (cb * (k_ld / 32) + kb) << 10.  One thread per 16 bytes.
@@ -1361,80 +1332,11 @@ __global__ __launch_bounds__(256) void weights_to_fragment_order_kernel(const u3
 }
 
 constexpr int DW_BM = 192;
-
-template <typename T>
-int launch_halo_dw(const HaloArgs &a0, hipStream_t s) {
-  HaloArgs a = a0;
-  static Y3DeviceOnce once;
-  int n_cu = 256;
-  {
-    const int rc = once.run([]() -> int {
-      Y3_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(conv_halo_dw_kernel<T, 4>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      Y3_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(conv_halo_dw_kernel<T, 5>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      Y3_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(conv_halo_dw_kernel<T, 6>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      return Y3_OK;
-    }, &n_cu);
-    if (rc != Y3_OK) return rc;
-  }
-  a.hr = DW_BM + 2 * a.W + 2;
-  a.na = y3_ceil_div(a.hr + 2, 64);                   // + the two zero rows
-  a.hr_pad = a.na * 64;
-  a.a_bytes = a.hr_pad * 128;
-  size_t lds = (size_t)2 * a.a_bytes;
-  if (lds < (size_t)DW_BM * 128 * 4) lds = (size_t)DW_BM * 128 * 4;
-  Y3_REQUIRE(a.na >= 4 && a.na <= 6 && lds <= 160 * 1024, "direct-weights halo kernel: row width %d does not fit", a.W);
-  a.m_tiles = y3_ceil_div(a.M, DW_BM);
-  a.n_tiles = a.Cout / 256;
-  {
-    // tile order over the XCDs: as launch_halo_ws
-    const double in_b = (double)a.M * a.Cin, w_b = 9.0 * a.Cin * a.Cout;
-    int best = 1;
-    double best_cost = 0;
-    for (int pn = 1; pn <= 8; pn <<= 1) {
-      if (a.n_tiles % pn) break;
-      const double cost = pn * in_b + (8.0 / pn) * w_b;
-      if (pn == 1 || cost < 0.9 * best_cost) { best = pn; best_cost = cost; }
-    }
-    a.ngrp_w = a.n_tiles / best;
-  }
-  const dim3 grid(a.m_tiles * a.n_tiles);
-  // halo passes per chunk: 4 (rows of up to 30 pixels), 5 (up to 62), 6 (up to 94)
-  if (a.na == 4) Y3_LAUNCH((conv_halo_dw_kernel<T, 4>), grid, dim3(512), lds, s, a);
-  else if (a.na == 5) Y3_LAUNCH((conv_halo_dw_kernel<T, 5>), grid, dim3(512), lds, s, a);
-  else Y3_LAUNCH((conv_halo_dw_kernel<T, 6>), grid, dim3(512), lds, s, a);
-  Y3_HIP_CHECK(hipGetLastError());
-  return Y3_OK;
-}
-
-template <typename T>
-int launch_patch_wsp(const HaloArgs &a0, hipStream_t s) {
-  HaloArgs a = a0;
-  constexpr int TY = 8, TX = 32, PROWS = (TY + 2) * (TX + 2);
-  a.na = y3_ceil_div(PROWS, 32);
-  a.hr_pad = a.na * 32;
-  a.a_bytes = a.hr_pad * 128;
-  const size_t lds = (size_t)4 * 128 * 128 + (size_t)2 * a.a_bytes;
-  static_assert(PROWS <= 12 * 32, "all patch slices must be out by tap 5 (4-slot ring)");
-  static Y3DeviceOnce once;
-  int n_cu = 0;
-  {
-    const int rc = once.run([]() -> int {
-      Y3_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(conv_patch_wsp_kernel<T, 4>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      return Y3_OK;
-    }, &n_cu);
-    if (rc != Y3_OK) return rc;
-  }
-  const int tiles_x = y3_ceil_div(a.W, TX), tiles_y = y3_ceil_div(a.H, TY);
-  const int tiles = tiles_x * tiles_y * (a.M / a.HW) * a.n_tiles;
-  const int grid = tiles < n_cu ? tiles : n_cu;
-  Y3_LAUNCH((conv_patch_wsp_kernel<T, 4>), dim3(grid), dim3(768), lds, s, a, tiles, tiles_x, tiles_y);
-  Y3_HIP_CHECK(hipGetLastError());
-  return Y3_OK;
-}
+// instantiated forms: wave-specialised kernel 64-pixel fragments per tile (MI) x weight slots (NSB); direct-weights kernel
+// halo passes per chunk (NA: 4 for rows of up to 30 pixels, 5 up to 62, 6 up to 94)
+using HaloWsMi = y3_ints<4, 3>;
+using HaloWsNsb = y3_ints<3, 4>;
+using HaloDwNa = y3_ints<4, 5, 6>;
 
 }  // namespace
 
@@ -1463,7 +1365,7 @@ bool y3_conv_halo_ws_fits(const y3_op &op) {
 bool y3_conv_halo_dw_fits(const y3_op &op) {
   if (!y3_conv_halo_eligible(op) || !y3_is16(op.dtype) || op.out_c % 256 != 0 || op.cout_pad % 32 != 0 || op.k_ld % 32 != 0) return false;
   const int na = y3_ceil_div(DW_BM + 2 * op.in_w + 4, 64);
-  return na >= 4 && na <= 6 && y3_conv_halo_ws_fits(op);
+  return HaloDwNa::has(na) && y3_conv_halo_ws_fits(op);
 }
 
 // Where it is the better kernel.  Per workgroup the two strip kernels do the same work per cycle (PMC, profiles/r05s: 64 % of
@@ -1498,26 +1400,22 @@ int y3_conv_halo_dw_make_weights(const y3_op &op, void *dst, hipStream_t s) {
 
 static int launch_conv_halo_dw(const y3_op *ops, const y3_step &st, const void *d_in, const void *d_zero, hipStream_t s) {
   const y3_op &op = ops[0];
-  HaloArgs a;
-  a.in = static_cast<const char *>(d_in);
-  a.wgt = static_cast<const char *>(st.frag_w);
-  a.scale = op.d_scale; a.bias = op.d_bias;
-  a.res = static_cast<const char *>(op.d_res);
-  a.out = static_cast<char *>(op.d_out);
-  a.zero = static_cast<const char *>(d_zero);
-  a.H = op.in_h; a.W = op.in_w; a.Cin = op.in_c; a.in_ld = op.in_ld;
-  a.Cout = op.out_c; a.out_ld = op.out_ld; a.res_ld = op.res_ld;
-  a.HW = op.in_h * op.in_w;
-  a.M = op.batch * a.HW;
-  a.k_ld = op.k_ld;
-  a.nchunks = op.in_c / 64;
-  a.n_tiles = op.out_c / 256;
-  a.hr = a.hr_pad = a.na = a.a_bytes = 0;
-  a.ngrp_w = a.n_tiles; a.m_tiles = 0;
-  fast_div((uint32_t)a.HW, a.mul_hw, a.sh_hw);
-  fast_div((uint32_t)a.W, a.mul_w, a.sh_w);
-  a.flags = op.flags;
-  return y3_by_dtype16(op.dtype, [&](auto tag) { return launch_halo_dw<decltype(tag)>(a, s); });
+  HaloArgs a = halo_args(op, st.frag_w, d_in, d_zero, 256);
+  a.hr = DW_BM + 2 * a.W + 2;
+  a.na = y3_ceil_div(a.hr + 2, 64);                   // + the two zero rows
+  a.hr_pad = a.na * 64;
+  a.a_bytes = a.hr_pad * 128;
+  size_t lds = (size_t)2 * a.a_bytes;
+  if (lds < (size_t)DW_BM * 128 * 4) lds = (size_t)DW_BM * 128 * 4;
+  Y3_REQUIRE(HaloDwNa::has(a.na) && lds <= 160 * 1024, "direct-weights halo kernel: row width %d does not fit", a.W);
+  a.m_tiles = y3_ceil_div(a.M, DW_BM);
+  a.ngrp_w = halo_tile_groups(a);
+  const dim3 grid(a.m_tiles * a.n_tiles);
+  return y3_by_dtype16(op.dtype, [&](auto tag) {
+    return HaloDwNa::pick(a.na, [&](auto na) {
+      return y3_launch<conv_halo_dw_kernel<decltype(tag), na.value>>(grid, dim3(512), lds, s, a);
+    });
+  });
 }
 
 int y3_choose_conv_halo_dw(const y3_op &op, y3_step &st) {
@@ -1542,26 +1440,20 @@ bool y3_conv_patch_fits(const y3_op &op) {
 
 static int launch_conv_patch(const y3_op *ops, const y3_step &, const void *d_in, const void *d_zero, hipStream_t s) {
   const y3_op &op = ops[0];
-  const int es = y3_elem_size(op.dtype);
-  HaloArgs a;
-  a.in = static_cast<const char *>(d_in);
-  a.wgt = static_cast<const char *>(op.d_weight);
-  a.scale = op.d_scale; a.bias = op.d_bias;
-  a.res = static_cast<const char *>(op.d_res);
-  a.out = static_cast<char *>(op.d_out);
-  a.zero = static_cast<const char *>(d_zero);
-  a.H = op.in_h; a.W = op.in_w; a.Cin = op.in_c; a.in_ld = op.in_ld;
-  a.Cout = op.out_c; a.out_ld = op.out_ld; a.res_ld = op.res_ld;
-  a.HW = op.in_h * op.in_w;
-  a.M = op.batch * a.HW;
-  a.k_ld = op.k_ld;
-  a.nchunks = op.in_c / (128 / es);
-  a.n_tiles = op.out_c / 128;
-  a.hr_pad = a.na = a.a_bytes = 0;
-  a.ngrp_w = a.n_tiles; a.m_tiles = 0;
-  a.mul_hw = a.sh_hw = a.mul_w = a.sh_w = 0;
-  a.flags = op.flags | (y3_debug_flags() ? 0x40000000u : 0u);
-  return y3_by_dtype(op.dtype, [&](auto tag) { return launch_patch_wsp<decltype(tag)>(a, s); });
+  HaloArgs a = halo_args(op, op.d_weight, d_in, d_zero, 128);
+  a.flags |= y3_debug_flags() ? 0x40000000u : 0u;
+  constexpr int TY = 8, TX = 32, PROWS = (TY + 2) * (TX + 2);
+  static_assert(PROWS <= 12 * 32, "all patch slices must be out by tap 5 (4-slot ring)");
+  a.na = y3_ceil_div(PROWS, 32);
+  a.hr_pad = a.na * 32;
+  a.a_bytes = a.hr_pad * 128;
+  const size_t lds = (size_t)4 * 128 * 128 + (size_t)2 * a.a_bytes;
+  const int tiles_x = y3_ceil_div(a.W, TX), tiles_y = y3_ceil_div(a.H, TY);
+  const int tiles = tiles_x * tiles_y * (a.M / a.HW) * a.n_tiles, n_cu = y3_device_cus();
+  const dim3 grid(tiles < n_cu ? tiles : n_cu);
+  return y3_by_dtype(op.dtype, [&](auto tag) {
+    return y3_launch<conv_patch_wsp_kernel<decltype(tag), 4>>(grid, dim3(768), lds, s, a, tiles, tiles_x, tiles_y);
+  });
 }
 
 int y3_choose_conv_patch(const y3_op &op, y3_step &st) {
@@ -1573,27 +1465,34 @@ int y3_choose_conv_patch(const y3_op &op, y3_step &st) {
 
 static int launch_conv_halo(const y3_op *ops, const y3_step &st, const void *d_in, const void *d_zero, hipStream_t s) {
   const y3_op &op = ops[0];
-  const int es = y3_elem_size(op.dtype);
-  HaloArgs a;
-  a.in = static_cast<const char *>(d_in);
-  a.wgt = static_cast<const char *>(op.d_weight);
-  a.scale = op.d_scale; a.bias = op.d_bias;
-  a.res = static_cast<const char *>(op.d_res);
-  a.out = static_cast<char *>(op.d_out);
-  a.zero = static_cast<const char *>(d_zero);
-  a.H = op.in_h; a.W = op.in_w; a.Cin = op.in_c; a.in_ld = op.in_ld;
-  a.Cout = op.out_c; a.out_ld = op.out_ld; a.res_ld = op.res_ld;
-  a.HW = op.in_h * op.in_w;
-  a.M = op.batch * a.HW;
-  a.k_ld = op.k_ld;
-  a.nchunks = op.in_c / (128 / es);
-  a.n_tiles = op.out_c / 128;
-  a.hr_pad = a.na = a.a_bytes = 0;
-  a.ngrp_w = a.n_tiles; a.m_tiles = 0;
-  fast_div((uint32_t)a.HW, a.mul_hw, a.sh_hw);
-  fast_div((uint32_t)a.W, a.mul_w, a.sh_w);
-  a.flags = op.flags | (y3_debug_flags() ? 0x40000000u : 0u);
-  return y3_by_dtype(op.dtype, [&](auto tag) { return launch_halo_ws<decltype(tag)>(a, st.bm / 64, s); });
+  HaloArgs a = halo_args(op, op.d_weight, d_in, d_zero, 128);
+  a.flags |= y3_debug_flags() ? 0x40000000u : 0u;
+  const int mi = st.bm / 64;
+  const int bm = 64 * mi;
+  a.hr = bm + 2 * a.W + 2;
+  a.na = y3_ceil_div(a.hr + 2, 32);                   // + the two zero rows (hr is even: rows hr, hr + 1 = one 256-byte bank row)
+  a.hr_pad = a.na * 32;
+  a.a_bytes = a.hr_pad * 128;
+  // the next chunk's halo goes out two passes per K-step and must be older than the last loads allowed in flight
+  int nsb = 0;
+  size_t lds = 0;
+  for (int c = 4; c >= 3; --c) {
+    if (a.na > (c == 4 ? 12 : 14)) continue;   // all real halo slices out by tap 5 (4 slots) / 6 (3 slots)
+    lds = (size_t)c * 128 * 128 + (size_t)2 * a.a_bytes;
+    if (lds < (size_t)bm * 128 * 4) lds = (size_t)bm * 128 * 4;
+    if (lds <= 160 * 1024) { nsb = c; break; }
+  }
+  Y3_REQUIRE(nsb != 0, "wave-specialised halo kernel: row width %d does not fit", a.W);
+  a.m_tiles = y3_ceil_div(a.M, bm);
+  a.ngrp_w = halo_tile_groups(a);
+  const dim3 grid(a.m_tiles * a.n_tiles);
+  return y3_by_dtype(op.dtype, [&](auto tag) {
+    return HaloWsMi::pick(mi, [&](auto m) {
+      return HaloWsNsb::pick(nsb, [&](auto ns) {
+        return y3_launch<conv_halo_ws_kernel<decltype(tag), ns.value, m.value>>(grid, dim3(768), lds, s, a);
+      });
+    });
+  });
 }
 
 int y3_choose_conv_halo(const y3_op &op, const y3_options &o, y3_step &st) {

@@ -45,11 +45,9 @@ struct IgemmArgs {
   uint32_t flags;
   // detection-head fusion (conv_igemm2_kernel<..., DECODE = true>): the YOLO decode of yolo_decode.hip runs on the
   // parked fp32 tile instead of a second kernel reading it back from HBM
-  float *y_bbox, *y_prob;
-  long long *y_cls;
-  int y_anchors, y_attr, y_row_offset, y_rows_total;
-  float y_net_w, y_net_h, y_sxy, y_aw[8], y_ah[8];
+  Y3DecodeArgs dec;
 };
+static_assert(offsetof(IgemmArgs, dec) == 168 && sizeof(IgemmArgs) == 288, "kernel argument layout");
 
 template <typename T>
 struct Mma {
@@ -886,50 +884,51 @@ void conv_igemm3_kernel(IgemmArgs p) {
 // y3_options: igemm_version 1 = register-staged single buffer, 2 = LDS-DMA double buffer, 3 = wave-specialised;
 // igemm_bm 64 = 64-pixel tiles for the wave-specialised kernel (bf16), else 128; igemm_ns = its LDS stages (3 or 4)
 
-template <typename T, int BM, int BN, int WM, int WN, int NS>
-int launch_cfg3x(IgemmArgs a, int kmode, hipStream_t s) {
-  a.m_tiles = y3_ceil_div(a.M, BM);
-  a.n_tiles = y3_ceil_div(a.Cout, BN);
-  const dim3 grid(a.m_tiles * a.n_tiles), block(128 * WM * WN);
-  if (kmode == 0) Y3_LAUNCH((conv_igemm3_kernel<T, BM, BN, WM, WN, 0, NS>), grid, block, 0, s, a);
-  else if (kmode == 2) Y3_LAUNCH((conv_igemm3_kernel<T, BM, BN, WM, WN, 2, NS>), grid, block, 0, s, a);
-  else Y3_LAUNCH((conv_igemm3_kernel<T, BM, BN, WM, WN, 1, NS>), grid, block, 0, s, a);
-  Y3_HIP_CHECK(hipGetLastError());
-  return Y3_OK;
+// Instantiated forms: the K-tiling modes (igemm_ktiles), and the tiles of each version as codes BM << 16 | BN, whose waves
+// are 2 x 2, or 4 x 1 for 32-channel tiles and 1 x 4 for 64-pixel tiles
+using IgemmKmodes = y3_ints<0, 2, 1>;
+constexpr int igemm_tile(int bm, int bn) { return bm << 16 | bn; }
+using IgemmTiles1 = y3_ints<igemm_tile(128, 128), igemm_tile(128, 64), igemm_tile(128, 32)>;
+using IgemmTiles2 = y3_ints<igemm_tile(96, 64), igemm_tile(128, 128), igemm_tile(128, 64), igemm_tile(128, 32)>;
+using IgemmTiles3 = y3_ints<igemm_tile(64, 128), igemm_tile(128, 128)>;   // 64-pixel tiles: 16-bit modes only
+using IgemmNs = y3_ints<4, 3>;
+
+template <int TILE>
+struct IgemmShape {
+  static constexpr int BM = TILE >> 16, BN = TILE & 0xffff;
+  static constexpr int WM = BM == 64 ? 1 : (BN == 32 ? 4 : 2), WN = 4 / WM;
+};
+
+template <typename T, int TILE, int NS>
+int launch_cfg3(IgemmArgs a, int kmode, hipStream_t s) {
+  typedef IgemmShape<TILE> S;
+  a.m_tiles = y3_ceil_div(a.M, S::BM);
+  a.n_tiles = y3_ceil_div(a.Cout, S::BN);
+  const dim3 grid(a.m_tiles * a.n_tiles), block(128 * S::WM * S::WN);
+  return IgemmKmodes::pick(kmode, [&](auto k) {
+    return y3_launch<conv_igemm3_kernel<T, S::BM, S::BN, S::WM, S::WN, k.value, NS>>(grid, block, 0, s, a);
+  });
 }
 
-template <typename T, int BM, int BN, int WM, int WN>
-int launch_cfg3(const IgemmArgs &a, int kmode, int ns, hipStream_t s) {
-  // (a two-stage form existed; it needed more than the 128 VGPRs that two co-resident workgroups leave and measured
-  // slower than every other variant, so 2 now means 3)
-  if (ns == 4) return launch_cfg3x<T, BM, BN, WM, WN, 4>(a, kmode, s);
-  return launch_cfg3x<T, BM, BN, WM, WN, 3>(a, kmode, s);
-}
-
-template <typename T, int BM, int BN, int WM, int WN>
+template <typename T, int TILE>
 int launch_cfg2(IgemmArgs a, int kmode, hipStream_t s) {
-  a.m_tiles = y3_ceil_div(a.M, BM);
-  a.n_tiles = y3_ceil_div(a.Cout, BN);
-  const dim3 grid(a.m_tiles * a.n_tiles), block(64 * WM * WN);
-  if (kmode == 0) Y3_LAUNCH((conv_igemm2_kernel<T, BM, BN, WM, WN, 0>), grid, block, 0, s, a);
-  else if (kmode == 2) Y3_LAUNCH((conv_igemm2_kernel<T, BM, BN, WM, WN, 2>), grid, block, 0, s, a);
-  else Y3_LAUNCH((conv_igemm2_kernel<T, BM, BN, WM, WN, 1>), grid, block, 0, s, a);
-  Y3_HIP_CHECK(hipGetLastError());
-  return Y3_OK;
+  typedef IgemmShape<TILE> S;
+  a.m_tiles = y3_ceil_div(a.M, S::BM);
+  a.n_tiles = y3_ceil_div(a.Cout, S::BN);
+  const dim3 grid(a.m_tiles * a.n_tiles), block(64 * S::WM * S::WN);
+  return IgemmKmodes::pick(kmode, [&](auto k) {
+    return y3_launch<conv_igemm2_kernel<T, S::BM, S::BN, S::WM, S::WN, k.value>>(grid, block, 0, s, a);
+  });
 }
 
-template <typename T, int BM, int BN, int WM, int WN>
-int launch_cfg(const IgemmArgs &a0, bool generic, hipStream_t s) {
-  IgemmArgs a = a0;
-  a.m_tiles = y3_ceil_div(a.M, BM);
-  a.n_tiles = y3_ceil_div(a.Cout, BN);
+template <typename T, int TILE>
+int launch_cfg(IgemmArgs a, bool generic, hipStream_t s) {
+  typedef IgemmShape<TILE> S;
+  a.m_tiles = y3_ceil_div(a.M, S::BM);
+  a.n_tiles = y3_ceil_div(a.Cout, S::BN);
   const dim3 grid(a.m_tiles * a.n_tiles), block(256);
-  if (generic)
-    Y3_LAUNCH((conv_igemm_kernel<T, BM, BN, WM, WN, true>), grid, block, 0, s, a);
-  else
-    Y3_LAUNCH((conv_igemm_kernel<T, BM, BN, WM, WN, false>), grid, block, 0, s, a);
-  Y3_HIP_CHECK(hipGetLastError());
-  return Y3_OK;
+  if (generic) return y3_launch<conv_igemm_kernel<T, S::BM, S::BN, S::WM, S::WN, true>>(grid, block, 0, s, a);
+  return y3_launch<conv_igemm_kernel<T, S::BM, S::BN, S::WM, S::WN, false>>(grid, block, 0, s, a);
 }
 
 }  // namespace
@@ -946,14 +945,6 @@ bool y3_conv_igemm_supported(const y3_op &op) {
   const int bke = 128 / es;
   if (op.k_ld % bke != 0 || op.k_ld < op.ksize * op.ksize * op.in_c) return false;
   return true;
-}
-
-// n / d == (umulhi(n, mul) + n) >> sh for 0 <= n < 2^31 (round-up method, d >= 1)
-static void igemm_fast_div(uint32_t d, uint32_t &mul, uint32_t &sh) {
-  if (d <= 1) { mul = 0; sh = 0; return; }
-  sh = 0;
-  while ((1u << sh) < d) ++sh;
-  mul = (uint32_t)((((uint64_t)1 << 32) * (((uint64_t)1 << sh) - d)) / d + 1);
 }
 
 // K-tiling mode: 0 one tap per tile, 2 several whole taps per tile, 1 per-chunk taps; and the number of K-tiles
@@ -995,24 +986,36 @@ static int launch_conv_igemm(const y3_op *ops, const y3_step &st, const void *d_
   // launch for 16 MB algorithmic before this, profiles/r03_traffic.json).  Placement only: results do not change.
   a.n_major = (double)op.out_c * a.K > (double)op.batch * op.in_h * op.in_w * op.in_c ? 1 : 0;
   a.flags = op.flags | (y3_debug_flags() ? 0x40000000u : 0u) | (y3_debug_flags() == 2 ? 0x80000000u : 0u);
-  igemm_fast_div((uint32_t)a.HoWo, a.mul_hw, a.sh_hw);
-  igemm_fast_div((uint32_t)a.Wo, a.mul_w, a.sh_w);
-  const int dt = op.dtype, bm = st.bm, bn = st.bn, ns = st.ns;
+  y3_fast_div((uint32_t)a.HoWo, a.mul_hw, a.sh_hw);
+  y3_fast_div((uint32_t)a.Wo, a.mul_w, a.sh_w);
+  const int tile = igemm_tile(st.bm, st.bn);
   if (st.version == 1) {
     const bool generic = kmode != 0;
     if (generic) a.n_ktiles = y3_ceil_div(a.K, bke);
-    if (bn == 128) return y3_by_dtype(dt, [&](auto tag) { return launch_cfg<decltype(tag), 128, 128, 2, 2>(a, generic, s); });
-    if (bn == 64) return y3_by_dtype(dt, [&](auto tag) { return launch_cfg<decltype(tag), 128, 64, 2, 2>(a, generic, s); });
-    return y3_by_dtype(dt, [&](auto tag) { return launch_cfg<decltype(tag), 128, 32, 4, 1>(a, generic, s); });
+    return IgemmTiles1::pick(tile, [&](auto t) {
+      return y3_by_dtype(op.dtype, [&](auto tag) { return launch_cfg<decltype(tag), t.value>(a, generic, s); });
+    });
   }
   if (st.version == 3) {
-    if (bm == 64) return y3_by_dtype16(dt, [&](auto tag) { return launch_cfg3<decltype(tag), 64, 128, 1, 4>(a, kmode, ns, s); });
-    return y3_by_dtype(dt, [&](auto tag) { return launch_cfg3<decltype(tag), 128, 128, 2, 2>(a, kmode, ns, s); });
+    // (a two-stage form existed; it needed more than the 128 VGPRs that two co-resident workgroups leave and measured
+    // slower than every other variant, so 2 now means 3)
+    const int ns = st.ns == 4 ? 4 : 3;
+    return IgemmTiles3::pick(tile, [&](auto t) {
+      auto go = [&](auto tag) {
+        return IgemmNs::pick(ns, [&](auto n) { return launch_cfg3<decltype(tag), t.value, n.value>(a, kmode, s); });
+      };
+      if constexpr (IgemmShape<t.value>::BM == 64) {
+        Y3_REQUIRE(y3_is16(op.dtype), "conv block %d: no 64-pixel float32 tiles", op.block_idx);
+        return y3_by_dtype16(op.dtype, go);
+      } else {
+        return y3_by_dtype(op.dtype, go);
+      }
+    });
   }
-  if (bm == 96) return y3_by_dtype(dt, [&](auto tag) { return launch_cfg2<decltype(tag), 96, 64, 2, 2>(a, kmode, s); });
-  if (bn == 128) return y3_by_dtype(dt, [&](auto tag) { return launch_cfg2<decltype(tag), 128, 128, 2, 2>(a, kmode, s); });
-  if (bn == 64) return y3_by_dtype(dt, [&](auto tag) { return launch_cfg2<decltype(tag), 128, 64, 2, 2>(a, kmode, s); });
-  return y3_by_dtype(dt, [&](auto tag) { return launch_cfg2<decltype(tag), 128, 32, 4, 1>(a, kmode, s); });
+  Y3_REQUIRE(st.version == 2, "implicit GEMM version %d has no kernel", st.version);
+  return IgemmTiles2::pick(tile, [&](auto t) {
+    return y3_by_dtype(op.dtype, [&](auto tag) { return launch_cfg2<decltype(tag), t.value>(a, kmode, s); });
+  });
 }
 
 int y3_choose_conv_igemm(const y3_op &op, const y3_options &o, y3_step &st, int force_version, int force_ns, int force_bm) {
@@ -1124,14 +1127,9 @@ static int launch_head_decode(const y3_op *ops, const y3_step &, const void *, c
   a.n_taps = 1;
   a.n_ktiles = a.ktiles_per_tap;
   a.flags = op0.flags;
-  igemm_fast_div((uint32_t)a.HoWo, a.mul_hw, a.sh_hw);
-  igemm_fast_div((uint32_t)a.Wo, a.mul_w, a.sh_w);
-  a.y_bbox = op1.d_bbox; a.y_prob = op1.d_prob; a.y_cls = reinterpret_cast<long long *>(op1.d_cls);
-  a.y_anchors = op1.n_anchor; a.y_attr = op1.n_attr;
-  a.y_row_offset = op1.row_offset; a.y_rows_total = op1.rows_total;
-  a.y_net_w = op1.net_w; a.y_net_h = op1.net_h;
-  a.y_sxy = y3_op_scale_xy(op1);
-  for (int i = 0; i < 8; ++i) { a.y_aw[i] = op1.anchor_w[i]; a.y_ah[i] = op1.anchor_h[i]; }
+  y3_fast_div((uint32_t)a.HoWo, a.mul_hw, a.sh_hw);
+  y3_fast_div((uint32_t)a.Wo, a.mul_w, a.sh_w);
+  a.dec = y3_decode_args(op1);
   // 64 pixels x all 255 channels per workgroup: 80 KiB of LDS (two operand stages; the padded logit tile of 64 x 260 floats
   // is parked in them), so two workgroups share a CU and one's decode runs under the other's loads (128-pixel tiles, one
   // per CU, measured equal in isolation: profiles/r02n_heads.txt)
@@ -1139,8 +1137,6 @@ static int launch_head_decode(const y3_op *ops, const y3_step &, const void *, c
   a.n_major = 0;
   a.m_tiles = y3_ceil_div(a.M, 64);
   return y3_by_dtype16(op0.dtype, [&](auto tag) {
-    Y3_LAUNCH((conv_igemm2_kernel<decltype(tag), 64, 256, 1, 4, 0, true>), dim3(a.m_tiles), dim3(256), 0, s, a);
-    Y3_HIP_CHECK(hipGetLastError());
-    return Y3_OK;
+    return y3_launch<conv_igemm2_kernel<decltype(tag), 64, 256, 1, 4, 0, true>>(dim3(a.m_tiles), dim3(256), 0, s, a);
   });
 }

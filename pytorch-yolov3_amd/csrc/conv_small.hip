@@ -283,10 +283,8 @@ static int launch_conv_small(const y3_op *ops, const y3_step &, const void *d_in
   const dim3 grid(y3_ceil_div(a.M, 256)), block(256);
   const size_t lds = ((size_t)27 * op.cout_pad + 256) * sizeof(float);
   return y3_by_dtype(odt, [&](auto tag) {
-    if (u8) Y3_LAUNCH((conv_stem3x3_kernel<decltype(tag), 1>), grid, block, lds, s, a);
-    else Y3_LAUNCH((conv_stem3x3_kernel<decltype(tag), 0>), grid, block, lds, s, a);
-    Y3_HIP_CHECK(hipGetLastError());
-    return Y3_OK;
+    if (u8) return y3_launch<conv_stem3x3_kernel<decltype(tag), 1>>(grid, block, lds, s, a);
+    return y3_launch<conv_stem3x3_kernel<decltype(tag), 0>>(grid, block, lds, s, a);
   });
 }
 
@@ -322,9 +320,7 @@ static int launch_conv_stem_mfma(const y3_op *ops, const y3_step &, const void *
     a.tiles_x = y3_ceil_div(op.in_w, kStemTW);
     a.tiles_y = y3_ceil_div(op.in_h, kStemTH);
     a.flags = op.flags;
-    Y3_LAUNCH(conv_stem_mfma_kernel<T>, dim3(a.tiles_x * a.tiles_y * op.batch), dim3(256), 0, s, a);
-    Y3_HIP_CHECK(hipGetLastError());
-    return Y3_OK;
+    return y3_launch<conv_stem_mfma_kernel<T>>(dim3(a.tiles_x * a.tiles_y * op.batch), dim3(256), 0, s, a);
   });
 }
 
@@ -347,9 +343,7 @@ static int launch_conv_direct(const y3_op *ops, const y3_step &, const void *d_i
   a.flags = op.flags;
   const dim3 grid((unsigned)((a.total + 255) / 256)), block(256);
   return y3_by_dtype(op.dtype, [&](auto tag) {
-    Y3_LAUNCH(conv_direct_kernel<decltype(tag)>, grid, block, 0, s, a);
-    Y3_HIP_CHECK(hipGetLastError());
-    return Y3_OK;
+    return y3_launch<conv_direct_kernel<decltype(tag)>>(grid, block, 0, s, a);
   });
 }
 

@@ -14,6 +14,8 @@
 // The box tail is spread over the four lanes (sub 0: x, 1: y, 2: w + objectness, 3: h + best / sum) with selects
 // instead of branches, so no lane idles while one lane does five exponentials and seven divisions.
 #pragma once
+#include <stddef.h>
+
 #include "common.h"
 
 __device__ __forceinline__ float y3_quad_xor1(float v) {
@@ -38,6 +40,27 @@ __device__ __forceinline__ float y3_scale_xy(float sig, float s) {
 }
 // y3_op.scale_x_y as the kernels take it: 0 (a caller that zero-initialises the op) means 1
 static inline float y3_op_scale_xy(const y3_op &op) { return op.scale_x_y == 0.0f ? 1.0f : op.scale_x_y; }
+
+// The decode fields of a fused head kernel's arguments (IgemmArgs, DwArgs: their last member), from the Y3_OP_YOLO op that
+// reads the head conv
+struct Y3DecodeArgs {
+  float *bbox, *prob;
+  long long *cls;
+  int anchors, attr, row_offset, rows_total;
+  float net_w, net_h, sxy, aw[8], ah[8];
+};
+static_assert(sizeof(Y3DecodeArgs) == 120 && offsetof(Y3DecodeArgs, anchors) == 24 && offsetof(Y3DecodeArgs, net_w) == 40 &&
+              offsetof(Y3DecodeArgs, ah) == 84, "layout of the decode fields in the kernel arguments");
+static inline Y3DecodeArgs y3_decode_args(const y3_op &yolo) {
+  Y3DecodeArgs d;
+  d.bbox = yolo.d_bbox; d.prob = yolo.d_prob; d.cls = reinterpret_cast<long long *>(yolo.d_cls);
+  d.anchors = yolo.n_anchor; d.attr = yolo.n_attr;
+  d.row_offset = yolo.row_offset; d.rows_total = yolo.rows_total;
+  d.net_w = yolo.net_w; d.net_h = yolo.net_h;
+  d.sxy = y3_op_scale_xy(yolo);
+  for (int i = 0; i < 8; ++i) { d.aw[i] = yolo.anchor_w[i]; d.ah[i] = yolo.anchor_h[i]; }
+  return d;
+}
 
 // t_: the box's n_attr logits (LDS).  Called by all four lanes of the box together (EXEC must hold whole quads).
 // cell_*: grid column / row of the box's cell; grid_*: grid size; anchor_*: the box's anchor (pixels); net_*: the network
@@ -127,14 +150,15 @@ __device__ __forceinline__ void y3_decode_box4(const float *t_, int n_attr, int 
 // YOLO decode of `rows` pixels whose float32 logits (conv sums with scale / bias already applied) are parked in LDS with
 // a row stride of LD floats (LD odd in units of banks: the per-box reads of adjacent lanes spread over the banks): four
 // lanes per box, y3_decode_box4 above -- the same code as yolo_decode_kernel<4>.  Args: the launch arguments of a fused head kernel
-// (conv_igemm.hip: IgemmArgs, conv_1x1.hip: DwArgs) -- M, HoWo, Wo, Ho, the fast-division constants and the y_* fields of the decode.
+// (conv_igemm.hip: IgemmArgs, conv_1x1.hip: DwArgs) -- M, HoWo, Wo, Ho, the fast-division constants and the decode fields `dec`.
 template <int NT, int LD, typename Args>
 __device__ __forceinline__ void y3_head_decode_rows(const Args &p, const float *sL, int mbase, int rows, int tid) {
-  const int nbox = rows * p.y_anchors;
-  const uint32_t inv_a = (65536u + (uint32_t)p.y_anchors - 1u) / (uint32_t)p.y_anchors;   // box / anchors for box < 8192
+  const Y3DecodeArgs &d = p.dec;
+  const int nbox = rows * d.anchors;
+  const uint32_t inv_a = (65536u + (uint32_t)d.anchors - 1u) / (uint32_t)d.anchors;   // box / anchors for box < 8192
   for (int t = tid; t < nbox * 4; t += NT) {
     const int box = t >> 2, sub = t & 3;
-    const int pl = (int)(((uint32_t)box * inv_a) >> 16), a = box - pl * p.y_anchors;
+    const int pl = (int)(((uint32_t)box * inv_a) >> 16), a = box - pl * d.anchors;
     const long long m = (long long)mbase + pl;
     const bool live = m < p.M;
     const uint32_t um = (uint32_t)(live ? m : p.M - 1);
@@ -144,14 +168,14 @@ __device__ __forceinline__ void y3_head_decode_rows(const Args &p, const float *
     const uint32_t x = rem - y * (uint32_t)p.Wo;
     float comp, score;
     int best_c;
-    y3_decode_box4(sL + pl * LD + a * p.y_attr, p.y_attr, sub, (float)x, (float)y, (float)p.Wo, (float)p.Ho, p.y_aw[a],
-                   p.y_ah[a], p.y_net_w, p.y_net_h, p.y_sxy, comp, score, best_c);
+    y3_decode_box4(sL + pl * LD + a * d.attr, d.attr, sub, (float)x, (float)y, (float)p.Wo, (float)p.Ho, d.aw[a], d.ah[a],
+                   d.net_w, d.net_h, d.sxy, comp, score, best_c);
     if (!live) continue;
-    const long long row = (long long)b * p.y_rows_total + p.y_row_offset + (long long)a * p.HoWo + (long long)y * p.Wo + x;
-    p.y_bbox[row * 4 + sub] = comp;
+    const long long row = (long long)b * d.rows_total + d.row_offset + (long long)a * p.HoWo + (long long)y * p.Wo + x;
+    d.bbox[row * 4 + sub] = comp;
     if (sub == 2) {
-      p.y_prob[row] = score;
-      p.y_cls[row] = best_c;
+      d.prob[row] = score;
+      d.cls[row] = best_c;
     }
   }
 }

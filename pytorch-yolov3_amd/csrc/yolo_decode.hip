@@ -137,10 +137,9 @@ static int launch_yolo(const y3_op *ops, const y3_step &st, const void *d_in, co
   const long long npix = (long long)op.batch * op.in_h * op.in_w;
   const size_t lds = (size_t)kPix * (op.in_ld + 1) * sizeof(float);
   const dim3 grid((unsigned)((npix + kPix - 1) / kPix));
-  if (st.lanes == 4) Y3_LAUNCH(yolo_decode_kernel<4>, grid, dim3(384), lds, s, a);
-  else Y3_LAUNCH(yolo_decode_kernel<1>, grid, dim3(256), lds, s, a);
-  Y3_HIP_CHECK(hipGetLastError());
-  return Y3_OK;
+  return y3_ints<4, 1>::pick(st.lanes, [&](auto lanes) {   // lanes per box
+    return y3_launch<yolo_decode_kernel<lanes.value>>(grid, dim3(lanes.value == 1 ? 256 : 384), lds, s, a);
+  });
 }
 
 int y3_choose_yolo(const y3_op &op, const y3_options &o, y3_step &st) {
