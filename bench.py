@@ -17,15 +17,20 @@ Rank 0 prints ONE JSON line.  `value` = frames of all ranks / max-over-ranks wal
 The timed loop runs exactly K steps after max(W, --streams) warm-up steps (--repeats R: R such windows back to back, the median counts).
 --dump-outputs DIR then writes the detections the last timed step returned as DIR/<name>.npy (frames and weights are
 procedural and seeded: the same arguments give the same inputs, so two builds can be compared output for output).
-At N = 1 the same run also measures and reports, in that line:
+That is all a plain run does: set up, warm up, time, dump, print.  With --full it also measures and reports, in that line:
+  roofline        dominant kernel and per-kernel times (`kernels`), dispatch-bound HIP events on the launch stream
+                  (serial passes after --sustain seconds of load; rank 0, at any N)
+and at N = 1:
   resident        the same steps with the frames already in HBM and the records left there (the kernels alone; r01-r03's `value`)
-  roofline        dominant kernel, HIP events around every launch on the launch stream (serial passes)
   cpu_baseline    the CPU oracle (the reference's "-d cpu" op sequence) on the host cores, SURVEY.md 8(d) protocol
   other_configs   BASELINE.json's other single-GPU configurations (parity cases, each with its own roofline)
   detection_regimes  the headline workload at the reference test's thresholds (0.2 / 0.3) and with ~4000 candidates per frame
                   (the cost of NMS depends on the data)
   bf16_agreement  bf16 detections against the reference's float32 detections on the golden frames (tests/golden)
   f16_agreement   the same for the fp16 storage mode (same kernels on the f16 MFMA; `other_configs` has its rate)
+  latency         batch-1 inference() wall time and the package's batched loops
+--no-cpu-baseline, --no-extras and --no-latency leave sections out of a --full run.  --dump-ops FILE runs the per-kernel passes
+(and reports `roofline` / `kernels`) without --full as well: the table is made from them.
 """
 import argparse
 import hashlib
@@ -67,7 +72,10 @@ def parse_args(argv=None):
     ap.add_argument("--obj-bias", type=float, default=-8.5,
                     help="objectness bias of the procedural weights (sets candidates/frame)")
     ap.add_argument("--kmax", type=int, default=512, help="detection records per frame in the gather")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: per-kernel roofline, and at N = 1 the CPU baseline, the "
+                         "resident rate, the other configurations, detection regimes, latency and detection agreement")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-baseline-child", action="store_true", help="(internal) run only the CPU baseline and print its JSON object")
     ap.add_argument("--repeats", type=int, default=1,
                     help="timed windows of --steps steps each, back to back (default 1: exactly --steps timed steps); value / "
@@ -76,13 +84,14 @@ def parse_args(argv=None):
                     help="after the timed steps, write the detections the last timed step returned (what "
                          "Pipeline.results hands a caller) as DIR/<name>.npy, float32 / float64 (dump_outputs)")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip pcie_inclusive / other_configs / bf16_agreement (A/B runs, profiling)")
+                    help="with --full: skip resident / other_configs / detection_regimes / latency / agreement (A/B runs, profiling)")
     ap.add_argument("--cpu-budget", type=float, default=30.0, help="seconds of CPU-baseline work (bounded sample)")
     ap.add_argument("--profile-passes", type=int, default=24,
                     help="serial passes of the per-kernel report (median per op), right after --sustain seconds of the timed loop")
     ap.add_argument("--sustain", type=float, default=2.0, help="seconds of sustained load before the per-kernel passes")
-    ap.add_argument("--no-latency", action="store_true", help="skip the batch-1 latency / video-loop section")
-    ap.add_argument("--dump-ops", default=None, help="write the per-op timing table (text) to this file")
+    ap.add_argument("--no-latency", action="store_true", help="with --full: skip the batch-1 latency / video-loop section")
+    ap.add_argument("--dump-ops", default=None,
+                    help="write the per-op timing table (text) to this file (runs the per-kernel passes, with or without --full)")
     ap.add_argument("--streams", type=int, default=3,
                     help="batches in flight per GPU: step i runs on HIP stream i %% streams with its own arena, so "
                          "one batch's kernel tails overlap the next batch's ramp-up (1 = strictly serial steps)")
@@ -1201,9 +1210,9 @@ def main(argv=None):
         sys.stderr.write("bench.py: rank %d needs GPU %d, %d visible\n" % (rank, local_rank, torch.cuda.device_count()))
         return 2
     # ---- everything that must happen BEFORE this process touches the GPU (device_count above does not) ----------------
-    # (1) the CPU baseline, in a fresh pinned child process, on an otherwise idle job (rank 0 at N = 1 only)
+    # (1) the CPU baseline, in a fresh pinned child process, on an otherwise idle job (rank 0 at N = 1 only, --full)
     cpu_base = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cpu_base = cpu_baseline_in_child(args)
         phases["cpu_baseline_s"] = round(time.perf_counter() - t_start, 1)
     # (2) this rank's threads onto the CPUs of its GPU's NUMA node (pinned buffers are allocated after this)
@@ -1282,18 +1291,20 @@ def main(argv=None):
     per_rank["placement"] = gathered
     per_rank["cpus_per_rank"] = [p.get("cpus") for p in gathered]
     per_rank["numa_node"] = [p.get("numa_node") for p in gathered]
-    extras = rank == 0 and world == 1 and not args.no_extras and not args.resident and args.scaling == "weak"
+    extras = rank == 0 and world == 1 and args.full and not args.no_extras and not args.resident and args.scaling == "weak"
     line = None
     if rank == 0:
-        traffic_table, traffic_note = load_traffic_table()
-        telemetry = GpuTelemetry(placement.get("gpu_bdf_runtime") or placement.get("gpu_bdf"))
-        sustain_steps = int(args.sustain / max(elapsed / args.steps, 1e-4)) if args.sustain > 0 else 0
-        report = wl.kernel_report(args.profile_passes, args.dump_ops, telemetry=telemetry, sustain_steps=sustain_steps)
+        report = roof = traffic_table = None
+        if args.full or args.dump_ops:        # the per-kernel passes: runs of their own after the timed windows
+            traffic_table, traffic_note = load_traffic_table()
+            telemetry = GpuTelemetry(placement.get("gpu_bdf_runtime") or placement.get("gpu_bdf"))
+            sustain_steps = int(args.sustain / max(elapsed / args.steps, 1e-4)) if args.sustain > 0 else 0
+            report = wl.kernel_report(args.profile_passes, args.dump_ops, telemetry=telemetry, sustain_steps=sustain_steps)
+            roof = wl.roofline(report, traffic_table)
+            roof["traffic_unit"] = traffic_note
         b, dim = my_frames, args.dim
         fps = sum(all_frames) * args.steps / elapsed
         flops_frame = MODEL_FLOPS_PER_FRAME.get((args.model, dim))
-        roof = wl.roofline(report, traffic_table)
-        roof["traffic_unit"] = traffic_note
         line = {
             "metric": "frames/sec (608x608)" if dim == 608 else "frames/sec (%dx%d)" % (dim, dim),
             "value": round(fps, 2), "unit": "frames/s", "n_gpus": world, "steps": args.steps,
@@ -1302,7 +1313,7 @@ def main(argv=None):
             "repeats": {"windows": len(windows_ms), "ms_per_step_min": round(windows_ms[0], 4),
                         "ms_per_step_median": round(elapsed / args.steps * 1e3, 4), "ms_per_step_max": round(windows_ms[-1], 4),
                         "value_min": round(sum(all_frames) / windows_ms[-1] * 1e3, 1), "value_max": round(sum(all_frames) / windows_ms[0] * 1e3, 1)},
-            "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
+            "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None, "full": bool(args.full),
             "dtype": args.dtype, "data": "synthetic",
             "config": {"workload": "%s %dx%d batch=%d/GPU %s, procedural weights, uint8 frames %s -> "
                                    "detections (thr 0.05, NMS IoU 0.3), ~%d kept/frame" % (
@@ -1323,11 +1334,10 @@ def main(argv=None):
             # a library other than the in-tree product build (Y3_HIP_LIB: stamps / experiment variants) or a debug knob:
             # the line then is a diagnostic, not a result
             "diagnostic_build": bool(os.environ.get("Y3_HIP_LIB") or os.environ.get("Y3_BENCH_DEBUG_AFTER_WARMUP")),
-            "roofline": roof,
             "per_rank": per_rank,
             "cpu_baseline": None,
-            "cpu_baseline_why": None if world == 1 and not args.no_cpu_baseline else (
-                "--no-cpu-baseline" if world == 1 else
+            "cpu_baseline_why": None if world == 1 and args.full and not args.no_cpu_baseline else (
+                "measured with --full only" if not args.full else "--no-cpu-baseline" if world == 1 else
                 "measured on rank 0 at N = 1 only (the host cores are busy feeding N ranks; see the N = 1 line)"),
             "lib_sha256": lib_sha256()[:16],
             "device_code_sha256": (device_code_sha256() or "")[:16],
@@ -1338,11 +1348,13 @@ def main(argv=None):
         if flops_frame:
             line["end_to_end_tflops"] = round(fps * flops_frame / 1e12, 2)
             line["end_to_end_frac_of_peak"] = round(fps * flops_frame / 1e12 / (PEAK_TFLOPS[args.dtype] * world), 4)
-        line["kernels"] = {k: {"ms": round(v["ms"], 4), "ms_min": round(v["ms_min"], 4), "ms_event_bracket": round(v["ms_bracket"], 4),
-                               "launches": v["launches"],
-                               "tflops": round(v["flops"] / max(v["ms"], 1e-9) / 1e9, 2),
-                               "GBps": round(v["bytes"] / max(v["ms"], 1e-9) / 1e6, 1)}
-                           for k, v in report["by_kernel"].items()}
+        if report is not None:
+            line["roofline"] = roof
+            line["kernels"] = {k: {"ms": round(v["ms"], 4), "ms_min": round(v["ms_min"], 4), "ms_event_bracket": round(v["ms_bracket"], 4),
+                                   "launches": v["launches"],
+                                   "tflops": round(v["flops"] / max(v["ms"], 1e-9) / 1e9, 2),
+                                   "GBps": round(v["bytes"] / max(v["ms"], 1e-9) / 1e6, 1)}
+                               for k, v in report["by_kernel"].items()}
 
     phases["report_s"] = abs(round(time.perf_counter() - t_timed0 - phases["warmup_and_timed_s"], 1))
     t_extras0 = time.perf_counter()

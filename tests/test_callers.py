@@ -162,14 +162,39 @@ def _check_dump(dump, d, n_frames):
 
 
 @pytest.mark.gpu
-def test_bench_prints_one_contract_json_line(tmp_path):
-    """bench.py's output contract (one JSON line with the driver's keys plus roofline / cpu_baseline objects), on a
-    small workload so the test stays short."""
+def test_bench_plain_run_prints_only_the_headline(tmp_path):
+    """A plain `bench.py` run (no --full) sets up, warms up, times, dumps and prints: the headline keys, none of the
+    sections that take runs of their own (CPU baseline, per-kernel passes, other configurations, agreement)."""
     import subprocess
     import sys
     from golden_util import ROOT
     dump = str(tmp_path / "dump")
     proc = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--model", "yolov3-tiny", "--dim", "416",
+                           "--batch", "2", "--steps", "3", "--warmup", "1", "--repeats", "5", "--dump-outputs", dump],
+                          capture_output=True, text=True, timeout=600)
+    assert proc.returncode == 0, proc.stderr[-2000:]
+    lines = [l for l in proc.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "config"):
+        assert key in d, key
+    assert d["full"] is False and d["steps"] == 3 and d["warmup"] == 1 and d["value"] > 0 and d["higher_is_better"] is True
+    assert d["repeats"]["windows"] == 5 and d["repeats"]["ms_per_step_min"] <= d["ms_per_step"] <= d["repeats"]["ms_per_step_max"]
+    for key in ("roofline", "kernels", "resident", "other_configs", "detection_regimes", "latency", "bf16_agreement", "f16_agreement"):
+        assert key not in d, key
+    assert d["cpu_baseline"] is None and "cpu_baseline_s" not in d["phases_s"]
+    _check_dump(dump, d, 2)
+
+
+@pytest.mark.gpu
+def test_bench_prints_one_contract_json_line(tmp_path):
+    """bench.py --full's output contract (one JSON line with the driver's keys plus roofline / cpu_baseline objects), on a
+    small workload so the test stays short."""
+    import subprocess
+    import sys
+    from golden_util import ROOT
+    dump = str(tmp_path / "dump")
+    proc = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--model", "yolov3-tiny", "--dim", "416",
                            "--batch", "2", "--steps", "3", "--warmup", "1", "--cpu-budget", "4", "--repeats", "5",
                            "--dump-outputs", dump],
                           capture_output=True, text=True, timeout=900)

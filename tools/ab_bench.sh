@@ -2,7 +2,7 @@
 for spec in "$@"; do
   t="${spec%%:*}"; st="${spec##*:}"
   echo "== tuning=[$t] streams=$st"
-  timeout 200 python bench.py --no-cpu-baseline --steps 30 --warmup 8 --streams $st ${t:+--tuning $t} 2>&1 | grep -v amdgpu | python -c "
+  timeout 200 python bench.py --full --no-cpu-baseline --steps 30 --warmup 8 --streams $st ${t:+--tuning $t} 2>&1 | grep -v amdgpu | python -c "
 import sys,json
 for l in sys.stdin:
     l=l.strip()

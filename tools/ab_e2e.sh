@@ -3,7 +3,7 @@ reps=$1; shift
 for rep in $(seq $reps); do
   for t in "$@"; do
     if [ "$t" = "-" ]; then targ=""; else targ="--tuning $t"; fi
-    timeout 300 python bench.py --no-extras --no-cpu-baseline --steps 80 --warmup 10 $targ 2>/dev/null | python -c "
+    timeout 300 python bench.py --full --no-extras --no-cpu-baseline --steps 80 --warmup 10 $targ 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -5,7 +5,7 @@ bash tools/ab_lib.sh pytorch-yolov3_amd/lib/libyolov3_hip_old.so pytorch-yolov3_
 Y3_HIP_LIB=pytorch-yolov3_amd/lib/libyolov3_hip_stamps.so python tools/conv_bench.py --only s76_128-256_k3,s38_256-512_k3,s19_512 --variants halo_ws_256 --stamps 2>&1 | grep -v amdgpu
 for rep in 1 2 3; do for L in old new; do
   if [ $L = old ]; then export Y3_HIP_LIB=pytorch-yolov3_amd/lib/libyolov3_hip_old.so; else unset Y3_HIP_LIB; fi
-  timeout 300 python bench.py --no-extras --no-cpu-baseline --steps 80 --warmup 10 2>/dev/null | python -c "
+  timeout 300 python bench.py --full --no-extras --no-cpu-baseline --steps 80 --warmup 10 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -11,7 +11,7 @@ cd /tmp && export TMPDIR=/tmp
 # serial steps (one stream) with the plan options of the default three-stream bench run (Y3_AM_DEFAULT | Y3_AM_HALO_TILE256 =
 # 0xb429d = 737949), so that every kernel runs the layers it runs in the headline measurement
 TUNE="--streams 1 --tuning auto_mask=737949"
-ARGS="--steps 5 --warmup 2 --no-cpu-baseline --no-extras $TUNE $*"
+ARGS="--full --steps 5 --warmup 2 --no-cpu-baseline --no-extras $TUNE $*"
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $REPO/bench.py $ARGS > $OUT/trace.log 2>&1
 timeout 600 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -- python3 $REPO/bench.py $ARGS > $OUT/pmc_fetch.log 2>&1
 timeout 600 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write -- python3 $REPO/bench.py $ARGS > $OUT/pmc_write.log 2>&1
@@ -20,7 +20,7 @@ timeout 600 rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCL
 for W in "yolov3-tiny 416 8 float32" "yolov3-spp 608 16 bf16" "yolov3 608 16 float32" "yolov3 608 16 fp16"; do
   set -- $W
   KEY=$1_$2_b$3_$4
-  WARGS="--steps 3 --warmup 1 --no-cpu-baseline --no-extras $TUNE --model $1 --dim $2 --batch $3 --dtype $4"
+  WARGS="--full --steps 3 --warmup 1 --no-cpu-baseline --no-extras $TUNE --model $1 --dim $2 --batch $3 --dtype $4"
   timeout 600 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch_$KEY -- python3 $REPO/bench.py $WARGS > $OUT/pmc_fetch_$KEY.log 2>&1
   timeout 600 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write_$KEY -- python3 $REPO/bench.py $WARGS > $OUT/pmc_write_$KEY.log 2>&1
 done

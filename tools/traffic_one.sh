@@ -5,7 +5,7 @@ TAG=$1; shift
 OUT=$REPO/gpurun_out/traffic_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-ARGS="--steps 3 --warmup 1 --no-cpu-baseline --no-extras --streams 1 --resident $*"
+ARGS="--full --steps 3 --warmup 1 --no-cpu-baseline --no-extras --streams 1 --resident $*"
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $REPO/bench.py $ARGS > $OUT/trace.log 2>&1
 timeout 600 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/f -- python3 $REPO/bench.py $ARGS > $OUT/f.log 2>&1
 timeout 600 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $OUT/w -- python3 $REPO/bench.py $ARGS > $OUT/w.log 2>&1

@@ -1,6 +1,6 @@
 #!/bin/bash
 # end-to-end A/B: tools/x_e2e.sh "tuning1" "tuning2" ...  ("" = defaults); two interleaved rounds
-B="python bench.py --no-cpu-baseline --no-extras --steps 40 --warmup 10"
+B="python bench.py --full --no-cpu-baseline --no-extras --steps 40 --warmup 10"
 show() { python -c "
 import sys,json
 for l in sys.stdin:

@@ -5,7 +5,7 @@ OUT=$REPO/gpurun_out/h2d_trace
 rm -rf $OUT; mkdir -p $OUT
 python3 $REPO/tools/h2d_probe.py 2>&1 | grep -v amdgpu
 cd /tmp && export TMPDIR=/tmp
-timeout 300 rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d $OUT -- python3 $REPO/bench.py --h2d --steps 12 --warmup 6 --no-cpu-baseline --no-extras > $OUT/bench.log 2>&1
+timeout 300 rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d $OUT -- python3 $REPO/bench.py --full --h2d --steps 12 --warmup 6 --no-cpu-baseline --no-extras > $OUT/bench.log 2>&1
 tail -c 400 $OUT/bench.log
 find $OUT -name "*.csv" | head
 python3 - <<PY
