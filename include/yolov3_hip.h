@@ -66,6 +66,12 @@ extern "C" {
 #define Y3_F_MISH 128u         /* mish, x * tanh(softplus(x)), after scale/bias instead of LeakyReLU (YOLOv4's backbone);
                                   exclusive with Y3_F_LEAKY; Y3_F_RESIDUAL still adds after it.  Kernels that do not
                                   implement it decline the op; y3_capabilities() reports Y3_CAP_MISH             */
+#define Y3_F_LOGISTIC 256u     /* logistic, 1 / (1 + e^-x), after scale/bias (the detection-head convs of new_coords networks:
+                                  Scaled-YOLOv4); exclusive with Y3_F_LEAKY and Y3_F_MISH; Y3_F_RESIDUAL still adds after it.
+                                  Exactly 1 above x ~ 17, exactly 0 below x ~ -88.7; y3_capabilities() reports Y3_CAP_LOGISTIC */
+#define Y3_F_NEW_COORDS 512u   /* Y3_OP_YOLO: Darknet's new_coords=1 decode of a head whose conv ends in Y3_F_LOGISTIC: the inputs are
+                                  probabilities already, so centre = (sxy(t) + cell) / grid, size = t * t * 4 * anchor / net,
+                                  prob = objectness * max_c t_c (no exp, no soft-max); y3_capabilities() reports Y3_CAP_NEW_COORDS */
 
 /*
  * One unit of work.  POD, 8-byte aligned, zero-initialise unused fields.
@@ -186,6 +192,8 @@ int y3_abi_version(void);
  * refused instead of running, say, mish as linear.                                                                   */
 #define Y3_CAP_MISH 1u         /* Y3_F_MISH on conv ops                      */
 #define Y3_CAP_SCALE_X_Y 2u    /* y3_op.scale_x_y on YOLO ops                */
+#define Y3_CAP_LOGISTIC 4u     /* Y3_F_LOGISTIC on conv ops                  */
+#define Y3_CAP_NEW_COORDS 8u   /* Y3_F_NEW_COORDS on YOLO ops                */
 uint32_t y3_capabilities(void);
 const char *y3_last_error(void);
 /* number of visible HIP devices whose arch is gfx950 (0 on a CPU-only machine) */

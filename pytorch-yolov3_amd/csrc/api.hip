@@ -79,8 +79,8 @@ int conv_path(const y3_op &op) {
 // The conv chooser: what a conv op runs under options `o`.  The rules are asked in this order and are not independent (the
 // SMALL_DW_WIDE 1x1 rule, for one, is asked only after the weights-resident kernel's).
 int choose_conv(const y3_op &op, const y3_options &o, y3_step &st) {
-  Y3_REQUIRE(!((op.flags & Y3_F_MISH) && (op.flags & Y3_F_LEAKY)), "conv block %d: Y3_F_MISH and Y3_F_LEAKY are exclusive",
-             op.block_idx);
+  const uint32_t acts = op.flags & (Y3_F_LEAKY | Y3_F_MISH | Y3_F_LOGISTIC);
+  Y3_REQUIRE((acts & (acts - 1)) == 0, "conv block %d: Y3_F_LEAKY, Y3_F_MISH and Y3_F_LOGISTIC are exclusive", op.block_idx);
   Y3_REQUIRE(op.out_h == (op.in_h + 2 * op.pad - op.ksize) / op.stride + 1 &&
                  op.out_w == (op.in_w + 2 * op.pad - op.ksize) / op.stride + 1,
              "conv block %d: output size mismatch", op.block_idx);
@@ -158,12 +158,17 @@ int choose_op(const y3_op &op, const y3_options &o, y3_step &st) {
 }
 
 // Every single-op conv kernel computes the op's activation code (common.h: y3_act); the fused conv groups hard-wire
-// LeakyReLU and their choosers decline mish ops.  Checked once more per step, so that a chooser that forgot would be an
-// error here and never a conv run as linear or leaky.
+// LeakyReLU and their choosers decline mish and logistic ops; the fused head kernels compute linear and logistic (the
+// head conv of a new_coords network).  Checked once more per step, so that a chooser that forgot would be an error here and
+// never a conv run as linear or leaky.
 int check_activation(const y3_op *ops, int n, const y3_step &st) {
-  for (int k = 0; k < n; ++k)
-    Y3_REQUIRE(!(ops[k].kind == Y3_OP_CONV && (ops[k].flags & Y3_F_MISH)) || st.fuse == y3_fuse::none,
+  for (int k = 0; k < n; ++k) {
+    if (ops[k].kind != Y3_OP_CONV) continue;
+    Y3_REQUIRE(!(ops[k].flags & Y3_F_MISH) || st.fuse == y3_fuse::none,
                "conv block %d: mish op given to %s, which does not compute mish", ops[k].block_idx, st.name);
+    Y3_REQUIRE(!(ops[k].flags & Y3_F_LOGISTIC) || st.fuse == y3_fuse::none || st.fuse == y3_fuse::head_decode,
+               "conv block %d: logistic op given to %s, which does not compute logistic", ops[k].block_idx, st.name);
+  }
   return Y3_OK;
 }
 
@@ -236,7 +241,7 @@ extern "C" {
 
 int y3_abi_version(void) { return Y3_ABI_VERSION; }
 
-uint32_t y3_capabilities(void) { return Y3_CAP_MISH | Y3_CAP_SCALE_X_Y; }
+uint32_t y3_capabilities(void) { return Y3_CAP_MISH | Y3_CAP_SCALE_X_Y | Y3_CAP_LOGISTIC | Y3_CAP_NEW_COORDS; }
 
 const char *y3_last_error(void) { return g_err; }
 

@@ -249,9 +249,11 @@ __device__ __forceinline__ float y3_vmax(float a, float b) {
 }
 // Activation of a conv op, from its flags: a run-time value of the layer (uniform across the grid, so the branches on it
 // below are scalar branches, and the leaky / linear arithmetic is the same instruction sequence as before mish existed)
-enum : int { Y3_ACT_LINEAR = 0, Y3_ACT_LEAKY = 1, Y3_ACT_MISH = 2 };
+// (mish and logistic, the codes >= Y3_ACT_MISH, share one scalar branch after the linear form: y3_bn_act8)
+enum : int { Y3_ACT_LINEAR = 0, Y3_ACT_LEAKY = 1, Y3_ACT_MISH = 2, Y3_ACT_LOGISTIC = 3 };
 __host__ __device__ __forceinline__ int y3_act(uint32_t flags) {
-  return (flags & Y3_F_MISH) ? Y3_ACT_MISH : ((flags & Y3_F_LEAKY) ? Y3_ACT_LEAKY : Y3_ACT_LINEAR);
+  return (flags & Y3_F_LOGISTIC) ? Y3_ACT_LOGISTIC
+                                 : ((flags & Y3_F_MISH) ? Y3_ACT_MISH : ((flags & Y3_F_LEAKY) ? Y3_ACT_LEAKY : Y3_ACT_LINEAR));
 }
 // mish(x) = x tanh(softplus(x)) = x t / (t + 2) with n = e^x, t = n (n + 2) = (1 + n)^2 - 1: one v_exp_f32, one v_rcp_f32,
 // a few FMAs.  Above 20 the ratio is 1 in float32 (mish(x) == x there), and from about 44 on t overflows and the ratio
@@ -262,18 +264,35 @@ __device__ __forceinline__ float y3_mish(float x) {
   const float y = x * t * __builtin_amdgcn_rcpf(t + 2.0f);
   return x > 20.0f ? x : y;
 }
+// logistic(x) = 1 / (1 + e^-x): one v_exp_f32, one v_rcp_f32.  Saturates without a select: from x ~ 17 on e^-x is below half an
+// ulp of 1, so the denominator is 1 and the result exactly 1; below x ~ -88.7 (and at -inf) e^-x is inf and the result exactly 0.
+// The fused head kernels apply this same function to their logits, so fused and two-kernel heads give the same bits.
+__device__ __forceinline__ float y3_logistic(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
+// Mish or logistic (the codes >= Y3_ACT_MISH, behind the caller's one scalar branch) as ONE instruction sequence: both are an
+// exponential and a reciprocal, so the choice is a few selects on a uniform condition rather than a second code path (which
+// made an epilogue spill).  Mish: x * t * rcp(t + 2), y3_mish's operations; logistic: 1 * rcp(1 + e^-x), y3_logistic's bits
+// (the product with 1 is exact).
+__device__ __forceinline__ float y3_act_tail(float x, int act) {
+#pragma clang fp contract(off)   // t + 2 stays an add, as the eight-value mish loop it replaces compiled (no fma)
+  const bool lg = act == Y3_ACT_LOGISTIC;
+  const float n = __expf(lg ? -x : x);
+  const float t = n * (n + 2.0f);
+  const float y = (lg ? 1.0f : x * t) * __builtin_amdgcn_rcpf(lg ? 1.0f + n : t + 2.0f);
+  return !lg && x > 20.0f ? x : y;
+}
 // one value: the scalar epilogues (float32 kernels, stem kernels)
 __device__ __forceinline__ float y3_act1(float t, int act) {
   if (act == Y3_ACT_MISH) return y3_mish(t);
+  if (act == Y3_ACT_LOGISTIC) return y3_logistic(t);
   return act == Y3_ACT_LEAKY ? (t > 0.f ? t : Y3_LEAKY_SLOPE * t) : t;
 }
 // eight values, activation `act` (Y3_ACT_*).  Leaky / linear: a slope of 1 makes max(v, slope * v) the identity without a
-// branch (phi copies of all eight values otherwise).  Mish runs the linear form and then, behind one scalar branch per eight
-// values, replaces each value in place: the leaky / linear path keeps its instruction sequence and nothing of the mish
-// arithmetic is live across it.
-__device__ __forceinline__ void y3_mish8(float (&v)[8]) {
+// branch (phi copies of all eight values otherwise).  Mish and logistic run the linear form and then, behind one scalar branch
+// per eight values, replace each value in place: the leaky / linear path keeps its instruction sequence and nothing of the
+// mish / logistic arithmetic is live across it.
+__device__ __forceinline__ void y3_act_tail8(float (&v)[8], int act) {
 #pragma unroll
-  for (int i = 0; i < 8; ++i) v[i] = y3_mish(v[i]);
+  for (int i = 0; i < 8; ++i) v[i] = y3_act_tail(v[i], act);
 }
 __device__ __forceinline__ void y3_bn_act8(float (&v)[8], const f32x4 &lo, const f32x4 &hi, const f32x4 &sc_lo,
                                            const f32x4 &sc_hi, const f32x4 &bi_lo, const f32x4 &bi_hi, int act) {
@@ -289,7 +308,7 @@ __device__ __forceinline__ void y3_bn_act8(float (&v)[8], const f32x4 &lo, const
     v[2 * i] = y3_vmax(t[i][0], s[0]);
     v[2 * i + 1] = y3_vmax(t[i][1], s[1]);
   }
-  if (act == Y3_ACT_MISH) y3_mish8(v);
+  if (act >= Y3_ACT_MISH) y3_act_tail8(v, act);
 }
 
 // Diagnostic build only (-DY3_STAMPS, `make stamps`): per-workgroup phase timing with s_memtime.

@@ -242,7 +242,7 @@ __device__ __forceinline__ void dw1_wait_vm(u32x4 (&w)[2][2]) {
   asm volatile("s_waitcnt vmcnt(%4)" : "+v"(w[0][0]), "+v"(w[0][1]), "+v"(w[1][0]), "+v"(w[1][1]) : "n"(N) : "memory");
 }
 
-// HEAD = true: the detection-head conv (bias, no activation, <= 256 logits per pixel = ONE channel tile) + YOLOLayer decode
+// HEAD = true: the detection-head conv (bias, linear or logistic, <= 256 logits per pixel = ONE channel tile) + YOLOLayer decode
 // (/root/reference/yolov3/darknet.py:86-116) in one launch: after the K loop the float32 logits (sum * scale + bias, one fused rounding
 // -- the arithmetic of the tiled head kernel, conv_igemm.hip) are parked in the LDS the activation tile no longer needs, rows of
 // 260 floats, and decoded four lanes per box by the code every other decode path runs (decode_core.h): same bits.
@@ -365,6 +365,13 @@ __global__ __launch_bounds__(512, 2) void conv1x1_dw_kernel(DwArgs p) {
         lo[r] = __builtin_fmaf(acc[mi][0][r], hs_lo[r], hb_lo[r]);
         hi[r] = __builtin_fmaf(acc[mi][1][r], hs_hi[r], hb_hi[r]);
       }
+      if (p.flags & Y3_F_LOGISTIC) {   // new_coords heads: the unfused head conv's function, so the same bits
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          lo[r] = y3_logistic(lo[r]);
+          hi[r] = y3_logistic(hi[r]);
+        }
+      }
       float *row = sL + (mi * 16 + fr) * LDL + co;
       *reinterpret_cast<f32x4 *>(row) = lo;
       *reinterpret_cast<f32x4 *>(row + 4) = hi;
@@ -416,7 +423,7 @@ int dw_head_bm(const y3_op &op, const y3_options &o) {
   const int mode = o.fuse_head;
   if (mode == 0 || mode == 2) return 0;
   if (op.kind != Y3_OP_CONV || !y3_is16(op.dtype) || op.ksize != 1 || op.stride != 1 || op.pad != 0 || !(op.flags & Y3_F_OUT_F32)) return 0;
-  if (op.flags & (Y3_F_LEAKY | Y3_F_MISH | Y3_F_RESIDUAL | Y3_F_IN_NCHW_F32 | Y3_F_IN_NHWC_U8BGR | Y3_F_PLAN_INPUT)) return 0;
+  if (op.flags & (Y3_F_LEAKY | Y3_F_MISH | Y3_F_RESIDUAL | Y3_F_IN_NCHW_F32 | Y3_F_IN_NHWC_U8BGR | Y3_F_PLAN_INPUT)) return 0;   // (logistic: new_coords heads)
   if (op.out_c > 256 || op.cout_pad < 256 || op.cout_pad % 32 != 0 || op.in_ld % 8 != 0 || op.k_ld % 32 != 0 || op.k_ld < op.in_c) return 0;
   const int nkt = op.in_c / 64;
   if (op.in_c % 128 != 0 || !DwHeadNkt<48>::has(nkt)) return 0;

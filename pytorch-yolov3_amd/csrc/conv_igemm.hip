@@ -524,6 +524,10 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N) void conv_igemm2_kernel(Ige
             f32x4 lg;
 #pragma unroll
             for (int r = 0; r < 4; ++r) lg[r] = __builtin_fmaf(acc[mi][ni][r], hs[r], hb[r]);
+            if (act == Y3_ACT_LOGISTIC) {   // new_coords heads: the unfused head conv's function, so the same bits
+#pragma unroll
+              for (int r = 0; r < 4; ++r) lg[r] = y3_logistic(lg[r]);
+            }
             *reinterpret_cast<f32x4 *>(sC + pl * LDL + cl) = lg;
           } else {
             *reinterpret_cast<f32x4 *>(sC + pl * BN + (((cl >> 2) ^ (pl & SWZ)) << 2)) = acc[mi][ni];
@@ -1080,7 +1084,7 @@ int y3_choose_conv_igemm(const y3_op &op, const y3_options &o, y3_step &st, int 
 
 Y3_STAMP_READER(y3_debug_stamps_igemm)
 
-// ---- detection head: 1x1 conv (bias, no activation, float32 logits) + YOLO decode in one launch -------------------
+// ---- detection head: 1x1 conv (bias, linear or logistic, float32 logits) + YOLO decode in one launch -------------------
 // op0: the head conv as the plan holds it (Y3_F_OUT_F32, Cout = anchors * attributes <= 256); op1: the Y3_OP_YOLO op
 // reading it.  16-bit networks (bf16 / fp16) only: the float32 parity path keeps the two kernels (sequential class loop).
 
@@ -1091,6 +1095,7 @@ bool y3_choose_conv_head_decode(const y3_op &op0, const y3_op &op1, const y3_opt
   if (op0.kind != Y3_OP_CONV || op1.kind != Y3_OP_YOLO || !y3_is16(op0.dtype)) return false;
   if (op0.ksize != 1 || op0.stride != 1 || !(op0.flags & Y3_F_OUT_F32)) return false;
   if (op0.flags & (Y3_F_LEAKY | Y3_F_MISH | Y3_F_RESIDUAL | Y3_F_IN_NCHW_F32 | Y3_F_IN_NHWC_U8BGR | Y3_F_PLAN_INPUT)) return false;
+  // (a logistic head conv -- new_coords networks -- is fine: the kernel applies the op's activation to its logits, linear or logistic)
   if (!y3_conv_igemm_supported(op0) || op0.in_c % 64 != 0 || op0.out_c > 256 || op0.cout_pad < 256) return false;
   if (op1.d_in != op0.d_out || op1.in_ld != op0.out_ld || op1.in_h != op0.out_h || op1.in_w != op0.out_w) return false;
   if (op1.batch != op0.batch || op1.n_anchor < 1 || op1.n_anchor > 8 || op1.n_attr <= 5) return false;

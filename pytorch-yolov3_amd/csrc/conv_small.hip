@@ -86,7 +86,7 @@ __global__ __launch_bounds__(256) void conv_stem3x3_kernel(SmallArgs p) {
       if (act == Y3_ACT_LEAKY) t = t > 0.f ? t : Y3_LEAKY_SLOPE * t;
       v[j] = t;
     }
-    if (act == Y3_ACT_MISH) y3_mish8(v);
+    if (act >= Y3_ACT_MISH) y3_act_tail8(v, act);
     if (nvalid == 8 && (p.out_ld % 8) == 0) {
       if constexpr (sizeof(TO) == 2) {
         *reinterpret_cast<u32x4 *>(orow + co) = y3_pack8<TO>(v);

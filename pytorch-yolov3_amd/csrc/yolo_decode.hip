@@ -11,6 +11,9 @@
 // Output: row = row_offset + a*h*w + y*w + x   (darknet.py:118-120, heads in cfg order)
 //   bbox[row] = ((sxy(sigmoid(tx))+x)/w, (sxy(sigmoid(ty))+y)/h, exp(tw)*Aw/net_w, exp(th)*Ah/net_h)
 //   prob[row] = max_c softmax(tc)_c * sigmoid(to)       cls[row] = argmax (first on ties), int64
+// Y3_F_NEW_COORDS (Darknet's new_coords=1; the head conv ended in a sigmoid, so t are probabilities already):
+//   bbox[row] = ((sxy(tx)+x)/w, (sxy(ty)+y)/h, ((tw*tw)*4)*Aw/net_w, ((th*th)*4)*Ah/net_h)
+//   prob[row] = max_c tc * to                            cls[row] = argmax of the stored tc (first on ties)
 // Built with -ffp-contract=off: each operation rounds like the reference's separate torch ops.
 #include "common.h"
 #include "decode_core.h"
@@ -24,6 +27,7 @@ struct YoloArgs {
   long long *cls;
   int B, h, w, ld, n_anchor, n_attr, row_offset, rows_total;
   float net_w, net_h, sxy;       // sxy: scale_x_y (1 for YOLOv3)
+  int new_coords;                // Y3_F_NEW_COORDS
   float aw[8], ah[8];
   long long total;
 };
@@ -79,7 +83,7 @@ __global__ __launch_bounds__(LANES == 1 ? 256 : 384) void yolo_decode_kernel(Yol
       float comp, score;
       int best_c;
       y3_decode_box4(t_, p.n_attr, sub, (float)x, (float)y, (float)p.w, (float)p.h, p.aw[a], p.ah[a], p.net_w, p.net_h, p.sxy,
-                     comp, score, best_c);
+                     p.new_coords != 0, comp, score, best_c);
       if (!live) continue;
       const long long row = (long long)b * p.rows_total + p.row_offset + (long long)a * p.h * p.w + (long long)y * p.w + x;
       p.bbox[row * 4 + sub] = comp;
@@ -90,6 +94,27 @@ __global__ __launch_bounds__(LANES == 1 ? 256 : 384) void yolo_decode_kernel(Yol
       continue;
     }
     const int ncls = p.n_attr - 5;
+    if (p.new_coords) {
+      // no soft-max and no sigmoid: the stored class values and objectness are probabilities
+      float best = -1.f;
+      int best_c = 0;
+      for (int c = 0; c < ncls; ++c) {
+        if (t_[5 + c] > best) {  // strict: first index wins ties
+          best = t_[5 + c];
+          best_c = c;
+        }
+      }
+      if (!live) continue;
+      const float bx = (y3_scale_xy(t_[0], p.sxy) + (float)x) / (float)p.w;
+      const float by = (y3_scale_xy(t_[1], p.sxy) + (float)y) / (float)p.h;
+      const float bw = (((t_[2] * t_[2]) * 4.0f) * p.aw[a]) / p.net_w;
+      const float bh = (((t_[3] * t_[3]) * 4.0f) * p.ah[a]) / p.net_h;
+      const long long row = (long long)b * p.rows_total + p.row_offset + (long long)a * p.h * p.w + (long long)y * p.w + x;
+      *reinterpret_cast<f32x4 *>(p.bbox + row * 4) = f32x4{bx, by, bw, bh};
+      p.prob[row] = best * t_[4];
+      p.cls[row] = best_c;
+      continue;
+    }
     float mx = -INFINITY;
     for (int c = 0; c < ncls; ++c) mx = fmaxf(mx, t_[5 + c]);
     float sum = 0.f, best = -1.f;
@@ -132,6 +157,7 @@ static int launch_yolo(const y3_op *ops, const y3_step &st, const void *d_in, co
   a.row_offset = op.row_offset; a.rows_total = op.rows_total;
   a.net_w = op.net_w; a.net_h = op.net_h;
   a.sxy = y3_op_scale_xy(op);
+  a.new_coords = (op.flags & Y3_F_NEW_COORDS) != 0;
   for (int i = 0; i < 8; ++i) { a.aw[i] = op.anchor_w[i]; a.ah[i] = op.anchor_h[i]; }
   a.total = (long long)op.batch * op.in_h * op.in_w * op.n_anchor;
   const long long npix = (long long)op.batch * op.in_h * op.in_w;

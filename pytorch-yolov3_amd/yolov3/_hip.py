@@ -34,9 +34,9 @@ LIB_PATH = os.environ.get("Y3_HIP_LIB") or os.path.join(_HERE, "..", "lib", "lib
 Y3_F32, Y3_BF16, Y3_F16, Y3_F64 = 0, 1, 2, 3
 OP_CONV, OP_MAXPOOL, OP_UPSAMPLE, OP_ADD, OP_COPY, OP_YOLO = 1, 2, 3, 4, 5, 6
 F_LEAKY, F_RESIDUAL, F_OUT_F32, F_IN_NCHW_F32, F_IN_NHWC_U8BGR, F_PLAN_INPUT, F_FUSE_NEXT = 1, 2, 4, 8, 16, 32, 64
-F_MISH = 128
+F_MISH, F_LOGISTIC, F_NEW_COORDS = 128, 256, 512
 # y3_capabilities() bits: what the loaded library computes beyond ABI 6 as first released
-CAP_MISH, CAP_SCALE_X_Y = 1, 2
+CAP_MISH, CAP_SCALE_X_Y, CAP_LOGISTIC, CAP_NEW_COORDS = 1, 2, 4, 8
 PATH_IGEMM, PATH_STEM, PATH_DIRECT, PATH_STEM_MFMA = 0, 1, 2, 3
 
 
@@ -179,10 +179,11 @@ def capabilities():
 
 def require_capabilities(needs, what):
     """Refuse a plan that needs a computation the loaded library does not report: a stale library would run mish as
-    linear and ignore scale_x_y."""
+    linear, ignore scale_x_y, run a logistic head as linear or decode new_coords heads the YOLOv3 way."""
     missing = needs & ~capabilities()
     if missing:
-        names = [n for n, b in (("mish", CAP_MISH), ("scale_x_y", CAP_SCALE_X_Y)) if missing & b]
+        names = [n for n, b in (("mish", CAP_MISH), ("scale_x_y", CAP_SCALE_X_Y), ("logistic", CAP_LOGISTIC),
+                                ("new_coords", CAP_NEW_COORDS)) if missing & b]
         raise HipLibraryError("{}: the loaded libyolov3_hip.so cannot compute {} (rebuild: make -C pytorch-yolov3_amd/csrc)"
                               .format(what, ", ".join(names)))
 

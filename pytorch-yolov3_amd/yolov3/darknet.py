@@ -349,6 +349,9 @@ class Darknet(object):
                 if od.get("mish"):
                     op.flags |= _hip.F_MISH
                     needs |= _hip.CAP_MISH
+                if od.get("logistic"):
+                    op.flags |= _hip.F_LOGISTIC
+                    needs |= _hip.CAP_LOGISTIC
                 if od.get("fuse_next"):
                     op.flags |= _hip.F_FUSE_NEXT
                 if res is not None:
@@ -393,6 +396,9 @@ class Darknet(object):
                 if "scale_x_y" in od:
                     op.scale_x_y = od["scale_x_y"]
                     needs |= _hip.CAP_SCALE_X_Y
+                if od.get("new_coords"):
+                    op.flags |= _hip.F_NEW_COORDS
+                    needs |= _hip.CAP_NEW_COORDS
             else:
                 raise AssertionError(kind)
         _hip.require_capabilities(needs, self.config_fpath)

@@ -38,7 +38,7 @@ class Tensor(object):
             self.buf, self.off, self.ld, self.c, self.h, self.w, " f32" if self.f32 else "")
 
 
-ACTIVATIONS = ("leaky", "linear", "mish")
+ACTIVATIONS = ("leaky", "linear", "mish", "logistic")
 
 
 def route_groups(blk):
@@ -70,7 +70,12 @@ def check_blocks(blocks):
                 raise ValueError("route block {}: group_id={} out of range for groups={}".format(i, gid, groups))
         elif kind == "yolo":
             if int(blk.get("new_coords", 0)) != 0:
-                raise ValueError("yolo block {}: new_coords=1 is not supported".format(i))
+                # Darknet's new_coords decode reads probabilities (no exp, no sigmoid): the conv in front of the block must
+                # end in a sigmoid, or the boxes would come out up to 4 * anchor * t^2 wide without an error
+                head = blocks[i - 1] if i > 0 else {}
+                if head.get("type") != "convolutional" or head.get("activation") != "logistic":
+                    raise ValueError("yolo block {}: new_coords=1 is supported only behind a conv with activation=logistic "
+                                     "(block {} is {} {!r})".format(i, i - 1, head.get("type"), head.get("activation")))
         elif kind == "shortcut":
             if "weights_type" in blk:
                 raise ValueError("shortcut block {}: weighted shortcuts (weights_type) are not supported".format(i))
@@ -245,6 +250,8 @@ def build_plan(blocks, net_info, batch, height, width, elem_size, reuse=True, fu
                                            kinds[i + 1] == "convolutional" and readers[i] == [(i + 1, "in")]))
             if blk["activation"] == "mish":
                 op["mish"] = True
+            elif blk["activation"] == "logistic":
+                op["logistic"] = True
             ops.append(op)
             conv_slot += 1
             if i in conv_fused:
@@ -295,6 +302,8 @@ def build_plan(blocks, net_info, batch, height, width, elem_size, reuse=True, fu
                       row_offset=row_offset, rows_total=rows_total)
             if float(blk.get("scale_x_y", 1)) != 1.0:
                 op["scale_x_y"] = float(blk["scale_x_y"])     # Darknet's centre stretch (default 1: the YOLOv3 decode)
+            if int(blk.get("new_coords", 0)) != 0:
+                op["new_coords"] = True                       # Darknet's decode of a logistic head (check_blocks)
             ops.append(op)
             row_offset += na * h * w
             tensor_of[i] = src

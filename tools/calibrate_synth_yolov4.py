@@ -1,8 +1,9 @@
-"""One-off: per-BN-layer output statistics of procedural weights for the YOLOv4 cfgs (the synth_calibration.json entries
-"yolov4" and "yolov4-tiny").
+"""Per-BN-layer output statistics of procedural weights for the YOLOv4 cfgs (the synth_calibration.json entries "yolov4",
+"yolov4-tiny" and "yolov4-csp"; `python tools/calibrate_synth_yolov4.py yolov4-csp` redoes one of them).
 
 tools/calibrate_synth.py walks a cfg with the reference's modules, which have no mish, grouped route or scale_x_y; this tool
-walks it with the float32 CPU restatement of those semantics (tests/yolov4_restate.py) instead, the same way: before a BN
+walks it with the float32 CPU restatement of those semantics (tests/yolov4_restate.py; tests/new_coords_restate.py for
+yolov4-csp's logistic heads) instead, the same way: before a BN
 conv is evaluated its conv output (pre-BN) mean / variance over the same seeded batch is measured, rounded to 6 significant
 digits and installed as that layer's running statistics (yolov3.weights.synth_params' formula).  Merges the entries into
 pytorch-yolov3_amd/yolov3/synth_calibration.json; prints the rms of every block.
@@ -22,6 +23,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 sys.path.insert(0, ROOT)
 from yolov3 import weights as W  # noqa: E402
 import yolov4_restate as R  # noqa: E402
+import new_coords_restate as NR  # noqa: E402
 
 CFG_DIR = os.path.join(ROOT, "pytorch-yolov3_amd", "models")
 OUT = os.path.join(ROOT, "pytorch-yolov3_amd", "yolov3", "synth_calibration.json")
@@ -31,7 +33,7 @@ def calibrate(model, dim, seed=0):
     cfg = os.path.join(CFG_DIR, model + ".cfg")
     blocks, net_info = R.ref_io.read_cfg(cfg)
     params = W.synth_params(blocks, net_info, seed=seed)          # weights do not depend on the calibration
-    net = R.Restatement(cfg, params)
+    net = NR.Restatement(cfg, params)
     rs = np.random.RandomState(1234)
     frames = rs.randint(0, 256, size=(2, dim, dim, 3), dtype=np.uint8)
     x = R.frames_to_input(frames)
@@ -74,7 +76,8 @@ def calibrate(model, dim, seed=0):
 if __name__ == "__main__":
     with open(OUT) as fh:
         table = json.load(fh)
-    for model, dim in (("yolov4-tiny", 416), ("yolov4", 608)):
-        table[model] = calibrate(model, dim)
+    dims = {"yolov4-tiny": 416, "yolov4": 608, "yolov4-csp": 512}
+    for model in sys.argv[1:] or list(dims):
+        table[model] = calibrate(model, dims[model])
     with open(OUT, "w") as fh:
         json.dump(table, fh, indent=0)
