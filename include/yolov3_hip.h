@@ -194,6 +194,7 @@ int y3_abi_version(void);
 #define Y3_CAP_SCALE_X_Y 2u    /* y3_op.scale_x_y on YOLO ops                */
 #define Y3_CAP_LOGISTIC 4u     /* Y3_F_LOGISTIC on conv ops                  */
 #define Y3_CAP_NEW_COORDS 8u   /* Y3_F_NEW_COORDS on YOLO ops                */
+#define Y3_CAP_LETTERBOX 16u   /* y3_letterbox_geometry, y3_letterbox_u8, y3_detect_letterbox */
 uint32_t y3_capabilities(void);
 const char *y3_last_error(void);
 /* number of visible HIP devices whose arch is gfx950 (0 on a CPU-only machine) */
@@ -262,6 +263,20 @@ int y3_detect(const float *d_bbox, const float *d_prob, const int64_t *d_cls, in
               size_t workspace_bytes, int32_t *d_det_count, int64_t *d_det_tlbr, float *d_det_prob,
               int64_t *d_det_cls, int32_t *d_det_row, void *stream);
 
+/* the same with Darknet's letterbox box correction (correct_yolo_boxes(..., letter=1)) for frames that went through
+ * y3_letterbox_u8 into a (net_h, net_w) network.  Per frame, with {new_h, new_w} = the y3_letterbox_geometry of its
+ * d_orig_hw entry (computed on the device), every candidate's relative box is corrected before the * orig_w / * orig_h
+ * product:
+ *   deltaw = (float)(net_w - new_w),  ratiow = (float)new_w / net_w                                  (float32)
+ *   x' = (float)(((double)x - (double)deltaw / 2.0 / (double)net_w) / (double)ratiow),  w' = w * (1.0f / ratiow)
+ * and likewise y, h with net_h, new_h.  The image is shifted by the INTEGER top / left while the boxes are corrected by
+ * delta / 2, which may end in .5 -- Darknet's mismatch, kept.  A net-sized frame's correction is the identity: the output
+ * then equals y3_detect's bit for bit.  net_h, net_w > 0.                                                           */
+int y3_detect_letterbox(const float *d_bbox, const float *d_prob, const int64_t *d_cls, int batch, int rows,
+                        const int32_t *d_orig_hw, float prob_thresh, double iou_thresh, void *d_workspace,
+                        size_t workspace_bytes, int32_t *d_det_count, int64_t *d_det_tlbr, float *d_det_prob,
+                        int64_t *d_det_cls, int32_t *d_det_row, int net_h, int net_w, void *stream);
+
 /* non_max_suppression (inference.py:161-266) on caller-provided integer boxes -------------- */
 size_t y3_nms_workspace_bytes(int n);
 /*
@@ -294,6 +309,30 @@ int y3_cxywh_to_tlbr_float(const void *d_xywh, void *d_tlbr, int n, int cols, in
  * and xofs / ialpha tables, computed on the host (yolov3/preprocess.py:axis_table). */
 int y3_resize_bilinear_u8(const uint8_t *d_src, int src_h, int src_w, uint8_t *d_dst, int dst_h, int dst_w,
                           const int32_t *d_ytab, const int32_t *d_xtab, void *stream);
+
+/* Darknet letterboxing (letterbox_image): the frame keeps its aspect ratio inside the network input and the rest is
+ * filled.  Not in the reference, which stretches every frame (cv2.resize).
+ * y3_letterbox_geometry: out = {new_h, new_w, top, left} of a (src_h, src_w) frame in a (net_h, net_w) network:
+ *   if (float)net_w / src_w < (float)net_h / src_h:  new_w = net_w, new_h = src_h * net_w / src_w   (int64, truncated)
+ *   else:                                             new_h = net_h, new_w = src_w * net_h / src_h
+ *   new_h, new_w clamped to >= 1;  top = (net_h - new_h) / 2,  left = (net_w - new_w) / 2.
+ * Host function: the device side of y3_letterbox_u8 / y3_detect_letterbox uses the same definition.             */
+int y3_letterbox_geometry(int src_h, int src_w, int net_h, int net_w, int32_t out[4]);
+/* One frame of a letterboxed batch: d_src uint8 (src_h, src_w, 3) on the device; d_ytab (new_h, 4) / d_xtab (new_w, 4)
+ * the y3_resize_bilinear_u8 tap tables of a (src_h, src_w) -> (new_h, new_w) resize, {new_h, new_w} from
+ * y3_letterbox_geometry (the kernel trusts their indices: tables of another size read out of bounds).            */
+typedef struct {
+  const uint8_t *d_src;
+  int32_t src_h, src_w;
+  const int32_t *d_ytab, *d_xtab;
+} y3_letterbox_frame;
+/* d_dst (batch, net_h, net_w, 3) uint8: frame i resized to (new_h, new_w) with y3_resize_bilinear_u8's arithmetic and
+ * pasted at (top, left) on a canvas of the byte `fill` (0..255; Darknet fills with 0.5 in float, which a uint8 frame
+ * read as v / 255 cannot hold -- 128 is the usual choice).  `frames` is a HOST array of `batch` descriptors: they travel
+ * as kernel arguments (a fixed number per launch, several launches on `stream` for bigger batches), so the array may
+ * be reused as soon as the call returns.  Frames of different sizes share one call.                              */
+int y3_letterbox_u8(const y3_letterbox_frame *frames, int batch, uint8_t *d_dst, int net_h, int net_w, int fill,
+                    void *stream);
 
 /* frames in / detections out without a copy engine: what yolov3/pipeline.py (the loop bench.py times and detect_in_frames
  * runs) uses in place of the `.to(device)` / `.cpu()` transfers around Darknet.forward (inference.py:335, :338-340).  A small

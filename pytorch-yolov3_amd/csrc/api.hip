@@ -241,7 +241,9 @@ extern "C" {
 
 int y3_abi_version(void) { return Y3_ABI_VERSION; }
 
-uint32_t y3_capabilities(void) { return Y3_CAP_MISH | Y3_CAP_SCALE_X_Y | Y3_CAP_LOGISTIC | Y3_CAP_NEW_COORDS; }
+uint32_t y3_capabilities(void) {
+  return Y3_CAP_MISH | Y3_CAP_SCALE_X_Y | Y3_CAP_LOGISTIC | Y3_CAP_NEW_COORDS | Y3_CAP_LETTERBOX;
+}
 
 const char *y3_last_error(void) { return g_err; }
 

@@ -20,6 +20,7 @@
 // survivor with ds_bpermute shuffles and clears victims with a ballot mask.
 // Built with -ffp-contract=off.
 #include "common.h"
+#include "letterbox.h"
 
 namespace {
 
@@ -38,6 +39,7 @@ struct DetectArgs {
   const float *prob;
   const long long *cls;
   const int *orig_hw;
+  int lb_net_h, lb_net_w;   // y3_detect_letterbox: the network size the frames were letterboxed into; 0 = no correction
   // caller-boxes mode (y3_nms)
   const long long *in_tlbr;
   const float *in_prob;
@@ -169,6 +171,22 @@ __global__ __launch_bounds__(kThreads) void detect_kernel(DetectArgs p) {
     int *w_cls = p.c_cls + (long long)b * R;
     int *w_row = p.c_row + (long long)b * R;
     const float oh = (float)p.orig_hw[b * 2 + 0], ow = (float)p.orig_hw[b * 2 + 1];
+    // letterbox correction (Darknet's correct_yolo_boxes with letter=1; include/yolov3_hip.h, y3_detect_letterbox):
+    // x' = (x - deltaw / 2 / net_w) / ratiow in float64 rounded to float32, w' = w * (1 / ratiow) in float32
+    const bool lb = p.lb_net_h > 0;
+    float ratiow = 1.f, ratioh = 1.f, inv_rw = 1.f, inv_rh = 1.f;
+    double shift_x = 0.0, shift_y = 0.0;
+    if (lb) {
+      const int h = p.orig_hw[b * 2 + 0], w = p.orig_hw[b * 2 + 1];
+      const Y3LetterboxGeom g = y3_letterbox_geom(h > 0 ? h : 1, w > 0 ? w : 1, p.lb_net_h, p.lb_net_w);
+      const float deltaw = (float)(p.lb_net_w - g.new_w), deltah = (float)(p.lb_net_h - g.new_h);
+      ratiow = (float)g.new_w / (float)p.lb_net_w;
+      ratioh = (float)g.new_h / (float)p.lb_net_h;
+      inv_rw = 1.0f / ratiow;
+      inv_rh = 1.0f / ratioh;
+      shift_x = (double)deltaw / 2.0 / (double)p.lb_net_w;
+      shift_y = (double)deltah / 2.0 / (double)p.lb_net_h;
+    }
     // kIt row-chunks per pass: the kIt score loads of a thread fly together (one memory latency per pass instead
     // of one per chunk), and the ordered slots of all kIt x 16 wave-chunks come from ONE workgroup barrier plus a
     // wave-level scan of the 128 ballot counts (every wave scans them redundantly: no second barrier to publish).
@@ -206,7 +224,13 @@ __global__ __launch_bounds__(kThreads) void detect_kernel(DetectArgs p) {
         if (fl[it]) {
           const int r = base + it * kThreads + tid;
           const int slot = n + off + pre[it];
-          const f32x4 bb = *reinterpret_cast<const f32x4 *>(p.bbox + ((long long)b * R + r) * 4);
+          f32x4 bb = *reinterpret_cast<const f32x4 *>(p.bbox + ((long long)b * R + r) * 4);
+          if (lb) {
+            bb[0] = (float)(((double)bb[0] - shift_x) / (double)ratiow);
+            bb[1] = (float)(((double)bb[1] - shift_y) / (double)ratioh);
+            bb[2] = bb[2] * inv_rw;
+            bb[3] = bb[3] * inv_rh;
+          }
           // float32 products, then truncation toward zero (inference.py:351-353)
           const long long cx = (long long)(bb[0] * ow), cy = (long long)(bb[1] * oh);
           const long long bw = (long long)(bb[2] * ow), bh = (long long)(bb[3] * oh);
@@ -647,10 +671,11 @@ extern "C" size_t y3_nms_workspace_bytes(int n) {
   return ws_layout(1, n).total;
 }
 
-extern "C" int y3_detect(const float *d_bbox, const float *d_prob, const int64_t *d_cls, int batch, int rows,
-                         const int32_t *d_orig_hw, float prob_thresh, double iou_thresh, void *d_workspace,
-                         size_t workspace_bytes, int32_t *d_det_count, int64_t *d_det_tlbr, float *d_det_prob,
-                         int64_t *d_det_cls, int32_t *d_det_row, void *stream) {
+namespace {
+int detect_launch(const float *d_bbox, const float *d_prob, const int64_t *d_cls, int batch, int rows, const int32_t *d_orig_hw,
+                  float prob_thresh, double iou_thresh, void *d_workspace, size_t workspace_bytes, int32_t *d_det_count,
+                  int64_t *d_det_tlbr, float *d_det_prob, int64_t *d_det_cls, int32_t *d_det_row, int lb_net_h, int lb_net_w,
+                  void *stream) {
   Y3_REQUIRE(batch > 0 && rows > 0, "y3_detect: batch and rows must be positive");
   Y3_REQUIRE(d_bbox && d_prob && d_cls && d_orig_hw && d_workspace && d_det_count && d_det_tlbr && d_det_prob &&
                  d_det_cls && d_det_row, "y3_detect: null pointer argument");
@@ -659,6 +684,7 @@ extern "C" int y3_detect(const float *d_bbox, const float *d_prob, const int64_t
   char *ws = static_cast<char *>(d_workspace);
   DetectArgs a = {};
   a.bbox = d_bbox; a.prob = d_prob; a.cls = reinterpret_cast<const long long *>(d_cls); a.orig_hw = d_orig_hw;
+  a.lb_net_h = lb_net_h; a.lb_net_w = lb_net_w;
   a.rows = rows; a.rows_p2 = next_pow2(rows);
   a.prob_thresh = prob_thresh; a.iou_thresh = iou_thresh;
   a.c_box = reinterpret_cast<long long *>(ws + w.box);
@@ -674,6 +700,24 @@ extern "C" int y3_detect(const float *d_bbox, const float *d_prob, const int64_t
   Y3_LAUNCH(detect_kernel<false>, dim3(batch), dim3(kThreads), 0, static_cast<hipStream_t>(stream), a);
   Y3_HIP_CHECK(hipGetLastError());
   return Y3_OK;
+}
+}  // namespace
+
+extern "C" int y3_detect(const float *d_bbox, const float *d_prob, const int64_t *d_cls, int batch, int rows,
+                         const int32_t *d_orig_hw, float prob_thresh, double iou_thresh, void *d_workspace,
+                         size_t workspace_bytes, int32_t *d_det_count, int64_t *d_det_tlbr, float *d_det_prob,
+                         int64_t *d_det_cls, int32_t *d_det_row, void *stream) {
+  return detect_launch(d_bbox, d_prob, d_cls, batch, rows, d_orig_hw, prob_thresh, iou_thresh, d_workspace, workspace_bytes,
+                       d_det_count, d_det_tlbr, d_det_prob, d_det_cls, d_det_row, 0, 0, stream);
+}
+
+extern "C" int y3_detect_letterbox(const float *d_bbox, const float *d_prob, const int64_t *d_cls, int batch, int rows,
+                                   const int32_t *d_orig_hw, float prob_thresh, double iou_thresh, void *d_workspace,
+                                   size_t workspace_bytes, int32_t *d_det_count, int64_t *d_det_tlbr, float *d_det_prob,
+                                   int64_t *d_det_cls, int32_t *d_det_row, int net_h, int net_w, void *stream) {
+  Y3_REQUIRE(net_h > 0 && net_w > 0, "y3_detect_letterbox: network size must be positive");
+  return detect_launch(d_bbox, d_prob, d_cls, batch, rows, d_orig_hw, prob_thresh, iou_thresh, d_workspace, workspace_bytes,
+                       d_det_count, d_det_tlbr, d_det_prob, d_det_cls, d_det_row, net_h, net_w, stream);
 }
 
 extern "C" int y3_nms(const int64_t *d_tlbr, const float *d_prob, const int64_t *d_cls, int n, double iou_thresh,

@@ -30,6 +30,7 @@ _MODEL_OPTIONS = [
     (("-n", "--class-names"), dict(type=pathlib.Path, metavar="<path>", help="text file, one class name per line; labels show indices without it")),
     (("--dtype",), dict(default="float32", choices=["float32", "fp16", "bf16"], help="conv arithmetic: float32 (the reference's; default, boxes and scores within 1e-3 of its CPU path), fp16 or bf16 storage with float32 accumulation (about 7x the frames/s; scores within ~1e-3 / ~1e-2)")),
     (("-b", "--batch-size"), dict(type=int, default=16, metavar="<n>", help="frames per GPU batch for folders and videos (default 16)")),
+    (("--letterbox",), dict(action="store_true", help="Darknet letterboxing: keep each frame's aspect ratio and fill the rest of the network input with grey (128) instead of stretching the frame; use it with yolov4-csp, which was trained that way")),
 ]
 _OUTPUT_OPTIONS = [
     (("-o", "--output"), dict(type=pathlib.Path, metavar="<path>", help="annotated frames: a folder of PNGs, or an .mp4 when OpenCV is installed")),
@@ -114,7 +115,8 @@ def main(argv=None):
         directory, names = stream.list_image_files(args["image"])
         images = [stream.load_image_bgr(os.path.join(directory, n)) for n in names]
         results = list(stream.detect_in_frames(net, images, batch_size=args["batch_size"],
-                                               prob_thresh=args["prob_thresh"], nms_iou_thresh=args["iou_thresh"]))
+                                               prob_thresh=args["prob_thresh"], nms_iou_thresh=args["iou_thresh"],
+                                               letterbox=args["letterbox"]))
         if frames is not None:
             for image, (bbox_tlbr, class_prob, class_idx) in zip(images, results):
                 stream.draw_boxes(image, bbox_tlbr, class_idx=class_idx, class_names=class_names)
@@ -123,7 +125,8 @@ def main(argv=None):
         fps = stream.video_fps(args["video"], fps)
         results = stream.detect_in_video(net, args["video"], device=device, prob_thresh=args["prob_thresh"],
                                          nms_iou_thresh=args["iou_thresh"], class_names=class_names,
-                                         frames=frames, show_video=False, batch_size=args["batch_size"])
+                                         frames=frames, show_video=False, batch_size=args["batch_size"],
+                                         letterbox=args["letterbox"])
         names = ["frame_%06d" % i for i in range(len(results))]
     else:
         cam = args["cam"]
@@ -131,7 +134,7 @@ def main(argv=None):
             cam = int(cam)
         stream.detect_in_cam(net, cam_id=cam, device=device, prob_thresh=args["prob_thresh"],
                              nms_iou_thresh=args["iou_thresh"], class_names=class_names,
-                             show_fps=args["show_fps"], frames=frames)
+                             show_fps=args["show_fps"], frames=frames, letterbox=args["letterbox"])
     elapsed = time.time() - t0
     if results is not None and args["verbose"]:
         kept = sum(len(r[1]) for r in results)

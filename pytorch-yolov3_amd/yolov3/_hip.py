@@ -36,7 +36,7 @@ OP_CONV, OP_MAXPOOL, OP_UPSAMPLE, OP_ADD, OP_COPY, OP_YOLO = 1, 2, 3, 4, 5, 6
 F_LEAKY, F_RESIDUAL, F_OUT_F32, F_IN_NCHW_F32, F_IN_NHWC_U8BGR, F_PLAN_INPUT, F_FUSE_NEXT = 1, 2, 4, 8, 16, 32, 64
 F_MISH, F_LOGISTIC, F_NEW_COORDS = 128, 256, 512
 # y3_capabilities() bits: what the loaded library computes beyond ABI 6 as first released
-CAP_MISH, CAP_SCALE_X_Y, CAP_LOGISTIC, CAP_NEW_COORDS = 1, 2, 4, 8
+CAP_MISH, CAP_SCALE_X_Y, CAP_LOGISTIC, CAP_NEW_COORDS, CAP_LETTERBOX = 1, 2, 4, 8, 16
 PATH_IGEMM, PATH_STEM, PATH_DIRECT, PATH_STEM_MFMA = 0, 1, 2, 3
 
 
@@ -59,6 +59,12 @@ class Y3Op(ctypes.Structure):
         ("block_idx", ctypes.c_int32), ("scale_x_y", ctypes.c_float),
         ("d_weight_frag", ctypes.c_void_p),
     ]
+
+
+class Y3LetterboxFrame(ctypes.Structure):
+    """Mirror of ``y3_letterbox_frame`` (include/yolov3_hip.h): one frame of a ``y3_letterbox_u8`` batch."""
+    _fields_ = [("d_src", ctypes.c_void_p), ("src_h", ctypes.c_int32), ("src_w", ctypes.c_int32),
+                ("d_ytab", ctypes.c_void_p), ("d_xtab", ctypes.c_void_p)]
 
 
 class Y3Options(ctypes.Structure):
@@ -115,6 +121,10 @@ PROTOTYPES = {
                                  ctypes.c_void_p, ctypes.c_float, ctypes.c_double, ctypes.c_void_p,
                                  ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "y3_detect_letterbox": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                           ctypes.c_void_p, ctypes.c_float, ctypes.c_double, ctypes.c_void_p,
+                                           ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
     "y3_nms_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int]),
     "y3_nms": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_double,
                               ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p,
@@ -128,6 +138,10 @@ PROTOTYPES = {
                                               ctypes.c_void_p]),
     "y3_resize_bilinear_u8": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
                                              ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "y3_letterbox_geometry": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                             ctypes.POINTER(ctypes.c_int32)]),
+    "y3_letterbox_u8": (ctypes.c_int, [ctypes.POINTER(Y3LetterboxFrame), ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
+                                       ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
     "y3_copy_bytes": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p]),
     "y3_pack_records": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                        ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
@@ -136,7 +150,7 @@ PROTOTYPES = {
 
 
 # symbols a library of ABI 6 built before they were added lacks: asked for through capabilities()
-_OPTIONAL = ("y3_capabilities",)
+_OPTIONAL = ("y3_capabilities", "y3_detect_letterbox", "y3_letterbox_geometry", "y3_letterbox_u8")
 
 
 class HipLibraryError(RuntimeError):
@@ -179,11 +193,12 @@ def capabilities():
 
 def require_capabilities(needs, what):
     """Refuse a plan that needs a computation the loaded library does not report: a stale library would run mish as
-    linear, ignore scale_x_y, run a logistic head as linear or decode new_coords heads the YOLOv3 way."""
+    linear, ignore scale_x_y, run a logistic head as linear, decode new_coords heads the YOLOv3 way or stretch frames
+    that were to be letterboxed."""
     missing = needs & ~capabilities()
     if missing:
         names = [n for n, b in (("mish", CAP_MISH), ("scale_x_y", CAP_SCALE_X_Y), ("logistic", CAP_LOGISTIC),
-                                ("new_coords", CAP_NEW_COORDS)) if missing & b]
+                                ("new_coords", CAP_NEW_COORDS), ("letterbox", CAP_LETTERBOX)) if missing & b]
         raise HipLibraryError("{}: the loaded libyolov3_hip.so cannot compute {} (rebuild: make -C pytorch-yolov3_amd/csrc)"
                               .format(what, ", ".join(names)))
 

@@ -10,7 +10,10 @@
   per-class NMS in one device kernel per batch (libyolov3_hip ``y3_detect``) and copies
   only the surviving detections back to the host;
 * frames that are not net-sized are resized on the GPU (``y3_resize_bilinear_u8``, bit-identical to
-  ``preprocess.resize_bilinear_u8``; the reference uses ``cv2.resize``, see that module's docstring).
+  ``preprocess.resize_bilinear_u8``; the reference uses ``cv2.resize``, see that module's docstring);
+* ``letterbox=True`` (opt-in, not in the reference) letterboxes the frames the Darknet way instead of stretching them
+  (``y3_letterbox_u8``, bit-identical to ``preprocess.letterbox_u8``) and corrects the boxes back to the frame
+  (``y3_detect_letterbox``, the same as ``preprocess.correct_letterbox_boxes`` followed by the reference's tail).
 
 There is no CPU fallback: without the HIP library / a GPU these functions raise.
 """
@@ -20,7 +23,7 @@ import numpy as np
 import torch
 
 from . import _hip
-from .preprocess import prepare_frames_device
+from .preprocess import letterbox_frames_device, prepare_frames_device
 
 
 def _device(device=None):
@@ -164,8 +167,9 @@ class Detector(object):
         self.orig_hw = torch.empty((batch, 2), dtype=torch.int32, device=device)
         self._records = {}      # kmax -> (batch, kmax, 8) int32 staging buffer of fetch()
 
-    def run(self, out, orig_hw, prob_thresh, iou_thresh):
-        """out: Darknet.forward dict (device tensors).  orig_hw: (batch,2) int32 tensor/array."""
+    def run(self, out, orig_hw, prob_thresh, iou_thresh, letterbox=None):
+        """out: Darknet.forward dict (device tensors).  orig_hw: (batch,2) int32 tensor/array.  letterbox: the
+        (net_h, net_w) the frames were letterboxed into -- the boxes are then corrected back (``y3_detect_letterbox``)."""
         if not isinstance(orig_hw, torch.Tensor):
             orig_hw = torch.from_numpy(np.ascontiguousarray(orig_hw, dtype=np.int32))
         if (orig_hw.device == self.orig_hw.device and orig_hw.dtype == torch.int32 and orig_hw.is_contiguous()
@@ -175,11 +179,16 @@ class Detector(object):
             self.orig_hw.copy_(orig_hw, non_blocking=True)
             hw = self.orig_hw
         bbox, prob, cls = out["bbox_xywh"], out["class_prob"], out["class_idx"]
-        _hip.check(_hip.lib().y3_detect(
-            bbox.data_ptr(), prob.data_ptr(), cls.data_ptr(), self.batch, self.rows, hw.data_ptr(),
-            ctypes.c_float(prob_thresh), ctypes.c_double(iou_thresh), self.ws.data_ptr(), self.ws_bytes,
-            self.count.data_ptr(), self.tlbr.data_ptr(), self.prob.data_ptr(), self.cls.data_ptr(),
-            self.row.data_ptr(), _hip.stream_ptr()))
+        args = (bbox.data_ptr(), prob.data_ptr(), cls.data_ptr(), self.batch, self.rows, hw.data_ptr(),
+                ctypes.c_float(prob_thresh), ctypes.c_double(iou_thresh), self.ws.data_ptr(), self.ws_bytes,
+                self.count.data_ptr(), self.tlbr.data_ptr(), self.prob.data_ptr(), self.cls.data_ptr(),
+                self.row.data_ptr())
+        if letterbox is None:
+            _hip.check(_hip.lib().y3_detect(*args, _hip.stream_ptr()))
+        else:
+            _hip.require_capabilities(_hip.CAP_LETTERBOX, "Detector.run(letterbox=...)")
+            net_h, net_w = (int(v) for v in letterbox)
+            _hip.check(_hip.lib().y3_detect_letterbox(*args, net_h, net_w, _hip.stream_ptr()))
 
     def fetch(self, return_rows=False, kmax=1024):
         """Detections of the last ``run`` on the host: ONE device-to-host copy per batch.  The device packs every
@@ -220,23 +229,35 @@ def get_detector(batch, rows, device):
 
 
 def inference(net, images, device="cuda", prob_thresh=0.05, nms_iou_thresh=0.3, resize=True,
-              return_rows=False):
+              return_rows=False, letterbox=False, letterbox_fill=128):
     """Run detection on one frame or a list of HxWx3 uint8 BGR frames.
 
     Returns, per frame, ``[bbox_tlbr int64 (K,4), class_prob float32 (K,), class_idx int64 (K,)]``
     (plus the prediction-row index of every detection when ``return_rows``), in original-frame
     pixel coordinates -- same contract as the reference's ``inference()``.
+
+    ``letterbox=True``: Darknet letterboxing instead of the stretched resize (aspect ratio kept, the rest of the network
+    input filled with the byte ``letterbox_fill``), boxes corrected back to the frame; frames of different sizes may
+    then share the call.  It needs ``resize`` (a ValueError otherwise).
     """
+    if letterbox and not resize:
+        raise ValueError("letterbox=True resizes every frame: it cannot be combined with resize=False")
     if not isinstance(images, (list, tuple)):
         images = [images]
     if str(device).startswith("cuda") and not str(net.device).startswith("cuda"):
         net.cuda(device)
     dev = net._torch_device()
-    frames, shapes = prepare_frames_device(list(images), net.net_info["height"], net.net_info["width"], dev, resize)
+    net_h, net_w = net.net_info["height"], net.net_info["width"]
+    if letterbox:
+        _hip.require_capabilities(_hip.CAP_LETTERBOX, "inference(letterbox=True)")
+        frames, shapes = letterbox_frames_device(list(images), net_h, net_w, dev, letterbox_fill)
+    else:
+        frames, shapes = prepare_frames_device(list(images), net_h, net_w, dev, resize)
     out = net.forward_frames(frames, fresh=False)
     batch, rows = out["class_prob"].shape
     det = get_detector(batch, rows, dev)
     orig_hw = np.array([[s[0], s[1]] for s in shapes], dtype=np.int32)
     with torch.cuda.device(dev):
-        det.run(out, orig_hw, float(np.float32(prob_thresh)), float(nms_iou_thresh))
+        det.run(out, orig_hw, float(np.float32(prob_thresh)), float(nms_iou_thresh),
+                letterbox=(net_h, net_w) if letterbox else None)
         return det.fetch(return_rows=return_rows)

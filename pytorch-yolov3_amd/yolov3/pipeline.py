@@ -163,10 +163,14 @@ class Pipeline(object):
         return self.streams[self._n % self.in_flight], self._n % self.max_open
 
     # ------------------------------------------------------------------ the pipelined step
-    def submit(self, frames, orig_hw=None, n_frames=None, to_host=True):
+    def submit(self, frames, orig_hw=None, n_frames=None, to_host=True, letterbox=False):
         """Enqueue one batch.  ``orig_hw``: (batch, 2) original frame sizes when the frames were resized to the network's
         size (default: they are net-sized).  ``n_frames``: how many leading frames of the batch are real (a short last
-        batch).  ``to_host=False`` leaves the records on the device (resident-rate measurements).  Returns the ticket."""
+        batch).  ``to_host=False`` leaves the records on the device (resident-rate measurements).  ``letterbox``: the
+        frames were letterboxed (``preprocess.letterbox_frames_device``), so the boxes are corrected back to ``orig_hw``
+        (``y3_detect_letterbox``).  Returns the ticket."""
+        if letterbox:
+            _hip.require_capabilities(_hip.CAP_LETTERBOX, "Pipeline.submit(letterbox=True)")
         i = self._n
         k, d = i % self.in_flight, i % self.max_open        # stream / arena of the batch; detector / record buffers of the ticket
         lib = _hip.lib()
@@ -205,7 +209,8 @@ class Pipeline(object):
             if j is not None:
                 self.free_ev[j].record(cur)
             det = self.dets[d]
-            det.run(out, self.full_hw if orig_hw is None else orig_hw, self.prob_thresh, self.nms_iou_thresh)
+            det.run(out, self.full_hw if orig_hw is None else orig_hw, self.prob_thresh, self.nms_iou_thresh,
+                    letterbox=(self.height, self.width) if letterbox else None)
             if n_frames is not None and int(n_frames) < self.batch:
                 # padding frames of a short last batch (copies of real frames, or whatever the staging buffer held) must not
                 # count: their detections are dropped here, BEFORE the records are packed and gathered, so that they can neither

@@ -25,6 +25,14 @@ bit-identical to each other; net-sized frames -- the benchmark's case, and the c
 skip the resize exactly like the reference does (inference.py:322-326).
 Like the reference, ``dsize`` is passed as ``(net_h, net_w)`` although cv2 reads it as (width, height): for the
 square networks shipped here that is the same thing, and :func:`reference_dsize` keeps the quirk for others.
+
+Letterboxing (opt-in; not in the reference, which stretches): Darknet's ``letterbox_image`` keeps the frame's aspect
+ratio, resizes it to :func:`letterbox_geometry`'s (new_h, new_w) with the resize above and pastes it at (top, left) of a
+net-sized canvas of the byte ``fill`` (:func:`letterbox_u8`; on the GPU :func:`letterbox_frames_device`, one
+``y3_letterbox_u8`` call per batch, bit-identical).  Differences from Darknet: the fill is a byte, 128 by default (Darknet
+fills with 0.5 in float, which a uint8 frame read as v / 255 cannot hold), and the resize is OpenCV's bilinear, not
+Darknet's ``resize_image``.  :func:`correct_letterbox_boxes` maps the network's relative boxes back to the frame
+(``correct_yolo_boxes(..., letter=1)``; on the GPU inside ``y3_detect_letterbox``).
 """
 import numpy as np
 
@@ -92,6 +100,16 @@ def axis_table(src_len, dst_len, clamp_weights):
 _device_tables = {}
 
 
+def _tables(sh, sw, out_h, out_w, device):
+    """Device tap tables of an (sh, sw) -> (out_h, out_w) resize, made once per geometry and device."""
+    import torch
+    key = (sh, sw, out_h, out_w, str(device))
+    if key not in _device_tables:
+        _device_tables[key] = (torch.from_numpy(axis_table(sh, out_h, False)).to(device),
+                               torch.from_numpy(axis_table(sw, out_w, True)).to(device))
+    return _device_tables[key]
+
+
 def resize_on_device(frame, out_h, out_w, device, out=None):
     """uint8 (H,W,3) numpy / torch frame -> uint8 (out_h,out_w,3) torch tensor on ``device`` (HIP kernel;
     identical result to :func:`resize_bilinear_u8`).  ``out`` may be a preallocated slice of a batch tensor."""
@@ -105,11 +123,7 @@ def resize_on_device(frame, out_h, out_w, device, out=None):
     if (sh, sw) == (out_h, out_w):
         out.copy_(src)
         return out
-    key = (sh, sw, out_h, out_w, str(device))
-    if key not in _device_tables:
-        _device_tables[key] = (torch.from_numpy(axis_table(sh, out_h, False)).to(device),
-                               torch.from_numpy(axis_table(sw, out_w, True)).to(device))
-    ytab, xtab = _device_tables[key]
+    ytab, xtab = _tables(sh, sw, out_h, out_w, device)
     with torch.cuda.device(device):
         _hip.check(_hip.lib().y3_resize_bilinear_u8(src.data_ptr(), sh, sw, out.data_ptr(), out_h, out_w,
                                                     ytab.data_ptr(), xtab.data_ptr(), _hip.stream_ptr()))
@@ -150,3 +164,93 @@ def prepare_frames(images, net_h, net_w, resize=True):
     out_h, out_w = _target_shapes(shapes, net_h, net_w, resize)
     images = [resize_bilinear_u8(im, out_h, out_w) for im in images]
     return np.ascontiguousarray(np.stack(images)), shapes
+
+
+# ---------------------------------------------------------------------------------------------- letterboxing
+def letterbox_geometry(h, w, net_h, net_w):
+    """(new_h, new_w, top, left) of an (h, w) frame letterboxed into (net_h, net_w): Darknet's ``letterbox_image``.
+    The side whose float32 scale is smaller fills the network, the other is scaled by the integer product (truncated)
+    and clamped to at least 1; the pad splits with integer halves.  Same definition as ``y3_letterbox_geometry``."""
+    h, w, net_h, net_w = int(h), int(w), int(net_h), int(net_w)
+    if min(h, w, net_h, net_w) <= 0:
+        raise ValueError("letterbox_geometry: sizes must be positive, got {}".format((h, w, net_h, net_w)))
+    if np.float32(net_w) / np.float32(w) < np.float32(net_h) / np.float32(h):
+        new_w, new_h = net_w, (h * net_w) // w
+    else:
+        new_h, new_w = net_h, (w * net_h) // h
+    new_h, new_w = max(new_h, 1), max(new_w, 1)
+    return new_h, new_w, (net_h - new_h) // 2, (net_w - new_w) // 2
+
+
+def _fill_byte(fill):
+    fill = int(fill)
+    if not 0 <= fill <= 255:
+        raise ValueError("letterbox fill must be a byte (0..255), got {}".format(fill))
+    return fill
+
+
+def letterbox_u8(img, net_h, net_w, fill=128):
+    """uint8 (H,W,3) -> uint8 (net_h,net_w,3): the frame resized to :func:`letterbox_geometry`'s size with
+    :func:`resize_bilinear_u8` and pasted at (top, left) of a canvas of ``fill``.  A net-sized frame comes back unchanged."""
+    img = np.asarray(img)
+    new_h, new_w, top, left = letterbox_geometry(img.shape[0], img.shape[1], net_h, net_w)
+    out = np.full((net_h, net_w, 3), _fill_byte(fill), dtype=np.uint8)
+    out[top:top + new_h, left:left + new_w] = resize_bilinear_u8(img, new_h, new_w)
+    return out
+
+
+def letterbox_frames_device(images, net_h, net_w, device, fill=128):
+    """Letterbox a list of uint8 (H,W,3) frames -- sizes may differ -- into a (B, net_h, net_w, 3) uint8 device tensor
+    with ONE ``y3_letterbox_u8`` call on the current stream (bit-identical to :func:`letterbox_u8`).  Every frame is
+    uploaded as :func:`prepare_frames_device` does; the tap tables are cached per geometry.  Returns (batch, shapes)."""
+    import torch
+    from . import _hip
+    _hip.require_capabilities(_hip.CAP_LETTERBOX, "letterbox_frames_device")
+    if not isinstance(images, (list, tuple)):
+        images = [images]
+    fill = _fill_byte(fill)
+    shapes = [tuple(im.shape) for im in images]
+    batch = torch.empty((len(images), net_h, net_w, 3), dtype=torch.uint8, device=device)
+    descs = (_hip.Y3LetterboxFrame * len(images))()
+    keep = []                                            # uploads alive until the launch is queued
+    for i, im in enumerate(images):
+        src = im if isinstance(im, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(im))
+        src = src.to(device).contiguous()
+        sh, sw = int(src.shape[0]), int(src.shape[1])
+        if src.dim() != 3 or src.shape[2] != 3 or src.dtype != torch.uint8:
+            raise ValueError("letterbox_frames_device: frame {} is not uint8 (H, W, 3): {} {}".format(
+                i, tuple(src.shape), src.dtype))
+        new_h, new_w, _, _ = letterbox_geometry(sh, sw, net_h, net_w)
+        ytab, xtab = _tables(sh, sw, new_h, new_w, device)
+        descs[i] = _hip.Y3LetterboxFrame(src.data_ptr(), sh, sw, ytab.data_ptr(), xtab.data_ptr())
+        keep.append(src)
+    with torch.cuda.device(device):
+        _hip.check(_hip.lib().y3_letterbox_u8(descs, len(images), batch.data_ptr(), net_h, net_w, fill, _hip.stream_ptr()))
+    return batch, shapes
+
+
+def correct_letterbox_boxes(bbox_xywh, orig_hw, net_h, net_w):
+    """Darknet's ``correct_yolo_boxes(..., letter=1)`` on relative boxes, for callers who run ``forward`` on
+    letterboxed frames themselves: bbox_xywh (B, N, 4) (or (N, 4) with one (h, w)), orig_hw (B, 2) frame sizes.
+    Per frame: ``x' = (float32)((x - deltaw / 2 / net_w) / ratiow)`` in float64 and ``w' = w * (1 / ratiow)`` in float32,
+    with ``deltaw = float32(net_w - new_w)`` and ``ratiow = float32(new_w) / net_w``; y, h likewise.  The correction
+    uses delta / 2 even where the image was shifted by the integer top / left (Darknet's own mismatch).  Returns a new
+    float32 array; feed it to the reference's ``* orig_w`` / ``* orig_h`` post-processing.  ``y3_detect_letterbox``
+    computes exactly this."""
+    box = np.array(bbox_xywh, dtype=np.float32)
+    hw = np.asarray(orig_hw).reshape(-1, 2)
+    single = box.ndim == 2
+    if single:
+        box = box[None]
+    if box.ndim != 3 or box.shape[2] < 4 or box.shape[0] != hw.shape[0]:
+        raise ValueError("correct_letterbox_boxes: expected (B, N, >=4) boxes and (B, 2) sizes, got {} and {}".format(
+            np.shape(bbox_xywh), np.shape(orig_hw)))
+    for i, (h, w) in enumerate(hw.tolist()):
+        new_h, new_w, _, _ = letterbox_geometry(h, w, net_h, net_w)
+        for c, (new, net) in ((0, (new_w, net_w)), (1, (new_h, net_h))):
+            delta = np.float32(net - new)
+            ratio = np.float32(new) / np.float32(net)
+            shift = np.float64(delta) / 2.0 / np.float64(net)
+            box[i, :, c] = ((box[i, :, c].astype(np.float64) - shift) / np.float64(ratio)).astype(np.float32)
+            box[i, :, c + 2] = box[i, :, c + 2] * (np.float32(1.0) / ratio)
+    return box[0] if single else box

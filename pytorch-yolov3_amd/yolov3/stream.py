@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from . import _hip
-from .preprocess import prepare_frames_device
+from .preprocess import letterbox_frames_device, prepare_frames_device
 
 IMAGE_EXTENSIONS = (".jpg", ".jpeg", ".png", ".bmp", ".ppm", ".webp", ".tif", ".tiff")
 
@@ -65,7 +65,7 @@ def _batches(frames, batch_size):
 
 
 def detect_in_frames(net, frames, batch_size=16, prob_thresh=0.05, nms_iou_thresh=0.3, resize=True,
-                     in_flight=3, kmax=512):
+                     in_flight=3, kmax=512, letterbox=False, letterbox_fill=128):
     """Generator over ``[bbox_tlbr, class_prob, class_idx]`` for every frame of the iterable
     ``frames`` (HxWx3 uint8 BGR arrays; sizes may differ when ``resize``), in order.
 
@@ -76,11 +76,20 @@ def detect_in_frames(net, frames, batch_size=16, prob_thresh=0.05, nms_iou_thres
     other sizes are uploaded one by one and resized on the GPU.  ``frames`` may also yield whole (B, H, W, 3) batches
     of net-sized frames: a pinned torch tensor is then uploaded from where it lies (no host copy at all), which is how
     a decoder that fills ``Pipeline.host_frames`` reaches the benchmark's rate.
+
+    ``letterbox=True`` letterboxes the frames that are not net-sized (one ``y3_letterbox_u8`` launch per batch, fill
+    byte ``letterbox_fill``) instead of stretching them, and corrects their boxes back; net-sized frames take the pinned
+    path above unchanged, since letterboxing is the identity on them.  Results equal per-frame
+    ``inference(letterbox=True)``.
     """
     from .pipeline import Pipeline
     _hip.require_gpu()
     if batch_size < 1 or in_flight < 1:
         raise ValueError("batch_size and in_flight must be positive")
+    if letterbox and not resize:
+        raise ValueError("letterbox=True resizes every frame: it cannot be combined with resize=False")
+    if letterbox:
+        _hip.require_capabilities(_hip.CAP_LETTERBOX, "detect_in_frames(letterbox=True)")
     if not str(net.device).startswith("cuda"):
         net.cuda()
     dev = net._torch_device()
@@ -124,14 +133,18 @@ def detect_in_frames(net, frames, batch_size=16, prob_thresh=0.05, nms_iou_thres
             for i, f in enumerate(batch):
                 host[i] = f.numpy() if isinstance(f, torch.Tensor) else f
             return pipe.submit(pipe.host_frames(j), n_frames=n)
-        # frames of other sizes: uploaded one by one and resized on the GPU, on the stream the pipeline will run the batch on
+        # frames of other sizes: uploaded one by one and resized (or letterboxed, the whole batch in one launch) on the GPU,
+        # on the stream the pipeline will run the batch on
         stream, slot = pipe.next_slot()
         pad = batch + [batch[-1]] * (pipe.batch - n)
         with torch.cuda.device(dev), torch.cuda.stream(stream):
-            dev_frames, shapes = prepare_frames_device(pad, height, width, dev, resize)
+            if letterbox:
+                dev_frames, shapes = letterbox_frames_device(pad, height, width, dev, letterbox_fill)
+            else:
+                dev_frames, shapes = prepare_frames_device(pad, height, width, dev, resize)
         state["keep"][slot] = dev_frames                      # alive until the ticket's buffers are reused
         orig_hw = np.array([[s[0], s[1]] for s in shapes], dtype=np.int32)
-        return pipe.submit(dev_frames, orig_hw=orig_hw, n_frames=n)
+        return pipe.submit(dev_frames, orig_hw=orig_hw, n_frames=n, letterbox=letterbox)
 
     def batches():
         group = []
@@ -165,12 +178,12 @@ def detect_in_frames(net, frames, batch_size=16, prob_thresh=0.05, nms_iou_thres
             state["pipe"].busy = False
 
 
-def detect_in_images(net, path, batch_size=16, prob_thresh=0.05, nms_iou_thresh=0.3):
+def detect_in_images(net, path, batch_size=16, prob_thresh=0.05, nms_iou_thresh=0.3, letterbox=False, letterbox_fill=128):
     """The CLI's ``--image`` mode: ``path`` is a file or a directory.  Returns (file names, results)."""
     directory, names = list_image_files(path)
     frames = (load_image_bgr(os.path.join(directory, n)) for n in names)
     results = list(detect_in_frames(net, frames, batch_size=batch_size, prob_thresh=prob_thresh,
-                                    nms_iou_thresh=nms_iou_thresh))
+                                    nms_iou_thresh=nms_iou_thresh, letterbox=letterbox, letterbox_fill=letterbox_fill))
     return names, results
 
 
@@ -217,7 +230,7 @@ def _video_frames(filepath):
 
 
 def detect_in_video(net, filepath, device="cuda", prob_thresh=0.05, nms_iou_thresh=0.3, class_names=None,
-                    frames=None, show_video=False, batch_size=16):
+                    frames=None, show_video=False, batch_size=16, letterbox=False, letterbox_fill=128):
     """Run detection over a video (or a directory of frames), draw the boxes on every frame and
     append the frames to ``frames`` when a list is given -- the reference's contract, batched.
     Returns the list of per-frame results."""
@@ -235,7 +248,7 @@ def detect_in_video(net, filepath, device="cuda", prob_thresh=0.05, nms_iou_thre
     results = []
     for i, (bbox_tlbr, class_prob, class_idx) in enumerate(
             detect_in_frames(net, tap(), batch_size=batch_size, prob_thresh=prob_thresh,
-                             nms_iou_thresh=nms_iou_thresh)):
+                             nms_iou_thresh=nms_iou_thresh, letterbox=letterbox, letterbox_fill=letterbox_fill)):
         frame = kept[i]
         kept[i] = None
         draw_boxes(frame, bbox_tlbr, class_idx=class_idx, class_names=class_names)
@@ -251,7 +264,7 @@ def detect_in_video(net, filepath, device="cuda", prob_thresh=0.05, nms_iou_thre
 
 
 def detect_in_cam(net, cam_id=0, device="cuda", prob_thresh=0.05, nms_iou_thresh=0.3, class_names=None,
-                  show_fps=False, frames=None):
+                  show_fps=False, frames=None, letterbox=False, letterbox_fill=128):
     """Live camera loop (latency-bound, one frame per step like the reference).  Needs OpenCV for
     capture and display."""
     cv2 = _cv2()
@@ -267,7 +280,8 @@ def detect_in_cam(net, cam_id=0, device="cuda", prob_thresh=0.05, nms_iou_thresh
             if not grabbed:
                 break
             bbox_tlbr, _, class_idx = inference(net, frame, device=device, prob_thresh=prob_thresh,
-                                                nms_iou_thresh=nms_iou_thresh)[0]
+                                                nms_iou_thresh=nms_iou_thresh, letterbox=letterbox,
+                                                letterbox_fill=letterbox_fill)[0]
             draw_boxes(frame, bbox_tlbr, class_idx=class_idx, class_names=class_names)
             if show_fps:
                 cv2.putText(frame, "%d fps" % int(1.0 / max(time.time() - t0, 1e-6)), (2, 20),
