@@ -48,7 +48,11 @@ extern "C" {
 
 /* op kinds of a plan (one per Darknet block that does work) */
 #define Y3_OP_CONV 1      /* conv -> (BN as per-channel scale/bias) -> LeakyReLU -> (+residual)  darknet.py:236-264, :376-379 */
-#define Y3_OP_MAXPOOL 2   /* darknet.py:16-29 (zero-pad right/bottom quirk when stride==1)        */
+#define Y3_OP_MAXPOOL 2   /* darknet.py:16-29 (zero-pad right/bottom quirk when stride==1): stride 1 takes the window
+                             [y, y+k) x [x, x+k) and counts out-of-range taps as 0.0; other strides pool unpadded,
+                             out = (in - k) / stride + 1.  With Y3_F_POOL_DARKNET: Darknet's own rule instead, with
+                             p = y3_op.pad: out = (in + p - k) / stride + 1, window origin o * stride - p / 2, taps
+                             outside the image ignored (size k odd, stride 1, p = k - 1: the centred "same" pool)  */
 #define Y3_OP_UPSAMPLE 3  /* nearest, integer factor: darknet.py:299-305                        */
 #define Y3_OP_ADD 4       /* unfused shortcut: darknet.py:376-379                               */
 #define Y3_OP_COPY 5      /* unfused route slice copy: darknet.py:369-375                       */
@@ -72,6 +76,16 @@ extern "C" {
 #define Y3_F_NEW_COORDS 512u   /* Y3_OP_YOLO: Darknet's new_coords=1 decode of a head whose conv ends in Y3_F_LOGISTIC: the inputs are
                                   probabilities already, so centre = (sxy(t) + cell) / grid, size = t * t * 4 * anchor / net,
                                   prob = objectness * max_c t_c (no exp, no soft-max); y3_capabilities() reports Y3_CAP_NEW_COORDS */
+#define Y3_F_POOL_DARKNET 1024u /* Y3_OP_MAXPOOL: Darknet's pooling rule.  y3_op.pad carries the cfg's `padding` p (Darknet's default:
+                                  ksize - 1); out_h = (in_h + p - ksize) / stride + 1, likewise out_w; output (i, j) is the max
+                                  over n, m in [0, ksize) of in[i * stride + n - p / 2][j * stride + m - p / 2], taking only taps
+                                  inside the image (integer p / 2).  An op some window of which would hold no tap is refused.
+                                  Without the flag `pad` is ignored on pools; the flag on any other op kind is an error.  Max of
+                                  stored values is exact, so results are bit-exact in every dtype for NaN-free inputs.  NaN taps:
+                                  the single-pool kernels (every dtype) and the float32 pyramid ignore them (fmaxf; a window whose
+                                  taps are all NaN gives -inf from the former); the 16-bit pyramid compares with
+                                  `a >= b ? a : b`, so whether a NaN survives depends on where it sits in the window -- the same
+                                  as without the flag.  y3_capabilities() reports Y3_CAP_POOL_DARKNET                         */
 
 /*
  * One unit of work.  POD, 8-byte aligned, zero-initialise unused fields.
@@ -90,7 +104,7 @@ typedef struct y3_op {
   int32_t batch;
   int32_t in_h, in_w, in_c, in_ld;
   int32_t out_h, out_w, out_c, out_ld;
-  int32_t ksize, stride, pad;     /* conv / maxpool / upsample factor in `stride` */
+  int32_t ksize, stride, pad;     /* conv / maxpool / upsample factor in `stride`; pad: conv, and maxpool with Y3_F_POOL_DARKNET */
   int32_t res_ld;
   int32_t k_ld;                   /* weight row stride (elements)                  */
   int32_t cout_pad;               /* padded rows of weight / length of scale, bias */
@@ -170,7 +184,8 @@ typedef struct y3_plan y3_plan;
  *                    y3_op.d_weight_frag or a private copy; 48-pixel tiles), else on the tiled kernel; 2: the tiled kernel only; 3 / 4:
  *                    the direct-weights kernel with 48- / 96-pixel tiles wherever the shape allows (same bits all four: A/B and tests);
  *                    0: two launches
- *   fuse_spp         1 [default]: three stride-1 max-pools (5 / 9 / 13) of one tensor in one launch
+ *   fuse_spp         1 [default]: three stride-1 max-pools (5 / 9 / 13) of one tensor in one launch, when all three pool by the
+ *                    same rule (all with Y3_F_POOL_DARKNET and pad = ksize - 1, or none with it); 0: three launches, same bits
  *   decode_lanes     4 [default]: four lanes per box in the bf16 decode; 1: sequential class loop everywhere
  *   fuse_block       0 [default]: off.  1: a 1x1 conv (-> 128 channels) + the 3x3 conv that is its only reader (+ the
  *                    shortcut add) run as ONE kernel with the 128-channel tensor kept in LDS (csrc/conv_block.hip), where map
@@ -195,6 +210,7 @@ int y3_abi_version(void);
 #define Y3_CAP_LOGISTIC 4u     /* Y3_F_LOGISTIC on conv ops                  */
 #define Y3_CAP_NEW_COORDS 8u   /* Y3_F_NEW_COORDS on YOLO ops                */
 #define Y3_CAP_LETTERBOX 16u   /* y3_letterbox_geometry, y3_letterbox_u8, y3_detect_letterbox */
+#define Y3_CAP_POOL_DARKNET 32u /* Y3_F_POOL_DARKNET and y3_op.pad on max-pool ops */
 uint32_t y3_capabilities(void);
 const char *y3_last_error(void);
 /* number of visible HIP devices whose arch is gfx950 (0 on a CPU-only machine) */

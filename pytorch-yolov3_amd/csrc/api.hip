@@ -143,10 +143,19 @@ int choose_conv(const y3_op &op, const y3_options &o, y3_step &st) {
   return y3_choose_conv_igemm(op, o, st);
 }
 
+// flags that belong to one op kind only (checked for every op of a plan, the ones a fused step absorbs included)
+int check_flags(const y3_op &op) {
+  Y3_REQUIRE(!(op.flags & Y3_F_POOL_DARKNET) || op.kind == Y3_OP_MAXPOOL,
+             "op for block %d: Y3_F_POOL_DARKNET on an op of kind %d (max-pool ops only)", op.block_idx, op.kind);
+  return Y3_OK;
+}
+
 // what one op runs on its own under options `o`
 int choose_op(const y3_op &op, const y3_options &o, y3_step &st) {
   Y3_REQUIRE(op.dtype == Y3_F32 || op.dtype == Y3_BF16 || op.dtype == Y3_F16, "op for block %d: unknown dtype %d", op.block_idx, op.dtype);
   Y3_REQUIRE(op.batch > 0 && op.in_h > 0 && op.in_w > 0 && op.in_c > 0, "op for block %d: empty input shape", op.block_idx);
+  const int rc = check_flags(op);
+  if (rc != Y3_OK) return rc;
   switch (op.kind) {
     case Y3_OP_CONV: return choose_conv(op, o, st);
     case Y3_OP_MAXPOOL: case Y3_OP_UPSAMPLE: case Y3_OP_ADD: case Y3_OP_COPY: return y3_choose_layer(op, st);
@@ -242,7 +251,7 @@ extern "C" {
 int y3_abi_version(void) { return Y3_ABI_VERSION; }
 
 uint32_t y3_capabilities(void) {
-  return Y3_CAP_MISH | Y3_CAP_SCALE_X_Y | Y3_CAP_LOGISTIC | Y3_CAP_NEW_COORDS | Y3_CAP_LETTERBOX;
+  return Y3_CAP_MISH | Y3_CAP_SCALE_X_Y | Y3_CAP_LOGISTIC | Y3_CAP_NEW_COORDS | Y3_CAP_LETTERBOX | Y3_CAP_POOL_DARKNET;
 }
 
 const char *y3_last_error(void) { return g_err; }
@@ -305,8 +314,12 @@ int y3_plan_create_ex(const y3_op *ops, int n_ops, const void *d_zero, const y3_
   bool private_frag = false;
   for (int i = 0; i < n_ops; ++i) {
     y3_step &st = p->steps[i];
+    int rc = check_flags(q[i]);
+    if (rc != Y3_OK) {
+      y3_plan_destroy(p);
+      return rc;
+    }
     if (st.fuse == y3_fuse::into_prev) { st.name = "(fused into the previous op)"; continue; }
-    int rc = Y3_OK;
     if (i + 2 < n_ops && o.fuse_spp && y3_choose_maxpool_spp(q[i], q[i + 1], q[i + 2], st)) {
       st.fuse = y3_fuse::spp;           // SPP pyramid: pool 5 / 9 / 13 of one tensor in one launch
     } else if (i + 1 < n_ops && (q[i].flags & Y3_F_FUSE_NEXT) && q[i].kind == Y3_OP_CONV &&

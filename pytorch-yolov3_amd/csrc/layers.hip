@@ -5,6 +5,7 @@
 // (/root/reference/yolov3/darknet.py:369-375) and no concat copy is needed on the usual path.
 #include "common.h"
 #include <initializer_list>
+#include <type_traits>
 
 namespace {
 
@@ -12,7 +13,7 @@ struct LayerArgs {
   const void *in;
   const void *in2;
   void *out;
-  int B, H, W, C, in_ld, in2_ld, Ho, Wo, out_ld, k, stride, zero_pad;
+  int B, H, W, C, in_ld, in2_ld, Ho, Wo, out_ld, k, stride, zero_pad, pad_lo;
   long long total;  // B*Ho*Wo*(C/VEC)
 };
 
@@ -98,6 +99,34 @@ __global__ __launch_bounds__(256) void maxpool_kernel(LayerArgs p) {
   store_vec<T, VEC>(static_cast<T *>(p.out) + (((long long)b * p.Ho + oy) * p.Wo + ox) * p.out_ld + cg * VEC, best);
 }
 
+// Darknet's rule (Y3_F_POOL_DARKNET; include/yolov3_hip.h): the window of output (oy, ox) starts at
+// (oy * stride - pad_lo, ox * stride - pad_lo) with pad_lo = padding / 2, and only its taps inside [0, H) x [0, W)
+// count: the tap ranges are clipped up front, nothing stands in for the taps left out.  y3_choose_layer has checked that
+// no window is empty, so `best` never stays at its -inf start on NaN-free input (fmaxf ignores a NaN tap).
+template <typename T, int VEC>
+__global__ __launch_bounds__(256) void maxpool_dk_kernel(LayerArgs p) {
+  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= p.total) return;
+  int b, oy, ox, cg;
+  decode_idx(idx, p.C / VEC, p.Wo, p.Ho, b, oy, ox, cg);
+  const int y0 = oy * p.stride - p.pad_lo, x0 = ox * p.stride - p.pad_lo;
+  const int ky0 = y0 < 0 ? -y0 : 0, ky1 = min(p.k, p.H - y0);
+  const int kx0 = x0 < 0 ? -x0 : 0, kx1 = min(p.k, p.W - x0);
+  float best[VEC];
+#pragma unroll
+  for (int j = 0; j < VEC; ++j) best[j] = -INFINITY;
+  for (int ky = ky0; ky < ky1; ++ky) {
+    const T *row = static_cast<const T *>(p.in) + (((long long)b * p.H + y0 + ky) * p.W + x0) * p.in_ld + cg * VEC;
+    for (int kx = kx0; kx < kx1; ++kx) {
+      float v[VEC];
+      load_vec<T, VEC>(row + (long long)kx * p.in_ld, v);
+#pragma unroll
+      for (int j = 0; j < VEC; ++j) best[j] = fmaxf(best[j], v[j]);
+    }
+  }
+  store_vec<T, VEC>(static_cast<T *>(p.out) + (((long long)b * p.Ho + oy) * p.Wo + ox) * p.out_ld + cg * VEC, best);
+}
+
 // nn.Upsample(scale_factor, mode="nearest") (darknet.py:302-305)
 template <typename T, int VEC>
 __global__ __launch_bounds__(256) void upsample_kernel(LayerArgs p) {
@@ -140,13 +169,14 @@ __global__ __launch_bounds__(256) void copy_kernel(LayerArgs p) {
   store_vec<T, VEC>(static_cast<T *>(p.out) + pix * p.out_ld + cg * VEC, x);
 }
 
-enum Which { MAXPOOL, UPSAMPLE, ADD, COPY };
+enum Which { MAXPOOL, MAXPOOL_DK, UPSAMPLE, ADD, COPY };
 
 template <typename T, int VEC>
 void launch_one(Which w, const LayerArgs &a, hipStream_t s) {
   const dim3 grid((unsigned)((a.total + 255) / 256)), block(256);
   switch (w) {
     case MAXPOOL: Y3_LAUNCH((maxpool_kernel<T, VEC>), grid, block, 0, s, a); break;
+    case MAXPOOL_DK: Y3_LAUNCH((maxpool_dk_kernel<T, VEC>), grid, block, 0, s, a); break;
     case UPSAMPLE: Y3_LAUNCH((upsample_kernel<T, VEC>), grid, block, 0, s, a); break;
     case ADD: Y3_LAUNCH((add_kernel<T, VEC>), grid, block, 0, s, a); break;
     case COPY: Y3_LAUNCH((copy_kernel<T, VEC>), grid, block, 0, s, a); break;
@@ -155,7 +185,7 @@ void launch_one(Which w, const LayerArgs &a, hipStream_t s) {
 
 int launch_layer(const y3_op *ops, const y3_step &, const void *d_in, const void *, hipStream_t s) {
   const y3_op &op = ops[0];
-  const Which w = op.kind == Y3_OP_MAXPOOL ? MAXPOOL : op.kind == Y3_OP_UPSAMPLE ? UPSAMPLE : op.kind == Y3_OP_ADD ? ADD : COPY;
+  const Which w = op.kind == Y3_OP_MAXPOOL ? ((op.flags & Y3_F_POOL_DARKNET) ? MAXPOOL_DK : MAXPOOL) : op.kind == Y3_OP_UPSAMPLE ? UPSAMPLE : op.kind == Y3_OP_ADD ? ADD : COPY;
   LayerArgs a;
   a.in = d_in;
   a.in2 = op.d_res;
@@ -164,6 +194,7 @@ int launch_layer(const y3_op *ops, const y3_step &, const void *d_in, const void
   a.Ho = op.out_h; a.Wo = op.out_w; a.out_ld = op.out_ld;
   a.k = op.ksize; a.stride = op.stride;
   a.zero_pad = (op.ksize > 1 && op.stride == 1) ? 1 : 0;
+  a.pad_lo = op.pad / 2;
   const int es = y3_elem_size(op.dtype);
   const int vec = 16 / es;
   bool wide = op.in_c % vec == 0 && op.in_ld % vec == 0 && op.out_ld % vec == 0 &&
@@ -186,6 +217,20 @@ int y3_choose_layer(const y3_op &op, y3_step &st) {
   switch (op.kind) {
     case Y3_OP_MAXPOOL:
       Y3_REQUIRE(op.ksize >= 1 && op.stride >= 1, "maxpool block %d: bad size/stride", op.block_idx);
+      if (op.flags & Y3_F_POOL_DARKNET) {
+        Y3_REQUIRE(op.pad >= 0, "maxpool block %d: negative padding %d", op.block_idx, op.pad);
+        Y3_REQUIRE(op.in_h + op.pad >= op.ksize && op.in_w + op.pad >= op.ksize,
+                   "maxpool block %d: size %d does not fit the padded %d x %d map (padding %d)", op.block_idx, op.ksize, op.in_h, op.in_w, op.pad);
+        Y3_REQUIRE(op.out_h == (op.in_h + op.pad - op.ksize) / op.stride + 1 && op.out_w == (op.in_w + op.pad - op.ksize) / op.stride + 1,
+                   "maxpool block %d: output size mismatch (Darknet rule: (in + padding - size) / stride + 1)", op.block_idx);
+        // first window ends at size - 1 - padding / 2, last window starts at (out - 1) * stride - padding / 2: both must
+        // touch the image, or an output would be the max of nothing
+        Y3_REQUIRE(op.pad / 2 < op.ksize && (op.out_h - 1) * op.stride - op.pad / 2 < op.in_h && (op.out_w - 1) * op.stride - op.pad / 2 < op.in_w,
+                   "maxpool block %d: padding %d leaves a window of size %d without a tap inside the %d x %d map", op.block_idx, op.pad,
+                   op.ksize, op.in_h, op.in_w);
+        st.name = Y3_KNAME(op.dtype, "maxpool_dk_", "");
+        return Y3_OK;
+      }
       if (op.stride == 1) {
         Y3_REQUIRE(op.out_h == op.in_h && op.out_w == op.in_w, "maxpool block %d: stride-1 keeps H,W", op.block_idx);
       } else {
@@ -224,6 +269,17 @@ int y3_choose_layer(const y3_op &op, y3_step &st) {
 //   P13[y][x] = max of the same four taps of P9                   on H x W
 // 4 + 4 + 3 + 3 = 14 LDS reads per output vector instead of 25 + 81 + 169 global loads, and each result goes
 // straight into its channel slice of the concat buffer (out pointers / pixel stride of the three ops).
+//
+// Darknet's rule (DK = true; Y3_F_POOL_DARKNET with padding = k - 1 on all three ops): window [y - k/2, y + k/2] x
+// [x - k/2, x + k/2], out-of-range taps ignored.  The cascade above only ever combines tile positions, so it does not care
+// where the image sits in the tile: stage the image at offset (6, 6) of the same (H+12) x (W+12) tile and fill the border
+// with -inf of the element type (the identity of max, so a border tap is a tap left out).  Tile position t = image
+// position t - 6, and Pk[ty][tx] covers tile rows [ty, ty+k), i.e. image rows [ty - 6, ty - 6 + k):
+//   13 x 13 at (y, x): image rows [y-6, y+6] = tile rows [y,   y+12]  -> P13[y][x]
+//    9 x  9 at (y, x): image rows [y-4, y+4] = tile rows [y+2, y+10]  -> P9[y+2][x+2]     (y+2 <= H+1, inside P9's H+4 rows)
+//    5 x  5 at (y, x): image rows [y-2, y+2] = tile rows [y+4, y+8]   -> P5[y+4][x+4]     (y+4 <= H+3, inside P5's H+8 rows)
+// so the same five steps run, with the stores of steps 3 / 4 taken from tile rows and columns [4, H+4) / [2, H+2) instead
+// of [0, H).  Every window holds its own centre, so no result is -inf unless the image is.  Same LDS, same reads, same grid.
 namespace {
 
 struct SppArgs {
@@ -247,7 +303,7 @@ __device__ __forceinline__ u32x4 vmax16(const u32x4 &a, const u32x4 &b) {
   }
 }
 
-template <typename T>
+template <typename T, bool DK>
 __global__ __launch_bounds__(256) void maxpool_spp_kernel(SppArgs p) {
   extern __shared__ __attribute__((aligned(16))) u32x4 spp_lds[];
   constexpr int ES = sizeof(T), V = 2;                 // 16-byte vectors per position
@@ -256,13 +312,17 @@ __global__ __launch_bounds__(256) void maxpool_spp_kernel(SppArgs p) {
   u32x4 *A = spp_lds, *Bf = spp_lds + PH * PW * V;
   const int tid = threadIdx.x;
   const long long frame = (long long)b * p.H * p.W;
-  const u32x4 zero = u32x4{0u, 0u, 0u, 0u};
-  // 1. stage the zero-padded image
+  // image origin in the tile; tile origin of the 5 x 5 / 9 x 9 results (the 13 x 13 ones start at 0 either way)
+  constexpr int O = DK ? 6 : 0, S5 = DK ? 4 : 0, S9 = DK ? 2 : 0;
+  // border value: 0.0, or -inf of the element type (float32 0xFF800000, bf16 0xFF80, fp16 0xFC00)
+  constexpr uint32_t FILL = !DK ? 0u : (ES == 4 ? 0xFF800000u : (std::is_same<T, bf16_t>::value ? 0xFF80FF80u : 0xFC00FC00u));
+  const u32x4 border = u32x4{FILL, FILL, FILL, FILL};
+  // 1. stage the padded image
   for (int idx = tid; idx < PH * PW * V; idx += 256) {
-    const int pos = idx >> 1, v = idx & 1, y = pos / PW, x = pos - y * PW;
-    A[idx] = (y < p.H && x < p.W)
+    const int pos = idx >> 1, v = idx & 1, ty = pos / PW, tx = pos - ty * PW, y = ty - O, x = tx - O;
+    A[idx] = ((unsigned)y < (unsigned)p.H && (unsigned)x < (unsigned)p.W)
                  ? *reinterpret_cast<const u32x4 *>(p.in + ((frame + y * p.W + x) * p.in_ld) * ES + cg * 32 + v * 16)
-                 : zero;
+                 : border;
   }
   __syncthreads();
   // 2. row pass of the 5 x 5 pool
@@ -276,7 +336,7 @@ __global__ __launch_bounds__(256) void maxpool_spp_kernel(SppArgs p) {
     Bf[(y * PW + x) * V + v] = vmax16<T>(m, a[4 * V]);
   }
   __syncthreads();
-  // 3. column pass -> P5 on (H+8) x (W+8), kept in A; the H x W part is the 5 x 5 pool's output
+  // 3. column pass -> P5 on (H+8) x (W+8), kept in A; its H x W part from (S5, S5) on is the 5 x 5 pool's output
   for (int idx = tid; idx < H5 * W5 * V; idx += 256) {
     const int pos = idx >> 1, v = idx & 1, y = pos / W5, x = pos - y * W5;
     const u32x4 *r = Bf + (y * PW + x) * V + v;
@@ -285,19 +345,19 @@ __global__ __launch_bounds__(256) void maxpool_spp_kernel(SppArgs p) {
     m = vmax16<T>(m, r[3 * PW * V]);
     m = vmax16<T>(m, r[4 * PW * V]);
     A[(y * PW + x) * V + v] = m;
-    if (y < p.H && x < p.W)
-      *reinterpret_cast<u32x4 *>(p.out5 + ((frame + y * p.W + x) * p.ld5) * ES + cg * 32 + v * 16) = m;
+    if ((unsigned)(y - S5) < (unsigned)p.H && (unsigned)(x - S5) < (unsigned)p.W)
+      *reinterpret_cast<u32x4 *>(p.out5 + ((frame + (y - S5) * p.W + (x - S5)) * p.ld5) * ES + cg * 32 + v * 16) = m;
   }
   __syncthreads();
-  // 4. P9 on (H+4) x (W+4) from four taps of P5, kept in Bf
+  // 4. P9 on (H+4) x (W+4) from four taps of P5, kept in Bf; the 9 x 9 pool's output from (S9, S9) on
   const int W9 = PW - 8, H9 = PH - 8;
   for (int idx = tid; idx < H9 * W9 * V; idx += 256) {
     const int pos = idx >> 1, v = idx & 1, y = pos / W9, x = pos - y * W9;
     const u32x4 *a = A + (y * PW + x) * V + v;
     const u32x4 m = vmax16<T>(vmax16<T>(a[0], a[4 * V]), vmax16<T>(a[4 * PW * V], a[(4 * PW + 4) * V]));
     Bf[(y * PW + x) * V + v] = m;
-    if (y < p.H && x < p.W)
-      *reinterpret_cast<u32x4 *>(p.out9 + ((frame + y * p.W + x) * p.ld9) * ES + cg * 32 + v * 16) = m;
+    if ((unsigned)(y - S9) < (unsigned)p.H && (unsigned)(x - S9) < (unsigned)p.W)
+      *reinterpret_cast<u32x4 *>(p.out9 + ((frame + (y - S9) * p.W + (x - S9)) * p.ld9) * ES + cg * 32 + v * 16) = m;
   }
   __syncthreads();
   // 5. P13 on H x W from four taps of P9
@@ -316,12 +376,16 @@ size_t spp_lds_bytes(const y3_op &op) { return (size_t)(op.in_h + 12) * (op.in_w
 static int launch_maxpool_spp(const y3_op *ops, const y3_step &, const void *, const void *, hipStream_t s);
 
 // three consecutive max-pool ops of a plan.  True when they form the SPP pyramid this kernel computes: sizes {5, 9, 13} in
-// any order, stride 1, the same input view, 32-byte channel groups, and the image fits LDS.
+// any order, stride 1, the same input view, 32-byte channel groups, the image fits LDS, and one pooling rule for all three:
+// none with Y3_F_POOL_DARKNET, or all with it and padding = size - 1 (the centred pool the kernel's DK form computes).  Anything
+// else, a triple of mixed rules included, runs as three single pools.
 bool y3_choose_maxpool_spp(const y3_op &a, const y3_op &b, const y3_op &c, y3_step &st) {
   const y3_op *o[3] = {&a, &b, &c};
   int seen = 0;
   for (const y3_op *q : o) {
     if (q->kind != Y3_OP_MAXPOOL || q->stride != 1) return false;
+    if ((q->flags & Y3_F_POOL_DARKNET) != (a.flags & Y3_F_POOL_DARKNET)) return false;
+    if ((q->flags & Y3_F_POOL_DARKNET) && q->pad != q->ksize - 1) return false;
     if (q->ksize == 5) seen |= 1; else if (q->ksize == 9) seen |= 2; else if (q->ksize == 13) seen |= 4; else return false;
     if (q->d_in != a.d_in || q->in_ld != a.in_ld || q->in_h != a.in_h || q->in_w != a.in_w || q->in_c != a.in_c ||
         q->batch != a.batch || q->dtype != a.dtype || (q->flags & Y3_F_PLAN_INPUT))
@@ -333,7 +397,7 @@ bool y3_choose_maxpool_spp(const y3_op &a, const y3_op &b, const y3_op &c, y3_st
   }
   if (seen != 7 || spp_lds_bytes(a) > 64 * 1024) return false;
   st.launch = launch_maxpool_spp;
-  st.name = Y3_KNAME(a.dtype, "maxpool_spp_pyramid_", "");
+  st.name = (a.flags & Y3_F_POOL_DARKNET) ? Y3_KNAME(a.dtype, "maxpool_spp_pyramid_dk_", "") : Y3_KNAME(a.dtype, "maxpool_spp_pyramid_", "");
   return true;
 }
 
@@ -352,7 +416,8 @@ static int launch_maxpool_spp(const y3_op *ops, const y3_step &, const void *, c
   const size_t lds = spp_lds_bytes(a);
   const dim3 grid((unsigned)(a.batch * p.cgroups)), block(256);
   return y3_by_dtype(a.dtype, [&](auto tag) {
-    Y3_LAUNCH((maxpool_spp_kernel<decltype(tag)>), grid, block, lds, s, p);
+    if (a.flags & Y3_F_POOL_DARKNET) Y3_LAUNCH((maxpool_spp_kernel<decltype(tag), true>), grid, block, lds, s, p);
+    else Y3_LAUNCH((maxpool_spp_kernel<decltype(tag), false>), grid, block, lds, s, p);
     Y3_HIP_CHECK(hipGetLastError());
     return Y3_OK;
   });

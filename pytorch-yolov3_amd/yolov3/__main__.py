@@ -31,6 +31,7 @@ _MODEL_OPTIONS = [
     (("--dtype",), dict(default="float32", choices=["float32", "fp16", "bf16"], help="conv arithmetic: float32 (the reference's; default, boxes and scores within 1e-3 of its CPU path), fp16 or bf16 storage with float32 accumulation (about 7x the frames/s; scores within ~1e-3 / ~1e-2)")),
     (("-b", "--batch-size"), dict(type=int, default=16, metavar="<n>", help="frames per GPU batch for folders and videos (default 16)")),
     (("--letterbox",), dict(action="store_true", help="Darknet letterboxing: keep each frame's aspect ratio and fill the rest of the network input with grey (128) instead of stretching the frame; use it with yolov4-csp, which was trained that way")),
+    (("--darknet-pool",), dict(action="store_true", help="Darknet max-pooling (centred windows, out-of-range taps ignored) instead of the reference's; use it with weights trained by Darknet for yolov3-spp, yolov4 and yolov4-csp (the latter together with --letterbox)")),
 ]
 _OUTPUT_OPTIONS = [
     (("-o", "--output"), dict(type=pathlib.Path, metavar="<path>", help="annotated frames: a folder of PNGs, or an .mp4 when OpenCV is installed")),
@@ -95,7 +96,8 @@ def main(argv=None):
     import yolov3
     from yolov3 import stream
 
-    net = yolov3.Darknet(args["config"], device=device, dtype=args["dtype"])
+    net = yolov3.Darknet(args["config"], device=device, dtype=args["dtype"],
+                         pool="darknet" if args["darknet_pool"] else "reference")
     net.load_weights(args["weights"])
     net.eval()
     net.cuda(device=device)

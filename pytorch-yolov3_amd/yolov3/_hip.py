@@ -34,9 +34,9 @@ LIB_PATH = os.environ.get("Y3_HIP_LIB") or os.path.join(_HERE, "..", "lib", "lib
 Y3_F32, Y3_BF16, Y3_F16, Y3_F64 = 0, 1, 2, 3
 OP_CONV, OP_MAXPOOL, OP_UPSAMPLE, OP_ADD, OP_COPY, OP_YOLO = 1, 2, 3, 4, 5, 6
 F_LEAKY, F_RESIDUAL, F_OUT_F32, F_IN_NCHW_F32, F_IN_NHWC_U8BGR, F_PLAN_INPUT, F_FUSE_NEXT = 1, 2, 4, 8, 16, 32, 64
-F_MISH, F_LOGISTIC, F_NEW_COORDS = 128, 256, 512
+F_MISH, F_LOGISTIC, F_NEW_COORDS, F_POOL_DARKNET = 128, 256, 512, 1024
 # y3_capabilities() bits: what the loaded library computes beyond ABI 6 as first released
-CAP_MISH, CAP_SCALE_X_Y, CAP_LOGISTIC, CAP_NEW_COORDS, CAP_LETTERBOX = 1, 2, 4, 8, 16
+CAP_MISH, CAP_SCALE_X_Y, CAP_LOGISTIC, CAP_NEW_COORDS, CAP_LETTERBOX, CAP_POOL_DARKNET = 1, 2, 4, 8, 16, 32
 PATH_IGEMM, PATH_STEM, PATH_DIRECT, PATH_STEM_MFMA = 0, 1, 2, 3
 
 
@@ -193,12 +193,13 @@ def capabilities():
 
 def require_capabilities(needs, what):
     """Refuse a plan that needs a computation the loaded library does not report: a stale library would run mish as
-    linear, ignore scale_x_y, run a logistic head as linear, decode new_coords heads the YOLOv3 way or stretch frames
-    that were to be letterboxed."""
+    linear, ignore scale_x_y, run a logistic head as linear, decode new_coords heads the YOLOv3 way, stretch frames
+    that were to be letterboxed or pool the reference's way where Darknet's rule was asked for."""
     missing = needs & ~capabilities()
     if missing:
         names = [n for n, b in (("mish", CAP_MISH), ("scale_x_y", CAP_SCALE_X_Y), ("logistic", CAP_LOGISTIC),
-                                ("new_coords", CAP_NEW_COORDS), ("letterbox", CAP_LETTERBOX)) if missing & b]
+                                ("new_coords", CAP_NEW_COORDS), ("letterbox", CAP_LETTERBOX),
+                                ("Darknet max-pooling", CAP_POOL_DARKNET)) if missing & b]
         raise HipLibraryError("{}: the loaded libyolov3_hip.so cannot compute {} (rebuild: make -C pytorch-yolov3_amd/csrc)"
                               .format(what, ", ".join(names)))
 

@@ -20,7 +20,7 @@ import torch
 
 from . import _hip
 from .cfgparse import parse_config
-from .plan import build_plan, check_blocks
+from .plan import build_plan, check_blocks, check_pool_mode
 from .weights import conv_layout, read_darknet_weights
 
 BN_EPS = np.float32(1e-5)
@@ -66,6 +66,19 @@ class BlockInfo(object):
         return "BlockInfo({}, {})".format(self.index, self.type)
 
 
+def fill_maxpool_op(op, od):
+    """Kind, size, stride and pooling rule of a plan's maxpool op dict into the C ABI's ``y3_op``; returns the library
+    capabilities the op relies on.  Darknet's rule (``od["pool"] == "darknet"``) travels as Y3_F_POOL_DARKNET with the
+    cfg's ``padding`` in ``pad``; the default sets neither."""
+    op.kind = _hip.OP_MAXPOOL
+    op.ksize, op.stride = od["ksize"], od["stride"]
+    if od.get("pool") == "darknet":
+        op.flags |= _hip.F_POOL_DARKNET
+        op.pad = od["pad"]
+        return _hip.CAP_POOL_DARKNET
+    return 0
+
+
 class _CompiledPlan(object):
     def __init__(self):
         self.handle = None
@@ -89,7 +102,7 @@ class _CompiledPlan(object):
 
 
 class Darknet(object):
-    def __init__(self, config_fpath, device="cpu", dtype="float32", keep_all=False, fuse=None, options=None):
+    def __init__(self, config_fpath, device="cpu", dtype="float32", keep_all=False, fuse=None, options=None, pool="reference"):
         """
         Args:
             config_fpath (str): Darknet .cfg file.
@@ -99,7 +112,13 @@ class Darknet(object):
             dtype (str): "float32" (parity path, exact fp32 MFMA), "bf16" (bf16 activations/weights, fp32
                 accumulation; the benchmarked throughput path) or "fp16" (IEEE half storage, same kernels and rate,
                 eight times finer rounding: the throughput path closest to the reference's float32 results).
+            pool (str): max-pool semantics of every [maxpool] block.  "reference" [default]: the reference's (stride 1:
+                window [y, y+k), out-of-range taps count as 0.0).  "darknet": Darknet's (window centred by padding / 2,
+                out-of-range taps ignored, out = (in + padding - size) / stride + 1), what yolov3-spp / yolov4 / yolov4-csp
+                weights trained by Darknet expect from their SPP block.  Fixed for the life of the object; keys of the cfg
+                never switch it on.
         """
+        self._pool = check_pool_mode(pool)
         self.blocks, self.net_info = parse_config(config_fpath)
         if self.net_info is None:
             raise ValueError("cfg {!r} has no [net] section".format(config_fpath))
@@ -134,6 +153,12 @@ class Darknet(object):
         self._dev_weights = {}       # (slot, path) -> dict of device tensors
         self._plans = {}
         self._zero = None
+
+    @property
+    def pool(self):
+        """Max-pool semantics of this network, "reference" or "darknet": set by the constructor only, so that the cached
+        plans of one object never mix modes."""
+        return self._pool
 
     # ------------------------------------------------------------------ nn.Module-like surface
     def eval(self):
@@ -293,7 +318,8 @@ class Darknet(object):
         self._made_fragments = False
         c_dtype, es = DTYPES[self.dtype][0], DTYPES[self.dtype][1]
         bf16 = es == 2                       # a 16-bit storage mode (bf16 or fp16)
-        desc = build_plan(self.blocks, self.net_info, batch, height, width, es, reuse=not self.keep_all, fuse=self.fuse)
+        desc = build_plan(self.blocks, self.net_info, batch, height, width, es, reuse=not self.keep_all, fuse=self.fuse,
+                          pool=self.pool)
         cp = _CompiledPlan()
         cp.batch = batch
         cp.rows_total = desc["rows_total"]
@@ -373,8 +399,7 @@ class Darknet(object):
                     op.d_weight_frag = frag.data_ptr()
                     cp.keep.append(frag)
             elif kind == "maxpool":
-                op.kind = _hip.OP_MAXPOOL
-                op.ksize, op.stride = od["ksize"], od["stride"]
+                needs |= fill_maxpool_op(op, od)
             elif kind == "upsample":
                 op.kind = _hip.OP_UPSAMPLE
                 op.ksize, op.stride = 1, od["stride"]

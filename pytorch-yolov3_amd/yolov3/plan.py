@@ -39,6 +39,35 @@ class Tensor(object):
 
 
 ACTIVATIONS = ("leaky", "linear", "mish", "logistic")
+# max-pool semantics: "reference" (stride 1: window [y, y+k), out-of-range taps count as 0.0; else unpadded) or "darknet"
+# (window origin o * stride - padding / 2, out-of-range taps ignored: ``maxpool_geometry``)
+POOL_MODES = ("reference", "darknet")
+
+
+def check_pool_mode(pool):
+    if pool not in POOL_MODES:
+        raise ValueError("pool={!r}: expected one of {}".format(pool, ", ".join(repr(m) for m in POOL_MODES)))
+    return pool
+
+
+def maxpool_geometry(i, blk, h, w, pool):
+    """(out_h, out_w, padding) of [maxpool] block ``i`` on an (h, w) map.  "reference": stride 1 keeps the size, other strides
+    pool unpadded, floor mode; padding is 0 (unused).  "darknet": padding = the cfg's ``padding`` key (Darknet's default:
+    size - 1), out = (in + padding - size) // stride + 1; a block one of whose windows would hold no tap is refused."""
+    k, s = blk["size"], blk["stride"]
+    if pool != "darknet":
+        if k > 1 and s == 1:
+            return h, w, 0
+        return (h - k) // s + 1, (w - k) // s + 1, 0
+    p = int(blk.get("padding", k - 1))
+    if p < 0 or h + p < k or w + p < k:
+        raise ValueError("maxpool block {}: size={} padding={} does not fit a {}x{} map".format(i, k, p, h, w))
+    oh, ow = (h + p - k) // s + 1, (w + p - k) // s + 1
+    # the first window ends at k - 1 - p // 2, the last one starts at (out - 1) * s - p // 2
+    if p // 2 >= k or (oh - 1) * s - p // 2 >= h or (ow - 1) * s - p // 2 >= w:
+        raise ValueError("maxpool block {}: padding={} leaves a window of size={} without a tap inside the {}x{} map".format(
+            i, p, k, h, w))
+    return oh, ow, p
 
 
 def route_groups(blk):
@@ -62,6 +91,17 @@ def check_blocks(blocks):
             if int(blk.get("dilation", 1)) != 1:
                 raise ValueError("conv block {}: dilated convolution (dilation={}) is not supported".format(
                     i, blk["dilation"]))
+        elif kind == "maxpool":
+            # Darknet's other pools; the kernels compute the spatial k x k pool with one stride only
+            if int(blk.get("maxpool_depth", 0)) != 0:
+                raise ValueError("maxpool block {}: maxpool_depth={} (pooling over channels) is not supported".format(
+                    i, blk["maxpool_depth"]))
+            if int(blk.get("antialiasing", 0)) != 0:
+                raise ValueError("maxpool block {}: antialiasing={} is not supported".format(i, blk["antialiasing"]))
+            for key in ("stride_x", "stride_y"):
+                if key in blk and blk[key] != blk.get("stride", 1):
+                    raise ValueError("maxpool block {}: {}={} differs from stride={} (one stride for both axes only)".format(
+                        i, key, blk[key], blk.get("stride", 1)))
         elif kind == "route":
             groups, gid = route_groups(blk)
             if groups != 1 and len(blk["layers"]) != 1:
@@ -84,10 +124,11 @@ def check_blocks(blocks):
                     i, blk["activation"]))
 
 
-def infer_shapes(blocks, net_info, height, width):
+def infer_shapes(blocks, net_info, height, width, pool="reference"):
     """(C,H,W) of every block output for an input of size (height,width); conv arithmetic
-    as torch.nn.Conv2d / MaxPool2d / Upsample compute it."""
+    as torch.nn.Conv2d / MaxPool2d / Upsample compute it, max-pools by Darknet's size formula with ``pool="darknet"``."""
     check_blocks(blocks)
+    check_pool_mode(pool)
     shapes = []
     c, h, w = net_info["channels"], height, width
     for i, blk in enumerate(blocks):
@@ -99,10 +140,7 @@ def infer_shapes(blocks, net_info, height, width):
             w = (w + 2 * pad - k) // s + 1
             c = blk["filters"]
         elif kind == "maxpool":
-            k, s = blk["size"], blk["stride"]
-            if not (k > 1 and s == 1):
-                h = (h - k) // s + 1
-                w = (w - k) // s + 1
+            h, w, _ = maxpool_geometry(i, blk, h, w, pool)
         elif kind == "upsample":
             h, w = h * blk["stride"], w * blk["stride"]
         elif kind == "route":
@@ -129,7 +167,7 @@ def infer_shapes(blocks, net_info, height, width):
     return shapes
 
 
-def build_plan(blocks, net_info, batch, height, width, elem_size, reuse=True, fuse=None):
+def build_plan(blocks, net_info, batch, height, width, elem_size, reuse=True, fuse=None, pool="reference"):
     """Resolve the graph.  ``blocks`` must already carry absolute route indices.
 
     Returns dict(ops=[...], buffers={id: nbytes}, offsets={id: arena offset}, arena_bytes,
@@ -137,11 +175,13 @@ def build_plan(blocks, net_info, batch, height, width, elem_size, reuse=True, fu
     ``fuse`` (default: same as ``reuse``): mark conv pairs the executor may run as one kernel; with
     ``reuse=False, fuse=True`` (per-block parity tests) the intermediate tensor of a fused pair keeps
     its arena slot but is never written.
+    ``pool``: "reference" [default] or "darknet" max-pool semantics for every [maxpool] block; under "darknet" each maxpool op
+    carries ``pool="darknet"`` and ``pad`` (Darknet's ``padding``), under the default neither key.
     """
     if fuse is None:
         fuse = reuse
     n = len(blocks)
-    shapes = infer_shapes(blocks, net_info, height, width)
+    shapes = infer_shapes(blocks, net_info, height, width, pool)
     kinds = [b["type"] for b in blocks]
 
     # ---- consumers of every block output -------------------------------------------------
@@ -261,8 +301,11 @@ def build_plan(blocks, net_info, batch, height, width, elem_size, reuse=True, fu
                 tensor_of[i] = out
         elif kind in ("maxpool", "upsample"):
             out = placed[i] if i in placed else own_tensor(i)
-            ops.append(dict(kind=kind, block=i, inp=prev_tensor(i), out=out, ksize=blk.get("size", 1),
-                            stride=blk["stride"]))
+            op = dict(kind=kind, block=i, inp=prev_tensor(i), out=out, ksize=blk.get("size", 1), stride=blk["stride"])
+            if kind == "maxpool" and pool == "darknet":
+                op["pool"] = "darknet"
+                op["pad"] = maxpool_geometry(i, blk, op["inp"].h, op["inp"].w, pool)[2]
+            ops.append(op)
             tensor_of[i] = out
         elif kind == "shortcut":
             if i in fused_into:
