@@ -211,6 +211,7 @@ int y3_abi_version(void);
 #define Y3_CAP_NEW_COORDS 8u   /* Y3_F_NEW_COORDS on YOLO ops                */
 #define Y3_CAP_LETTERBOX 16u   /* y3_letterbox_geometry, y3_letterbox_u8, y3_detect_letterbox */
 #define Y3_CAP_POOL_DARKNET 32u /* Y3_F_POOL_DARKNET and y3_op.pad on max-pool ops */
+#define Y3_CAP_NMS_DARKNET 64u /* y3_detect_darknet, y3_nms_darknet and their workspace queries */
 uint32_t y3_capabilities(void);
 const char *y3_last_error(void);
 /* number of visible HIP devices whose arch is gfx950 (0 on a CPU-only machine) */
@@ -292,6 +293,43 @@ int y3_detect_letterbox(const float *d_bbox, const float *d_prob, const int64_t 
                         const int32_t *d_orig_hw, float prob_thresh, double iou_thresh, void *d_workspace,
                         size_t workspace_bytes, int32_t *d_det_count, int64_t *d_det_tlbr, float *d_det_prob,
                         int64_t *d_det_cls, int32_t *d_det_row, int net_h, int net_w, void *stream);
+
+/* Darknet's suppression rule (src/box.c: box_iou, box_diou, box_diounms; do_nms_sort, diounms_sort) instead of the
+ * reference's.  Not in the reference.  ONLY the decision which candidates survive changes: thresholding, candidate order
+ * (class ascending, score descending, higher row first), "a suppressed box suppresses nobody", independent classes and
+ * everything a kept detection carries are y3_detect's, so the detections are a subset of y3_detect's at iou_thresh = 1.0 with
+ * identical rows.  The rule works on the float32 centre / size boxes (x, y, w, h) of d_bbox as the network emitted them --
+ * with net_h, net_w > 0 on the letterbox-corrected values of y3_detect_letterbox, before the * orig_w / * orig_h product --
+ * in float32, one rounding per operation, except pow:
+ *   overlap(x1,w1,x2,w2) = min(x1 + w1/2, x2 + w2/2) - max(x1 - w1/2, x2 - w2/2)     min(p,q) = p < q ? p : q, max likewise
+ *   I   = (ow < 0 || oh < 0) ? 0 : ow * oh                 ow, oh = overlap in x, in y
+ *   U   = a.w*a.h + b.w*b.h - I
+ *   iou = (I == 0 || U == 0) ? 0 : I / U
+ *   cw  = max(a.x + a.w/2, b.x + b.w/2) - min(a.x - a.w/2, b.x - b.w/2)    ch likewise in y
+ *   c   = cw*cw + ch*ch          d = (a.x-b.x)*(a.x-b.x) + (a.y-b.y)*(a.y-b.y)
+ *   Y3_NMS_IOU     m = iou                                  (what a cfg without nms_kind gets)
+ *   Y3_NMS_GREEDY  m = (c == 0) ? iou : iou - d / c         (nms_kind=greedynms)
+ *   Y3_NMS_DIOU    m = (c == 0) ? iou : iou - (float)pow((double)(d / c), (double)beta_nms)    (nms_kind=diounms)
+ *   a suppresses b  iff  m > (float)iou_thresh
+ * NaN compares false everywhere: a NaN measure suppresses nothing.  beta_nms must be finite and > 0 (whatever the kind).
+ * net_h = net_w = 0: the frames were not letterboxed.  Workspace: y3_detect_darknet_workspace_bytes (larger than
+ * y3_detect's: it also holds the candidates' float boxes).                                                          */
+#define Y3_NMS_IOU 0
+#define Y3_NMS_GREEDY 1
+#define Y3_NMS_DIOU 2
+size_t y3_detect_darknet_workspace_bytes(int batch, int rows);
+int y3_detect_darknet(const float *d_bbox, const float *d_prob, const int64_t *d_cls, int batch, int rows,
+                      const int32_t *d_orig_hw, float prob_thresh, double iou_thresh, void *d_workspace,
+                      size_t workspace_bytes, int32_t *d_det_count, int64_t *d_det_tlbr, float *d_det_prob,
+                      int64_t *d_det_cls, int32_t *d_det_row, int net_h, int net_w, int nms_kind, float beta_nms,
+                      void *stream);
+/* the same rule on caller-provided boxes: d_xywh (n,4) float32 centre / size (16-byte aligned), d_prob (n) f32, d_cls (n)
+ * int64 or NULL (class-agnostic); d_keep (n) int64 receives the kept indices ordered by (class asc, score desc, index
+ * desc); d_keep_count (1) int32.                                                                                     */
+size_t y3_nms_darknet_workspace_bytes(int n);
+int y3_nms_darknet(const float *d_xywh, const float *d_prob, const int64_t *d_cls, int n, float thresh, int nms_kind,
+                   float beta_nms, void *d_workspace, size_t workspace_bytes, int64_t *d_keep, int32_t *d_keep_count,
+                   void *stream);
 
 /* non_max_suppression (inference.py:161-266) on caller-provided integer boxes -------------- */
 size_t y3_nms_workspace_bytes(int n);

@@ -65,7 +65,13 @@ struct DetectArgs {
   long long *det_cls;
   int *det_row;
   long long *keep_idx;
+  // Darknet suppression rule (detect_kernel<.., DK> with DK != kDkOff; y3_detect_darknet / y3_nms_darknet)
+  const float *in_xywh;         // caller-boxes mode: [n][4] centre / size
+  float *c_fbox;                // workspace, per frame: [rows][4] float32 (x, y, w, h) of every candidate
+  float dk_thresh, dk_beta;
 };
+
+constexpr int kDkOff = 0, kDkIou = 1, kDkGreedy = 2, kDkDiou = 3;   // kDkIou .. = Y3_NMS_IOU .. + 1
 
 __device__ __forceinline__ unsigned int score_desc_bits(float p) {
   unsigned int u = __float_as_uint(p);
@@ -122,6 +128,44 @@ __device__ __forceinline__ bool box_fits_i32(long long x1, long long y1, long lo
   return x1 > -lim && x1 < lim && y1 > -lim && y1 < lim && x2 > -lim && x2 < lim && y2 > -lim && y2 < lim;
 }
 
+__device__ __forceinline__ float readlane_f(float v, int k) {
+  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), k));
+}
+
+// Darknet's suppression test on float32 centre/size boxes (include/yolov3_hip.h, y3_detect_darknet, states the rule;
+// src/box.c: box_iou, box_diou, box_diounms).  Every operation rounds once to float32 (-ffp-contract=off), min / max are
+// Darknet's `a < b ? a : b` / `a > b ? a : b`, and a NaN anywhere ends in a false comparison.  The DIoU penalty d / c (or its
+// power) is never negative, and float32 subtraction is monotonic, so m <= iou: pairs with !(iou > thr) are decided without it
+// -- the double-precision pow runs only for pairs that plain IoU would suppress.  pow(0, beta) = 0 needs no call either.
+__device__ __forceinline__ float dk_overlap(float x1, float w1, float x2, float w2) {
+  const float l1 = x1 - w1 / 2.f, l2 = x2 - w2 / 2.f;
+  const float left = l1 > l2 ? l1 : l2;
+  const float r1 = x1 + w1 / 2.f, r2 = x2 + w2 / 2.f;
+  const float right = r1 < r2 ? r1 : r2;
+  return right - left;
+}
+
+template <int DK>
+__device__ __forceinline__ bool dk_suppresses(float ax, float ay, float aw, float ah, float bx, float by, float bw, float bh,
+                                              float thr, float beta) {
+  const float ow = dk_overlap(ax, aw, bx, bw), oh = dk_overlap(ay, ah, by, bh);
+  const float inter = (ow < 0.f || oh < 0.f) ? 0.f : ow * oh;
+  const float uni = aw * ah + bw * bh - inter;
+  const float iou = (inter == 0.f || uni == 0.f) ? 0.f : inter / uni;
+  if (DK == kDkIou || !(iou > thr)) return iou > thr;
+  const float r1 = ax + aw / 2.f, r2 = bx + bw / 2.f, l1 = ax - aw / 2.f, l2 = bx - bw / 2.f;
+  const float cw = (r1 > r2 ? r1 : r2) - (l1 < l2 ? l1 : l2);
+  const float b1 = ay + ah / 2.f, b2 = by + bh / 2.f, t1 = ay - ah / 2.f, t2 = by - bh / 2.f;
+  const float ch = (b1 > b2 ? b1 : b2) - (t1 < t2 ? t1 : t2);
+  const float c = cw * cw + ch * ch;
+  const float dx = ax - bx, dy = ay - by;
+  const float d = dx * dx + dy * dy;
+  if (c == 0.f) return true;                 // m = iou, and iou > thr
+  float q = d / c;
+  if (DK == kDkDiou && q != 0.f) q = (float)pow((double)q, (double)beta);
+  return iou - q > thr;
+}
+
 // block-wide ordered compaction step: returns this thread's output slot (valid when flag) and
 // adds the step's total to `running`.  Must be called by all threads.
 __device__ __forceinline__ int ordered_slot(bool flag, int &running, int *wave_tot) {
@@ -143,7 +187,9 @@ __device__ __forceinline__ int ordered_slot(bool flag, int &running, int *wave_t
   return slot;
 }
 
-template <bool NMS_MODE>
+// DK: kDkOff = the reference's rule on the integer corners (everything above); otherwise phase 1 also keeps every candidate's
+// float32 (x, y, w, h) and phase 4 decides survivors by Darknet's rule on them (do_chunk_dk).  Nothing else changes.
+template <bool NMS_MODE, int DK = kDkOff>
 __global__ __launch_bounds__(kThreads) void detect_kernel(DetectArgs p) {
   __shared__ unsigned long long skey[kLdsSort];
   __shared__ unsigned int spos[kLdsSort];
@@ -231,6 +277,7 @@ __global__ __launch_bounds__(kThreads) void detect_kernel(DetectArgs p) {
             bb[2] = bb[2] * inv_rw;
             bb[3] = bb[3] * inv_rh;
           }
+          if constexpr (DK != kDkOff) *reinterpret_cast<f32x4 *>(p.c_fbox + ((long long)b * R + slot) * 4) = bb;
           // float32 products, then truncation toward zero (inference.py:351-353)
           const long long cx = (long long)(bb[0] * ow), cy = (long long)(bb[1] * oh);
           const long long bw = (long long)(bb[2] * ow), bh = (long long)(bb[3] * oh);
@@ -445,6 +492,48 @@ __global__ __launch_bounds__(kThreads) void detect_kernel(DetectArgs p) {
       if (fb >= 0) __hip_atomic_store(&flags_sh[fb + j], 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
       else __threadfence_block();  // later chunks of this wavefront read these flags
   };
+  // the same chunk under Darknet's rule: one float32 centre/size box per lane, the survivor's four floats broadcast by
+  // v_readlane, victims cleared by ballot; chain, flags and publication exactly as above
+  const float *fbox = NMS_MODE ? p.in_xywh : p.c_fbox + (long long)b * R * 4;
+  auto do_chunk_dk = [&](int start, int end, int j, int fb) {
+      const int c0 = start + 64 * j;
+      const int idx = c0 + lane;
+      const bool valid = idx < end;
+      f32x4 me = {0.f, 0.f, 0.f, 0.f};
+      if (valid) me = *reinterpret_cast<const f32x4 *>(fbox + (long long)s_pos[idx] * 4);
+      bool dead = !valid;
+      for (int jj = 0; jj < j; ++jj) {
+        if (fb >= 0) {
+          while (__hip_atomic_load(&flags_sh[fb + jj], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) == 0)
+            __builtin_amdgcn_s_sleep(1);
+        }
+        const int p0 = start + 64 * jj;                 // an earlier chunk is full: p0 + lane < end
+        unsigned long long kept = __ballot(keep[p0 + lane] != 0);
+        if (kept == 0ull) continue;
+        const f32x4 q = *reinterpret_cast<const f32x4 *>(fbox + (long long)s_pos[p0 + lane] * 4);
+        while (kept) {
+          const int k = __ffsll((long long)kept) - 1;
+          kept &= kept - 1ull;
+          const bool hit = dk_suppresses<DK>(readlane_f(q[0], k), readlane_f(q[1], k), readlane_f(q[2], k), readlane_f(q[3], k),
+                                             me[0], me[1], me[2], me[3], p.dk_thresh, p.dk_beta);
+          dead = dead || hit;
+        }
+      }
+      unsigned long long alive = __ballot(!dead);
+      for (int k = 0; k < 64; ++k) {
+        if (!((alive >> k) & 1ull)) continue;  // wave-uniform
+        const bool hit = dk_suppresses<DK>(readlane_f(me[0], k), readlane_f(me[1], k), readlane_f(me[2], k), readlane_f(me[3], k),
+                                           me[0], me[1], me[2], me[3], p.dk_thresh, p.dk_beta);
+        alive &= ~__ballot(lane > k && hit);
+      }
+      if (valid) keep[idx] = (alive >> lane) & 1ull ? 1 : 0;
+      if (fb >= 0) __hip_atomic_store(&flags_sh[fb + j], 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+      else __threadfence_block();
+  };
+  auto run_chunk = [&](int start, int end, int j, int fb) {
+    if constexpr (DK == kDkOff) do_chunk(start, end, j, fb);
+    else do_chunk_dk(start, end, j, fb);
+  };
   const int wave_u = __builtin_amdgcn_readfirstlane(wave);
   for (int it = wave_u; it < nitem; it += kWaves) {
     const int start = __builtin_amdgcn_readfirstlane(items[it * 4 + 0]);
@@ -452,10 +541,10 @@ __global__ __launch_bounds__(kThreads) void detect_kernel(DetectArgs p) {
     const int j = __builtin_amdgcn_readfirstlane(items[it * 4 + 2]);
     const int fb = __builtin_amdgcn_readfirstlane(items[it * 4 + 3]);
     if (j >= 0) {
-      do_chunk(start, end, j, fb);
+      run_chunk(start, end, j, fb);
     } else {
       const int nch = (end - start + 63) >> 6;
-      for (int jj = 0; jj < nch; ++jj) do_chunk(start, end, jj, -1);
+      for (int jj = 0; jj < nch; ++jj) run_chunk(start, end, jj, -1);
     }
   }
   __syncthreads();
@@ -701,7 +790,100 @@ int detect_launch(const float *d_bbox, const float *d_prob, const int64_t *d_cls
   Y3_HIP_CHECK(hipGetLastError());
   return Y3_OK;
 }
+// Darknet rule: the reference layout plus the candidates' float32 boxes
+size_t dk_fbox_offset(int batch, int rows) { return ws_layout(batch, rows).total; }
+size_t dk_ws_total(int batch, int rows) { return dk_fbox_offset(batch, rows) + align_up((size_t)batch * (size_t)rows * 4 * sizeof(float)); }
+
+int dk_check(const char *who, int nms_kind, float beta_nms) {
+  Y3_REQUIRE(nms_kind == Y3_NMS_IOU || nms_kind == Y3_NMS_GREEDY || nms_kind == Y3_NMS_DIOU,
+             "%s: nms_kind %d is none of Y3_NMS_IOU, Y3_NMS_GREEDY, Y3_NMS_DIOU", who, nms_kind);
+  Y3_REQUIRE(beta_nms > 0.f && beta_nms <= 3.402823466e38f, "%s: beta_nms must be finite and > 0", who);
+  return Y3_OK;
+}
+
+template <bool NMS_MODE>
+int dk_launch(const DetectArgs &a, int grid, int nms_kind, hipStream_t s) {
+  if (nms_kind == Y3_NMS_IOU) Y3_LAUNCH((detect_kernel<NMS_MODE, kDkIou>), dim3(grid), dim3(kThreads), 0, s, a);
+  else if (nms_kind == Y3_NMS_GREEDY) Y3_LAUNCH((detect_kernel<NMS_MODE, kDkGreedy>), dim3(grid), dim3(kThreads), 0, s, a);
+  else Y3_LAUNCH((detect_kernel<NMS_MODE, kDkDiou>), dim3(grid), dim3(kThreads), 0, s, a);
+  Y3_HIP_CHECK(hipGetLastError());
+  return Y3_OK;
+}
 }  // namespace
+
+extern "C" size_t y3_detect_darknet_workspace_bytes(int batch, int rows) {
+  if (batch <= 0 || rows <= 0) return 0;
+  return dk_ws_total(batch, rows);
+}
+
+extern "C" size_t y3_nms_darknet_workspace_bytes(int n) {
+  if (n <= 0) return 256;
+  return ws_layout(1, n).total;
+}
+
+extern "C" int y3_detect_darknet(const float *d_bbox, const float *d_prob, const int64_t *d_cls, int batch, int rows,
+                                 const int32_t *d_orig_hw, float prob_thresh, double iou_thresh, void *d_workspace,
+                                 size_t workspace_bytes, int32_t *d_det_count, int64_t *d_det_tlbr, float *d_det_prob,
+                                 int64_t *d_det_cls, int32_t *d_det_row, int net_h, int net_w, int nms_kind, float beta_nms,
+                                 void *stream) {
+  Y3_REQUIRE(batch > 0 && rows > 0, "y3_detect_darknet: batch and rows must be positive");
+  Y3_REQUIRE(d_bbox && d_prob && d_cls && d_orig_hw && d_workspace && d_det_count && d_det_tlbr && d_det_prob &&
+                 d_det_cls && d_det_row, "y3_detect_darknet: null pointer argument");
+  Y3_REQUIRE((net_h == 0 && net_w == 0) || (net_h > 0 && net_w > 0),
+             "y3_detect_darknet: network size must be positive, or 0, 0 for frames that were not letterboxed");
+  if (int rc = dk_check("y3_detect_darknet", nms_kind, beta_nms)) return rc;
+  const size_t need = dk_ws_total(batch, rows);
+  Y3_REQUIRE(workspace_bytes >= need, "y3_detect_darknet: workspace too small (%zu < %zu)", workspace_bytes, need);
+  const WsLayout w = ws_layout(batch, rows);
+  char *ws = static_cast<char *>(d_workspace);
+  DetectArgs a = {};
+  a.bbox = d_bbox; a.prob = d_prob; a.cls = reinterpret_cast<const long long *>(d_cls); a.orig_hw = d_orig_hw;
+  a.lb_net_h = net_h; a.lb_net_w = net_w;
+  a.rows = rows; a.rows_p2 = next_pow2(rows);
+  a.prob_thresh = prob_thresh; a.iou_thresh = iou_thresh;
+  a.c_box = reinterpret_cast<long long *>(ws + w.box);
+  a.c_prob = reinterpret_cast<float *>(ws + w.prob);
+  a.c_cls = reinterpret_cast<int *>(ws + w.cls);
+  a.c_row = reinterpret_cast<int *>(ws + w.row);
+  a.s_key = reinterpret_cast<unsigned long long *>(ws + w.key);
+  a.s_pos = reinterpret_cast<unsigned int *>(ws + w.pos);
+  a.keep = reinterpret_cast<unsigned char *>(ws + w.keep);
+  a.seg = reinterpret_cast<int *>(ws + w.seg);
+  a.c_fbox = reinterpret_cast<float *>(ws + dk_fbox_offset(batch, rows));
+  a.dk_thresh = (float)iou_thresh; a.dk_beta = beta_nms;
+  a.det_count = d_det_count; a.det_tlbr = reinterpret_cast<long long *>(d_det_tlbr); a.det_prob = d_det_prob;
+  a.det_cls = reinterpret_cast<long long *>(d_det_cls); a.det_row = d_det_row;
+  return dk_launch<false>(a, batch, nms_kind, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int y3_nms_darknet(const float *d_xywh, const float *d_prob, const int64_t *d_cls, int n, float thresh, int nms_kind,
+                              float beta_nms, void *d_workspace, size_t workspace_bytes, int64_t *d_keep,
+                              int32_t *d_keep_count, void *stream) {
+  Y3_REQUIRE(n >= 0, "y3_nms_darknet: negative n");
+  Y3_REQUIRE(d_keep_count, "y3_nms_darknet: null d_keep_count");
+  if (int rc = dk_check("y3_nms_darknet", nms_kind, beta_nms)) return rc;
+  if (n == 0) {
+    Y3_HIP_CHECK(hipMemsetAsync(d_keep_count, 0, sizeof(int32_t), static_cast<hipStream_t>(stream)));
+    return Y3_OK;
+  }
+  Y3_REQUIRE(d_xywh && d_prob && d_workspace && d_keep, "y3_nms_darknet: null pointer argument");
+  Y3_REQUIRE((reinterpret_cast<uintptr_t>(d_xywh) & 15) == 0, "y3_nms_darknet: d_xywh must be 16-byte aligned");
+  const WsLayout w = ws_layout(1, n);
+  Y3_REQUIRE(workspace_bytes >= w.total, "y3_nms_darknet: workspace too small (%zu < %zu)", workspace_bytes, w.total);
+  char *ws = static_cast<char *>(d_workspace);
+  DetectArgs a = {};
+  a.in_xywh = d_xywh; a.in_prob = d_prob;
+  a.in_cls = reinterpret_cast<const long long *>(d_cls); a.n_in = n;
+  a.rows = n; a.rows_p2 = next_pow2(n);
+  a.dk_thresh = thresh; a.dk_beta = beta_nms;
+  a.s_key = reinterpret_cast<unsigned long long *>(ws + w.key);
+  a.s_pos = reinterpret_cast<unsigned int *>(ws + w.pos);
+  a.keep = reinterpret_cast<unsigned char *>(ws + w.keep);
+  a.seg = reinterpret_cast<int *>(ws + w.seg);
+  a.det_count = d_keep_count;
+  a.keep_idx = reinterpret_cast<long long *>(d_keep);
+  return dk_launch<true>(a, 1, nms_kind, static_cast<hipStream_t>(stream));
+}
 
 extern "C" int y3_detect(const float *d_bbox, const float *d_prob, const int64_t *d_cls, int batch, int rows,
                          const int32_t *d_orig_hw, float prob_thresh, double iou_thresh, void *d_workspace,

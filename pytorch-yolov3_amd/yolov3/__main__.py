@@ -32,6 +32,8 @@ _MODEL_OPTIONS = [
     (("-b", "--batch-size"), dict(type=int, default=16, metavar="<n>", help="frames per GPU batch for folders and videos (default 16)")),
     (("--letterbox",), dict(action="store_true", help="Darknet letterboxing: keep each frame's aspect ratio and fill the rest of the network input with grey (128) instead of stretching the frame; use it with yolov4-csp, which was trained that way")),
     (("--darknet-pool",), dict(action="store_true", help="Darknet max-pooling (centred windows, out-of-range taps ignored) instead of the reference's; use it with weights trained by Darknet for yolov3-spp, yolov4 and yolov4-csp (the latter together with --letterbox)")),
+    (("--nms-kind",), dict(choices=["iou", "greedynms", "diounms"], default=None, help="suppress by Darknet's rule on the float32 boxes instead of the reference's on integer pixel corners: iou (a cfg without nms_kind), greedynms (yolov4.cfg) or diounms (yolov4-csp.cfg); -i is its threshold (Darknet's own defaults are -p 0.25 -i 0.45)")),
+    (("--beta-nms",), dict(type=float, default=0.6, metavar="<beta>", help="exponent of the distance penalty of --nms-kind diounms (default 0.6, the cfgs' beta_nms)")),
 ]
 _OUTPUT_OPTIONS = [
     (("-o", "--output"), dict(type=pathlib.Path, metavar="<path>", help="annotated frames: a folder of PNGs, or an .mp4 when OpenCV is installed")),
@@ -118,7 +120,8 @@ def main(argv=None):
         images = [stream.load_image_bgr(os.path.join(directory, n)) for n in names]
         results = list(stream.detect_in_frames(net, images, batch_size=args["batch_size"],
                                                prob_thresh=args["prob_thresh"], nms_iou_thresh=args["iou_thresh"],
-                                               letterbox=args["letterbox"]))
+                                               letterbox=args["letterbox"], nms_kind=args["nms_kind"],
+                                               beta_nms=args["beta_nms"]))
         if frames is not None:
             for image, (bbox_tlbr, class_prob, class_idx) in zip(images, results):
                 stream.draw_boxes(image, bbox_tlbr, class_idx=class_idx, class_names=class_names)
@@ -128,7 +131,7 @@ def main(argv=None):
         results = stream.detect_in_video(net, args["video"], device=device, prob_thresh=args["prob_thresh"],
                                          nms_iou_thresh=args["iou_thresh"], class_names=class_names,
                                          frames=frames, show_video=False, batch_size=args["batch_size"],
-                                         letterbox=args["letterbox"])
+                                         letterbox=args["letterbox"], nms_kind=args["nms_kind"], beta_nms=args["beta_nms"])
         names = ["frame_%06d" % i for i in range(len(results))]
     else:
         cam = args["cam"]
@@ -136,7 +139,8 @@ def main(argv=None):
             cam = int(cam)
         stream.detect_in_cam(net, cam_id=cam, device=device, prob_thresh=args["prob_thresh"],
                              nms_iou_thresh=args["iou_thresh"], class_names=class_names,
-                             show_fps=args["show_fps"], frames=frames, letterbox=args["letterbox"])
+                             show_fps=args["show_fps"], frames=frames, letterbox=args["letterbox"],
+                             nms_kind=args["nms_kind"], beta_nms=args["beta_nms"])
     elapsed = time.time() - t0
     if results is not None and args["verbose"]:
         kept = sum(len(r[1]) for r in results)

@@ -37,6 +37,10 @@ F_LEAKY, F_RESIDUAL, F_OUT_F32, F_IN_NCHW_F32, F_IN_NHWC_U8BGR, F_PLAN_INPUT, F_
 F_MISH, F_LOGISTIC, F_NEW_COORDS, F_POOL_DARKNET = 128, 256, 512, 1024
 # y3_capabilities() bits: what the loaded library computes beyond ABI 6 as first released
 CAP_MISH, CAP_SCALE_X_Y, CAP_LOGISTIC, CAP_NEW_COORDS, CAP_LETTERBOX, CAP_POOL_DARKNET = 1, 2, 4, 8, 16, 32
+CAP_NMS_DARKNET = 64
+# Darknet's suppression measures (include/yolov3_hip.h: Y3_NMS_*), by the cfg's spelling of `nms_kind`
+NMS_IOU, NMS_GREEDY, NMS_DIOU = 0, 1, 2
+NMS_KINDS = {"iou": NMS_IOU, "greedynms": NMS_GREEDY, "diounms": NMS_DIOU}
 PATH_IGEMM, PATH_STEM, PATH_DIRECT, PATH_STEM_MFMA = 0, 1, 2, 3
 
 
@@ -125,6 +129,16 @@ PROTOTYPES = {
                                            ctypes.c_void_p, ctypes.c_float, ctypes.c_double, ctypes.c_void_p,
                                            ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    "y3_detect_darknet_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
+    "y3_detect_darknet": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                         ctypes.c_void_p, ctypes.c_float, ctypes.c_double, ctypes.c_void_p,
+                                         ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                         ctypes.c_float, ctypes.c_void_p]),
+    "y3_nms_darknet_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int]),
+    "y3_nms_darknet": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_float,
+                                      ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
+                                      ctypes.c_void_p, ctypes.c_void_p]),
     "y3_nms_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int]),
     "y3_nms": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_double,
                               ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p,
@@ -150,7 +164,8 @@ PROTOTYPES = {
 
 
 # symbols a library of ABI 6 built before they were added lacks: asked for through capabilities()
-_OPTIONAL = ("y3_capabilities", "y3_detect_letterbox", "y3_letterbox_geometry", "y3_letterbox_u8")
+_OPTIONAL = ("y3_capabilities", "y3_detect_letterbox", "y3_letterbox_geometry", "y3_letterbox_u8",
+             "y3_detect_darknet_workspace_bytes", "y3_detect_darknet", "y3_nms_darknet_workspace_bytes", "y3_nms_darknet")
 
 
 class HipLibraryError(RuntimeError):
@@ -194,14 +209,30 @@ def capabilities():
 def require_capabilities(needs, what):
     """Refuse a plan that needs a computation the loaded library does not report: a stale library would run mish as
     linear, ignore scale_x_y, run a logistic head as linear, decode new_coords heads the YOLOv3 way, stretch frames
-    that were to be letterboxed or pool the reference's way where Darknet's rule was asked for."""
+    that were to be letterboxed, pool the reference's way where Darknet's rule was asked for or suppress by the
+    reference's rule where Darknet's was asked for."""
     missing = needs & ~capabilities()
     if missing:
         names = [n for n, b in (("mish", CAP_MISH), ("scale_x_y", CAP_SCALE_X_Y), ("logistic", CAP_LOGISTIC),
                                 ("new_coords", CAP_NEW_COORDS), ("letterbox", CAP_LETTERBOX),
-                                ("Darknet max-pooling", CAP_POOL_DARKNET)) if missing & b]
+                                ("Darknet max-pooling", CAP_POOL_DARKNET), ("Darknet NMS", CAP_NMS_DARKNET)) if missing & b]
         raise HipLibraryError("{}: the loaded libyolov3_hip.so cannot compute {} (rebuild: make -C pytorch-yolov3_amd/csrc)"
                               .format(what, ", ".join(names)))
+
+
+def nms_mode(nms_kind, beta_nms=0.6):
+    """(Y3_NMS_* code, beta as a float32-exact Python float) of a Darknet suppression mode, or None for ``nms_kind=None``
+    (the reference's rule).  ValueError for a kind this package does not compute (``cornersnms`` ...) or a ``beta_nms``
+    that is not finite and > 0.  Needs no GPU."""
+    if nms_kind is None:
+        return None
+    if not isinstance(nms_kind, str) or nms_kind not in NMS_KINDS:
+        raise ValueError("nms_kind {!r}: this package computes {} (None = the reference's rule on integer pixel boxes)".format(
+            nms_kind, ", ".join(sorted(NMS_KINDS))))
+    beta = ctypes.c_float(float(beta_nms)).value
+    if not (beta > 0.0 and beta != float("inf")):
+        raise ValueError("beta_nms must be finite and > 0 (as float32), got {!r}".format(beta_nms))
+    return NMS_KINDS[nms_kind], beta
 
 
 def options(**overrides):

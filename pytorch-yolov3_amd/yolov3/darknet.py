@@ -160,6 +160,20 @@ class Darknet(object):
         plans of one object never mix modes."""
         return self._pool
 
+    @property
+    def nms_hint(self):
+        """``(nms_kind, beta_nms)`` as the last [yolo] block of the cfg states them, or None when it has neither key
+        (``beta_nms`` alone gives kind "iou", Darknet's default; ``nms_kind`` alone gives beta 0.6).  A hint only: no cfg key
+        switches Darknet's suppression on -- pass it on, ``inference(net, f, nms_kind=net.nms_hint[0],
+        beta_nms=net.nms_hint[1])``.  A kind this package does not compute (``cornersnms``) is reported as written, and
+        using it raises the ValueError any unknown kind does."""
+        heads = [b for b in self.blocks if b["type"] == "yolo"]
+        if not heads or not ("nms_kind" in heads[-1] or "beta_nms" in heads[-1]):
+            return None
+        kind = heads[-1].get("nms_kind", "iou")
+        kind = "iou" if kind == "default" else kind     # Darknet's name for plain IoU in a cfg
+        return str(kind), float(heads[-1].get("beta_nms", 0.6))
+
     # ------------------------------------------------------------------ nn.Module-like surface
     def eval(self):
         self.training = False

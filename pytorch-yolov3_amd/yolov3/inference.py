@@ -13,7 +13,11 @@
   ``preprocess.resize_bilinear_u8``; the reference uses ``cv2.resize``, see that module's docstring);
 * ``letterbox=True`` (opt-in, not in the reference) letterboxes the frames the Darknet way instead of stretching them
   (``y3_letterbox_u8``, bit-identical to ``preprocess.letterbox_u8``) and corrects the boxes back to the frame
-  (``y3_detect_letterbox``, the same as ``preprocess.correct_letterbox_boxes`` followed by the reference's tail).
+  (``y3_detect_letterbox``, the same as ``preprocess.correct_letterbox_boxes`` followed by the reference's tail);
+* ``nms_kind="iou" | "greedynms" | "diounms"`` (opt-in, not in the reference) chooses the survivors by Darknet's rule on the
+  float32 centre / size boxes (``y3_detect_darknet``; include/yolov3_hip.h states the rule) instead of the reference's on
+  integer pixel corners; everything else about a detection stays.  ``non_max_suppression_darknet`` is that rule on
+  caller-provided boxes.
 
 There is no CPU fallback: without the HIP library / a GPU these functions raise.
 """
@@ -124,6 +128,57 @@ def non_max_suppression(bbox_tlbr, class_prob, class_idx=None, iou_thresh=0.3):
     return keep[:k].cpu().numpy().tolist()
 
 
+def non_max_suppression_darknet(bbox_xywh, class_prob, class_idx=None, thresh=0.45, nms_kind="iou", beta_nms=0.6):
+    """Greedy NMS by Darknet's rule on float32 centre / size boxes ``[x, y, w, h]``; per class when ``class_idx`` is given.
+    Returns the kept indices in canonical order (class ascending, score descending, higher index first).
+
+    ``nms_kind``: "iou" (what a cfg without ``nms_kind`` gets), "greedynms" (IoU minus the DIoU penalty d / c) or "diounms"
+    (IoU - (d / c) ** beta_nms); a suppresses b iff the measure is > ``thresh`` in float32 (include/yolov3_hip.h,
+    ``y3_detect_darknet``, states every operation).  The boxes must BE float32: float64 (and float16, and integers) are
+    refused, not rounded, because the rule is defined on the float32 values.
+    """
+    mode = _hip.nms_mode(nms_kind, beta_nms)
+    if mode is None:
+        raise ValueError("nms_kind=None is the reference's rule: non_max_suppression() computes it")
+    barr = np.asarray(bbox_xywh)
+    if barr.dtype != np.float32:
+        raise TypeError("non_max_suppression_darknet works on float32 boxes (Darknet's rule is float32 arithmetic), got dtype {}; "
+                        "convert explicitly if rounding them is what you mean".format(barr.dtype))
+    if barr.size == 0:
+        barr = barr.reshape(0, 4)
+    if barr.ndim != 2 or barr.shape[1] < 4:
+        raise ValueError("expected an (n, >=4) array of [x, y, w, h] boxes")
+    _require_finite(barr[:, :4], "bbox_xywh")
+    boxes = np.ascontiguousarray(barr[:, :4])
+    prob = np.ascontiguousarray(class_prob, dtype=np.float32)
+    n = boxes.shape[0]
+    if prob.ndim != 1 or prob.shape[0] != n:
+        raise ValueError("bbox_xywh and class_prob disagree on the number of boxes")
+    cls = None
+    if class_idx is not None:
+        cls = np.ascontiguousarray(class_idx, dtype=np.int64)
+        if cls.ndim != 1 or cls.shape[0] != n:
+            raise ValueError("class_idx has the wrong length")
+    thresh = float(np.float32(thresh))
+    if n == 0:
+        return []
+    dev = _device()
+    _hip.require_capabilities(_hip.CAP_NMS_DARKNET, "non_max_suppression_darknet")
+    lib = _hip.lib()
+    d_box = torch.from_numpy(boxes).to(dev)
+    d_prob = torch.from_numpy(prob).to(dev)
+    d_cls = torch.from_numpy(cls).to(dev) if cls is not None else None
+    ws_bytes = lib.y3_nms_darknet_workspace_bytes(n)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    keep = torch.empty(n, dtype=torch.int64, device=dev)
+    count = torch.zeros(1, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _hip.check(lib.y3_nms_darknet(d_box.data_ptr(), d_prob.data_ptr(), d_cls.data_ptr() if d_cls is not None else None, n,
+                                      thresh, mode[0], mode[1], ws.data_ptr(), ws_bytes, keep.data_ptr(), count.data_ptr(),
+                                      _hip.stream_ptr()))
+        return keep[:int(count.cpu()[0])].cpu().numpy().tolist()
+
+
 def _nms_float(barr, class_prob, class_idx, iou_thresh):
     code, work = _float_kind(barr.dtype)
     _require_finite(barr[:, :4], "bbox_tlbr")
@@ -166,10 +221,14 @@ class Detector(object):
         self.row = torch.empty((batch, rows), dtype=torch.int32, device=device)
         self.orig_hw = torch.empty((batch, 2), dtype=torch.int32, device=device)
         self._records = {}      # kmax -> (batch, kmax, 8) int32 staging buffer of fetch()
+        self._ws_darknet = None  # (bytes, tensor): the larger workspace of y3_detect_darknet, made when first asked for
 
-    def run(self, out, orig_hw, prob_thresh, iou_thresh, letterbox=None):
+    def run(self, out, orig_hw, prob_thresh, iou_thresh, letterbox=None, nms_kind=None, beta_nms=0.6):
         """out: Darknet.forward dict (device tensors).  orig_hw: (batch,2) int32 tensor/array.  letterbox: the
-        (net_h, net_w) the frames were letterboxed into -- the boxes are then corrected back (``y3_detect_letterbox``)."""
+        (net_h, net_w) the frames were letterboxed into -- the boxes are then corrected back (``y3_detect_letterbox``).
+        nms_kind: None = the reference's suppression rule; "iou" / "greedynms" / "diounms" = Darknet's, on the float32
+        boxes (``y3_detect_darknet``; with ``letterbox``, on the corrected ones), ``beta_nms`` for "diounms"."""
+        mode = _hip.nms_mode(nms_kind, beta_nms)
         if not isinstance(orig_hw, torch.Tensor):
             orig_hw = torch.from_numpy(np.ascontiguousarray(orig_hw, dtype=np.int32))
         if (orig_hw.device == self.orig_hw.device and orig_hw.dtype == torch.int32 and orig_hw.is_contiguous()
@@ -183,7 +242,18 @@ class Detector(object):
                 ctypes.c_float(prob_thresh), ctypes.c_double(iou_thresh), self.ws.data_ptr(), self.ws_bytes,
                 self.count.data_ptr(), self.tlbr.data_ptr(), self.prob.data_ptr(), self.cls.data_ptr(),
                 self.row.data_ptr())
-        if letterbox is None:
+        if mode is not None:
+            _hip.require_capabilities(_hip.CAP_NMS_DARKNET, "Detector.run(nms_kind=...)")
+            if letterbox is not None:
+                _hip.require_capabilities(_hip.CAP_LETTERBOX, "Detector.run(letterbox=...)")
+            net_h, net_w = (int(v) for v in letterbox) if letterbox is not None else (0, 0)
+            if self._ws_darknet is None:
+                nbytes = _hip.lib().y3_detect_darknet_workspace_bytes(self.batch, self.rows)
+                self._ws_darknet = (nbytes, torch.empty(nbytes, dtype=torch.uint8, device=self.device))
+            nbytes, ws = self._ws_darknet
+            args = args[:8] + (ws.data_ptr(), nbytes) + args[10:]
+            _hip.check(_hip.lib().y3_detect_darknet(*args, net_h, net_w, mode[0], ctypes.c_float(mode[1]), _hip.stream_ptr()))
+        elif letterbox is None:
             _hip.check(_hip.lib().y3_detect(*args, _hip.stream_ptr()))
         else:
             _hip.require_capabilities(_hip.CAP_LETTERBOX, "Detector.run(letterbox=...)")
@@ -229,7 +299,7 @@ def get_detector(batch, rows, device):
 
 
 def inference(net, images, device="cuda", prob_thresh=0.05, nms_iou_thresh=0.3, resize=True,
-              return_rows=False, letterbox=False, letterbox_fill=128):
+              return_rows=False, letterbox=False, letterbox_fill=128, nms_kind=None, beta_nms=0.6):
     """Run detection on one frame or a list of HxWx3 uint8 BGR frames.
 
     Returns, per frame, ``[bbox_tlbr int64 (K,4), class_prob float32 (K,), class_idx int64 (K,)]``
@@ -239,7 +309,12 @@ def inference(net, images, device="cuda", prob_thresh=0.05, nms_iou_thresh=0.3, 
     ``letterbox=True``: Darknet letterboxing instead of the stretched resize (aspect ratio kept, the rest of the network
     input filled with the byte ``letterbox_fill``), boxes corrected back to the frame; frames of different sizes may
     then share the call.  It needs ``resize`` (a ValueError otherwise).
+
+    ``nms_kind``: None [default] = the reference's suppression (integer pixel corners, +1 areas, IoU > ``nms_iou_thresh``);
+    "iou", "greedynms" or "diounms" = Darknet's on the float32 boxes, with ``nms_iou_thresh`` as its threshold and
+    ``beta_nms`` as the exponent of "diounms" (``net.nms_hint`` holds what the cfg asks for).  ValueError for any other kind.
     """
+    _hip.nms_mode(nms_kind, beta_nms)
     if letterbox and not resize:
         raise ValueError("letterbox=True resizes every frame: it cannot be combined with resize=False")
     if not isinstance(images, (list, tuple)):
@@ -259,5 +334,5 @@ def inference(net, images, device="cuda", prob_thresh=0.05, nms_iou_thresh=0.3, 
     orig_hw = np.array([[s[0], s[1]] for s in shapes], dtype=np.int32)
     with torch.cuda.device(dev):
         det.run(out, orig_hw, float(np.float32(prob_thresh)), float(nms_iou_thresh),
-                letterbox=(net_h, net_w) if letterbox else None)
+                letterbox=(net_h, net_w) if letterbox else None, nms_kind=nms_kind, beta_nms=beta_nms)
         return det.fetch(return_rows=return_rows)

@@ -55,11 +55,12 @@ class Pipeline(object):
     running one while the host is still reading an older batch's records (waiting for the oldest of only ``in_flight`` open
     tickets before every submit costs 8-15 % of the rate: profiles/r04m_pipeline_depth.txt).  Submitting ticket
     i + max_open reuses ticket i's buffers: its results must have been taken, or are dropped (the benchmark does that on
-    purpose).
+    purpose).  ``nms_kind`` / ``beta_nms``: Darknet's suppression rule instead of the reference's (``inference()`` explains).
     """
 
     def __init__(self, net, batch, height=None, width=None, in_flight=3, prob_thresh=0.05, nms_iou_thresh=0.3, kmax=512,
-                 world=1, group=None, options=None, copy_blocks=8):
+                 world=1, group=None, options=None, copy_blocks=8, nms_kind=None, beta_nms=0.6):
+        _hip.nms_mode(nms_kind, beta_nms)               # ValueError for a kind this package does not compute
         _hip.require_gpu()
         if batch < 1 or in_flight < 1:
             raise ValueError("batch and in_flight must be positive")
@@ -69,6 +70,8 @@ class Pipeline(object):
         self.height = int(height or net.net_info["height"])
         self.width = int(width or net.net_info["width"])
         self.prob_thresh, self.nms_iou_thresh = float(np.float32(prob_thresh)), float(nms_iou_thresh)
+        # suppression rule of every batch submitted from now on: None = the reference's, else Darknet's (Detector.run)
+        self.nms_kind, self.beta_nms = nms_kind, beta_nms
         self.dev = dev = net._torch_device()
         self.group = group
         nq, sure = _hip.hw_queues()
@@ -210,7 +213,7 @@ class Pipeline(object):
                 self.free_ev[j].record(cur)
             det = self.dets[d]
             det.run(out, self.full_hw if orig_hw is None else orig_hw, self.prob_thresh, self.nms_iou_thresh,
-                    letterbox=(self.height, self.width) if letterbox else None)
+                    letterbox=(self.height, self.width) if letterbox else None, nms_kind=self.nms_kind, beta_nms=self.beta_nms)
             if n_frames is not None and int(n_frames) < self.batch:
                 # padding frames of a short last batch (copies of real frames, or whatever the staging buffer held) must not
                 # count: their detections are dropped here, BEFORE the records are packed and gathered, so that they can neither

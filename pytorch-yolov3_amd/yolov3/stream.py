@@ -65,7 +65,7 @@ def _batches(frames, batch_size):
 
 
 def detect_in_frames(net, frames, batch_size=16, prob_thresh=0.05, nms_iou_thresh=0.3, resize=True,
-                     in_flight=3, kmax=512, letterbox=False, letterbox_fill=128):
+                     in_flight=3, kmax=512, letterbox=False, letterbox_fill=128, nms_kind=None, beta_nms=0.6):
     """Generator over ``[bbox_tlbr, class_prob, class_idx]`` for every frame of the iterable
     ``frames`` (HxWx3 uint8 BGR arrays; sizes may differ when ``resize``), in order.
 
@@ -81,8 +81,12 @@ def detect_in_frames(net, frames, batch_size=16, prob_thresh=0.05, nms_iou_thres
     byte ``letterbox_fill``) instead of stretching them, and corrects their boxes back; net-sized frames take the pinned
     path above unchanged, since letterboxing is the identity on them.  Results equal per-frame
     ``inference(letterbox=True)``.
+
+    ``nms_kind`` / ``beta_nms``: Darknet's suppression rule ("iou", "greedynms", "diounms") instead of the reference's, as in
+    ``inference()``; None changes nothing.
     """
     from .pipeline import Pipeline
+    _hip.nms_mode(nms_kind, beta_nms)
     _hip.require_gpu()
     if batch_size < 1 or in_flight < 1:
         raise ValueError("batch_size and in_flight must be positive")
@@ -109,6 +113,7 @@ def detect_in_frames(net, frames, batch_size=16, prob_thresh=0.05, nms_iou_thres
                     cache[key] = pipe
             pipe.busy = True
             pipe.prob_thresh, pipe.nms_iou_thresh = float(np.float32(prob_thresh)), float(nms_iou_thresh)
+            pipe.nms_kind, pipe.beta_nms = nms_kind, beta_nms
             state["pipe"] = pipe
         return state["pipe"]
 
@@ -178,12 +183,14 @@ def detect_in_frames(net, frames, batch_size=16, prob_thresh=0.05, nms_iou_thres
             state["pipe"].busy = False
 
 
-def detect_in_images(net, path, batch_size=16, prob_thresh=0.05, nms_iou_thresh=0.3, letterbox=False, letterbox_fill=128):
+def detect_in_images(net, path, batch_size=16, prob_thresh=0.05, nms_iou_thresh=0.3, letterbox=False, letterbox_fill=128,
+                     nms_kind=None, beta_nms=0.6):
     """The CLI's ``--image`` mode: ``path`` is a file or a directory.  Returns (file names, results)."""
     directory, names = list_image_files(path)
     frames = (load_image_bgr(os.path.join(directory, n)) for n in names)
     results = list(detect_in_frames(net, frames, batch_size=batch_size, prob_thresh=prob_thresh,
-                                    nms_iou_thresh=nms_iou_thresh, letterbox=letterbox, letterbox_fill=letterbox_fill))
+                                    nms_iou_thresh=nms_iou_thresh, letterbox=letterbox, letterbox_fill=letterbox_fill,
+                                    nms_kind=nms_kind, beta_nms=beta_nms))
     return names, results
 
 
@@ -230,7 +237,8 @@ def _video_frames(filepath):
 
 
 def detect_in_video(net, filepath, device="cuda", prob_thresh=0.05, nms_iou_thresh=0.3, class_names=None,
-                    frames=None, show_video=False, batch_size=16, letterbox=False, letterbox_fill=128):
+                    frames=None, show_video=False, batch_size=16, letterbox=False, letterbox_fill=128, nms_kind=None,
+                    beta_nms=0.6):
     """Run detection over a video (or a directory of frames), draw the boxes on every frame and
     append the frames to ``frames`` when a list is given -- the reference's contract, batched.
     Returns the list of per-frame results."""
@@ -248,7 +256,8 @@ def detect_in_video(net, filepath, device="cuda", prob_thresh=0.05, nms_iou_thre
     results = []
     for i, (bbox_tlbr, class_prob, class_idx) in enumerate(
             detect_in_frames(net, tap(), batch_size=batch_size, prob_thresh=prob_thresh,
-                             nms_iou_thresh=nms_iou_thresh, letterbox=letterbox, letterbox_fill=letterbox_fill)):
+                             nms_iou_thresh=nms_iou_thresh, letterbox=letterbox, letterbox_fill=letterbox_fill,
+                             nms_kind=nms_kind, beta_nms=beta_nms)):
         frame = kept[i]
         kept[i] = None
         draw_boxes(frame, bbox_tlbr, class_idx=class_idx, class_names=class_names)
@@ -264,9 +273,10 @@ def detect_in_video(net, filepath, device="cuda", prob_thresh=0.05, nms_iou_thre
 
 
 def detect_in_cam(net, cam_id=0, device="cuda", prob_thresh=0.05, nms_iou_thresh=0.3, class_names=None,
-                  show_fps=False, frames=None, letterbox=False, letterbox_fill=128):
+                  show_fps=False, frames=None, letterbox=False, letterbox_fill=128, nms_kind=None, beta_nms=0.6):
     """Live camera loop (latency-bound, one frame per step like the reference).  Needs OpenCV for
     capture and display."""
+    _hip.nms_mode(nms_kind, beta_nms)
     cv2 = _cv2()
     if cv2 is None:
         raise RuntimeError("camera capture needs OpenCV (cv2), which is not installed")
@@ -281,7 +291,7 @@ def detect_in_cam(net, cam_id=0, device="cuda", prob_thresh=0.05, nms_iou_thresh
                 break
             bbox_tlbr, _, class_idx = inference(net, frame, device=device, prob_thresh=prob_thresh,
                                                 nms_iou_thresh=nms_iou_thresh, letterbox=letterbox,
-                                                letterbox_fill=letterbox_fill)[0]
+                                                letterbox_fill=letterbox_fill, nms_kind=nms_kind, beta_nms=beta_nms)[0]
             draw_boxes(frame, bbox_tlbr, class_idx=class_idx, class_names=class_names)
             if show_fps:
                 cv2.putText(frame, "%d fps" % int(1.0 / max(time.time() - t0, 1e-6)), (2, 20),
