@@ -1,0 +1,689 @@
+"""Memory footprint of every kernel family: layout, fills, checks and the case table (tests/test_footprint_host.py checks
+the table, the arithmetic and the helpers without a GPU; tests/test_gpu_footprint.py runs the cases on an MI355X).
+
+Every operand of a one-op or one-fused-group plan lies inside ONE device allocation as ``[guard | body | guard]``:
+
+  body    pixels x ld elements; the operand's channels are the slice [c0, c0 + c) of every pixel, with c0 > 0 and
+          c0 + c < ld in the strided layout (a margin on both sides, as in a route-concat buffer of the arena), c0 = 0 and
+          ld = c in the dense layout.  c0 and ld are ODD multiples of the alignment unit the family's chooser demands, so
+          they are multiples of nothing larger.  Parameters, the zero page, frames and decode outputs are flat bodies.
+  guard   on each side at least max(64 KiB, 256 pixels x ld x element size) -- the widest tile of any kernel is 256 pixels --
+          and bodies start on 4 KiB boundaries.  Guards are part of the allocation: a stray access is recorded, it never
+          faults.  No operand is ever placed at the end of an allocation.
+
+Input-side operands are surrounded by quiet NaN of their storage type (margins and guards), so a result that depends on a
+byte the op does not own is NaN or differs from the dense run.  Output-side operands are surrounded by a fixed byte pattern
+and their slice is pre-filled with NaN, so a stray store and a missing store both show.  The whole allocation is compared as
+bytes before and after the run."""
+import ctypes
+
+import torch
+
+GUARD_MIN = 64 * 1024
+TILE_PIXELS = 256
+ALIGN = 4096
+ES = {"float32": 4, "bf16": 2, "fp16": 2}
+TAG = {"float32": "f32", "bf16": "bf16", "fp16": "f16"}
+TORCH_DT = {"float32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}
+# quiet NaN of each storage type, as the little-endian bytes of one element
+NAN_BYTES = {"float32": (0x00, 0x00, 0xC0, 0x7F), "bf16": (0xC0, 0x7F), "fp16": (0x00, 0x7E)}
+PATTERN_PERIOD = 251            # output-side fill: byte i of the allocation holds 1 + i % 251 (never 0, no power-of-two period)
+
+
+def round_up(a, b):
+    return (a + b - 1) // b * b
+
+
+class Operand:
+    """One ``[guard | body | guard]`` of the allocation.  ``side``: "in" (read only), "out" (the slices are written),
+    "inout" (written slices that hold data before the run: the in-place add) or "scratch" (private intermediate of a fused
+    group: its body may or may not be written).  ``fmt``: "float32" / "bf16" / "fp16" / "u8" / "i32" / "i64" / "f64"."""
+
+    def __init__(self, name, side, fmt, pixels, ld, slices, tile_elems=None):
+        """``tile_elems``: elements one pixel of a tile spans, where that is not ``ld`` (flat parameter arrays: 1; the decode's
+        output rows: 4 / 1 / 1)"""
+        self.name, self.side, self.fmt = name, side, fmt
+        self.es = {"u8": 1, "i32": 4, "i64": 8, "f64": 8}.get(fmt) or ES[fmt]
+        self.pixels, self.ld, self.slices = int(pixels), int(ld), [(int(a), int(b)) for a, b in slices]
+        self.tile_elems = int(tile_elems or ld)
+        self.guard = round_up(max(GUARD_MIN, TILE_PIXELS * self.tile_elems * self.es), ALIGN)
+        self.body_bytes = self.pixels * self.ld * self.es
+        self.front = self.body = self.end = None         # byte offsets in the allocation (Layout sets them)
+
+    def ptr(self, base, k=0):
+        return base + self.body + self.slices[k][0] * self.es
+
+    def region(self, off):
+        """(region name, pixel, channel) of byte ``off`` of the allocation, which lies in this operand"""
+        if off < self.body:
+            return "front guard", -1, -1
+        if off >= self.body + self.body_bytes:
+            return "back guard", -1, -1
+        e = (off - self.body) // self.es
+        pix, ch = e // self.ld, e % self.ld
+        for k, (c0, c) in enumerate(self.slices):
+            if c0 <= ch < c0 + c:
+                return "slice %d" % k, pix, ch - c0
+        if ch < self.slices[0][0]:
+            return "left margin", pix, ch
+        if ch >= self.slices[-1][0] + self.slices[-1][1]:
+            return "right margin", pix, ch
+        return "margin between slices", pix, ch
+
+
+class Layout:
+    def __init__(self, operands):
+        self.operands = list(operands)
+        off = 0
+        for o in self.operands:
+            o.front = off
+            o.body = off + o.guard
+            o.end = round_up(o.body + o.body_bytes + o.guard, ALIGN)
+            off = o.end
+        self.total = off
+
+    def __getitem__(self, name):
+        return next(o for o in self.operands if o.name == name)
+
+    def has(self, name):
+        return any(o.name == name for o in self.operands)
+
+    def owner(self, off):
+        return next(o for o in self.operands if o.front <= off < o.end)
+
+
+def strided_ld(c, unit, v, avoid=()):
+    """(c0, ld) of a ``c``-channel slice for alignment unit ``unit``; variant ``v`` (0, 1, 2 ...) gives different strides
+    to the operands of one op.  c0 and ld are odd multiples of ``unit``; c0 >= unit and ld - c0 - c >= unit."""
+    c0 = unit * (1 + 2 * v)
+    ld = round_up(c, unit) + c0 + unit * (1 + 2 * v)
+    if (ld // unit) % 2 == 0:
+        ld += unit
+    while ld in avoid:                      # (another operand of the op has this stride already)
+        ld += 2 * unit
+    return c0, ld
+
+
+# ------------------------------------------------------------------------------------------------ fills and checks (torch)
+
+def _bytes_tensor(vals, n, device):
+    t = torch.tensor(vals, dtype=torch.uint8, device=device)
+    return t.repeat(n // len(vals))
+
+
+def fill(alloc, layout, data, poisoned, u8_guard=0):
+    """Lay ``data`` ({operand name: [tensor per slice]}; "out" operands have none) into ``alloc`` (uint8, layout.total bytes).
+    ``poisoned``: NaN / pattern around the operands (the strided and aliasing runs); else zeros (the dense run)."""
+    dev = alloc.device
+    if poisoned:
+        pat = (torch.arange(PATTERN_PERIOD, device=dev) + 1).to(torch.uint8)
+        alloc.copy_(pat.repeat(layout.total // PATTERN_PERIOD + 1)[:layout.total])
+    else:
+        alloc.zero_()
+    for o in layout.operands:
+        whole = alloc[o.front:o.end]
+        body = alloc[o.body:o.body + o.body_bytes]
+        if o.side in ("in", "inout") and poisoned:
+            if o.fmt in NAN_BYTES:
+                whole.copy_(_bytes_tensor(NAN_BYTES[o.fmt], o.end - o.front, dev))
+            elif o.fmt == "u8":
+                whole.fill_(u8_guard)
+            else:                                    # integer inputs have no NaN: all-ones (-1; float64: a NaN)
+                whole.fill_(0xFF)
+        b2 = body.view(o.pixels, o.ld * o.es)
+        for k, (c0, c) in enumerate(o.slices):
+            sl = b2[:, c0 * o.es:(c0 + c) * o.es]
+            if o.side in ("in", "inout"):
+                src = data[o.name][k].contiguous().to(dev)
+                sl.copy_(src.view(torch.uint8).reshape(o.pixels, c * o.es))
+            elif o.side == "out":
+                if o.fmt in NAN_BYTES:
+                    sl.copy_(_bytes_tensor(NAN_BYTES[o.fmt], o.pixels * c * o.es, dev).view(o.pixels, c * o.es))
+                else:
+                    sl.fill_(0x7F)                   # integer outputs: a value no kernel here writes (0x7F7F... )
+            else:
+                sl.fill_(0xFF if poisoned else 0)    # scratch / workspace: no kernel may rely on what it finds there
+
+
+def read_slice(alloc, o, k, dtype):
+    """slice ``k`` of operand ``o`` as a (pixels, c) tensor of ``dtype`` (a copy)"""
+    c0, c = o.slices[k]
+    b2 = alloc[o.body:o.body + o.body_bytes].view(o.pixels, o.ld * o.es)
+    return b2[:, c0 * o.es:(c0 + c) * o.es].contiguous().view(dtype).reshape(o.pixels, -1)
+
+
+def footprint_violations(before, after, layout, writable=("out", "inout", "scratch")):
+    """None, or a message naming the first byte that changed outside the slices the run may write: which operand, which
+    region (left / right margin, front / back guard, or the slice of a read-only operand), pixel, channel, bytes changed."""
+    diff = before != after
+    for o in layout.operands:
+        if o.side not in writable:
+            continue
+        b2 = diff[o.body:o.body + o.body_bytes].view(o.pixels, o.ld * o.es)
+        if o.side == "scratch":
+            b2.zero_()
+            continue
+        for c0, c in o.slices:
+            b2[:, c0 * o.es:(c0 + c) * o.es] = False
+    if not bool(diff.any()):
+        return None
+    offs = torch.nonzero(diff).flatten().cpu().numpy()
+    return describe(offs, layout)
+
+
+def describe(offs, layout):
+    """message for the changed byte offsets ``offs`` (sorted, non-empty)"""
+    first = int(offs[0])
+    o = layout.owner(first)
+    region, pix, ch = o.region(first)
+    in_op = offs[(offs >= o.front) & (offs < o.end)]
+    same = sum(1 for x in in_op[:100000] if o.region(int(x))[0] == region)
+    where = "" if pix < 0 else ", first at pixel %d channel %d" % (pix, ch)
+    return "operand '%s' (%s): %s changed%s (allocation byte %d, %d bytes of it inside the operand); %d bytes changed in that region, %d in all" % (
+        o.name, o.side, region, where, first, first - o.front, same, len(offs))
+
+
+# ------------------------------------------------------------------------------------------------ the case table
+
+def _H():
+    from yolov3 import _hip
+    return _hip
+
+
+def _opts():
+    """option sets that force each family (the masks of tests/kernel_choice_util.py OPTION_SETS and tests/test_gpu_parity.py)"""
+    H = _H()
+    halo = H.AM_HALO_ALL | H.AM_NO_SMALL_GRID
+    return dict(
+        igemm1=dict(auto_mask=0, igemm_version=1),
+        igemm2=dict(auto_mask=0),
+        igemm2_noshrink=dict(auto_mask=H.AM_NO_BN_SHRINK),
+        igemm2_96=dict(auto_mask=0, igemm_bm=96),
+        igemm3=dict(auto_mask=0, igemm_version=3),
+        igemm3_64=dict(auto_mask=0, igemm_version=3, igemm_bm=64),
+        halo192=dict(auto_mask=halo),
+        halo256=dict(auto_mask=halo | H.AM_HALO_TILE256),
+        halo_dw=dict(auto_mask=halo | H.AM_HALO_DW_ALWAYS),
+        patch=dict(auto_mask=halo | H.AM_PATCH_WIDE),
+        wres=dict(auto_mask=H.AM_WRES_ALWAYS),
+        dw1x1=dict(auto_mask=H.AM_1X1_DW),
+        dw48=dict(auto_mask=H.AM_SMALL_DW | H.AM_SMALL_DW_ALWAYS),
+        default={},
+        fuse_block=dict(fuse_block=2),
+        head_tiled=dict(fuse_head=2),
+        head48=dict(fuse_head=3),
+        head96=dict(fuse_head=4),
+        head_unfused=dict(fuse_head=0),
+    )
+
+
+F32, B16, ALL = ("float32",), ("bf16", "fp16"), ("float32", "bf16", "fp16")
+
+
+def _conv(cid, family, opt, dtypes, B, h, w, cin, cout, k, s, res=False, inp="act", out_unit=None, **kw):
+    return dict(id=cid, group="conv", family=family, opt=opt, dtypes=dtypes, B=B, h=h, w=w, cin=cin, cout=cout, k=k, s=s,
+                res=res, inp=inp, out_unit=out_unit, **kw)
+
+
+def _layer(cid, family, kind, dtypes, B, h, w, c, k=1, s=1, wide=True, dk=False, alias=False, opt="default"):
+    return dict(id=cid, group="layer", family=family, kind=kind, opt=opt, dtypes=dtypes, B=B, h=h, w=w, c=c, k=k, s=s,
+                wide=wide, dk=dk, alias=alias)
+
+
+def cases():
+    """Every case: at least a full-tile and a ragged shape per family (the last pixel tile partial, the map not square where
+    the family allows it), with and without the shortcut operand where the family takes one.  ``family`` is the kernel name
+    with %s for the dtype tag.  Shapes stay at or below 16 x 76 x 76 x 512."""
+    C = []
+    # ---- implicit GEMMs (conv_igemm.hip).  Tile widths follow Cout (128 / 64 / 32); version 2 shrinks them on small grids
+    # unless AM_NO_BN_SHRINK; pixel tiles are 128 (96, 64): "full" shapes have B*Ho*Wo a multiple of the tile
+    for ver, opt, fam in (("igemm1", "igemm1", "conv_igemm_%s"), ("igemm2", "igemm2_noshrink", "conv_igemm2_%s")):
+        C += [
+            _conv(ver + "_128_full", fam + "_128x128", opt, ALL, 2, 16, 16, 64, 128, 3, 1, res=True),
+            _conv(ver + "_128_ragged", fam + "_128x128", opt, ALL, 3, 13, 11, 128, 256, 1, 1),
+            _conv(ver + "_128_ragged_s2_res", fam + "_128x128", opt, ALL, 1, 27, 21, 128, 128, 3, 2, res=True),
+            _conv(ver + "_64_full", fam + "_128x64", opt, ALL, 1, 16, 16, 128, 64, 1, 1),
+            _conv(ver + "_64_ragged_res", fam + "_128x64", opt, ALL, 2, 15, 9, 32, 64, 3, 1, res=True),
+            _conv(ver + "_32_full", fam + "_128x32", opt, ALL, 1, 16, 8, 64, 32, 1, 1, res=True),
+            _conv(ver + "_32_ragged", fam + "_128x32", opt, ALL, 1, 19, 13, 16, 32, 3, 1),
+        ]
+    C += [
+        # ragged channel tail: 255 float32 head channels (the head conv: bias only, float32 out).  Under the DEFAULT igemm_version
+        # 2 a 16-bit conv with Y3_F_OUT_F32 runs on the version-1 kernel, whose direct epilogue measured faster
+        # (conv_igemm.hip, y3_choose_conv_igemm): this is the form the shipped plans run, hence option set "igemm2"
+        _conv("igemm_head_f32out", "conv_igemm_%s_128x128", "igemm2", B16, 2, 13, 13, 256, 255, 1, 1, out_f32=True, leaky=False, dense_out_ld=256),
+        _conv("igemm2_96_full", "conv_igemm2_%s_96x64", "igemm2_96", ALL, 2, 12, 12, 128, 128, 1, 1, res=True),
+        _conv("igemm2_96_ragged", "conv_igemm2_%s_96x64", "igemm2_96", ALL, 3, 13, 7, 128, 192, 3, 1),
+        _conv("igemm3_128_full", "conv_igemm3_%s_128x128", "igemm3", ALL, 2, 16, 16, 128, 128, 3, 1, res=True),
+        _conv("igemm3_128_ragged", "conv_igemm3_%s_128x128", "igemm3", ALL, 3, 19, 13, 256, 256, 1, 1),
+        _conv("igemm3_128_ragged_s2", "conv_igemm3_%s_128x128", "igemm3", ALL, 2, 27, 21, 64, 128, 3, 2),
+        _conv("igemm3_64_full", "conv_igemm3_%s_64x128", "igemm3_64", B16, 1, 16, 16, 256, 128, 1, 1, res=True),
+        _conv("igemm3_64_ragged", "conv_igemm3_%s_64x128", "igemm3_64", B16, 3, 13, 9, 128, 256, 3, 1),
+        # ---- halo-reuse strip kernels (conv_halo.hip): 192- / 256-pixel strips of whole rows x 128 channels; float32 too
+        _conv("halo192_full", "conv_halo_ws_%s_192x128", "halo192", ALL, 2, 24, 16, 128, 128, 3, 1, res=True, out_unit=8),
+        _conv("halo192_ragged", "conv_halo_ws_%s_192x128", "halo192", ALL, 3, 19, 13, 128, 256, 3, 1, out_unit=8),
+        _conv("halo192_ragged_res", "conv_halo_ws_%s_192x128", "halo192", ALL, 2, 38, 26, 256, 128, 3, 1, res=True, out_unit=8),
+        _conv("halo256_full", "conv_halo_ws_%s_256x128", "halo256", ALL, 2, 16, 16, 128, 128, 3, 1, res=True, out_unit=8),
+        _conv("halo256_ragged", "conv_halo_ws_%s_256x128", "halo256", ALL, 3, 19, 13, 128, 256, 3, 1, out_unit=8),
+        _conv("halo256_ragged_76", "conv_halo_ws_%s_256x128", "halo256", ALL, 1, 76, 52, 128, 128, 3, 1, res=True, out_unit=8),
+        # direct-weights strip kernel: 192 pixels x 256 channels, fragment-order weights
+        _conv("halo_dw_full", "conv_halo_dw_%s_192x256", "halo_dw", B16, 2, 24, 16, 128, 256, 3, 1, res=True),
+        _conv("halo_dw_ragged", "conv_halo_dw_%s_192x256", "halo_dw", B16, 3, 19, 13, 256, 512, 3, 1),
+        _conv("halo_dw_ragged_res", "conv_halo_dw_%s_192x256", "halo_dw", B16, 2, 38, 26, 128, 256, 3, 1, res=True),
+        # 2-D patch kernel: 8 x 32 output tiles; its chooser asks rows wider than 128 px (api.hip: `w > 128`), so these maps are
+        # wide and low: h * w stays below 76 * 76
+        _conv("patch_full", "conv_patch_wsp_%s_8x32x128", "patch", ALL, 1, 16, 160, 64, 128, 3, 1, res=True, out_unit=8),
+        _conv("patch_ragged", "conv_patch_wsp_%s_8x32x128", "patch", ALL, 2, 13, 139, 64, 128, 3, 1, out_unit=8),
+        _conv("patch_ragged_res", "conv_patch_wsp_%s_8x32x128", "patch", ALL, 1, 21, 150, 64, 256, 3, 1, res=True, out_unit=8),
+        # ---- 1x1 kernels (conv_1x1.hip): weights-resident persistent (128-pixel tiles), direct-weights (48 / 96 pixels)
+        _conv("wres_128_full", "conv1x1_wres_%s_128x128", "wres", B16, 2, 16, 16, 256, 128, 1, 1),
+        _conv("wres_128_ragged", "conv1x1_wres_%s_128x128", "wres", B16, 3, 19, 13, 256, 128, 1, 1),
+        _conv("wres_64_full", "conv1x1_wres_%s_128x64", "wres", B16, 2, 16, 16, 128, 64, 1, 1),
+        _conv("wres_64_ragged", "conv1x1_wres_%s_128x64", "wres", B16, 3, 21, 17, 128, 64, 1, 1),
+        # (the direct-weights kernel takes grids of one round only: 96-pixel tiles from 192 tiles on, 48-pixel tiles for 64 ..
+        # 191 -- conv_1x1.hip dw1x1_bm -- hence the batches)
+        _conv("dw1x1_96_full", "conv1x1_dw_%s_96x256", "dw1x1", B16, 16, 36, 32, 512, 256, 1, 1),
+        _conv("dw1x1_96_ragged", "conv1x1_dw_%s_96x256", "dw1x1", B16, 16, 38, 37, 512, 256, 1, 1),
+        _conv("dw1x1_48_full", "conv1x1_dw_%s_48x256", "dw1x1", B16, 8, 24, 16, 512, 256, 1, 1),
+        _conv("dw1x1_48_ragged", "conv1x1_dw_%s_48x256", "dw1x1", B16, 9, 19, 19, 512, 256, 1, 1),
+        # ---- small-grid direct-weights kernel (conv_dw48.hip): 48-pixel tiles, one frame at a time
+        _conv("dw48_k1_full", "conv_dw48_k1_%s", "dw48", B16, 1, 24, 16, 256, 128, 1, 1, res=True),
+        _conv("dw48_k1_ragged", "conv_dw48_k1_%s", "dw48", B16, 2, 19, 13, 512, 256, 1, 1),
+        _conv("dw48_k3_full", "conv_dw48_k3_%s", "dw48", B16, 1, 24, 16, 128, 256, 3, 1, res=True),
+        _conv("dw48_k3_ragged", "conv_dw48_k3_%s", "dw48", B16, 2, 19, 13, 256, 512, 3, 1),
+        _conv("dw48_k3_ragged_res", "conv_dw48_k3_%s", "dw48", B16, 1, 38, 23, 128, 256, 3, 1, res=True),
+        _conv("dw48_k3s2_full", "conv_dw48_k3s2_%s", "dw48", B16, 1, 48, 32, 128, 256, 3, 2),
+        _conv("dw48_k3s2_ragged", "conv_dw48_k3s2_%s", "dw48", B16, 2, 38, 26, 256, 512, 3, 2),
+        _conv("dw48_k3s2_ragged_1frame", "conv_dw48_k3s2_%s", "dw48", B16, 1, 38, 22, 256, 512, 3, 2),
+        # ---- stems (conv_small.hip): the network input is a whole dense tensor by definition (no pixel stride), so only the
+        # output is a slice; the input is an exact-size body between guards (uint8 frames: guards 0x00 and 0xFF)
+        _conv("stem_nchw_full", "conv_stem3x3_nchw_%s", "default", ALL, 2, 32, 32, 3, 32, 3, 1, inp="nchw"),
+        _conv("stem_nchw_ragged", "conv_stem3x3_nchw_%s", "default", ALL, 3, 29, 21, 3, 16, 3, 1, inp="nchw"),
+        _conv("stem_u8_f32_full", "conv_stem3x3_u8_%s", "default", F32, 2, 32, 32, 3, 32, 3, 1, inp="u8"),
+        _conv("stem_u8_f32_ragged", "conv_stem3x3_u8_%s", "default", F32, 3, 29, 21, 3, 16, 3, 1, inp="u8"),
+        _conv("stem_mfma_full", "conv_stem_mfma_u8_%s", "default", B16, 2, 32, 32, 3, 32, 3, 1, inp="u8"),
+        _conv("stem_mfma_ragged", "conv_stem_mfma_u8_%s", "default", B16, 3, 29, 21, 3, 32, 3, 1, inp="u8"),
+        _conv("stem_mfma_ragged_16ch", "conv_stem_mfma_u8_%s", "default", B16, 1, 45, 37, 3, 16, 3, 1, inp="u8"),
+    ]
+    # ---- fused groups, laid out as the plan lays them: private intermediate, input and output are slices
+    C += [
+        dict(id="stem_s2_full", group="stem_pair", family="conv_stem_s2_fused_u8_%s", opt="default", dtypes=B16, B=2, h=64, w=64),
+        dict(id="stem_s2_ragged", group="stem_pair", family="conv_stem_s2_fused_u8_%s", opt="default", dtypes=B16, B=3, h=45, w=37),
+        # the shortcut operand of the fused residual block IS the group's input (always: the chooser requires it)
+        dict(id="resblock_full", group="resblock", family="conv_resblock_fused_%s_64_32_64", opt="default", dtypes=B16, B=2, h=32, w=32),
+        dict(id="resblock_ragged", group="resblock", family="conv_resblock_fused_%s_64_32_64", opt="default", dtypes=B16, B=3, h=29, w=21),
+        dict(id="block_full_res", group="block", family="conv_block_fused_%s_x128", opt="fuse_block", dtypes=B16, B=2, h=32, w=32, cin=256, cout=256, res=True),
+        dict(id="block_ragged_res", group="block", family="conv_block_fused_%s_x128", opt="fuse_block", dtypes=B16, B=3, h=19, w=13, cin=256, cout=256, res=True),
+        dict(id="block_ragged_nores", group="block", family="conv_block_fused_%s_x128", opt="fuse_block", dtypes=B16, B=2, h=21, w=17, cin=192, cout=128, res=False),
+        dict(id="head_tiled_full", group="head", family="conv_head_decode_%s_64x256", opt="head_tiled", dtypes=B16, B=2, h=16, w=16, cin=256),
+        dict(id="head_tiled_ragged", group="head", family="conv_head_decode_%s_64x256", opt="head_tiled", dtypes=B16, B=3, h=13, w=11, cin=192),
+        dict(id="head48_full", group="head", family="conv_head_decode_dw_%s_48x256", opt="head48", dtypes=B16, B=2, h=12, w=12, cin=256),
+        dict(id="head48_ragged", group="head", family="conv_head_decode_dw_%s_48x256", opt="head48", dtypes=B16, B=3, h=19, w=13, cin=512),
+        dict(id="head96_full", group="head", family="conv_head_decode_dw_%s_96x256", opt="head96", dtypes=B16, B=2, h=12, w=12, cin=256),
+        dict(id="head96_ragged", group="head", family="conv_head_decode_dw_%s_96x256", opt="head96", dtypes=B16, B=3, h=19, w=13, cin=512),
+    ]
+    # ---- layer kernels (layers.hip): the wide form (16-byte vectors) and the element-wise form, which is chosen when in_c or a
+    # stride is not a multiple of the vector width
+    for wide, tag, c in ((True, "wide", 64), (False, "elem", 13)):
+        C += [
+            _layer("maxpool_s1_" + tag, "maxpool_%s", "maxpool", ALL, 2, 13, 11, c, k=2, s=1, wide=wide),
+            _layer("maxpool_s1_k5_" + tag, "maxpool_%s", "maxpool", ALL, 1, 19, 13, c, k=5, s=1, wide=wide),
+            _layer("maxpool_s2_" + tag, "maxpool_%s", "maxpool", ALL, 3, 26, 22, c, k=2, s=2, wide=wide),
+            _layer("maxpool_dk_s1_" + tag, "maxpool_dk_%s", "maxpool", ALL, 2, 13, 11, c, k=5, s=1, wide=wide, dk=True),
+            _layer("maxpool_dk_s2_" + tag, "maxpool_dk_%s", "maxpool", ALL, 3, 27, 21, c, k=2, s=2, wide=wide, dk=True),
+            _layer("upsample_" + tag, "upsample_%s", "upsample", ALL, 2, 13, 11, c, s=2, wide=wide),
+            _layer("add_" + tag, "add_%s", "add", ALL, 3, 19, 13, c, wide=wide),
+            _layer("add_inplace_" + tag, "add_%s", "add", ALL, 3, 19, 13, c, wide=wide, alias=True),
+            _layer("copy_" + tag, "copy_%s", "copy", ALL, 3, 19, 13, c, wide=wide),
+        ]
+    C += [
+        dict(id="spp_full", group="spp", family="maxpool_spp_pyramid_%s", opt="default", dtypes=ALL, B=2, h=16, w=16, c=64, dk=False),
+        dict(id="spp_ragged", group="spp", family="maxpool_spp_pyramid_%s", opt="default", dtypes=ALL, B=3, h=19, w=13, c=48, dk=False),
+        dict(id="spp_dk_full", group="spp", family="maxpool_spp_pyramid_dk_%s", opt="default", dtypes=ALL, B=2, h=16, w=16, c=64, dk=True),
+        dict(id="spp_dk_ragged", group="spp", family="maxpool_spp_pyramid_dk_%s", opt="default", dtypes=ALL, B=3, h=19, w=13, c=48, dk=True),
+        # yolo decode: 255 channels at stride 256 (channel 255 poisoned) and a wider stride; rows at row_offset > 0 of more rows
+        dict(id="yolo_ld256", group="yolo", family="yolo_decode_f32", opt="default", dtypes=ALL, B=2, h=13, w=11, n_anchor=3, ncls=80, ld=256, c0=0),
+        dict(id="yolo_wide_stride", group="yolo", family="yolo_decode_f32", opt="default", dtypes=ALL, B=3, h=7, w=9, n_anchor=3, ncls=80, ld=268, c0=4),
+        dict(id="yolo_few_classes", group="yolo", family="yolo_decode_f32", opt="default", dtypes=ALL, B=2, h=5, w=6, n_anchor=2, ncls=7, ld=36, c0=4),
+    ]
+    return C
+
+
+# Families whose chooser declines every strided operand: none, every chooser takes pixel strides (the strided half of
+# test_every_case_gets_the_family_it_claims is the proof).  A family that comes to need one is entered here with the chooser
+# line that declines, and tests/test_footprint_host.py then gets the decline / fall-back assertions.
+DENSE_ONLY = {}
+
+# kernel names the choosers can produce that no plan of the shipped cfgs under kernel_choice_util.OPTION_SETS reaches, so
+# tests/golden/kernel_choice.json does not hold them: covered here all the same
+NOT_IN_FIXTURE = ("add_%s", "copy_%s", "maxpool_dk_%s", "maxpool_spp_pyramid_dk_%s")
+
+
+def case_ids():
+    return [(c["id"], d) for c in cases() for d in c["dtypes"]]
+
+
+def case_by_id(cid):
+    return next(c for c in cases() if c["id"] == cid)
+
+
+def family_name(case, dtype):
+    fam = case["family"]
+    if "%s" not in fam:
+        return fam
+    return fam % TAG[dtype]
+
+
+# ------------------------------------------------------------------------------------------------ ops of a case
+
+DT_CODE = {"float32": 0, "bf16": 1, "fp16": 2}
+
+
+def _act(used, name, side, dtype, pixels, c, mode, unit, v, fmt=None):
+    """an activation operand; ``used``: the strides the op's other activation operands have (this one's is added)"""
+    if mode == "dense":
+        return Operand(name, side, fmt or dtype, pixels, c, [(0, c)])
+    c0, ld = strided_ld(c, unit, v, used)
+    used.add(ld)
+    return Operand(name, side, fmt or dtype, pixels, ld, [(c0, c)])
+
+
+def flat(name, side, fmt, n, tile=1):
+    """a flat array of ``n`` elements between guards (parameters, frames, workspaces, the buffers of the other entry points)"""
+    return _flat(name, side, fmt, n, tile)
+
+
+def _flat(name, side, fmt, n, tile=1):
+    return Operand(name, side, fmt, 1, n, [(0, n)], tile_elems=tile)
+
+
+def _conv_weights(prefix, dtype, cin, cout, k, path, operands):
+    """weight / scale / bias operands of one conv in the layout of kernel family ``path``; returns (cout_pad, k_ld)"""
+    H = _H()
+    es = ES[dtype]
+    if path == H.PATH_STEM_MFMA:
+        cp, k_ld, wfmt = 32, 32, dtype
+    elif path == H.PATH_STEM:
+        cp = k_ld = round_up(cout, 8)
+        wfmt = "float32"
+    else:
+        cp, k_ld, wfmt = round_up(cout, 128), round_up(k * k * cin, 128 // es), dtype
+    n = (k * k * cin * cp) if path == H.PATH_STEM else cp * k_ld
+    operands += [_flat(prefix + "weight", "in", wfmt, n), _flat(prefix + "scale", "in", "float32", cp),
+                 _flat(prefix + "bias", "in", "float32", cp)]
+    return cp, k_ld
+
+
+def _set_conv(op, dtype, B, h, w, cin, cout, k, s, flags):
+    H = _H()
+    pad = (k - 1) // 2
+    op.kind, op.dtype, op.flags, op.batch = H.OP_CONV, DT_CODE[dtype], flags, B
+    op.in_h, op.in_w, op.in_c = h, w, cin
+    op.out_h, op.out_w, op.out_c = (h + 2 * pad - k) // s + 1, (w + 2 * pad - k) // s + 1, cout
+    op.ksize, op.stride, op.pad = k, s, pad
+
+
+def build(case, dtype, mode, opt, base=None):
+    """(ops, layout, n_frag) of ``case`` in layout ``mode`` ("dense", "strided"; the aliasing cases alias in both); ``base``: the allocation's device
+    address, or None for fake addresses (the chooser only decides).  ``n_frag``: {op index: operand name} of fragment-order
+    weight copies to make with y3_conv_make_fragment_weights before the run."""
+    H = _H()
+    lib = H.lib()
+    es = ES[dtype]
+    unit = 16 // es
+    g = case["group"]
+    B, h, w = case["B"], case["h"], case["w"]
+    P = B * h * w
+    operands, frag = [], {}
+    used = set()
+    zero = _flat("zero page", "in", dtype, 4096 // es)
+
+    def finish(ops, ptrs):
+        """lay out, then point the ops at their operands: ptrs = [(op index, field, operand name, slice)]"""
+        for i in list(frag):
+            # (the size of a fragment-order copy depends on the op's shape and flags only, not on its pointers)
+            n = int(lib.y3_conv_fragment_weight_bytes(ctypes.byref(ops[i]), ctypes.byref(opt)))
+            if n:
+                operands.append(_flat(frag[i], "in", dtype, n // es))
+            else:
+                del frag[i]
+        lay = Layout(operands + [zero])
+        b = base if base is not None else (1 << 44)
+        for i, field, name, k in ptrs:
+            setattr(ops[i], field, lay[name].ptr(b, k))
+        for i in frag:
+            ops[i].d_weight_frag = lay[frag[i]].ptr(b)
+        return ops, lay, frag
+
+    if g == "conv":
+        cin, cout, k, s = case["cin"], case["cout"], case["k"], case["s"]
+        flags = H.F_LEAKY if case.get("leaky", True) else 0
+        ops = (H.Y3Op * 1)()
+        op = ops[0]
+        out_f32 = bool(case.get("out_f32"))
+        if out_f32:
+            flags |= H.F_OUT_F32
+        if case["inp"] == "u8":
+            flags |= H.F_PLAN_INPUT | H.F_IN_NHWC_U8BGR
+        elif case["inp"] == "nchw":
+            flags |= H.F_PLAN_INPUT | H.F_IN_NCHW_F32
+        if case["res"]:
+            flags |= H.F_RESIDUAL
+        _set_conv(op, dtype, B, h, w, cin, cout, k, s, flags)
+        Po = B * op.out_h * op.out_w
+        ptrs = []
+        if case["inp"] == "act":
+            x = _act(used, "input", "in", dtype, P, cin, mode, unit, 0)
+            ptrs.append((0, "d_in", "input", 0))
+        elif case["inp"] == "u8":
+            x = _flat("input", "in", "u8", P * 3, 3)
+        else:
+            x = _flat("input", "in", "float32", P * 3, 3)
+        operands.append(x)
+        op.in_ld = x.ld if case["inp"] == "act" else 3
+        ofmt = "float32" if out_f32 else dtype
+        ounit = case["out_unit"] or (4 if out_f32 else unit)
+        o = _act(used, "output", "out", dtype, Po, cout, mode, ounit, 1, fmt=ofmt)
+        if mode == "dense" and case.get("dense_out_ld"):          # (255 head channels: the densest stride the kernels take)
+            o = Operand("output", "out", ofmt, Po, case["dense_out_ld"], [(0, cout)])
+        operands.append(o)
+        op.out_ld = o.ld
+        ptrs.append((0, "d_out", "output", 0))
+        if case["res"]:
+            r = _act(used, "residual", "in", dtype, Po, cout, mode, ounit, 2, fmt=ofmt)
+            operands.append(r)
+            op.res_ld = r.ld
+            ptrs.append((0, "d_res", "residual", 0))
+        # the weight layout follows the conv path, which needs provisional igemm-layout sizes to be asked
+        op.cout_pad, op.k_ld = round_up(cout, 128), round_up(k * k * cin, 128 // es)
+        path = lib.y3_conv_path(ctypes.byref(op))
+        op.cout_pad, op.k_ld = _conv_weights("", dtype, cin, cout, k, path, operands)
+        ptrs += [(0, "d_weight", "weight", 0), (0, "d_scale", "scale", 0), (0, "d_bias", "bias", 0)]
+        frag[0] = "fragment weights"
+        return finish(ops, ptrs) + (path,)
+
+    if g in ("stem_pair", "resblock", "block", "head"):
+        n_ops = 2
+        ops = (H.Y3Op * n_ops)()
+        ptrs = []
+        if g == "stem_pair":
+            shp = ((3, 32, 3, 1), (32, 64, 3, 2))
+        elif g == "resblock":
+            shp = ((64, 32, 1, 1), (32, 64, 3, 1))
+        elif g == "block":
+            shp = ((case["cin"], 128, 1, 1), (128, case["cout"], 3, 1))
+        else:
+            nattr = 85
+            shp = ((case["cin"], 3 * nattr, 1, 1),)
+        fl0 = H.F_LEAKY | H.F_FUSE_NEXT
+        if g == "stem_pair":
+            fl0 |= H.F_PLAN_INPUT | H.F_IN_NHWC_U8BGR
+        if g == "head":
+            fl0 = H.F_OUT_F32
+        _set_conv(ops[0], dtype, B, h, w, shp[0][0], shp[0][1], shp[0][2], shp[0][3], fl0)
+        if g == "stem_pair":
+            operands.append(_flat("input", "in", "u8", P * 3, 3))
+            ops[0].in_ld = 3
+        else:
+            x = _act(used, "input", "in", dtype, P, shp[0][0], mode, unit, 0)
+            operands.append(x)
+            ops[0].in_ld = x.ld
+            ptrs.append((0, "d_in", "input", 0))
+        if g == "head":
+            mid = Operand("logits", "scratch", "float32", P, 256, [(0, 255)])
+        else:
+            mid = Operand("intermediate", "scratch", dtype, P, shp[0][1], [(0, shp[0][1])])
+        operands.append(mid)
+        ops[0].out_ld = mid.ld
+        ptrs.append((0, "d_out", mid.name, 0))
+        ops[0].cout_pad, ops[0].k_ld = round_up(shp[0][1], 128), round_up(shp[0][2] ** 2 * shp[0][0], 128 // es)
+        path0 = lib.y3_conv_path(ctypes.byref(ops[0]))
+        ops[0].cout_pad, ops[0].k_ld = _conv_weights("op0 ", dtype, shp[0][0], shp[0][1], shp[0][2], path0, operands)
+        if g == "head":
+            ops[0].cout_pad = 256
+            operands[-3:] = []
+            _conv_weights("op0 ", dtype, shp[0][0], 256, 1, path0, operands)
+        ptrs += [(0, "d_weight", "op0 weight", 0), (0, "d_scale", "op0 scale", 0), (0, "d_bias", "op0 bias", 0)]
+        if g == "head":
+            yo = ops[1]
+            rows = 3 * h * w
+            yo.kind, yo.dtype, yo.batch = H.OP_YOLO, DT_CODE[dtype], B
+            yo.in_h, yo.in_w, yo.in_c, yo.in_ld = h, w, 255, 256
+            yo.out_h, yo.out_w = h, w
+            yo.n_anchor, yo.n_attr = 3, 85
+            for a, (aw, ah) in enumerate(((116, 90), (156, 198), (373, 326))):
+                yo.anchor_w[a], yo.anchor_h[a] = float(aw), float(ah)
+            yo.row_offset, yo.rows_total = 0, rows
+            yo.net_w = yo.net_h = 608.0
+            yo.block_idx = 1
+            operands += [_flat("bbox", "out", "float32", B * rows * 4, 4), _flat("prob", "out", "float32", B * rows),
+                         _flat("cls", "out", "i64", B * rows)]
+            ptrs += [(1, "d_in", "logits", 0), (1, "d_bbox", "bbox", 0), (1, "d_prob", "prob", 0), (1, "d_cls", "cls", 0)]
+            frag[0] = "fragment weights"
+            return finish(ops, ptrs) + (path0,)
+        fl1 = H.F_LEAKY | (H.F_RESIDUAL if (g == "resblock" or (g == "block" and case["res"])) else 0)
+        _set_conv(ops[1], dtype, B, h, w, shp[1][0], shp[1][1], shp[1][2], shp[1][3], fl1)
+        ops[1].block_idx = 1
+        ops[1].in_ld = mid.ld
+        ptrs.append((1, "d_in", mid.name, 0))
+        Po = B * ops[1].out_h * ops[1].out_w
+        o = _act(used, "output", "out", dtype, Po, shp[1][1], mode, unit, 1)
+        operands.append(o)
+        ops[1].out_ld = o.ld
+        ptrs.append((1, "d_out", "output", 0))
+        if fl1 & H.F_RESIDUAL:
+            ops[1].res_ld = ops[0].in_ld
+            ptrs.append((1, "d_res", "input", 0))
+        ops[1].cout_pad, ops[1].k_ld = _conv_weights("op1 ", dtype, shp[1][0], shp[1][1], shp[1][2], H.PATH_IGEMM, operands)
+        ptrs += [(1, "d_weight", "op1 weight", 0), (1, "d_scale", "op1 scale", 0), (1, "d_bias", "op1 bias", 0)]
+        return finish(ops, ptrs) + (path0,)
+
+    if g == "layer":
+        c, k, s, kind = case["c"], case["k"], case["s"], case["kind"]
+        lunit = unit if case["wide"] else 1
+        ops = (H.Y3Op * 1)()
+        op = ops[0]
+        op.kind = {"maxpool": H.OP_MAXPOOL, "upsample": H.OP_UPSAMPLE, "add": H.OP_ADD, "copy": H.OP_COPY}[kind]
+        op.dtype, op.batch, op.in_h, op.in_w, op.in_c, op.out_c = DT_CODE[dtype], B, h, w, c, c
+        op.ksize, op.stride = k, s
+        if kind == "maxpool" and case["dk"]:
+            op.flags |= H.F_POOL_DARKNET
+            op.pad = k - 1
+            op.out_h, op.out_w = (h + op.pad - k) // s + 1, (w + op.pad - k) // s + 1
+        elif kind == "maxpool":
+            op.out_h, op.out_w = (h, w) if s == 1 else ((h - k) // s + 1, (w - k) // s + 1)
+        elif kind == "upsample":
+            op.out_h, op.out_w = h * s, w * s
+        else:
+            op.out_h, op.out_w = h, w
+        Po = B * op.out_h * op.out_w
+        ptrs = []
+        if case["alias"]:
+            # the in-place add: d_out == d_in (the plan's shortcut into the buffer of one of its operands)
+            x = _act(used, "input/output", "inout", dtype, P, c, mode if mode == "dense" else "strided", lunit, 0)
+            operands.append(x)
+            op.in_ld = op.out_ld = x.ld
+            ptrs += [(0, "d_in", x.name, 0), (0, "d_out", x.name, 0)]
+        else:
+            x = _act(used, "input", "in", dtype, P, c, mode, lunit, 0)
+            o = _act(used, "output", "out", dtype, Po, c, mode, lunit, 1)
+            operands += [x, o]
+            op.in_ld, op.out_ld = x.ld, o.ld
+            ptrs += [(0, "d_in", "input", 0), (0, "d_out", "output", 0)]
+        if kind == "add":
+            r = _act(used, "residual", "in", dtype, P, c, mode, lunit, 2)
+            operands.append(r)
+            op.res_ld = r.ld
+            ptrs.append((0, "d_res", "residual", 0))
+        return finish(ops, ptrs) + (None,)
+
+    if g == "spp":
+        c = case["c"]
+        ops = (H.Y3Op * 3)()
+        x = _act(used, "input", "in", dtype, P, c, mode, unit, 0)
+        # three output slices of ONE concat buffer (the route the pyramid feeds), margins left, between and right
+        if mode == "dense":
+            cat = Operand("concat", "out", dtype, P, 3 * c, [(0, c), (c, c), (2 * c, c)])
+        else:
+            ld = 3 * c + 5 * unit
+            ld += unit if (ld // unit) % 2 == 0 else 0
+            cat = Operand("concat", "out", dtype, P, ld, [(unit, c), (c + 2 * unit, c), (2 * c + 3 * unit, c)])
+        operands += [x, cat]
+        ptrs = []
+        for i, k in enumerate((5, 9, 13)):
+            op = ops[i]
+            op.kind, op.dtype, op.batch = H.OP_MAXPOOL, DT_CODE[dtype], B
+            op.in_h = op.out_h = h
+            op.in_w = op.out_w = w
+            op.in_c = op.out_c = c
+            op.in_ld, op.out_ld, op.ksize, op.stride, op.block_idx = x.ld, cat.ld, k, 1, i
+            if case["dk"]:
+                op.flags |= H.F_POOL_DARKNET
+                op.pad = k - 1
+            ptrs += [(i, "d_in", "input", 0), (i, "d_out", "concat", i)]
+        return finish(ops, ptrs) + (None,)
+
+    if g == "yolo":
+        na, nattr = case["n_anchor"], case["ncls"] + 5
+        c = na * nattr
+        ops = (H.Y3Op * 1)()
+        yo = ops[0]
+        rows = na * h * w
+        # this head's rows sit at row_offset > 0 of a longer output (as the second head of a network's do)
+        off, total = (0, rows) if mode == "dense" else (37, rows + 37 + 53)
+        x = Operand("input", "in", "float32", P, round_up(c, 4) if mode == "dense" else case["ld"], [(0 if mode == "dense" else case["c0"], c)])
+        yo.kind, yo.dtype, yo.batch = H.OP_YOLO, DT_CODE[dtype], B
+        yo.in_h, yo.in_w, yo.in_c, yo.in_ld = h, w, c, x.ld
+        yo.out_h, yo.out_w = h, w
+        yo.n_anchor, yo.n_attr = na, nattr
+        for a in range(na):
+            yo.anchor_w[a], yo.anchor_h[a] = 30.0 + 40 * a, 60.0 + 25 * a
+        yo.row_offset, yo.rows_total = off, total
+        yo.net_w, yo.net_h = 416.0, 352.0
+        # outputs: (B, rows_total, 4 | 1 | 1); as operands: B "pixels" of rows_total * n elements, the op's rows one slice
+        operands += [x, Operand("bbox", "out", "float32", B, total * 4, [(off * 4, rows * 4)], tile_elems=4),
+                     Operand("prob", "out", "float32", B, total, [(off, rows)], tile_elems=1),
+                     Operand("cls", "out", "i64", B, total, [(off, rows)], tile_elems=1)]
+        lay = Layout(operands + [zero])
+        b = base if base is not None else (1 << 44)
+        yo.d_in = lay["input"].ptr(b)
+        # d_bbox / d_prob / d_cls are the bases of the WHOLE outputs: the op adds row_offset itself
+        yo.d_bbox, yo.d_prob, yo.d_cls = b + lay["bbox"].body, b + lay["prob"].body, b + lay["cls"].body
+        return ops, lay, {}, None
+    raise AssertionError(g)
+
+
+def chosen(case, dtype, mode, base=None):
+    """kernel names of the case's ops under its options (plan creation only decides when the addresses are fake: every conv
+    that reads fragment-order weights has a d_weight_frag)"""
+    H = _H()
+    lib = H.lib()
+    opt = H.options(**_opts()[case["opt"]])
+    ops, lay, frag, _ = build(case, dtype, mode, opt, base)
+    handle = ctypes.c_void_p()
+    zero = lay["zero page"].ptr(base if base is not None else (1 << 44))
+    H.check(lib.y3_plan_create_ex(ops, len(ops), zero, ctypes.byref(opt), ctypes.byref(handle)))
+    try:
+        return [lib.y3_plan_op_kernel(handle, i).decode() for i in range(len(ops))], lay
+    finally:
+        lib.y3_plan_destroy(handle)
