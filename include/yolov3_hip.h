@@ -86,6 +86,15 @@ extern "C" {
                                   taps are all NaN gives -inf from the former); the 16-bit pyramid compares with
                                   `a >= b ? a : b`, so whether a NaN survives depends on where it sits in the window -- the same
                                   as without the flag.  y3_capabilities() reports Y3_CAP_POOL_DARKNET                         */
+#define Y3_F_SCORES_DARKNET 2048u /* Y3_OP_YOLO: Darknet's class scores instead of the reference's soft-max.  Score and class only, the
+                                  box is untouched.  In float32, one rounding per operation:
+                                    obj = 1 / (1 + expf(-t4)),  p_c = 1 / (1 + expf(-t_c))         (Darknet's logistic_activate)
+                                    prob = p_best * obj,  cls = the first index c with p_c == max_c p_c
+                                  (the arg-max on the computed p_c, not on the logits: distinct logits above ~17 all give 1.0f and
+                                  the first wins).  16-bit networks compute the class terms with the hardware exp2, as they do the
+                                  soft-max's.  With Y3_F_NEW_COORDS the inputs are probabilities already and that decode is Darknet's:
+                                  the flag is accepted there and changes nothing, bit for bit.  On any other op kind it is an
+                                  error.  y3_capabilities() reports Y3_CAP_SCORES_DARKNET                                    */
 
 /*
  * One unit of work.  POD, 8-byte aligned, zero-initialise unused fields.
@@ -212,6 +221,8 @@ int y3_abi_version(void);
 #define Y3_CAP_LETTERBOX 16u   /* y3_letterbox_geometry, y3_letterbox_u8, y3_detect_letterbox */
 #define Y3_CAP_POOL_DARKNET 32u /* Y3_F_POOL_DARKNET and y3_op.pad on max-pool ops */
 #define Y3_CAP_NMS_DARKNET 64u /* y3_detect_darknet, y3_nms_darknet and their workspace queries */
+#define Y3_CAP_SCORES_DARKNET 128u /* Y3_F_SCORES_DARKNET on YOLO ops      */
+#define Y3_CAP_MULTI_LABEL 256u /* y3_expand_labels and its workspace query   */
 uint32_t y3_capabilities(void);
 const char *y3_last_error(void);
 /* number of visible HIP devices whose arch is gfx950 (0 on a CPU-only machine) */
@@ -330,6 +341,37 @@ size_t y3_nms_darknet_workspace_bytes(int n);
 int y3_nms_darknet(const float *d_xywh, const float *d_prob, const int64_t *d_cls, int n, float thresh, int nms_kind,
                    float beta_nms, void *d_workspace, size_t workspace_bytes, int64_t *d_keep, int32_t *d_keep_count,
                    void *stream);
+
+/* Darknet's multi-label candidates (get_yolo_detections): every class of a box whose score passes the threshold becomes a
+ * candidate of its own, where Darknet.forward's outputs carry the arg-max class only.  Not in the reference.
+ * A y3_head_view is one detection head's float32 conv output (B, h, w, ld), channel = anchor * n_attr + attr, exactly what the
+ * head's Y3_OP_YOLO op reads; prediction row = row_offset + anchor * h * w + y * w + x as in the decode.  new_coords != 0: the
+ * stored values are probabilities already (a head decoded with Y3_F_NEW_COORDS) and are used as they are.  `heads` is a HOST
+ * array (1..8 views whose row ranges lie inside [0, rows_total) and do not overlap); it travels as kernel arguments, so it may be
+ * reused as soon as the call returns.  Per frame f and row, in float32 with one rounding per operation (the sequential form of
+ * Y3_F_SCORES_DARKNET):
+ *   obj = 1 / (1 + expf(-t4));   if obj > thresh:   for every class c:   p_c = 1 / (1 + expf(-t_c)),  s_c = obj * p_c;
+ *                                                                        if s_c > thresh: emit label (row, c, s_c)
+ * Both comparisons are strict and a NaN compares false.  Labels are written as VIRTUAL ROWS in ascending (row, c) order -- the
+ * order does not depend on scheduling --:
+ *   d_vbbox (batch, cap, 4) f32 = d_bbox[f, row] bit for bit;  d_vprob (batch, cap) f32 = s_c;  d_vcls (batch, cap) i64 = c;
+ *   d_vrow (batch, cap) i32 = row;  slots k >= count: a box of zeros, vprob -1, vcls 0, vrow -1.
+ * d_vcount (batch) i32 is the TRUE label count of the frame even when it exceeds `cap`; only the first `cap` labels in that
+ * order are then written.  d_bbox (batch, rows_total, 4) f32 is the decode's output; it and d_vbbox are 16-byte aligned.
+ * thresh must be finite and >= 0, cap >= 1.  The virtual rows are what y3_detect / y3_detect_letterbox / y3_detect_darknet
+ * take as (d_bbox, d_prob, d_cls) with rows = cap and the same prob_thresh: every label is > thresh, so their >= keeps all of
+ * them and drops the padding, and their canonical order (class ascending, score descending, higher row first) holds on the
+ * real rows as well, because virtual rows ascend with them.  d_det_row then indexes virtual rows: map it through d_vrow.
+ * Two launches (count, then place and write); allocates nothing and never synchronises.  Workspace:
+ * y3_expand_labels_workspace_bytes (one counter per 64 rows and frame).                                              */
+typedef struct {
+  const float *d_head;
+  int32_t h, w, ld, n_anchor, n_attr, row_offset, new_coords;
+} y3_head_view;
+size_t y3_expand_labels_workspace_bytes(int batch, int rows_total, int cap);
+int y3_expand_labels(const y3_head_view *heads, int n_heads, const float *d_bbox, int batch, int rows_total, float thresh,
+                     int cap, void *d_ws, size_t ws_bytes, float *d_vbbox, float *d_vprob, int64_t *d_vcls, int32_t *d_vrow,
+                     int32_t *d_vcount, void *stream);
 
 /* non_max_suppression (inference.py:161-266) on caller-provided integer boxes -------------- */
 size_t y3_nms_workspace_bytes(int n);

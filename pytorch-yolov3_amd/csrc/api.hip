@@ -147,6 +147,8 @@ int choose_conv(const y3_op &op, const y3_options &o, y3_step &st) {
 int check_flags(const y3_op &op) {
   Y3_REQUIRE(!(op.flags & Y3_F_POOL_DARKNET) || op.kind == Y3_OP_MAXPOOL,
              "op for block %d: Y3_F_POOL_DARKNET on an op of kind %d (max-pool ops only)", op.block_idx, op.kind);
+  Y3_REQUIRE(!(op.flags & Y3_F_SCORES_DARKNET) || op.kind == Y3_OP_YOLO,
+             "op for block %d: Y3_F_SCORES_DARKNET on an op of kind %d (YOLO ops only)", op.block_idx, op.kind);
   return Y3_OK;
 }
 
@@ -252,7 +254,7 @@ int y3_abi_version(void) { return Y3_ABI_VERSION; }
 
 uint32_t y3_capabilities(void) {
   return Y3_CAP_MISH | Y3_CAP_SCALE_X_Y | Y3_CAP_LOGISTIC | Y3_CAP_NEW_COORDS | Y3_CAP_LETTERBOX | Y3_CAP_POOL_DARKNET |
-         Y3_CAP_NMS_DARKNET;
+         Y3_CAP_NMS_DARKNET | Y3_CAP_SCORES_DARKNET | Y3_CAP_MULTI_LABEL;
 }
 
 const char *y3_last_error(void) { return g_err; }

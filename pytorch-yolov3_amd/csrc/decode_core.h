@@ -11,6 +11,8 @@
 //     test_split_class_decode_matches_sequential_decode), far below the bf16 logits' own noise;
 //   * the exp-sum is a tree of four partial sums;
 //   * box coordinates, objectness and the final product keep expf and IEEE division: identical to the sequential form.
+// With Y3_F_SCORES_DARKNET the class terms are Darknet's independent logistics, p_c = 1 / (1 + exp2(-t_c * log2(e))) on the same
+// hardware instruction (no maximum, no sum); the arg-max is taken on those p_c and the score is p_best * objectness.
 // The box tail is spread over the four lanes (sub 0: x, 1: y, 2: w + objectness, 3: h + best / sum) with selects
 // instead of branches, so no lane idles while one lane does five exponentials and seven divisions.
 #pragma once
@@ -48,11 +50,20 @@ struct Y3DecodeArgs {
   long long *cls;
   int anchors, attr, row_offset, rows_total;
   float net_w, net_h, sxy, aw[8], ah[8];
-  int new_coords;   // Y3_F_NEW_COORDS of the YOLO op (in what was the struct's tail padding)
+  int mode;         // Y3_DECODE_* bits of the YOLO op (in what was the struct's tail padding; was `new_coords`, 0 / 1)
 };
 static_assert(sizeof(Y3DecodeArgs) == 120 && offsetof(Y3DecodeArgs, anchors) == 24 && offsetof(Y3DecodeArgs, net_w) == 40 &&
-              offsetof(Y3DecodeArgs, ah) == 84 && offsetof(Y3DecodeArgs, new_coords) == 116,
+              offsetof(Y3DecodeArgs, ah) == 84 && offsetof(Y3DecodeArgs, mode) == 116,
               "layout of the decode fields in the kernel arguments");
+// How a YOLO op scores a box, from its flags.  Y3_F_NEW_COORDS: the inputs are probabilities, and that decode is Darknet's
+// already -- Y3_F_SCORES_DARKNET changes nothing there, so it sets no bit.  Otherwise Y3_F_SCORES_DARKNET replaces the reference's
+// soft-max over the class logits by Darknet's independent logistic per class.
+#define Y3_DECODE_NEW_COORDS 1
+#define Y3_DECODE_SCORES_DARKNET 2
+static inline int y3_decode_mode(const y3_op &yolo) {
+  if (yolo.flags & Y3_F_NEW_COORDS) return Y3_DECODE_NEW_COORDS;
+  return (yolo.flags & Y3_F_SCORES_DARKNET) ? Y3_DECODE_SCORES_DARKNET : 0;
+}
 static inline Y3DecodeArgs y3_decode_args(const y3_op &yolo) {
   Y3DecodeArgs d;
   d.bbox = yolo.d_bbox; d.prob = yolo.d_prob; d.cls = reinterpret_cast<long long *>(yolo.d_cls);
@@ -61,20 +72,21 @@ static inline Y3DecodeArgs y3_decode_args(const y3_op &yolo) {
   d.net_w = yolo.net_w; d.net_h = yolo.net_h;
   d.sxy = y3_op_scale_xy(yolo);
   for (int i = 0; i < 8; ++i) { d.aw[i] = yolo.anchor_w[i]; d.ah[i] = yolo.anchor_h[i]; }
-  d.new_coords = (yolo.flags & Y3_F_NEW_COORDS) != 0;
+  d.mode = y3_decode_mode(yolo);
   return d;
 }
 
 // t_: the box's n_attr logits (LDS).  Called by all four lanes of the box together (EXEC must hold whole quads).
 // cell_*: grid column / row of the box's cell; grid_*: grid size; anchor_*: the box's anchor (pixels); net_*: the network
-// input size the anchors refer to; sxy: the head's scale_x_y; newc: Darknet's new_coords decode, a uniform flag of the launch
-// (every branch on it is a scalar branch): the inputs are the head conv's sigmoid outputs; centre (sxy(t) + cell) / grid, size
-// ((t * t) * 4) * anchor / net, score best * t4, cls the first index of the largest stored class value.  (Scalars by value:
+// input size the anchors refer to; sxy: the head's scale_x_y; mode: Y3_DECODE_* bits, uniform over the launch (every branch on
+// them is a scalar branch).  Y3_DECODE_NEW_COORDS: the inputs are the head conv's sigmoid outputs; centre (sxy(t) + cell) / grid, size
+// ((t * t) * 4) * anchor / net, score best * t4, cls the first index of the largest stored class value.  Y3_DECODE_SCORES_DARKNET:
+// the box as without it, score sigmoid(t_best) * sigmoid(t4), cls the first index of the largest class sigmoid.  (Scalars by value:
 // selecting between members of a struct in memory by lane turns into an indexed load from scratch memory.)
 // comp: this lane's box component (sub 0: bx, 1: by, 2: bw, 3: bh); score / cls are valid on the lane with sub == 2.
 __device__ __forceinline__ void y3_decode_box4(const float *t_, int n_attr, int sub, float cell_x, float cell_y, float grid_w,
                                                float grid_h, float anchor_w, float anchor_h, float net_w, float net_h,
-                                               float sxy, bool newc, float &comp, float &score, int &cls) {
+                                               float sxy, int mode, float &comp, float &score, int &cls) {
 #pragma clang fp contract(off)
   constexpr float kLog2e = 1.44269504088896340736f;
   const int ncls = n_attr - 5;
@@ -82,12 +94,24 @@ __device__ __forceinline__ void y3_decode_box4(const float *t_, int n_attr, int 
   const int c_lo = sub * per;
   float mx = -INFINITY, sum = 0.f, best = -1.f;
   int best_c = 0;
+  const bool newc = (mode & Y3_DECODE_NEW_COORDS) != 0, dark = (mode & Y3_DECODE_SCORES_DARKNET) != 0;
   if (newc) {
     // the class values are probabilities already: compare them as stored.  (A max over the logits followed by one sigmoid
     // would not be the same arg-max: distinct logits above ~17 all give 1.0f, and the first of those must win.)
     const int c_hi = c_lo + per < ncls ? c_lo + per : ncls;
     for (int c = c_lo; c < c_hi; ++c) {
       const float v = t_[5 + c];
+      if (v > best) {
+        best = v;
+        best_c = c;
+      }
+    }
+  } else if (dark) {
+    // Darknet's logistic per class.  The arg-max is taken on the probabilities as computed, as in the new_coords decode: distinct
+    // logits above ~17 all give 1.0f and the first of them must win.
+    const int c_hi = c_lo + per < ncls ? c_lo + per : ncls;
+    for (int c = c_lo; c < c_hi; ++c) {
+      const float v = 1.0f / (1.0f + __builtin_amdgcn_exp2f(-t_[5 + c] * kLog2e));
       if (v > best) {
         best = v;
         best_c = c;
@@ -156,9 +180,10 @@ __device__ __forceinline__ void y3_decode_box4(const float *t_, int n_attr, int 
   const float den = is_xy ? grid : net;
   comp = num / den;
   // sub 2: objectness = sigmoid(t4);  sub 3: best / sum;  score = (best / sum) * objectness on sub 2
-  // (new_coords: objectness = t4, sub 3: best, score = best * t4)
+  // (new_coords: objectness = t4, sub 3: best, score = best * t4;  Darknet scores: sub 3: best, a probability already)
   const float e4 = expf(-t_[4]);
-  const float r = newc ? (sub == 3 ? best : t_[4]) : (sub == 3 ? best : 1.0f) / (sub == 3 ? sum : 1.0f + e4);
+  const float den3 = dark ? 1.0f : sum;            // (best / 1.0f is best, exactly)
+  const float r = newc ? (sub == 3 ? best : t_[4]) : (sub == 3 ? best : 1.0f) / (sub == 3 ? den3 : 1.0f + e4);
   const float q = y3_quad_from3(r);
   score = q * r;
   cls = best_c;
@@ -186,7 +211,7 @@ __device__ __forceinline__ void y3_head_decode_rows(const Args &p, const float *
     float comp, score;
     int best_c;
     y3_decode_box4(sL + pl * LD + a * d.attr, d.attr, sub, (float)x, (float)y, (float)p.Wo, (float)p.Ho, d.aw[a], d.ah[a],
-                   d.net_w, d.net_h, d.sxy, d.new_coords != 0, comp, score, best_c);
+                   d.net_w, d.net_h, d.sxy, d.mode, comp, score, best_c);
     if (!live) continue;
     const long long row = (long long)b * d.rows_total + d.row_offset + (long long)a * p.HoWo + (long long)y * p.Wo + x;
     d.bbox[row * 4 + sub] = comp;

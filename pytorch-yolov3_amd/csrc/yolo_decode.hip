@@ -14,6 +14,8 @@
 // Y3_F_NEW_COORDS (Darknet's new_coords=1; the head conv ended in a sigmoid, so t are probabilities already):
 //   bbox[row] = ((sxy(tx)+x)/w, (sxy(ty)+y)/h, ((tw*tw)*4)*Aw/net_w, ((th*th)*4)*Ah/net_h)
 //   prob[row] = max_c tc * to                            cls[row] = argmax of the stored tc (first on ties)
+// Y3_F_SCORES_DARKNET (without Y3_F_NEW_COORDS, where it changes nothing): Darknet's independent logistic per class, box untouched:
+//   prob[row] = sigmoid(tc_best) * sigmoid(to)           cls[row] = argmax of sigmoid(tc) as computed (first on ties)
 // Built with -ffp-contract=off: each operation rounds like the reference's separate torch ops.
 #include "common.h"
 #include "decode_core.h"
@@ -27,7 +29,7 @@ struct YoloArgs {
   long long *cls;
   int B, h, w, ld, n_anchor, n_attr, row_offset, rows_total;
   float net_w, net_h, sxy;       // sxy: scale_x_y (1 for YOLOv3)
-  int new_coords;                // Y3_F_NEW_COORDS
+  int mode;                      // Y3_DECODE_* bits (decode_core.h)
   float aw[8], ah[8];
   long long total;
 };
@@ -83,7 +85,7 @@ __global__ __launch_bounds__(LANES == 1 ? 256 : 384) void yolo_decode_kernel(Yol
       float comp, score;
       int best_c;
       y3_decode_box4(t_, p.n_attr, sub, (float)x, (float)y, (float)p.w, (float)p.h, p.aw[a], p.ah[a], p.net_w, p.net_h, p.sxy,
-                     p.new_coords != 0, comp, score, best_c);
+                     p.mode, comp, score, best_c);
       if (!live) continue;
       const long long row = (long long)b * p.rows_total + p.row_offset + (long long)a * p.h * p.w + (long long)y * p.w + x;
       p.bbox[row * 4 + sub] = comp;
@@ -94,7 +96,7 @@ __global__ __launch_bounds__(LANES == 1 ? 256 : 384) void yolo_decode_kernel(Yol
       continue;
     }
     const int ncls = p.n_attr - 5;
-    if (p.new_coords) {
+    if (p.mode & Y3_DECODE_NEW_COORDS) {
       // no soft-max and no sigmoid: the stored class values and objectness are probabilities
       float best = -1.f;
       int best_c = 0;
@@ -115,16 +117,28 @@ __global__ __launch_bounds__(LANES == 1 ? 256 : 384) void yolo_decode_kernel(Yol
       p.cls[row] = best_c;
       continue;
     }
-    float mx = -INFINITY;
-    for (int c = 0; c < ncls; ++c) mx = fmaxf(mx, t_[5 + c]);
     float sum = 0.f, best = -1.f;
     int best_c = 0;
-    for (int c = 0; c < ncls; ++c) {
-      const float e = expf(t_[5 + c] - mx);
-      sum += e;
-      if (e > best) {  // strict: first index wins ties, like torch.max
-        best = e;
-        best_c = c;
+    if (p.mode & Y3_DECODE_SCORES_DARKNET) {
+      // Darknet's logistic_activate per class; compared as computed: distinct logits above ~17 all give 1.0f, the first wins
+      for (int c = 0; c < ncls; ++c) {
+        const float v = sigmoidf_ref(t_[5 + c]);
+        if (v > best) {
+          best = v;
+          best_c = c;
+        }
+      }
+      sum = 1.0f;        // (best / 1.0f below is best, exactly)
+    } else {
+      float mx = -INFINITY;
+      for (int c = 0; c < ncls; ++c) mx = fmaxf(mx, t_[5 + c]);
+      for (int c = 0; c < ncls; ++c) {
+        const float e = expf(t_[5 + c] - mx);
+        sum += e;
+        if (e > best) {  // strict: first index wins ties, like torch.max
+          best = e;
+          best_c = c;
+        }
       }
     }
     if (!live) continue;
@@ -157,7 +171,7 @@ static int launch_yolo(const y3_op *ops, const y3_step &st, const void *d_in, co
   a.row_offset = op.row_offset; a.rows_total = op.rows_total;
   a.net_w = op.net_w; a.net_h = op.net_h;
   a.sxy = y3_op_scale_xy(op);
-  a.new_coords = (op.flags & Y3_F_NEW_COORDS) != 0;
+  a.mode = y3_decode_mode(op);
   for (int i = 0; i < 8; ++i) { a.aw[i] = op.anchor_w[i]; a.ah[i] = op.anchor_h[i]; }
   a.total = (long long)op.batch * op.in_h * op.in_w * op.n_anchor;
   const long long npix = (long long)op.batch * op.in_h * op.in_w;

@@ -33,6 +33,8 @@ _MODEL_OPTIONS = [
     (("--letterbox",), dict(action="store_true", help="Darknet letterboxing: keep each frame's aspect ratio and fill the rest of the network input with grey (128) instead of stretching the frame; use it with yolov4-csp, which was trained that way")),
     (("--darknet-pool",), dict(action="store_true", help="Darknet max-pooling (centred windows, out-of-range taps ignored) instead of the reference's; use it with weights trained by Darknet for yolov3-spp, yolov4 and yolov4-csp (the latter together with --letterbox)")),
     (("--nms-kind",), dict(choices=["iou", "greedynms", "diounms"], default=None, help="suppress by Darknet's rule on the float32 boxes instead of the reference's on integer pixel corners: iou (a cfg without nms_kind), greedynms (yolov4.cfg) or diounms (yolov4-csp.cfg); -i is its threshold (Darknet's own defaults are -p 0.25 -i 0.45)")),
+    (("--darknet-scores",), dict(action="store_true", help="score every class of a box by Darknet's independent logistic, sigmoid(obj) * sigmoid(class), instead of the reference's soft-max over the classes; use it with weights trained by Darknet for yolov3, yolov3-tiny, yolov3-spp, yolov4 and yolov4-tiny (yolov4-csp scores that way already)")),
+    (("--multi-label",), dict(action="store_true", help="report every class of a box that scores above -p, as Darknet does, not the best class only (a box may then appear once per class); implies --darknet-scores")),
     (("--beta-nms",), dict(type=float, default=0.6, metavar="<beta>", help="exponent of the distance penalty of --nms-kind diounms (default 0.6, the cfgs' beta_nms)")),
 ]
 _OUTPUT_OPTIONS = [
@@ -99,7 +101,9 @@ def main(argv=None):
     from yolov3 import stream
 
     net = yolov3.Darknet(args["config"], device=device, dtype=args["dtype"],
-                         pool="darknet" if args["darknet_pool"] else "reference")
+                         pool="darknet" if args["darknet_pool"] else "reference",
+                         scores="darknet" if args["darknet_scores"] or args["multi_label"] else "reference",
+                         multi_label=args["multi_label"])
     net.load_weights(args["weights"])
     net.eval()
     net.cuda(device=device)

@@ -34,10 +34,10 @@ LIB_PATH = os.environ.get("Y3_HIP_LIB") or os.path.join(_HERE, "..", "lib", "lib
 Y3_F32, Y3_BF16, Y3_F16, Y3_F64 = 0, 1, 2, 3
 OP_CONV, OP_MAXPOOL, OP_UPSAMPLE, OP_ADD, OP_COPY, OP_YOLO = 1, 2, 3, 4, 5, 6
 F_LEAKY, F_RESIDUAL, F_OUT_F32, F_IN_NCHW_F32, F_IN_NHWC_U8BGR, F_PLAN_INPUT, F_FUSE_NEXT = 1, 2, 4, 8, 16, 32, 64
-F_MISH, F_LOGISTIC, F_NEW_COORDS, F_POOL_DARKNET = 128, 256, 512, 1024
+F_MISH, F_LOGISTIC, F_NEW_COORDS, F_POOL_DARKNET, F_SCORES_DARKNET = 128, 256, 512, 1024, 2048
 # y3_capabilities() bits: what the loaded library computes beyond ABI 6 as first released
 CAP_MISH, CAP_SCALE_X_Y, CAP_LOGISTIC, CAP_NEW_COORDS, CAP_LETTERBOX, CAP_POOL_DARKNET = 1, 2, 4, 8, 16, 32
-CAP_NMS_DARKNET = 64
+CAP_NMS_DARKNET, CAP_SCORES_DARKNET, CAP_MULTI_LABEL = 64, 128, 256
 # Darknet's suppression measures (include/yolov3_hip.h: Y3_NMS_*), by the cfg's spelling of `nms_kind`
 NMS_IOU, NMS_GREEDY, NMS_DIOU = 0, 1, 2
 NMS_KINDS = {"iou": NMS_IOU, "greedynms": NMS_GREEDY, "diounms": NMS_DIOU}
@@ -69,6 +69,13 @@ class Y3LetterboxFrame(ctypes.Structure):
     """Mirror of ``y3_letterbox_frame`` (include/yolov3_hip.h): one frame of a ``y3_letterbox_u8`` batch."""
     _fields_ = [("d_src", ctypes.c_void_p), ("src_h", ctypes.c_int32), ("src_w", ctypes.c_int32),
                 ("d_ytab", ctypes.c_void_p), ("d_xtab", ctypes.c_void_p)]
+
+
+class Y3HeadView(ctypes.Structure):
+    """Mirror of ``y3_head_view`` (include/yolov3_hip.h): one detection head's float32 conv output as ``y3_expand_labels``
+    reads it."""
+    _fields_ = [("d_head", ctypes.c_void_p)] + [(name, ctypes.c_int32) for name in (
+        "h", "w", "ld", "n_anchor", "n_attr", "row_offset", "new_coords")]
 
 
 class Y3Options(ctypes.Structure):
@@ -139,6 +146,10 @@ PROTOTYPES = {
     "y3_nms_darknet": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_float,
                                       ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
                                       ctypes.c_void_p, ctypes.c_void_p]),
+    "y3_expand_labels_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "y3_expand_labels": (ctypes.c_int, [ctypes.POINTER(Y3HeadView), ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                        ctypes.c_float, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
+                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "y3_nms_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int]),
     "y3_nms": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_double,
                               ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p,
@@ -165,7 +176,8 @@ PROTOTYPES = {
 
 # symbols a library of ABI 6 built before they were added lacks: asked for through capabilities()
 _OPTIONAL = ("y3_capabilities", "y3_detect_letterbox", "y3_letterbox_geometry", "y3_letterbox_u8",
-             "y3_detect_darknet_workspace_bytes", "y3_detect_darknet", "y3_nms_darknet_workspace_bytes", "y3_nms_darknet")
+             "y3_detect_darknet_workspace_bytes", "y3_detect_darknet", "y3_nms_darknet_workspace_bytes", "y3_nms_darknet",
+             "y3_expand_labels_workspace_bytes", "y3_expand_labels")
 
 
 class HipLibraryError(RuntimeError):
@@ -209,15 +221,29 @@ def capabilities():
 def require_capabilities(needs, what):
     """Refuse a plan that needs a computation the loaded library does not report: a stale library would run mish as
     linear, ignore scale_x_y, run a logistic head as linear, decode new_coords heads the YOLOv3 way, stretch frames
-    that were to be letterboxed, pool the reference's way where Darknet's rule was asked for or suppress by the
-    reference's rule where Darknet's was asked for."""
+    that were to be letterboxed, pool the reference's way where Darknet's rule was asked for, suppress by the
+    reference's rule where Darknet's was asked for, score boxes by the reference's soft-max where Darknet's logistic scores
+    were asked for, or lack the multi-label expansion."""
     missing = needs & ~capabilities()
     if missing:
         names = [n for n, b in (("mish", CAP_MISH), ("scale_x_y", CAP_SCALE_X_Y), ("logistic", CAP_LOGISTIC),
                                 ("new_coords", CAP_NEW_COORDS), ("letterbox", CAP_LETTERBOX),
-                                ("Darknet max-pooling", CAP_POOL_DARKNET), ("Darknet NMS", CAP_NMS_DARKNET)) if missing & b]
+                                ("Darknet max-pooling", CAP_POOL_DARKNET), ("Darknet NMS", CAP_NMS_DARKNET),
+                                ("Darknet class scores", CAP_SCORES_DARKNET),
+                                ("multi-label detections", CAP_MULTI_LABEL)) if missing & b]
         raise HipLibraryError("{}: the loaded libyolov3_hip.so cannot compute {} (rebuild: make -C pytorch-yolov3_amd/csrc)"
                               .format(what, ", ".join(names)))
+
+
+SCORE_MODES = ("reference", "darknet")
+
+
+def check_scores_mode(scores):
+    """``scores`` of ``Darknet(...)``: "reference" (soft-max over the class logits, the reference's) or "darknet" (an
+    independent logistic per class, what Darknet computes); ValueError for anything else.  Needs no GPU."""
+    if scores not in SCORE_MODES:
+        raise ValueError("scores {!r}: this package computes {}".format(scores, " and ".join(repr(m) for m in SCORE_MODES)))
+    return scores
 
 
 def nms_mode(nms_kind, beta_nms=0.6):

@@ -79,6 +79,17 @@ def fill_maxpool_op(op, od):
     return 0
 
 
+def yolo_decode_flags(od, scores):
+    """(y3_op.flags bits, library capabilities) of a plan's yolo op dict under the class scoring ``scores``.  A new_coords
+    head scores the Darknet way already, so it is the same op in both modes; any other head carries Y3_F_SCORES_DARKNET
+    under "darknet"."""
+    if od.get("new_coords"):
+        return _hip.F_NEW_COORDS, _hip.CAP_NEW_COORDS
+    if scores == "darknet":
+        return _hip.F_SCORES_DARKNET, _hip.CAP_SCORES_DARKNET
+    return 0, 0
+
+
 class _CompiledPlan(object):
     def __init__(self):
         self.handle = None
@@ -88,6 +99,7 @@ class _CompiledPlan(object):
         self.n_ops = 0
         self.rows_total = 0
         self.batch = 0
+        self.heads = None        # multi_label networks: y3_head_view array of the head convs' outputs
 
     def destroy(self):
         if self.handle is not None:
@@ -102,7 +114,8 @@ class _CompiledPlan(object):
 
 
 class Darknet(object):
-    def __init__(self, config_fpath, device="cpu", dtype="float32", keep_all=False, fuse=None, options=None, pool="reference"):
+    def __init__(self, config_fpath, device="cpu", dtype="float32", keep_all=False, fuse=None, options=None, pool="reference",
+                 scores="reference", multi_label=False):
         """
         Args:
             config_fpath (str): Darknet .cfg file.
@@ -117,11 +130,31 @@ class Darknet(object):
                 out-of-range taps ignored, out = (in + padding - size) / stride + 1), what yolov3-spp / yolov4 / yolov4-csp
                 weights trained by Darknet expect from their SPP block.  Fixed for the life of the object; keys of the cfg
                 never switch it on.
+            scores (str): how a box's classes are scored by heads without ``new_coords``.  "reference" [default]: the
+                reference's ``softmax(class logits).max() * sigmoid(obj)``.  "darknet": Darknet's independent logistic per class,
+                ``sigmoid(obj) * sigmoid(class_c)``, what yolov3 / yolov3-tiny / yolov3-spp / yolov4 / yolov4-tiny weights were
+                trained with (Y3_F_SCORES_DARKNET on every YOLO op; the heads stay fused).  ``new_coords`` heads (yolov4-csp)
+                score the Darknet way already: the mode changes nothing there.  Fixed for the life of the object; no cfg key
+                switches it on.
+            multi_label (bool): Darknet reports every class of a box whose score passes the threshold, the reference the
+                arg-max class only.  True keeps the head convs' float32 outputs (``label_heads``) so that ``inference()``,
+                ``detect_in_frames()`` ... and ``Pipeline`` expand them into one candidate per (box, class) before the
+                detection tail (``y3_expand_labels``).  It needs ``scores="darknet"`` or a network all of whose heads are
+                ``new_coords``: under the reference's soft-max the classes of a box are one distribution, not independent
+                labels.  ``forward()`` returns the single-label dict in every mode.
         """
         self._pool = check_pool_mode(pool)
+        self._scores = _hip.check_scores_mode(scores)
+        self._multi_label = bool(multi_label)
         self.blocks, self.net_info = parse_config(config_fpath)
         if self.net_info is None:
             raise ValueError("cfg {!r} has no [net] section".format(config_fpath))
+        if self._multi_label and self._scores != "darknet":
+            heads = [b for b in self.blocks if b["type"] == "yolo"]
+            if not heads or not all(int(b.get("new_coords", 0)) != 0 for b in heads):
+                raise ValueError("multi_label=True needs scores=\"darknet\" (or a cfg all of whose [yolo] heads are new_coords): "
+                                 "the reference's soft-max scores the classes of a box as ONE distribution, so they are not "
+                                 "independent labels")
         self.config_fpath = config_fpath
         self.keep_all = bool(keep_all)   # debugging: no arena reuse, so block_output() works
         # conv-pair fusion (stem + stride-2 conv, residual blocks): default on, off with keep_all unless asked for
@@ -159,6 +192,25 @@ class Darknet(object):
         """Max-pool semantics of this network, "reference" or "darknet": set by the constructor only, so that the cached
         plans of one object never mix modes."""
         return self._pool
+
+    @property
+    def scores(self):
+        """Class scoring of this network, "reference" or "darknet": set by the constructor only, like ``pool``."""
+        return self._scores
+
+    @property
+    def multi_label(self):
+        """Whether the detection entry points report every class of a box that passes the threshold (set by the
+        constructor only)."""
+        return self._multi_label
+
+    def label_heads(self, plan=None):
+        """The detection heads' float32 conv outputs of ``plan`` (default: the plan of the last forward) as a ctypes array of
+        ``y3_head_view`` for ``y3_expand_labels`` / ``Detector.run(labels=...)``.  They live in the plan's arena and are
+        overwritten by its next forward.  Needs ``multi_label=True``: other plans reuse (or never write) those tensors."""
+        if not self._multi_label:
+            raise RuntimeError("construct Darknet(..., multi_label=True) to keep the detection heads' outputs")
+        return (plan if plan is not None else self._last_plan).heads
 
     @property
     def nms_hint(self):
@@ -328,12 +380,15 @@ class Darknet(object):
         dev = self._torch_device()
         lib = _hip.lib()
         options = options if options is not None else self.options
+        if self._multi_label:
+            # the head convs' float32 outputs must reach memory: the fused head kernels keep them in LDS (fuse_head)
+            options = dict(options or {}, fuse_head=0)
         opt = _hip.options(**options) if options else None
         self._made_fragments = False
         c_dtype, es = DTYPES[self.dtype][0], DTYPES[self.dtype][1]
         bf16 = es == 2                       # a 16-bit storage mode (bf16 or fp16)
         desc = build_plan(self.blocks, self.net_info, batch, height, width, es, reuse=not self.keep_all, fuse=self.fuse,
-                          pool=self.pool)
+                          pool=self.pool, keep_heads=self._multi_label)
         cp = _CompiledPlan()
         cp.batch = batch
         cp.rows_total = desc["rows_total"]
@@ -435,12 +490,21 @@ class Darknet(object):
                 if "scale_x_y" in od:
                     op.scale_x_y = od["scale_x_y"]
                     needs |= _hip.CAP_SCALE_X_Y
-                if od.get("new_coords"):
-                    op.flags |= _hip.F_NEW_COORDS
-                    needs |= _hip.CAP_NEW_COORDS
+                flags, caps = yolo_decode_flags(od, self._scores)
+                op.flags |= flags
+                needs |= caps
             else:
                 raise AssertionError(kind)
+        if self._multi_label:
+            needs |= _hip.CAP_MULTI_LABEL
         _hip.require_capabilities(needs, self.config_fpath)
+        if self._multi_label:
+            yolo = [ops[n] for n in range(len(desc["ops"])) if ops[n].kind == _hip.OP_YOLO]
+            cp.heads = (_hip.Y3HeadView * len(yolo))()
+            for view, op in zip(cp.heads, yolo):
+                view.d_head, view.h, view.w, view.ld = op.d_in, op.in_h, op.in_w, op.in_ld
+                view.n_anchor, view.n_attr, view.row_offset = op.n_anchor, op.n_attr, op.row_offset
+                view.new_coords = int(bool(op.flags & _hip.F_NEW_COORDS))
         cp.ops = ops
         cp.n_ops = len(desc["ops"])
         cp.desc = desc
@@ -551,9 +615,15 @@ class Darknet(object):
         return arr[:, :, :, t.off:t.off + t.c].permute(0, 3, 1, 2).float().contiguous()
 
     def plan_report(self):
-        """Per-op (kernel name, flops, bytes, block) of the last executed plan (for bench/profiling)."""
+        """Per-op (kernel name, flops, bytes, block) of the last executed plan (for bench/profiling); YOLO ops also carry
+        ``scores``, the class scoring they compute ("reference" or "darknet"; a new_coords head reads "darknet" always)."""
         cp = self._last_plan
         lib = _hip.lib()
-        return [dict(kernel=lib.y3_plan_op_kernel(cp.handle, i).decode(),
-                     flops=lib.y3_plan_op_flops(cp.handle, i), bytes=lib.y3_plan_op_bytes(cp.handle, i),
-                     block=int(cp.ops[i].block_idx)) for i in range(cp.n_ops)]
+        report = [dict(kernel=lib.y3_plan_op_kernel(cp.handle, i).decode(),
+                       flops=lib.y3_plan_op_flops(cp.handle, i), bytes=lib.y3_plan_op_bytes(cp.handle, i),
+                       block=int(cp.ops[i].block_idx)) for i in range(cp.n_ops)]
+        for i, entry in enumerate(report):
+            if cp.ops[i].kind == _hip.OP_YOLO:
+                dark = cp.ops[i].flags & (_hip.F_SCORES_DARKNET | _hip.F_NEW_COORDS)
+                entry["scores"] = "darknet" if dark else "reference"
+        return report

@@ -17,7 +17,11 @@
 * ``nms_kind="iou" | "greedynms" | "diounms"`` (opt-in, not in the reference) chooses the survivors by Darknet's rule on the
   float32 centre / size boxes (``y3_detect_darknet``; include/yolov3_hip.h states the rule) instead of the reference's on
   integer pixel corners; everything else about a detection stays.  ``non_max_suppression_darknet`` is that rule on
-  caller-provided boxes.
+  caller-provided boxes;
+* a network built with ``multi_label=True`` (opt-in, not in the reference) reports every class of a box whose Darknet score
+  ``sigmoid(obj) * sigmoid(class_c)`` is ``>`` the threshold, not the arg-max class only: ``y3_expand_labels`` turns the
+  head outputs into one candidate per (box, class) and the detection tail runs on those unchanged, so a box may appear once
+  per class and a box's second class takes part in that class's suppression.
 
 There is no CPU fallback: without the HIP library / a GPU these functions raise.
 """
@@ -222,13 +226,25 @@ class Detector(object):
         self.orig_hw = torch.empty((batch, 2), dtype=torch.int32, device=device)
         self._records = {}      # kmax -> (batch, kmax, 8) int32 staging buffer of fetch()
         self._ws_darknet = None  # (bytes, tensor): the larger workspace of y3_detect_darknet, made when first asked for
+        self._labels = {}        # capacity -> _LabelBuffers of multi-label runs
+        self._tail = self        # the Detector that holds the last run's detections (another one for a capacity != rows)
+        self._label_run = None   # multi-label: the _LabelBuffers of the last run, whose true counts fetch() checks
 
-    def run(self, out, orig_hw, prob_thresh, iou_thresh, letterbox=None, nms_kind=None, beta_nms=0.6):
+    def run(self, out, orig_hw, prob_thresh, iou_thresh, letterbox=None, nms_kind=None, beta_nms=0.6, labels=None,
+            label_capacity=None):
         """out: Darknet.forward dict (device tensors).  orig_hw: (batch,2) int32 tensor/array.  letterbox: the
         (net_h, net_w) the frames were letterboxed into -- the boxes are then corrected back (``y3_detect_letterbox``).
         nms_kind: None = the reference's suppression rule; "iou" / "greedynms" / "diounms" = Darknet's, on the float32
-        boxes (``y3_detect_darknet``; with ``letterbox``, on the corrected ones), ``beta_nms`` for "diounms"."""
+        boxes (``y3_detect_darknet``; with ``letterbox``, on the corrected ones), ``beta_nms`` for "diounms".
+        labels: None, or the ``y3_head_view`` array of the forward that made ``out`` (``Darknet.label_heads()``): Darknet's
+        multi-label detections.  Every (box, class) whose score is > ``prob_thresh`` becomes a candidate
+        (``y3_expand_labels``), at most ``label_capacity`` per frame (default: the number of prediction rows), and the
+        tail chosen by the other arguments runs on those; the rows reported are the real prediction rows.  A frame with
+        more labels than the capacity is an error raised by ``fetch`` (``check_label_capacity``), never a truncation."""
         mode = _hip.nms_mode(nms_kind, beta_nms)
+        if labels is not None:
+            return self._run_labels(out, orig_hw, prob_thresh, iou_thresh, letterbox, nms_kind, beta_nms, labels, label_capacity)
+        self._tail, self._label_run = self, None
         if not isinstance(orig_hw, torch.Tensor):
             orig_hw = torch.from_numpy(np.ascontiguousarray(orig_hw, dtype=np.int32))
         if (orig_hw.device == self.orig_hw.device and orig_hw.dtype == torch.int32 and orig_hw.is_contiguous()
@@ -260,11 +276,53 @@ class Detector(object):
             net_h, net_w = (int(v) for v in letterbox)
             _hip.check(_hip.lib().y3_detect_letterbox(*args, net_h, net_w, _hip.stream_ptr()))
 
-    def fetch(self, return_rows=False, kmax=1024):
+    def _run_labels(self, out, orig_hw, prob_thresh, iou_thresh, letterbox, nms_kind, beta_nms, labels, label_capacity):
+        _hip.require_capabilities(_hip.CAP_MULTI_LABEL, "Detector.run(labels=...)")
+        bbox = out["bbox_xywh"]
+        batch, rows_total = int(bbox.shape[0]), int(bbox.shape[1])
+        if batch != self.batch:
+            raise ValueError("Detector of batch {} given outputs of batch {}".format(self.batch, batch))
+        cap = int(label_capacity) if label_capacity is not None else self.rows
+        if cap < 1:
+            raise ValueError("label_capacity must be >= 1, got {!r}".format(label_capacity))
+        lb = self._labels.get((cap, rows_total))
+        if lb is None:
+            lb = self._labels[(cap, rows_total)] = _LabelBuffers(self.batch, rows_total, cap, self.device)
+            lb.tail = self if cap == self.rows else Detector(self.batch, cap, self.device)
+        _hip.check(_hip.lib().y3_expand_labels(
+            labels, len(labels), bbox.data_ptr(), self.batch, rows_total, ctypes.c_float(prob_thresh), cap, lb.ws.data_ptr(),
+            lb.ws_bytes, lb.vbbox.data_ptr(), lb.vprob.data_ptr(), lb.vcls.data_ptr(), lb.vrow.data_ptr(), lb.vcount.data_ptr(),
+            _hip.stream_ptr()))
+        tail = lb.tail
+        Detector.run(tail, {"bbox_xywh": lb.vbbox, "class_prob": lb.vprob, "class_idx": lb.vcls}, orig_hw, prob_thresh,
+                     iou_thresh, letterbox=letterbox, nms_kind=nms_kind, beta_nms=beta_nms)
+        # the tail reports virtual rows: back to prediction rows on the device, before anything packs records (slots past a
+        # frame's count hold whatever was there: clamped for the lookup, never read by anyone)
+        # -- through buffers made once, like everything else on this path
+        lb.index.copy_(tail.row)
+        lb.index.clamp_(0, cap - 1)
+        torch.gather(lb.vrow, 1, lb.index, out=tail.row)
+        self._tail, self._label_run = tail, lb
+
+    def check_label_capacity(self, n_frames=None):
+        """After a multi-label ``run``: RuntimeError if one of the first ``n_frames`` frames (default: all) had more labels than
+        the capacity, in which case the candidates of that frame were cut off.  One small synchronising copy."""
+        lb = self._label_run
+        if lb is None:
+            return
+        counts = lb.vcount.cpu().numpy()
+        raise_label_overflow(counts[:n_frames], lb.cap)
+
+    def fetch(self, return_rows=False, kmax=1024, check_labels=True):
         """Detections of the last ``run`` on the host: ONE device-to-host copy per batch.  The device packs every
         frame's first ``kmax`` detections into fixed-size records that also carry the frame's true count
         (``y3_pack_records``, the multi-GPU gather's format); only if some frame kept more than ``kmax`` boxes is a
-        second, larger copy made."""
+        second, larger copy made.  After a multi-label run one more small copy checks the label counts of all frames, unless
+        the caller has checked them already (``check_labels=False``: ``Pipeline.results``, which knows the real frames)."""
+        if check_labels:
+            self.check_label_capacity()
+        if self._tail is not self:
+            return self._tail.fetch(return_rows=return_rows, kmax=kmax, check_labels=False)
         from .dist import unpack_records
         lib = _hip.lib()
         kmax = max(1, min(int(kmax), self.rows))
@@ -286,6 +344,30 @@ class Detector(object):
         return results
 
 
+class _LabelBuffers(object):
+    """Device buffers of ``y3_expand_labels`` for one (batch, rows_total, capacity): the virtual rows and its workspace."""
+
+    def __init__(self, batch, rows_total, cap, device):
+        self.cap = cap
+        self.ws_bytes = _hip.lib().y3_expand_labels_workspace_bytes(batch, rows_total, cap)
+        self.ws = torch.empty(self.ws_bytes, dtype=torch.uint8, device=device)
+        self.vbbox = torch.empty((batch, cap, 4), dtype=torch.float32, device=device)
+        self.vprob = torch.empty((batch, cap), dtype=torch.float32, device=device)
+        self.vcls = torch.empty((batch, cap), dtype=torch.int64, device=device)
+        self.vrow = torch.empty((batch, cap), dtype=torch.int32, device=device)
+        self.vcount = torch.zeros(batch, dtype=torch.int32, device=device)
+        self.index = torch.empty((batch, cap), dtype=torch.int64, device=device)     # the tail's rows as gather indices
+        self.tail = None
+
+
+def raise_label_overflow(counts, cap):
+    """RuntimeError naming the first frame whose true label count exceeds the capacity."""
+    for frame, count in enumerate(np.asarray(counts).tolist()):
+        if count > cap:
+            raise RuntimeError("multi-label detection: frame {} has {} labels above the threshold, more than label_capacity={}; "
+                               "pass a larger label_capacity= (or a higher prob_thresh)".format(frame, count, cap))
+
+
 _detectors = {}
 
 
@@ -299,7 +381,7 @@ def get_detector(batch, rows, device):
 
 
 def inference(net, images, device="cuda", prob_thresh=0.05, nms_iou_thresh=0.3, resize=True,
-              return_rows=False, letterbox=False, letterbox_fill=128, nms_kind=None, beta_nms=0.6):
+              return_rows=False, letterbox=False, letterbox_fill=128, nms_kind=None, beta_nms=0.6, label_capacity=None):
     """Run detection on one frame or a list of HxWx3 uint8 BGR frames.
 
     Returns, per frame, ``[bbox_tlbr int64 (K,4), class_prob float32 (K,), class_idx int64 (K,)]``
@@ -313,6 +395,10 @@ def inference(net, images, device="cuda", prob_thresh=0.05, nms_iou_thresh=0.3, 
     ``nms_kind``: None [default] = the reference's suppression (integer pixel corners, +1 areas, IoU > ``nms_iou_thresh``);
     "iou", "greedynms" or "diounms" = Darknet's on the float32 boxes, with ``nms_iou_thresh`` as its threshold and
     ``beta_nms`` as the exponent of "diounms" (``net.nms_hint`` holds what the cfg asks for).  ValueError for any other kind.
+
+    A network built with ``multi_label=True`` returns Darknet's multi-label detections: every class of a box whose score
+    is ``> prob_thresh`` (strictly), so a box may appear once per class.  ``label_capacity``: the most labels a frame may
+    have before suppression (default: the number of prediction rows); a frame with more raises a RuntimeError.
     """
     _hip.nms_mode(nms_kind, beta_nms)
     if letterbox and not resize:
@@ -334,5 +420,6 @@ def inference(net, images, device="cuda", prob_thresh=0.05, nms_iou_thresh=0.3, 
     orig_hw = np.array([[s[0], s[1]] for s in shapes], dtype=np.int32)
     with torch.cuda.device(dev):
         det.run(out, orig_hw, float(np.float32(prob_thresh)), float(nms_iou_thresh),
-                letterbox=(net_h, net_w) if letterbox else None, nms_kind=nms_kind, beta_nms=beta_nms)
+                letterbox=(net_h, net_w) if letterbox else None, nms_kind=nms_kind, beta_nms=beta_nms,
+                labels=net.label_heads() if getattr(net, "multi_label", False) else None, label_capacity=label_capacity)
         return det.fetch(return_rows=return_rows)

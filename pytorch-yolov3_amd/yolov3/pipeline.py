@@ -23,7 +23,7 @@ import torch
 
 from . import _hip
 from .dist import DetectionGather, all_gather_records, regather_if_truncated, unpack_records
-from .inference import Detector
+from .inference import Detector, raise_label_overflow
 
 
 # HIP deals streams onto its hardware queues (GPU_MAX_HW_QUEUES) in creation order and two streams on one queue run one
@@ -56,10 +56,17 @@ class Pipeline(object):
     tickets before every submit costs 8-15 % of the rate: profiles/r04m_pipeline_depth.txt).  Submitting ticket
     i + max_open reuses ticket i's buffers: its results must have been taken, or are dropped (the benchmark does that on
     purpose).  ``nms_kind`` / ``beta_nms``: Darknet's suppression rule instead of the reference's (``inference()`` explains).
+    A network built with ``multi_label=True`` gives Darknet's multi-label detections (``y3_expand_labels`` between the forward
+    and the detection tail, on the batch's stream); ``label_capacity``: the most labels a frame may have before suppression
+    (default: the number of prediction rows) -- ``results`` raises a RuntimeError for a frame that had more.  Under a process
+    group with more than one rank the label counts are LOCAL: only the rank whose own frame overflowed raises, while the others
+    go on and may wait in a later collective for a rank that has left.  Size ``label_capacity`` so that it cannot happen (the
+    default, one label per prediction row, holds for any threshold Darknet is used with), or run such jobs under a launcher
+    that ends all ranks when one fails.
     """
 
     def __init__(self, net, batch, height=None, width=None, in_flight=3, prob_thresh=0.05, nms_iou_thresh=0.3, kmax=512,
-                 world=1, group=None, options=None, copy_blocks=8, nms_kind=None, beta_nms=0.6):
+                 world=1, group=None, options=None, copy_blocks=8, nms_kind=None, beta_nms=0.6, label_capacity=None):
         _hip.nms_mode(nms_kind, beta_nms)               # ValueError for a kind this package does not compute
         _hip.require_gpu()
         if batch < 1 or in_flight < 1:
@@ -97,9 +104,19 @@ class Pipeline(object):
                      for k in range(self.in_flight)]
             self.rows = plans[0].rows_total
             self.max_open = 2 * self.in_flight
-            self.dets = [Detector(self.batch, self.rows, dev) for _ in range(self.max_open)]
-            self.gathers = [DetectionGather(self.batch, self.rows, self.kmax, dev, world, group=group, side=side)
+            # multi-label networks: the detection tail works on `label_capacity` candidates per frame, made from the head
+            # outputs each plan keeps in its own arena
+            self.multi_label = bool(getattr(net, "multi_label", False))
+            if label_capacity is not None and int(label_capacity) < 1:
+                raise ValueError("label_capacity must be >= 1, got {!r}".format(label_capacity))
+            self.label_capacity = int(label_capacity) if label_capacity is not None else self.rows
+            self._heads = [net.label_heads(p) for p in plans] if self.multi_label else None
+            det_rows = self.label_capacity if self.multi_label else self.rows
+            self.dets = [Detector(self.batch, det_rows, dev) for _ in range(self.max_open)]
+            self.gathers = [DetectionGather(self.batch, det_rows, self.kmax, dev, world, group=group, side=side)
                             for _ in range(self.max_open)]
+            self.host_labels = ([torch.zeros(self.batch, dtype=torch.int32).pin_memory() for _ in range(self.max_open)]
+                                if self.multi_label else None)
             self.world = world
             # TWO device frame buffers per batch in flight: with one, the upload of ticket i could only start when the
             # forward of ticket i - in_flight (same stream, same buffer) had finished -- exactly when that stream was ready
@@ -213,7 +230,11 @@ class Pipeline(object):
                 self.free_ev[j].record(cur)
             det = self.dets[d]
             det.run(out, self.full_hw if orig_hw is None else orig_hw, self.prob_thresh, self.nms_iou_thresh,
-                    letterbox=(self.height, self.width) if letterbox else None, nms_kind=self.nms_kind, beta_nms=self.beta_nms)
+                    letterbox=(self.height, self.width) if letterbox else None, nms_kind=self.nms_kind, beta_nms=self.beta_nms,
+                    labels=self._heads[k] if self.multi_label else None, label_capacity=self.label_capacity)
+            if self.multi_label:
+                # every frame's true label count rides to the host behind the tail (results() checks it against the capacity)
+                self.host_labels[d].copy_(det._label_run.vcount, non_blocking=True)
             if n_frames is not None and int(n_frames) < self.batch:
                 # padding frames of a short last batch (copies of real frames, or whatever the staging buffer held) must not
                 # count: their detections are dropped here, BEFORE the records are packed and gathered, so that they can neither
@@ -262,12 +283,15 @@ class Pipeline(object):
         same order, or the job hangs.  All ranks take the same branch because the first gather carried every frame's true count."""
         rec = self.records(ticket)
         k, d = ticket % self.in_flight, ticket % self.max_open
+        if self.multi_label:
+            raise_label_overflow(self.host_labels[d].numpy()[:self._frames_in[d]], self.label_capacity)
         mine = rec[:self.batch] if self.world == 1 else rec     # single rank: all frames are ours
         collective = self.gathers[d].collective                # a process group is up (N ranks, or one: tests)
         if not collective and mine.size and int(mine[:, 0, 7].max()) > self.kmax:
             # (the ticket's detector buffers still hold the whole batch: they are reused max_open tickets later)
             with torch.cuda.device(self.dev), torch.cuda.stream(self.streams[k]):
-                full = self.dets[d].fetch(return_rows=return_rows, kmax=int(mine[:, 0, 7].max()))
+                # (the label counts of the real frames were checked above: padding frames must not raise)
+                full = self.dets[d].fetch(return_rows=return_rows, kmax=int(mine[:, 0, 7].max()), check_labels=False)
             return full[:self._frames_in[d]]
         if collective:
             # N ranks: every kept box of every rank's frames (the reference returns them all: inference.py:355-366).  The true
@@ -281,7 +305,7 @@ class Pipeline(object):
                     rec2 = torch.zeros((self.batch, kmax2, 8), dtype=torch.int32, device=self.dev)
                     _hip.check(_hip.lib().y3_pack_records(
                         det.count.data_ptr(), det.tlbr.data_ptr(), det.prob.data_ptr(), det.cls.data_ptr(), det.row.data_ptr(),
-                        self.batch, self.rows, kmax2, rec2.data_ptr(), None, _hip.stream_ptr(self.streams[k])))
+                        self.batch, det.rows, kmax2, rec2.data_ptr(), None, _hip.stream_ptr(self.streams[k])))
                 return rec2
             with torch.cuda.device(self.dev), torch.cuda.stream(self.streams[k]):
                 mine = regather_if_truncated(mine, self.kmax, repack, self.world, self.group)

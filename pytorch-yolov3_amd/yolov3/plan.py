@@ -167,7 +167,7 @@ def infer_shapes(blocks, net_info, height, width, pool="reference"):
     return shapes
 
 
-def build_plan(blocks, net_info, batch, height, width, elem_size, reuse=True, fuse=None, pool="reference"):
+def build_plan(blocks, net_info, batch, height, width, elem_size, reuse=True, fuse=None, pool="reference", keep_heads=False):
     """Resolve the graph.  ``blocks`` must already carry absolute route indices.
 
     Returns dict(ops=[...], buffers={id: nbytes}, offsets={id: arena offset}, arena_bytes,
@@ -177,6 +177,8 @@ def build_plan(blocks, net_info, batch, height, width, elem_size, reuse=True, fu
     its arena slot but is never written.
     ``pool``: "reference" [default] or "darknet" max-pool semantics for every [maxpool] block; under "darknet" each maxpool op
     carries ``pool="darknet"`` and ``pad`` (Darknet's ``padding``), under the default neither key.
+    ``keep_heads``: the float32 outputs of the detection-head convs stay alive to the end of the plan (their arena slots are
+    not reused), for a caller that reads them after the forward (multi-label detections); the ops themselves do not change.
     """
     if fuse is None:
         fuse = reuse
@@ -368,6 +370,10 @@ def build_plan(blocks, net_info, batch, height, width, elem_size, reuse=True, fu
     for buf in buffers:
         if buf not in first:
             raise AssertionError("buffer {} never produced".format(buf))
+    if keep_heads:
+        for op in ops:
+            if op["kind"] == "yolo":
+                last[op["inp"].buf] = len(ops) - 1
 
     nbytes = {buf: _round_up(d["elems"] * d["es"], ALIGN) for buf, d in buffers.items()}
     offsets = {}

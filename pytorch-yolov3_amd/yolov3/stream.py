@@ -65,7 +65,8 @@ def _batches(frames, batch_size):
 
 
 def detect_in_frames(net, frames, batch_size=16, prob_thresh=0.05, nms_iou_thresh=0.3, resize=True,
-                     in_flight=3, kmax=512, letterbox=False, letterbox_fill=128, nms_kind=None, beta_nms=0.6):
+                     in_flight=3, kmax=512, letterbox=False, letterbox_fill=128, nms_kind=None, beta_nms=0.6,
+                     label_capacity=None):
     """Generator over ``[bbox_tlbr, class_prob, class_idx]`` for every frame of the iterable
     ``frames`` (HxWx3 uint8 BGR arrays; sizes may differ when ``resize``), in order.
 
@@ -84,6 +85,10 @@ def detect_in_frames(net, frames, batch_size=16, prob_thresh=0.05, nms_iou_thres
 
     ``nms_kind`` / ``beta_nms``: Darknet's suppression rule ("iou", "greedynms", "diounms") instead of the reference's, as in
     ``inference()``; None changes nothing.
+
+    A network built with ``multi_label=True`` yields Darknet's multi-label detections (a box once per class that scores
+    ``> prob_thresh``), at most ``label_capacity`` candidates per frame before suppression (default: the number of prediction
+    rows; a frame with more raises a RuntimeError), as in ``inference()``.
     """
     from .pipeline import Pipeline
     _hip.nms_mode(nms_kind, beta_nms)
@@ -105,10 +110,10 @@ def detect_in_frames(net, frames, batch_size=16, prob_thresh=0.05, nms_iou_thres
         # second of video at the rate they run at) and handed to one generator at a time
         if state["pipe"] is None:
             cache = net.__dict__.setdefault("_pipelines", {})
-            key = (batch, height, width, in_flight, kmax, str(net.device), net.dtype)
+            key = (batch, height, width, in_flight, kmax, str(net.device), net.dtype, label_capacity)
             pipe = cache.get(key)
             if pipe is None or pipe.busy:
-                pipe = Pipeline(net, batch, height, width, in_flight=in_flight, kmax=kmax)
+                pipe = Pipeline(net, batch, height, width, in_flight=in_flight, kmax=kmax, label_capacity=label_capacity)
                 if key not in cache or not cache[key].busy:
                     cache[key] = pipe
             pipe.busy = True
@@ -184,13 +189,14 @@ def detect_in_frames(net, frames, batch_size=16, prob_thresh=0.05, nms_iou_thres
 
 
 def detect_in_images(net, path, batch_size=16, prob_thresh=0.05, nms_iou_thresh=0.3, letterbox=False, letterbox_fill=128,
-                     nms_kind=None, beta_nms=0.6):
-    """The CLI's ``--image`` mode: ``path`` is a file or a directory.  Returns (file names, results)."""
+                     nms_kind=None, beta_nms=0.6, label_capacity=None):
+    """The CLI's ``--image`` mode: ``path`` is a file or a directory.  Returns (file names, results).  ``label_capacity``: as
+    in ``detect_in_frames`` (multi-label networks)."""
     directory, names = list_image_files(path)
     frames = (load_image_bgr(os.path.join(directory, n)) for n in names)
     results = list(detect_in_frames(net, frames, batch_size=batch_size, prob_thresh=prob_thresh,
                                     nms_iou_thresh=nms_iou_thresh, letterbox=letterbox, letterbox_fill=letterbox_fill,
-                                    nms_kind=nms_kind, beta_nms=beta_nms))
+                                    nms_kind=nms_kind, beta_nms=beta_nms, label_capacity=label_capacity))
     return names, results
 
 
@@ -238,10 +244,10 @@ def _video_frames(filepath):
 
 def detect_in_video(net, filepath, device="cuda", prob_thresh=0.05, nms_iou_thresh=0.3, class_names=None,
                     frames=None, show_video=False, batch_size=16, letterbox=False, letterbox_fill=128, nms_kind=None,
-                    beta_nms=0.6):
+                    beta_nms=0.6, label_capacity=None):
     """Run detection over a video (or a directory of frames), draw the boxes on every frame and
     append the frames to ``frames`` when a list is given -- the reference's contract, batched.
-    Returns the list of per-frame results."""
+    Returns the list of per-frame results.  ``label_capacity``: as in ``detect_in_frames`` (multi-label networks)."""
     if show_video and _cv2() is None:
         raise RuntimeError("show_video needs OpenCV (cv2), which is not installed")
     if str(device).startswith("cuda") and not str(net.device).startswith("cuda"):
@@ -257,7 +263,7 @@ def detect_in_video(net, filepath, device="cuda", prob_thresh=0.05, nms_iou_thre
     for i, (bbox_tlbr, class_prob, class_idx) in enumerate(
             detect_in_frames(net, tap(), batch_size=batch_size, prob_thresh=prob_thresh,
                              nms_iou_thresh=nms_iou_thresh, letterbox=letterbox, letterbox_fill=letterbox_fill,
-                             nms_kind=nms_kind, beta_nms=beta_nms)):
+                             nms_kind=nms_kind, beta_nms=beta_nms, label_capacity=label_capacity)):
         frame = kept[i]
         kept[i] = None
         draw_boxes(frame, bbox_tlbr, class_idx=class_idx, class_names=class_names)
@@ -273,9 +279,10 @@ def detect_in_video(net, filepath, device="cuda", prob_thresh=0.05, nms_iou_thre
 
 
 def detect_in_cam(net, cam_id=0, device="cuda", prob_thresh=0.05, nms_iou_thresh=0.3, class_names=None,
-                  show_fps=False, frames=None, letterbox=False, letterbox_fill=128, nms_kind=None, beta_nms=0.6):
+                  show_fps=False, frames=None, letterbox=False, letterbox_fill=128, nms_kind=None, beta_nms=0.6,
+                  label_capacity=None):
     """Live camera loop (latency-bound, one frame per step like the reference).  Needs OpenCV for
-    capture and display."""
+    capture and display.  ``label_capacity``: as in ``inference()`` (multi-label networks)."""
     _hip.nms_mode(nms_kind, beta_nms)
     cv2 = _cv2()
     if cv2 is None:
@@ -291,7 +298,8 @@ def detect_in_cam(net, cam_id=0, device="cuda", prob_thresh=0.05, nms_iou_thresh
                 break
             bbox_tlbr, _, class_idx = inference(net, frame, device=device, prob_thresh=prob_thresh,
                                                 nms_iou_thresh=nms_iou_thresh, letterbox=letterbox,
-                                                letterbox_fill=letterbox_fill, nms_kind=nms_kind, beta_nms=beta_nms)[0]
+                                                letterbox_fill=letterbox_fill, nms_kind=nms_kind, beta_nms=beta_nms,
+                                                label_capacity=label_capacity)[0]
             draw_boxes(frame, bbox_tlbr, class_idx=class_idx, class_names=class_names)
             if show_fps:
                 cv2.putText(frame, "%d fps" % int(1.0 / max(time.time() - t0, 1e-6)), (2, 20),
@@ -312,7 +320,8 @@ def to_coco(image_filenames, inference_output, class_names):
     Same layout as the reference: categories are (index, name) pairs, image ids are list
     positions, boxes are [x, y, w, h] with w = x2 - x1, h = y2 - y1, annotation ids count up
     from 0 across images; all numbers are plain Python ints / floats so the dict goes
-    straight into ``json.dump``.
+    straight into ``json.dump``.  One annotation per entry of a frame's lists: multi-label results, in which a box appears
+    once per class, give one annotation per label.
     """
     dataset = {
         "info": [],
