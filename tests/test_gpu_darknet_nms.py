@@ -2,7 +2,6 @@
 tests/darknet_nms_restate.py -- EXACT equality of the kept index lists -- and the public entry points with ``nms_kind=...``.
 The inputs are those tests/test_darknet_nms_host.py shows to be robust (no box decided by the last bit of ``pow``) and to tell
 the three kinds apart.  ``nms_kind=None`` must stay today's path bit for bit."""
-import ctypes
 import json
 import os
 import subprocess
@@ -20,6 +19,7 @@ from yolov3.preprocess import correct_letterbox_boxes, letterbox_u8
 from yolov3.synthdata import synth_frames
 
 import darknet_nms_restate as D
+from detect_util import dev as _dev, direct_detect as _direct_detect, out as _out, run_detector as _run, same as _same
 from golden_util import GOLDEN, MODELS, SAMPLE_IMAGES, golden_params, golden_weights_path, load_jpeg_bgr
 
 pytestmark = pytest.mark.gpu
@@ -88,56 +88,6 @@ def test_nms_darknet_beta_matters():
 
 
 # ---- Detector.run(nms_kind=...) ---------------------------------------------------------------------------------------------------
-def _dev():
-    return torch.device("cuda", torch.cuda.current_device())
-
-
-def _out(box, prob, cls):
-    return {"bbox_xywh": torch.from_numpy(box).cuda(), "class_prob": torch.from_numpy(prob).cuda(),
-            "class_idx": torch.from_numpy(cls).cuda()}
-
-
-def _run(box, prob, cls, orig_hw, prob_thresh, thresh, letterbox=None, **kw):
-    batch, rows = prob.shape
-    det = Detector(batch, rows, _dev())
-    det.run(_out(box, prob, cls), np.asarray(orig_hw, np.int32), float(F(prob_thresh)), thresh, letterbox=letterbox, **kw)
-    return det.fetch(return_rows=True)
-
-
-def _direct_detect(box, prob, cls, orig_hw, prob_thresh, thresh):
-    """``y3_detect`` through ctypes with buffers of its own: per frame (tlbr, prob, cls, row)."""
-    lib = _hip.lib()
-    batch, rows = prob.shape
-    dev = _dev()
-    o = _out(box, prob, cls)
-    hw = torch.from_numpy(np.ascontiguousarray(orig_hw, dtype=np.int32)).to(dev)
-    nbytes = lib.y3_detect_workspace_bytes(batch, rows)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    count = torch.zeros(batch, dtype=torch.int32, device=dev)
-    tlbr = torch.empty((batch, rows, 4), dtype=torch.int64, device=dev)
-    dprob = torch.empty((batch, rows), dtype=torch.float32, device=dev)
-    dcls = torch.empty((batch, rows), dtype=torch.int64, device=dev)
-    drow = torch.empty((batch, rows), dtype=torch.int32, device=dev)
-    _hip.check(lib.y3_detect(o["bbox_xywh"].data_ptr(), o["class_prob"].data_ptr(), o["class_idx"].data_ptr(), batch, rows,
-                             hw.data_ptr(), ctypes.c_float(float(F(prob_thresh))), ctypes.c_double(thresh), ws.data_ptr(), nbytes,
-                             count.data_ptr(), tlbr.data_ptr(), dprob.data_ptr(), dcls.data_ptr(), drow.data_ptr(),
-                             _hip.stream_ptr()))
-    torch.cuda.synchronize()
-    n = count.cpu().numpy()
-    return [(tlbr[f, :n[f]].cpu().numpy(), dprob[f, :n[f]].cpu().numpy(), dcls[f, :n[f]].cpu().numpy(),
-             drow[f, :n[f]].cpu().numpy().astype(np.int64))
-            for f in range(batch)]
-
-
-def _same(a, b):
-    assert len(a) == len(b)
-    for fa, fb in zip(a, b):
-        assert len(fa) == len(fb)
-        for x, y in zip(fa, fb):
-            x, y = np.asarray(x), np.asarray(y)
-            assert x.dtype == y.dtype and np.array_equal(x, y)
-
-
 @pytest.mark.parametrize("letterbox", [False, True])
 @pytest.mark.parametrize("kind", D.KINDS)
 def test_detector_darknet_rows_equal_restatement(kind, letterbox):
