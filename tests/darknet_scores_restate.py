@@ -121,7 +121,8 @@ def check_argmax(t, new_coords=False, margin=MARGIN):
 # ---- inputs ---------------------------------------------------------------------------------------------------------------------
 
 def decode_logits(seed, batch, h, w, anchors, classes):
-    """(B, h, w, A, 5 + classes) float32 for the decode tests: ordinary logits, +-20 and +-90 in every attribute somewhere,
+    """(B, h, w, A, 5 + classes) float32 for the decode tests: ordinary logits; +-20 and +-90 in the objectness of some boxes, -20
+    and -90 in the two last class logits of others (tx, ty, tw, th stay within +-2: tests/yolo_decode_cases.py saturates those);
     planted ties (two equal maximal logits; a pair above 20), and an arg-max that no last bit decides (check_argmax)."""
     rng = np.random.default_rng(seed)
     t = rng.uniform(-6.0, 4.0, size=(batch, h, w, anchors, 5 + classes)).astype(F)

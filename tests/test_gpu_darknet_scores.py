@@ -27,13 +27,13 @@ import darknet_nms_restate as D
 import darknet_scores_restate as S
 import footprint_util as fu
 from golden_util import GOLDEN, ROOT
+from yolo_op_util import yolo_op as _yolo_op
 from oracle import darknet_oracle as orc
 
 pytestmark = pytest.mark.gpu
 
 F = np.float32
 SCORE_RTOL, SCORE_ATOL = 5e-4, 2e-5            # tests/test_gpu_yolov4.py's bounds for decoded scores
-ANCHORS = ((10.0, 14.0), (23.0, 27.0), (37.0, 58.0))
 MINI = os.path.join(GOLDEN, "cfg", "mini.cfg")
 
 
@@ -55,31 +55,7 @@ def _run(net, frames, f32_input):
 
 
 # ---- the decode with the flag: one-op plans -----------------------------------------------------------------------------------------
-def _yolo_op(t, dtype, flags):
-    """t (B, h, w, A, n_attr) float32 -> (bbox, prob, cls) of a one-op Y3_OP_YOLO plan; dtype Y3_F32: the sequential form,
-    Y3_BF16: four lanes per box (the logits are float32 either way)"""
-    b, h, w, a, n = t.shape
-    ld = (a * n + 3) // 4 * 4 + 4
-    x = torch.full((b, h, w, ld), float("nan"), dtype=torch.float32)
-    x[..., :a * n] = torch.from_numpy(t.reshape(b, h, w, a * n))
-    x = x.cuda()
-    rows = a * h * w
-    bbox = torch.full((b, rows, 4), float("nan"), dtype=torch.float32, device="cuda")
-    prob = torch.full((b, rows), float("nan"), dtype=torch.float32, device="cuda")
-    cls = torch.full((b, rows), -7, dtype=torch.int64, device="cuda")
-    zero = torch.zeros(4096, dtype=torch.uint8, device="cuda")
-    op = _hip.Y3Op()
-    op.kind, op.dtype, op.flags, op.batch = _hip.OP_YOLO, dtype, flags, b
-    op.in_h, op.in_w, op.in_c, op.in_ld = h, w, a * n, ld
-    op.n_anchor, op.n_attr = a, n
-    for k, (aw, ah) in enumerate(ANCHORS[:a]):
-        op.anchor_w[k], op.anchor_h[k] = aw, ah
-    op.row_offset, op.rows_total = 0, rows
-    op.net_w, op.net_h = 32.0 * w, 32.0 * h
-    op.d_in, op.d_bbox, op.d_prob, op.d_cls = x.data_ptr(), bbox.data_ptr(), prob.data_ptr(), cls.data_ptr()
-    rc = _hip.lib().y3_op_run(ctypes.byref(op), None, zero.data_ptr(), _hip.stream_ptr())
-    torch.cuda.synchronize()
-    return rc, bbox.cpu().numpy(), prob.cpu().numpy(), cls.cpu().numpy()
+# (tests/yolo_op_util.py: shared with tests/test_gpu_yolo_decode.py)
 
 
 _WANT = {}
