@@ -223,6 +223,7 @@ int y3_abi_version(void);
 #define Y3_CAP_NMS_DARKNET 64u /* y3_detect_darknet, y3_nms_darknet and their workspace queries */
 #define Y3_CAP_SCORES_DARKNET 128u /* Y3_F_SCORES_DARKNET on YOLO ops      */
 #define Y3_CAP_MULTI_LABEL 256u /* y3_expand_labels and its workspace query   */
+#define Y3_CAP_PREPROCESS_DARKNET 512u /* y3_preprocess_darknet_f32            */
 uint32_t y3_capabilities(void);
 const char *y3_last_error(void);
 /* number of visible HIP devices whose arch is gfx950 (0 on a CPU-only machine) */
@@ -429,6 +430,34 @@ typedef struct {
  * be reused as soon as the call returns.  Frames of different sizes share one call.                              */
 int y3_letterbox_u8(const y3_letterbox_frame *frames, int batch, uint8_t *d_dst, int net_h, int net_w, int fill,
                     void *stream);
+
+/* Darknet's own preprocessing (load_image -> letterbox_image / resize_image): uint8 BGR frames of any size -> the float32
+ * network input, bit for bit what `darknet detector test` / `map` feed the network.  Not in the reference, which resizes the
+ * 8-bit frame (cv2.resize) and divides by 255 afterwards; y3_letterbox_u8 above differs from Darknet in the resize arithmetic
+ * and in the pad value (a byte), this entry point in neither.  All arithmetic is float32, one rounding per operation (no fused
+ * multiply-add).  Per frame (h, w) and channel, with p(r, c) = (float)byte / 255.0f of the frame's pixel (equal to Darknet's
+ * (float)(byte / 255.) for every byte):
+ *   target (H, W) = {new_h, new_w} of y3_letterbox_geometry when `letterbox`, else (net_h, net_w)   (no dsize quirk here)
+ *   (h, w) == (H, W): out = p.   Otherwise   w_scale = (float)(w - 1) / (float)(W - 1),  h_scale likewise, and
+ *   part(r, c) = p(r, w - 1)                                        if c == W - 1 or w == 1, else
+ *              = (1 - dx) * p(r, ix) + dx * p(r, ix + 1)            sx = (float)c * w_scale, ix = (int)sx, dx = sx - (float)ix
+ *   out(r, c)  = (1 - dy) * part(iy, c)  [+ dy * part(iy + 1, c)  unless r == H - 1 or h == 1]
+ *                                                                   sy = (float)r * h_scale, iy = (int)sy, dy = sy - (float)iy
+ * dy is NOT forced to 0 on the last row: where (H - 1) * h_scale rounds to just below h - 1, that row is (1 - dy) * part(h - 2)
+ * with dy just below 1 -- Darknet's quirk, kept.  An axis with h == 1 (w == 1) takes scale 0 (Darknet's 0 / 0 for 1 -> 1 is
+ * never used for a pixel that matters).  A target of ONE row / column from a longer source divides by zero in Darknet and is
+ * refused here (Y3_ERR_INVALID) -- with `letterbox` that is a frame more than net-size times longer than wide, or the reverse.
+ * d_dst (batch, 3, net_h, net_w) float32, planar R, G, B from the BGR frame; with `letterbox` the canvas is 0.5f and the resized
+ * frame lies at (top, left); 4-byte aligned (16-byte alignment and net_w % 4 == 0 give 16-byte stores).  `frames` is a HOST
+ * array of `batch` descriptors, d_src uint8 (src_h, src_w, 3) on the device: they travel as kernel arguments (64 per launch,
+ * so one launch for any usual batch), and the array may be reused as soon as the call returns.  Frames of different sizes share
+ * one call.  All sizes must be below 2^24.  Darknet.forward (Y3_F_IN_NCHW_F32) takes d_dst as it is.                       */
+typedef struct {
+  const uint8_t *d_src;
+  int32_t src_h, src_w;
+} y3_darknet_frame;
+int y3_preprocess_darknet_f32(const y3_darknet_frame *frames, int batch, float *d_dst, int net_h, int net_w, int letterbox,
+                              void *stream);
 
 /* frames in / detections out without a copy engine: what yolov3/pipeline.py (the loop bench.py times and detect_in_frames
  * runs) uses in place of the `.to(device)` / `.cpu()` transfers around Darknet.forward (inference.py:335, :338-340).  A small

@@ -254,7 +254,7 @@ int y3_abi_version(void) { return Y3_ABI_VERSION; }
 
 uint32_t y3_capabilities(void) {
   return Y3_CAP_MISH | Y3_CAP_SCALE_X_Y | Y3_CAP_LOGISTIC | Y3_CAP_NEW_COORDS | Y3_CAP_LETTERBOX | Y3_CAP_POOL_DARKNET |
-         Y3_CAP_NMS_DARKNET | Y3_CAP_SCORES_DARKNET | Y3_CAP_MULTI_LABEL;
+         Y3_CAP_NMS_DARKNET | Y3_CAP_SCORES_DARKNET | Y3_CAP_MULTI_LABEL | Y3_CAP_PREPROCESS_DARKNET;
 }
 
 const char *y3_last_error(void) { return g_err; }

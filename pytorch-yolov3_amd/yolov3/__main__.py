@@ -31,6 +31,7 @@ _MODEL_OPTIONS = [
     (("--dtype",), dict(default="float32", choices=["float32", "fp16", "bf16"], help="conv arithmetic: float32 (the reference's; default, boxes and scores within 1e-3 of its CPU path), fp16 or bf16 storage with float32 accumulation (about 7x the frames/s; scores within ~1e-3 / ~1e-2)")),
     (("-b", "--batch-size"), dict(type=int, default=16, metavar="<n>", help="frames per GPU batch for folders and videos (default 16)")),
     (("--letterbox",), dict(action="store_true", help="Darknet letterboxing: keep each frame's aspect ratio and fill the rest of the network input with grey (128) instead of stretching the frame; use it with yolov4-csp, which was trained that way")),
+    (("--darknet-resize",), dict(action="store_true", help="prepare every frame the way Darknet itself does: byte / 255 first, then Darknet's float32 resize_image (align-corners geometry) instead of the 8-bit bilinear resize; with --letterbox its letterbox_image, padded with 0.5 instead of the byte 128")),
     (("--darknet-pool",), dict(action="store_true", help="Darknet max-pooling (centred windows, out-of-range taps ignored) instead of the reference's; use it with weights trained by Darknet for yolov3-spp, yolov4 and yolov4-csp (the latter together with --letterbox)")),
     (("--nms-kind",), dict(choices=["iou", "greedynms", "diounms"], default=None, help="suppress by Darknet's rule on the float32 boxes instead of the reference's on integer pixel corners: iou (a cfg without nms_kind), greedynms (yolov4.cfg) or diounms (yolov4-csp.cfg); -i is its threshold (Darknet's own defaults are -p 0.25 -i 0.45)")),
     (("--darknet-scores",), dict(action="store_true", help="score every class of a box by Darknet's independent logistic, sigmoid(obj) * sigmoid(class), instead of the reference's soft-max over the classes; use it with weights trained by Darknet for yolov3, yolov3-tiny, yolov3-spp, yolov4 and yolov4-tiny (yolov4-csp scores that way already)")),
@@ -117,6 +118,7 @@ def main(argv=None):
             class_names = [line.strip() for line in fh.readlines()]
 
     frames = [] if args["output"] else None
+    preprocess = "darknet" if args["darknet_resize"] else None
     names, results, fps = None, None, 25.0
     t0 = time.time()
     if args["image"]:
@@ -125,7 +127,7 @@ def main(argv=None):
         results = list(stream.detect_in_frames(net, images, batch_size=args["batch_size"],
                                                prob_thresh=args["prob_thresh"], nms_iou_thresh=args["iou_thresh"],
                                                letterbox=args["letterbox"], nms_kind=args["nms_kind"],
-                                               beta_nms=args["beta_nms"]))
+                                               beta_nms=args["beta_nms"], preprocess=preprocess))
         if frames is not None:
             for image, (bbox_tlbr, class_prob, class_idx) in zip(images, results):
                 stream.draw_boxes(image, bbox_tlbr, class_idx=class_idx, class_names=class_names)
@@ -135,7 +137,8 @@ def main(argv=None):
         results = stream.detect_in_video(net, args["video"], device=device, prob_thresh=args["prob_thresh"],
                                          nms_iou_thresh=args["iou_thresh"], class_names=class_names,
                                          frames=frames, show_video=False, batch_size=args["batch_size"],
-                                         letterbox=args["letterbox"], nms_kind=args["nms_kind"], beta_nms=args["beta_nms"])
+                                         letterbox=args["letterbox"], nms_kind=args["nms_kind"], beta_nms=args["beta_nms"],
+                                         preprocess=preprocess)
         names = ["frame_%06d" % i for i in range(len(results))]
     else:
         cam = args["cam"]
@@ -144,7 +147,7 @@ def main(argv=None):
         stream.detect_in_cam(net, cam_id=cam, device=device, prob_thresh=args["prob_thresh"],
                              nms_iou_thresh=args["iou_thresh"], class_names=class_names,
                              show_fps=args["show_fps"], frames=frames, letterbox=args["letterbox"],
-                             nms_kind=args["nms_kind"], beta_nms=args["beta_nms"])
+                             nms_kind=args["nms_kind"], beta_nms=args["beta_nms"], preprocess=preprocess)
     elapsed = time.time() - t0
     if results is not None and args["verbose"]:
         kept = sum(len(r[1]) for r in results)

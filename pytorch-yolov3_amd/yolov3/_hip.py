@@ -37,7 +37,7 @@ F_LEAKY, F_RESIDUAL, F_OUT_F32, F_IN_NCHW_F32, F_IN_NHWC_U8BGR, F_PLAN_INPUT, F_
 F_MISH, F_LOGISTIC, F_NEW_COORDS, F_POOL_DARKNET, F_SCORES_DARKNET = 128, 256, 512, 1024, 2048
 # y3_capabilities() bits: what the loaded library computes beyond ABI 6 as first released
 CAP_MISH, CAP_SCALE_X_Y, CAP_LOGISTIC, CAP_NEW_COORDS, CAP_LETTERBOX, CAP_POOL_DARKNET = 1, 2, 4, 8, 16, 32
-CAP_NMS_DARKNET, CAP_SCORES_DARKNET, CAP_MULTI_LABEL = 64, 128, 256
+CAP_NMS_DARKNET, CAP_SCORES_DARKNET, CAP_MULTI_LABEL, CAP_PREPROCESS_DARKNET = 64, 128, 256, 512
 # Darknet's suppression measures (include/yolov3_hip.h: Y3_NMS_*), by the cfg's spelling of `nms_kind`
 NMS_IOU, NMS_GREEDY, NMS_DIOU = 0, 1, 2
 NMS_KINDS = {"iou": NMS_IOU, "greedynms": NMS_GREEDY, "diounms": NMS_DIOU}
@@ -69,6 +69,11 @@ class Y3LetterboxFrame(ctypes.Structure):
     """Mirror of ``y3_letterbox_frame`` (include/yolov3_hip.h): one frame of a ``y3_letterbox_u8`` batch."""
     _fields_ = [("d_src", ctypes.c_void_p), ("src_h", ctypes.c_int32), ("src_w", ctypes.c_int32),
                 ("d_ytab", ctypes.c_void_p), ("d_xtab", ctypes.c_void_p)]
+
+
+class Y3DarknetFrame(ctypes.Structure):
+    """Mirror of ``y3_darknet_frame`` (include/yolov3_hip.h): one frame of a ``y3_preprocess_darknet_f32`` batch."""
+    _fields_ = [("d_src", ctypes.c_void_p), ("src_h", ctypes.c_int32), ("src_w", ctypes.c_int32)]
 
 
 class Y3HeadView(ctypes.Structure):
@@ -167,6 +172,8 @@ PROTOTYPES = {
                                              ctypes.POINTER(ctypes.c_int32)]),
     "y3_letterbox_u8": (ctypes.c_int, [ctypes.POINTER(Y3LetterboxFrame), ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
                                        ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    "y3_preprocess_darknet_f32": (ctypes.c_int, [ctypes.POINTER(Y3DarknetFrame), ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
+                                                 ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
     "y3_copy_bytes": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p]),
     "y3_pack_records": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                        ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
@@ -177,7 +184,7 @@ PROTOTYPES = {
 # symbols a library of ABI 6 built before they were added lacks: asked for through capabilities()
 _OPTIONAL = ("y3_capabilities", "y3_detect_letterbox", "y3_letterbox_geometry", "y3_letterbox_u8",
              "y3_detect_darknet_workspace_bytes", "y3_detect_darknet", "y3_nms_darknet_workspace_bytes", "y3_nms_darknet",
-             "y3_expand_labels_workspace_bytes", "y3_expand_labels")
+             "y3_expand_labels_workspace_bytes", "y3_expand_labels", "y3_preprocess_darknet_f32")
 
 
 class HipLibraryError(RuntimeError):
@@ -223,14 +230,15 @@ def require_capabilities(needs, what):
     linear, ignore scale_x_y, run a logistic head as linear, decode new_coords heads the YOLOv3 way, stretch frames
     that were to be letterboxed, pool the reference's way where Darknet's rule was asked for, suppress by the
     reference's rule where Darknet's was asked for, score boxes by the reference's soft-max where Darknet's logistic scores
-    were asked for, or lack the multi-label expansion."""
+    were asked for, lack the multi-label expansion, or lack Darknet's float preprocessing."""
     missing = needs & ~capabilities()
     if missing:
         names = [n for n, b in (("mish", CAP_MISH), ("scale_x_y", CAP_SCALE_X_Y), ("logistic", CAP_LOGISTIC),
                                 ("new_coords", CAP_NEW_COORDS), ("letterbox", CAP_LETTERBOX),
                                 ("Darknet max-pooling", CAP_POOL_DARKNET), ("Darknet NMS", CAP_NMS_DARKNET),
                                 ("Darknet class scores", CAP_SCORES_DARKNET),
-                                ("multi-label detections", CAP_MULTI_LABEL)) if missing & b]
+                                ("multi-label detections", CAP_MULTI_LABEL),
+                                ("Darknet preprocessing", CAP_PREPROCESS_DARKNET)) if missing & b]
         raise HipLibraryError("{}: the loaded libyolov3_hip.so cannot compute {} (rebuild: make -C pytorch-yolov3_amd/csrc)"
                               .format(what, ", ".join(names)))
 
@@ -244,6 +252,18 @@ def check_scores_mode(scores):
     if scores not in SCORE_MODES:
         raise ValueError("scores {!r}: this package computes {}".format(scores, " and ".join(repr(m) for m in SCORE_MODES)))
     return scores
+
+
+PREPROCESS_MODES = (None, "darknet")
+
+
+def check_preprocess_mode(preprocess):
+    """``preprocess`` of the detection entry points: None (uint8 frames resized with OpenCV's 8-bit bilinear, the default) or
+    "darknet" (Darknet's float ``resize_image`` / ``letterbox_image``: ``y3_preprocess_darknet_f32``); ValueError for
+    anything else.  Needs no GPU."""
+    if preprocess is not None and not (isinstance(preprocess, str) and preprocess == "darknet"):
+        raise ValueError("preprocess {!r}: this package computes None (the default 8-bit resize) and 'darknet'".format(preprocess))
+    return preprocess
 
 
 def nms_mode(nms_kind, beta_nms=0.6):

@@ -21,7 +21,10 @@
 * a network built with ``multi_label=True`` (opt-in, not in the reference) reports every class of a box whose Darknet score
   ``sigmoid(obj) * sigmoid(class_c)`` is ``>`` the threshold, not the arg-max class only: ``y3_expand_labels`` turns the
   head outputs into one candidate per (box, class) and the detection tail runs on those unchanged, so a box may appear once
-  per class and a box's second class takes part in that class's suppression.
+  per class and a box's second class takes part in that class's suppression;
+* ``preprocess="darknet"`` (opt-in, not in the reference) prepares the frames the way Darknet itself does: ``byte / 255`` first,
+  then Darknet's float32 ``resize_image`` (or ``letterbox_image`` on a canvas of 0.5 with ``letterbox=True``) in one launch per
+  batch (``y3_preprocess_darknet_f32``), and the network runs from that float input instead of the fused uint8 stem.
 
 There is no CPU fallback: without the HIP library / a GPU these functions raise.
 """
@@ -31,7 +34,7 @@ import numpy as np
 import torch
 
 from . import _hip
-from .preprocess import letterbox_frames_device, prepare_frames_device
+from .preprocess import darknet_frames_device, letterbox_frames_device, prepare_frames_device
 
 
 def _device(device=None):
@@ -381,7 +384,8 @@ def get_detector(batch, rows, device):
 
 
 def inference(net, images, device="cuda", prob_thresh=0.05, nms_iou_thresh=0.3, resize=True,
-              return_rows=False, letterbox=False, letterbox_fill=128, nms_kind=None, beta_nms=0.6, label_capacity=None):
+              return_rows=False, letterbox=False, letterbox_fill=128, nms_kind=None, beta_nms=0.6, label_capacity=None,
+              preprocess=None):
     """Run detection on one frame or a list of HxWx3 uint8 BGR frames.
 
     Returns, per frame, ``[bbox_tlbr int64 (K,4), class_prob float32 (K,), class_idx int64 (K,)]``
@@ -399,22 +403,37 @@ def inference(net, images, device="cuda", prob_thresh=0.05, nms_iou_thresh=0.3, 
     A network built with ``multi_label=True`` returns Darknet's multi-label detections: every class of a box whose score
     is ``> prob_thresh`` (strictly), so a box may appear once per class.  ``label_capacity``: the most labels a frame may
     have before suppression (default: the number of prediction rows); a frame with more raises a RuntimeError.
+
+    ``preprocess``: None [default] = the uint8 path above; "darknet" = Darknet's own float preprocessing
+    (``preprocess.darknet_frames_device``): ``letterbox=True`` then selects its ``letterbox_image`` (pad 0.5;
+    ``letterbox_fill`` is ignored) with the same box correction, False its ``resize_image`` to the whole network input, boxes
+    scaled as in the default mode.  Frames of different sizes may share the call either way.  It needs ``resize``; any other
+    value is a ValueError, as is a frame so long and thin that its target would be one pixel wide.
     """
     _hip.nms_mode(nms_kind, beta_nms)
+    mode = _hip.check_preprocess_mode(preprocess)
     if letterbox and not resize:
         raise ValueError("letterbox=True resizes every frame: it cannot be combined with resize=False")
+    if mode and not resize:
+        raise ValueError("preprocess='darknet' resizes every frame: it cannot be combined with resize=False")
     if not isinstance(images, (list, tuple)):
         images = [images]
     if str(device).startswith("cuda") and not str(net.device).startswith("cuda"):
         net.cuda(device)
     dev = net._torch_device()
     net_h, net_w = net.net_info["height"], net.net_info["width"]
-    if letterbox:
+    if mode == "darknet":
+        _hip.require_capabilities(_hip.CAP_PREPROCESS_DARKNET | (_hip.CAP_LETTERBOX if letterbox else 0),
+                                  "inference(preprocess='darknet')")
+        x, shapes = darknet_frames_device(list(images), net_h, net_w, dev, letterbox)
+        out = net._run(x, "f32", fresh=False)
+    elif letterbox:
         _hip.require_capabilities(_hip.CAP_LETTERBOX, "inference(letterbox=True)")
         frames, shapes = letterbox_frames_device(list(images), net_h, net_w, dev, letterbox_fill)
+        out = net.forward_frames(frames, fresh=False)
     else:
         frames, shapes = prepare_frames_device(list(images), net_h, net_w, dev, resize)
-    out = net.forward_frames(frames, fresh=False)
+        out = net.forward_frames(frames, fresh=False)
     batch, rows = out["class_prob"].shape
     det = get_detector(batch, rows, dev)
     orig_hw = np.array([[s[0], s[1]] for s in shapes], dtype=np.int32)

@@ -62,12 +62,18 @@ class Pipeline(object):
     group with more than one rank the label counts are LOCAL: only the rank whose own frame overflowed raises, while the others
     go on and may wait in a later collective for a rank that has left.  Size ``label_capacity`` so that it cannot happen (the
     default, one label per prediction row, holds for any threshold Darknet is used with), or run such jobs under a launcher
-    that ends all ranks when one fails.
+    that ends all ranks when one fails.  ``preprocess``: only None; Darknet's float preprocessing (``preprocess="darknet"`` of
+    ``inference()`` / ``detect_in_frames()``) is refused with a ValueError, because the frames enter this class as uint8 batches
+    for the fused stem.
     """
 
     def __init__(self, net, batch, height=None, width=None, in_flight=3, prob_thresh=0.05, nms_iou_thresh=0.3, kmax=512,
-                 world=1, group=None, options=None, copy_blocks=8, nms_kind=None, beta_nms=0.6, label_capacity=None):
+                 world=1, group=None, options=None, copy_blocks=8, nms_kind=None, beta_nms=0.6, label_capacity=None,
+                 preprocess=None):
         _hip.nms_mode(nms_kind, beta_nms)               # ValueError for a kind this package does not compute
+        if _hip.check_preprocess_mode(preprocess) is not None:
+            raise ValueError("Pipeline does not run preprocess={!r}: it takes uint8 batches into the fused stem; use inference() "
+                             "or detect_in_frames(), which prepare the float input and run the network from it".format(preprocess))
         _hip.require_gpu()
         if batch < 1 or in_flight < 1:
             raise ValueError("batch and in_flight must be positive")

@@ -29,10 +29,19 @@ square networks shipped here that is the same thing, and :func:`reference_dsize`
 Letterboxing (opt-in; not in the reference, which stretches): Darknet's ``letterbox_image`` keeps the frame's aspect
 ratio, resizes it to :func:`letterbox_geometry`'s (new_h, new_w) with the resize above and pastes it at (top, left) of a
 net-sized canvas of the byte ``fill`` (:func:`letterbox_u8`; on the GPU :func:`letterbox_frames_device`, one
-``y3_letterbox_u8`` call per batch, bit-identical).  Differences from Darknet: the fill is a byte, 128 by default (Darknet
-fills with 0.5 in float, which a uint8 frame read as v / 255 cannot hold), and the resize is OpenCV's bilinear, not
-Darknet's ``resize_image``.  :func:`correct_letterbox_boxes` maps the network's relative boxes back to the frame
+``y3_letterbox_u8`` call per batch, bit-identical).  Differences from Darknet on this uint8 path: the fill is a byte, 128 by
+default (Darknet fills with 0.5 in float, which a uint8 frame read as v / 255 cannot hold), and the resize is OpenCV's
+bilinear, not Darknet's ``resize_image``.  :func:`correct_letterbox_boxes` maps the network's relative boxes back to the frame
 (``correct_yolo_boxes(..., letter=1)``; on the GPU inside ``y3_detect_letterbox``).
+
+Darknet's own preprocessing (opt-in, ``preprocess="darknet"`` on the detection entry points; not in the reference) has neither
+difference: :func:`darknet_frames_device` turns uint8 BGR frames of any size into the float32 (B, 3, net_h, net_w) RGB input
+that Darknet's ``load_image`` -> ``letterbox_image`` / ``resize_image`` produce, bit for bit, with one
+``y3_preprocess_darknet_f32`` launch per batch: ``byte / 255`` first, then Darknet's float32 bilinear with its align-corners
+geometry ``(src - 1) / (dst - 1)`` (include/yolov3_hip.h states every operation; tests/darknet_resize_restate.py restates it
+in numpy), pasted on a canvas of 0.5f when letterboxing.  The result feeds ``Darknet.forward``'s float input, not the fused
+uint8 stem.  :func:`darknet_target` gives the size a frame is resized to and where it lies; ``reference_dsize`` and
+``letterbox_fill`` play no part in this mode.
 """
 import numpy as np
 
@@ -254,3 +263,48 @@ def correct_letterbox_boxes(bbox_xywh, orig_hw, net_h, net_w):
             box[i, :, c] = ((box[i, :, c].astype(np.float64) - shift) / np.float64(ratio)).astype(np.float32)
             box[i, :, c + 2] = box[i, :, c + 2] * (np.float32(1.0) / ratio)
     return box[0] if single else box
+
+
+# ---------------------------------------------------------------------------------------------- Darknet's float preprocessing
+def darknet_target(h, w, net_h, net_w, letterbox):
+    """(new_h, new_w, top, left): the size Darknet resizes an (h, w) frame to and where the result lies in the network input --
+    :func:`letterbox_geometry` when ``letterbox`` (``letterbox_image``), else the whole (net_h, net_w) input (``resize_image``;
+    rows first: there is no ``reference_dsize`` quirk in this mode).  ValueError for a target of one row / column from a longer
+    source: Darknet's ``resize_image`` divides by ``target - 1`` there."""
+    h, w, net_h, net_w = int(h), int(w), int(net_h), int(net_w)
+    if min(h, w, net_h, net_w) <= 0:
+        raise ValueError("darknet_target: sizes must be positive, got {}".format((h, w, net_h, net_w)))
+    new_h, new_w, top, left = letterbox_geometry(h, w, net_h, net_w) if letterbox else (net_h, net_w, 0, 0)
+    if (new_h == 1 and h > 1) or (new_w == 1 and w > 1):
+        raise ValueError("preprocess='darknet': a {} x {} frame would be resized to {} x {}, and Darknet's resize_image divides "
+                         "by target - 1 (a 1-pixel target needs a 1-pixel source)".format(h, w, new_h, new_w))
+    return new_h, new_w, top, left
+
+
+def darknet_frames_device(images, net_h, net_w, device, letterbox=False):
+    """uint8 (H,W,3) BGR frames -- sizes may differ -- into the float32 (B, 3, net_h, net_w) RGB network input Darknet makes of
+    them, on ``device``, with ONE ``y3_preprocess_darknet_f32`` call on the current stream: ``letterbox=True`` is Darknet's
+    ``letterbox_image`` (aspect ratio kept, canvas 0.5), False its ``resize_image`` to the whole input.  Every frame is uploaded
+    as :func:`prepare_frames_device` does.  Returns (input, shapes); ``Darknet.forward`` takes the input as it is."""
+    import torch
+    from . import _hip
+    _hip.require_capabilities(_hip.CAP_PREPROCESS_DARKNET | (_hip.CAP_LETTERBOX if letterbox else 0), "darknet_frames_device")
+    if not isinstance(images, (list, tuple)):
+        images = [images]
+    shapes = [tuple(im.shape) for im in images]
+    for i, s in enumerate(shapes):
+        if len(s) != 3 or s[2] != 3 or images[i].dtype != (torch.uint8 if isinstance(images[i], torch.Tensor) else np.uint8):
+            raise ValueError("darknet_frames_device: frame {} is not uint8 (H, W, 3): {} {}".format(i, s, images[i].dtype))
+        darknet_target(s[0], s[1], net_h, net_w, letterbox)
+    x = torch.empty((len(images), 3, net_h, net_w), dtype=torch.float32, device=device)
+    descs = (_hip.Y3DarknetFrame * len(images))()
+    keep = []                                            # uploads alive until the launch is queued
+    for i, im in enumerate(images):
+        src = im if isinstance(im, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(im))
+        src = src.to(device).contiguous()
+        descs[i] = _hip.Y3DarknetFrame(src.data_ptr(), int(src.shape[0]), int(src.shape[1]))
+        keep.append(src)
+    with torch.cuda.device(device):
+        _hip.check(_hip.lib().y3_preprocess_darknet_f32(descs, len(images), x.data_ptr(), net_h, net_w, 1 if letterbox else 0,
+                                                        _hip.stream_ptr()))
+    return x, shapes

@@ -66,7 +66,7 @@ def _batches(frames, batch_size):
 
 def detect_in_frames(net, frames, batch_size=16, prob_thresh=0.05, nms_iou_thresh=0.3, resize=True,
                      in_flight=3, kmax=512, letterbox=False, letterbox_fill=128, nms_kind=None, beta_nms=0.6,
-                     label_capacity=None):
+                     label_capacity=None, preprocess=None):
     """Generator over ``[bbox_tlbr, class_prob, class_idx]`` for every frame of the iterable
     ``frames`` (HxWx3 uint8 BGR arrays; sizes may differ when ``resize``), in order.
 
@@ -89,14 +89,38 @@ def detect_in_frames(net, frames, batch_size=16, prob_thresh=0.05, nms_iou_thres
     A network built with ``multi_label=True`` yields Darknet's multi-label detections (a box once per class that scores
     ``> prob_thresh``), at most ``label_capacity`` candidates per frame before suppression (default: the number of prediction
     rows; a frame with more raises a RuntimeError), as in ``inference()``.
+
+    ``preprocess="darknet"``: Darknet's own float preprocessing, as in ``inference()`` (``letterbox=True`` then means its
+    ``letterbox_image``; ``letterbox_fill`` is ignored).  ``Pipeline`` takes uint8 batches into the fused stem, so in this mode
+    every batch -- whatever the frames' sizes -- runs through ``inference()`` instead, one batch at a time on the current
+    stream (``in_flight`` and ``kmax`` play no part); the results equal per-frame ``inference(preprocess="darknet")``.
     """
     from .pipeline import Pipeline
     _hip.nms_mode(nms_kind, beta_nms)
+    mode = _hip.check_preprocess_mode(preprocess)
     _hip.require_gpu()
     if batch_size < 1 or in_flight < 1:
         raise ValueError("batch_size and in_flight must be positive")
     if letterbox and not resize:
         raise ValueError("letterbox=True resizes every frame: it cannot be combined with resize=False")
+    if mode and not resize:
+        raise ValueError("preprocess='darknet' resizes every frame: it cannot be combined with resize=False")
+    if mode:
+        from .inference import inference
+
+        def single():
+            for item in frames:
+                if getattr(item, "ndim", 3) == 4:             # a whole (B, H, W, 3) batch: frame by frame
+                    for frame in item:
+                        yield frame
+                else:
+                    yield item
+
+        for batch in _batches(single(), batch_size):
+            for result in inference(net, batch, prob_thresh=prob_thresh, nms_iou_thresh=nms_iou_thresh, letterbox=letterbox,
+                                    nms_kind=nms_kind, beta_nms=beta_nms, label_capacity=label_capacity, preprocess=mode):
+                yield result
+        return
     if letterbox:
         _hip.require_capabilities(_hip.CAP_LETTERBOX, "detect_in_frames(letterbox=True)")
     if not str(net.device).startswith("cuda"):
@@ -189,14 +213,16 @@ def detect_in_frames(net, frames, batch_size=16, prob_thresh=0.05, nms_iou_thres
 
 
 def detect_in_images(net, path, batch_size=16, prob_thresh=0.05, nms_iou_thresh=0.3, letterbox=False, letterbox_fill=128,
-                     nms_kind=None, beta_nms=0.6, label_capacity=None):
+                     nms_kind=None, beta_nms=0.6, label_capacity=None, preprocess=None):
     """The CLI's ``--image`` mode: ``path`` is a file or a directory.  Returns (file names, results).  ``label_capacity``: as
-    in ``detect_in_frames`` (multi-label networks)."""
+    in ``detect_in_frames`` (multi-label networks); ``preprocess``: as there (None, or "darknet")."""
+    _hip.check_preprocess_mode(preprocess)
     directory, names = list_image_files(path)
     frames = (load_image_bgr(os.path.join(directory, n)) for n in names)
     results = list(detect_in_frames(net, frames, batch_size=batch_size, prob_thresh=prob_thresh,
                                     nms_iou_thresh=nms_iou_thresh, letterbox=letterbox, letterbox_fill=letterbox_fill,
-                                    nms_kind=nms_kind, beta_nms=beta_nms, label_capacity=label_capacity))
+                                    nms_kind=nms_kind, beta_nms=beta_nms, label_capacity=label_capacity,
+                                    preprocess=preprocess))
     return names, results
 
 
@@ -244,10 +270,12 @@ def _video_frames(filepath):
 
 def detect_in_video(net, filepath, device="cuda", prob_thresh=0.05, nms_iou_thresh=0.3, class_names=None,
                     frames=None, show_video=False, batch_size=16, letterbox=False, letterbox_fill=128, nms_kind=None,
-                    beta_nms=0.6, label_capacity=None):
+                    beta_nms=0.6, label_capacity=None, preprocess=None):
     """Run detection over a video (or a directory of frames), draw the boxes on every frame and
     append the frames to ``frames`` when a list is given -- the reference's contract, batched.
-    Returns the list of per-frame results.  ``label_capacity``: as in ``detect_in_frames`` (multi-label networks)."""
+    Returns the list of per-frame results.  ``label_capacity``: as in ``detect_in_frames`` (multi-label networks);
+    ``preprocess``: as there (None, or "darknet")."""
+    _hip.check_preprocess_mode(preprocess)
     if show_video and _cv2() is None:
         raise RuntimeError("show_video needs OpenCV (cv2), which is not installed")
     if str(device).startswith("cuda") and not str(net.device).startswith("cuda"):
@@ -263,7 +291,7 @@ def detect_in_video(net, filepath, device="cuda", prob_thresh=0.05, nms_iou_thre
     for i, (bbox_tlbr, class_prob, class_idx) in enumerate(
             detect_in_frames(net, tap(), batch_size=batch_size, prob_thresh=prob_thresh,
                              nms_iou_thresh=nms_iou_thresh, letterbox=letterbox, letterbox_fill=letterbox_fill,
-                             nms_kind=nms_kind, beta_nms=beta_nms, label_capacity=label_capacity)):
+                             nms_kind=nms_kind, beta_nms=beta_nms, label_capacity=label_capacity, preprocess=preprocess)):
         frame = kept[i]
         kept[i] = None
         draw_boxes(frame, bbox_tlbr, class_idx=class_idx, class_names=class_names)
@@ -280,10 +308,12 @@ def detect_in_video(net, filepath, device="cuda", prob_thresh=0.05, nms_iou_thre
 
 def detect_in_cam(net, cam_id=0, device="cuda", prob_thresh=0.05, nms_iou_thresh=0.3, class_names=None,
                   show_fps=False, frames=None, letterbox=False, letterbox_fill=128, nms_kind=None, beta_nms=0.6,
-                  label_capacity=None):
+                  label_capacity=None, preprocess=None):
     """Live camera loop (latency-bound, one frame per step like the reference).  Needs OpenCV for
-    capture and display.  ``label_capacity``: as in ``inference()`` (multi-label networks)."""
+    capture and display.  ``label_capacity``: as in ``inference()`` (multi-label networks); ``preprocess``: as there (None, or
+    "darknet")."""
     _hip.nms_mode(nms_kind, beta_nms)
+    _hip.check_preprocess_mode(preprocess)
     cv2 = _cv2()
     if cv2 is None:
         raise RuntimeError("camera capture needs OpenCV (cv2), which is not installed")
@@ -299,7 +329,7 @@ def detect_in_cam(net, cam_id=0, device="cuda", prob_thresh=0.05, nms_iou_thresh
             bbox_tlbr, _, class_idx = inference(net, frame, device=device, prob_thresh=prob_thresh,
                                                 nms_iou_thresh=nms_iou_thresh, letterbox=letterbox,
                                                 letterbox_fill=letterbox_fill, nms_kind=nms_kind, beta_nms=beta_nms,
-                                                label_capacity=label_capacity)[0]
+                                                label_capacity=label_capacity, preprocess=preprocess)[0]
             draw_boxes(frame, bbox_tlbr, class_idx=class_idx, class_names=class_names)
             if show_fps:
                 cv2.putText(frame, "%d fps" % int(1.0 / max(time.time() - t0, 1e-6)), (2, 20),
