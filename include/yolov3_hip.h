@@ -57,6 +57,19 @@ extern "C" {
 #define Y3_OP_ADD 4       /* unfused shortcut: darknet.py:376-379                               */
 #define Y3_OP_COPY 5      /* unfused route slice copy: darknet.py:369-375                       */
 #define Y3_OP_YOLO 6      /* YOLOLayer.forward + head concat + wh/net size: darknet.py:48-122, :389-399 */
+#define Y3_OP_REORG 7     /* Darknet's [reorg] (YOLOv2's pass-through layer), factor s = y3_op.stride: (C, H, W) per frame ->
+                             (C*s*s, H/s, W/s).  Needs H % s == 0 and W % s == 0.  Two forms, both stated on the frame's NCHW
+                             arrays (the kernel works on the NHWC tensors with their pixel strides in_ld / out_ld):
+                               default -- Darknet's original layer (later Darknet: "reorg_old"), what the published yolov2
+                               weights were trained with.  Needs C % (s*s) == 0.  With oc = C / (s*s), for k < C, j < H, i < W:
+                                 c2 = k % oc, off = k / oc, w2 = i*s + off % s, h2 = j*s + off / s
+                                 out_flat[i + W*(j + H*k)] = in_flat[w2 + (W*s)*(h2 + (H*s)*c2)]
+                               with both arrays C*H*W floats long and out_flat then read as (C*s*s, H/s, W/s): a fixed
+                               permutation of the frame's elements that is NOT a space-to-depth;
+                               Y3_F_REORG_3D -- the space-to-depth of later Darknet ([reorg3d]): for k < C*s*s, g = k / C:
+                                 out[k][j][i] = in[k % C][j*s + g / s][i*s + g % s].
+                             A move of storage elements: bit-exact in every dtype.  in_c = C, out_c = C*s*s, out_h = H/s,
+                             out_w = W/s.  y3_capabilities() reports Y3_CAP_REORG                                        */
 
 /* y3_op.flags */
 #define Y3_F_LEAKY 1u          /* LeakyReLU(0.1) after scale/bias                        */
@@ -95,6 +108,7 @@ extern "C" {
                                   soft-max's.  With Y3_F_NEW_COORDS the inputs are probabilities already and that decode is Darknet's:
                                   the flag is accepted there and changes nothing, bit for bit.  On any other op kind it is an
                                   error.  y3_capabilities() reports Y3_CAP_SCORES_DARKNET                                    */
+#define Y3_F_REORG_3D 4096u    /* Y3_OP_REORG: the [reorg3d] form (see Y3_OP_REORG); on any other op kind it is an error      */
 
 /*
  * One unit of work.  POD, 8-byte aligned, zero-initialise unused fields.
@@ -224,6 +238,7 @@ int y3_abi_version(void);
 #define Y3_CAP_SCORES_DARKNET 128u /* Y3_F_SCORES_DARKNET on YOLO ops      */
 #define Y3_CAP_MULTI_LABEL 256u /* y3_expand_labels and its workspace query   */
 #define Y3_CAP_PREPROCESS_DARKNET 512u /* y3_preprocess_darknet_f32            */
+#define Y3_CAP_REORG 1024u     /* Y3_OP_REORG and Y3_F_REORG_3D              */
 uint32_t y3_capabilities(void);
 const char *y3_last_error(void);
 /* number of visible HIP devices whose arch is gfx950 (0 on a CPU-only machine) */

@@ -149,6 +149,8 @@ int check_flags(const y3_op &op) {
              "op for block %d: Y3_F_POOL_DARKNET on an op of kind %d (max-pool ops only)", op.block_idx, op.kind);
   Y3_REQUIRE(!(op.flags & Y3_F_SCORES_DARKNET) || op.kind == Y3_OP_YOLO,
              "op for block %d: Y3_F_SCORES_DARKNET on an op of kind %d (YOLO ops only)", op.block_idx, op.kind);
+  Y3_REQUIRE(!(op.flags & Y3_F_REORG_3D) || op.kind == Y3_OP_REORG,
+             "op for block %d: Y3_F_REORG_3D on an op of kind %d (reorg ops only)", op.block_idx, op.kind);
   return Y3_OK;
 }
 
@@ -161,6 +163,7 @@ int choose_op(const y3_op &op, const y3_options &o, y3_step &st) {
   switch (op.kind) {
     case Y3_OP_CONV: return choose_conv(op, o, st);
     case Y3_OP_MAXPOOL: case Y3_OP_UPSAMPLE: case Y3_OP_ADD: case Y3_OP_COPY: return y3_choose_layer(op, st);
+    case Y3_OP_REORG: return y3_choose_reorg(op, st);
     case Y3_OP_YOLO: return y3_choose_yolo(op, o, st);
     default: break;
   }
@@ -254,7 +257,7 @@ int y3_abi_version(void) { return Y3_ABI_VERSION; }
 
 uint32_t y3_capabilities(void) {
   return Y3_CAP_MISH | Y3_CAP_SCALE_X_Y | Y3_CAP_LOGISTIC | Y3_CAP_NEW_COORDS | Y3_CAP_LETTERBOX | Y3_CAP_POOL_DARKNET |
-         Y3_CAP_NMS_DARKNET | Y3_CAP_SCORES_DARKNET | Y3_CAP_MULTI_LABEL | Y3_CAP_PREPROCESS_DARKNET;
+         Y3_CAP_NMS_DARKNET | Y3_CAP_SCORES_DARKNET | Y3_CAP_MULTI_LABEL | Y3_CAP_PREPROCESS_DARKNET | Y3_CAP_REORG;
 }
 
 const char *y3_last_error(void) { return g_err; }

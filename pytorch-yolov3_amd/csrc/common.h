@@ -433,6 +433,7 @@ int y3_choose_conv_direct(const y3_op &op, y3_step &st);
 bool y3_conv_stem_mfma_supported(const y3_op &op);
 int y3_choose_conv_stem_mfma(const y3_op &op, y3_step &st);
 int y3_choose_layer(const y3_op &op, y3_step &st);   // max-pool, upsample, add, copy (layers.hip)
+int y3_choose_reorg(const y3_op &op, y3_step &st);   // Darknet's [reorg], both forms (layers.hip)
 int y3_choose_yolo(const y3_op &op, const y3_options &o, y3_step &st);
 // Fused groups: true (and the step filled) when the kernel takes the group
 bool y3_choose_maxpool_spp(const y3_op &a, const y3_op &b, const y3_op &c, y3_step &st);

@@ -1,4 +1,4 @@
-// Memory-bound NHWC layer kernels: max-pool, nearest upsample, add, channel-slice copy.
+// Memory-bound NHWC layer kernels: max-pool, nearest upsample, add, channel-slice copy, reorg.
 // One thread moves one 16-byte channel chunk of one output pixel when strides allow it
 // (VEC = 16 / sizeof(T)), else one element (VEC = 1).  All of them take pixel strides
 // (in_ld / out_ld) so producers write straight into route-concat buffers
@@ -253,6 +253,94 @@ int y3_choose_layer(const y3_op &op, y3_step &st) {
       st.name = Y3_KNAME(op.dtype, "copy_", "");
       return Y3_OK;
   }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Darknet's [reorg] (Y3_OP_REORG; include/yolov3_hip.h), YOLOv2's pass-through layer: (C, H, W) per frame ->
+// (C*s*s, H/s, W/s), a pure move of storage elements (U = an unsigned integer of the element's size, so every dtype is
+// bit-exact).  Both forms are defined on the frame's NCHW arrays; the tensors here are NHWC with pixel strides, so one thread
+// takes one OUTPUT element (adjacent threads: adjacent output channels, i.e. coalesced stores into the route's channel
+// slice), works out the NCHW coordinates of its source and gathers it:
+//   flat form  : the output element (ko, oy, ox) is number f = ox + Wo*(oy + Ho*ko) of the frame's flat array; Darknet
+//                writes out_flat[f] = in_flat[src] with f read as (k, j, i) of the INPUT shape, c2 = k % oc, off = k / oc,
+//                src = (i*s + off % s) + (W*s)*((j*s + off / s) + (H*s)*c2), and src is read as (ci, yi, xi) of the input shape;
+//   3d form    : g = ko / C, source (ko % C, oy*s + g / s, ox*s + g % s).
+// y3_choose_reorg has checked the divisibility the formulas rely on, so src < C*H*W (flat) and yi < H, xi < W (3d).
+// The yolov2 layer is 64 x 26 x 26 per frame, about 1 % of the network's traffic: no LDS staging, no tuning.
+namespace {
+
+struct ReorgArgs {
+  const void *in;
+  void *out;
+  int C, H, W, in_ld, Co, Ho, Wo, out_ld, s, oc, form3d;
+  long long total;  // B*Ho*Wo*Co
+};
+
+template <typename U>
+__global__ __launch_bounds__(256) void reorg_kernel(ReorgArgs p) {
+  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= p.total) return;
+  int b, oy, ox, ko;
+  decode_idx(idx, p.Co, p.Wo, p.Ho, b, oy, ox, ko);
+  int ci, yi, xi;
+  if (p.form3d) {
+    const int g = ko / p.C;
+    ci = ko - g * p.C;
+    yi = oy * p.s + g / p.s;
+    xi = ox * p.s + g % p.s;
+  } else {
+    const int f = ox + p.Wo * (oy + p.Ho * ko);
+    const int i = f % p.W, jk = f / p.W, j = jk % p.H, k = jk / p.H;
+    const int c2 = k % p.oc, off = k / p.oc;
+    const int src = (i * p.s + off % p.s) + (p.W * p.s) * ((j * p.s + off / p.s) + (p.H * p.s) * c2);
+    xi = src % p.W;
+    const int yc = src / p.W;
+    yi = yc % p.H;
+    ci = yc / p.H;
+  }
+  static_cast<U *>(p.out)[(((long long)b * p.Ho + oy) * p.Wo + ox) * p.out_ld + ko] =
+      static_cast<const U *>(p.in)[(((long long)b * p.H + yi) * p.W + xi) * p.in_ld + ci];
+}
+
+int launch_reorg(const y3_op *ops, const y3_step &, const void *d_in, const void *, hipStream_t s) {
+  const y3_op &op = ops[0];
+  ReorgArgs a;
+  a.in = d_in;
+  a.out = op.d_out;
+  a.C = op.in_c; a.H = op.in_h; a.W = op.in_w; a.in_ld = op.in_ld;
+  a.Co = op.out_c; a.Ho = op.out_h; a.Wo = op.out_w; a.out_ld = op.out_ld;
+  a.s = op.stride;
+  a.oc = op.in_c / (op.stride * op.stride);
+  a.form3d = (op.flags & Y3_F_REORG_3D) ? 1 : 0;
+  a.total = (long long)op.batch * op.out_h * op.out_w * op.out_c;
+  const dim3 grid((unsigned)((a.total + 255) / 256)), block(256);
+  if (y3_elem_size(op.dtype) == 4) Y3_LAUNCH(reorg_kernel<uint32_t>, grid, block, 0, s, a);
+  else Y3_LAUNCH(reorg_kernel<uint16_t>, grid, block, 0, s, a);
+  Y3_HIP_CHECK(hipGetLastError());
+  return Y3_OK;
+}
+
+}  // namespace
+
+int y3_choose_reorg(const y3_op &op, y3_step &st) {
+  const int s = op.stride;
+  Y3_REQUIRE(!(op.flags & (Y3_F_PLAN_INPUT | Y3_F_IN_NCHW_F32 | Y3_F_IN_NHWC_U8BGR | Y3_F_OUT_F32)),
+             "reorg block %d: reads and writes NHWC tensors of the plan's element type only", op.block_idx);
+  Y3_REQUIRE(s >= 1 && s <= 64, "reorg block %d: stride %d (1..64)", op.block_idx, s);
+  Y3_REQUIRE(op.in_h % s == 0 && op.in_w % s == 0, "reorg block %d: stride %d does not divide the %d x %d map", op.block_idx, s,
+             op.in_h, op.in_w);
+  Y3_REQUIRE((op.flags & Y3_F_REORG_3D) || op.in_c % (s * s) == 0,
+             "reorg block %d: %d channels are not a multiple of stride^2 = %d (the flat form needs it)", op.block_idx, op.in_c, s * s);
+  Y3_REQUIRE(op.out_h == op.in_h / s && op.out_w == op.in_w / s && (long long)op.out_c == (long long)op.in_c * s * s,
+             "reorg block %d: output shape mismatch (C*s*s, H/s, W/s)", op.block_idx);
+  Y3_REQUIRE(op.in_ld >= op.in_c && op.out_ld >= op.out_c, "reorg block %d: pixel stride below the channel count (in %d < %d or out %d < %d)",
+             op.block_idx, op.in_ld, op.in_c, op.out_ld, op.out_c);
+  // (the kernel keeps a frame's flat NCHW indices in int)
+  Y3_REQUIRE((long long)op.in_c * op.in_h * op.in_w < (1ll << 31), "reorg block %d: a frame of %d x %d x %d elements is too large",
+             op.block_idx, op.in_c, op.in_h, op.in_w);
+  st.launch = launch_reorg;
+  st.name = (op.flags & Y3_F_REORG_3D) ? Y3_KNAME(op.dtype, "reorg3d_", "") : Y3_KNAME(op.dtype, "reorg_", "");
+  return Y3_OK;
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -32,12 +32,12 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("Y3_HIP_LIB") or os.path.join(_HERE, "..", "lib", "libyolov3_hip.so")
 
 Y3_F32, Y3_BF16, Y3_F16, Y3_F64 = 0, 1, 2, 3
-OP_CONV, OP_MAXPOOL, OP_UPSAMPLE, OP_ADD, OP_COPY, OP_YOLO = 1, 2, 3, 4, 5, 6
+OP_CONV, OP_MAXPOOL, OP_UPSAMPLE, OP_ADD, OP_COPY, OP_YOLO, OP_REORG = 1, 2, 3, 4, 5, 6, 7
 F_LEAKY, F_RESIDUAL, F_OUT_F32, F_IN_NCHW_F32, F_IN_NHWC_U8BGR, F_PLAN_INPUT, F_FUSE_NEXT = 1, 2, 4, 8, 16, 32, 64
-F_MISH, F_LOGISTIC, F_NEW_COORDS, F_POOL_DARKNET, F_SCORES_DARKNET = 128, 256, 512, 1024, 2048
+F_MISH, F_LOGISTIC, F_NEW_COORDS, F_POOL_DARKNET, F_SCORES_DARKNET, F_REORG_3D = 128, 256, 512, 1024, 2048, 4096
 # y3_capabilities() bits: what the loaded library computes beyond ABI 6 as first released
 CAP_MISH, CAP_SCALE_X_Y, CAP_LOGISTIC, CAP_NEW_COORDS, CAP_LETTERBOX, CAP_POOL_DARKNET = 1, 2, 4, 8, 16, 32
-CAP_NMS_DARKNET, CAP_SCORES_DARKNET, CAP_MULTI_LABEL, CAP_PREPROCESS_DARKNET = 64, 128, 256, 512
+CAP_NMS_DARKNET, CAP_SCORES_DARKNET, CAP_MULTI_LABEL, CAP_PREPROCESS_DARKNET, CAP_REORG = 64, 128, 256, 512, 1024
 # Darknet's suppression measures (include/yolov3_hip.h: Y3_NMS_*), by the cfg's spelling of `nms_kind`
 NMS_IOU, NMS_GREEDY, NMS_DIOU = 0, 1, 2
 NMS_KINDS = {"iou": NMS_IOU, "greedynms": NMS_GREEDY, "diounms": NMS_DIOU}
@@ -230,7 +230,7 @@ def require_capabilities(needs, what):
     linear, ignore scale_x_y, run a logistic head as linear, decode new_coords heads the YOLOv3 way, stretch frames
     that were to be letterboxed, pool the reference's way where Darknet's rule was asked for, suppress by the
     reference's rule where Darknet's was asked for, score boxes by the reference's soft-max where Darknet's logistic scores
-    were asked for, lack the multi-label expansion, or lack Darknet's float preprocessing."""
+    were asked for, lack the multi-label expansion, lack Darknet's float preprocessing, or reject a [reorg] op as of unknown kind."""
     missing = needs & ~capabilities()
     if missing:
         names = [n for n, b in (("mish", CAP_MISH), ("scale_x_y", CAP_SCALE_X_Y), ("logistic", CAP_LOGISTIC),
@@ -238,7 +238,7 @@ def require_capabilities(needs, what):
                                 ("Darknet max-pooling", CAP_POOL_DARKNET), ("Darknet NMS", CAP_NMS_DARKNET),
                                 ("Darknet class scores", CAP_SCORES_DARKNET),
                                 ("multi-label detections", CAP_MULTI_LABEL),
-                                ("Darknet preprocessing", CAP_PREPROCESS_DARKNET)) if missing & b]
+                                ("Darknet preprocessing", CAP_PREPROCESS_DARKNET), ("reorg", CAP_REORG)) if missing & b]
         raise HipLibraryError("{}: the loaded libyolov3_hip.so cannot compute {} (rebuild: make -C pytorch-yolov3_amd/csrc)"
                               .format(what, ", ".join(names)))
 

@@ -82,9 +82,11 @@ def fill_maxpool_op(op, od):
 def yolo_decode_flags(od, scores):
     """(y3_op.flags bits, library capabilities) of a plan's yolo op dict under the class scoring ``scores``.  A new_coords
     head scores the Darknet way already, so it is the same op in both modes; any other head carries Y3_F_SCORES_DARKNET
-    under "darknet"."""
+    under "darknet".  A [region] head (YOLOv2, softmax=1) is the default decode in both modes as well."""
     if od.get("new_coords"):
         return _hip.F_NEW_COORDS, _hip.CAP_NEW_COORDS
+    if od.get("region"):
+        return 0, 0          # a [region] head with softmax=1: Darknet's rule for it IS the soft-max, in both modes
     if scores == "darknet":
         return _hip.F_SCORES_DARKNET, _hip.CAP_SCORES_DARKNET
     return 0, 0
@@ -134,14 +136,16 @@ class Darknet(object):
                 reference's ``softmax(class logits).max() * sigmoid(obj)``.  "darknet": Darknet's independent logistic per class,
                 ``sigmoid(obj) * sigmoid(class_c)``, what yolov3 / yolov3-tiny / yolov3-spp / yolov4 / yolov4-tiny weights were
                 trained with (Y3_F_SCORES_DARKNET on every YOLO op; the heads stay fused).  ``new_coords`` heads (yolov4-csp)
-                score the Darknet way already: the mode changes nothing there.  Fixed for the life of the object; no cfg key
+                score the Darknet way already: the mode changes nothing there, nor on a [region] head (YOLOv2, softmax=1), whose
+                Darknet rule is the soft-max.  Fixed for the life of the object; no cfg key
                 switches it on.
             multi_label (bool): Darknet reports every class of a box whose score passes the threshold, the reference the
                 arg-max class only.  True keeps the head convs' float32 outputs (``label_heads``) so that ``inference()``,
                 ``detect_in_frames()`` ... and ``Pipeline`` expand them into one candidate per (box, class) before the
                 detection tail (``y3_expand_labels``).  It needs ``scores="darknet"`` or a network all of whose heads are
                 ``new_coords``: under the reference's soft-max the classes of a box are one distribution, not independent
-                labels.  ``forward()`` returns the single-label dict in every mode.
+                labels; a cfg with a [region] head (YOLOv2) is refused for the same reason.  ``forward()`` returns the
+                single-label dict in every mode.
         """
         self._pool = check_pool_mode(pool)
         self._scores = _hip.check_scores_mode(scores)
@@ -149,6 +153,11 @@ class Darknet(object):
         self.blocks, self.net_info = parse_config(config_fpath)
         if self.net_info is None:
             raise ValueError("cfg {!r} has no [net] section".format(config_fpath))
+        if self._multi_label:
+            for i, blk in enumerate(self.blocks):
+                if blk["type"] == "region":
+                    raise ValueError("region block {}: multi_label=True is not supported on a [region] head: its soft-max scores "
+                                     "the classes of a box as ONE distribution, so they are not independent labels".format(i))
         if self._multi_label and self._scores != "darknet":
             heads = [b for b in self.blocks if b["type"] == "yolo"]
             if not heads or not all(int(b.get("new_coords", 0)) != 0 for b in heads):
@@ -478,6 +487,12 @@ class Darknet(object):
             elif kind == "copy":
                 op.kind = _hip.OP_COPY
                 op.ksize = op.stride = 1
+            elif kind == "reorg":
+                op.kind = _hip.OP_REORG
+                op.ksize, op.stride = 1, od["stride"]
+                if od.get("form3d"):
+                    op.flags |= _hip.F_REORG_3D
+                needs |= _hip.CAP_REORG
             elif kind == "yolo":
                 op.kind = _hip.OP_YOLO
                 op.n_anchor = len(od["anchors"])

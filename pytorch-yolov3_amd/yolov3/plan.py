@@ -17,6 +17,7 @@ shortcut (``+``) as a new tensor.  Here the graph is resolved once, on the host:
 
 Pure Python, no GPU needed: unit-tested on CPU.
 """
+import ctypes
 
 ALIGN = 256          # bytes, arena slot alignment
 CH_ALIGN = 8         # channel-slice / pixel-stride granularity (elements): 16 B for bf16
@@ -76,6 +77,50 @@ def route_groups(blk):
     return int(blk.get("groups", 1)), int(blk.get("group_id", 0))
 
 
+REORG_KINDS = ("reorg", "reorg3d")
+HEAD_KINDS = ("yolo", "region")
+MAX_ANCHORS = 8      # y3_op.anchor_w[8]
+
+
+def _f32(v):
+    """the float32 nearest to ``v`` (one rounding), as a Python float"""
+    return ctypes.c_float(v).value
+
+
+def region_anchors(blk, net_info, grid_h, grid_w):
+    """The pixel anchors of a [region] block's decode on a grid_h x grid_w map.  Region anchors are in grid cells; the decode op
+    takes pixels of the cfg's net size and divides by it again, so ``a * net_w / grid_w`` (float64, rounded once to float32)
+    makes its ``exp(tw) * anchor / net_w`` Darknet's ``exp(tw) * a / grid_w``."""
+    num = int(blk.get("num", 1))
+    return [(_f32(float(aw) * net_info["width"] / grid_w), _f32(float(ah) * net_info["height"] / grid_h))
+            for aw, ah in blk["anchors"][:num]]
+
+
+def check_region(blocks, i):
+    """Refuse, naming block and key, a [region] head the decode kernels would not score as Darknet does."""
+    blk = blocks[i]
+    for key in ("softmax_tree", "tree"):
+        if key in blk:
+            raise ValueError("region block {}: {} (a class hierarchy, YOLO9000) is not supported".format(i, key))
+    if int(blk.get("softmax", 0)) != 1:
+        raise ValueError("region block {}: softmax={} is not supported (softmax=1 only: sigmoid(obj) * softmax(classes))".format(
+            i, blk.get("softmax", 0)))
+    if int(blk.get("coords", 4)) != 4:
+        raise ValueError("region block {}: coords={} is not supported (4 only)".format(i, blk["coords"]))
+    num, classes = int(blk.get("num", 1)), int(blk.get("classes", 20))
+    if not 1 <= num <= MAX_ANCHORS:
+        raise ValueError("region block {}: num={} anchors per cell (1..{} only)".format(i, num, MAX_ANCHORS))
+    if classes < 1:
+        raise ValueError("region block {}: classes={}".format(i, classes))
+    anchors = blk.get("anchors")
+    if not isinstance(anchors, list) or len(anchors) < num or any(not isinstance(a, list) or len(a) != 2 for a in anchors[:num]):
+        raise ValueError("region block {}: anchors does not hold num={} (w, h) pairs".format(i, num))
+    head = blocks[i - 1] if i > 0 else {}
+    if head.get("type") != "convolutional" or head.get("filters") != num * (5 + classes):
+        raise ValueError("region block {}: the conv before it must have filters = num * (5 + classes) = {} (block {} is {} "
+                         "filters={})".format(i, num * (5 + classes), i - 1, head.get("type"), head.get("filters")))
+
+
 def check_blocks(blocks):
     """Refuse, naming the block, what the kernels cannot compute: any of it would otherwise run with different semantics
     and return wrong boxes without an error."""
@@ -116,6 +161,18 @@ def check_blocks(blocks):
                 if head.get("type") != "convolutional" or head.get("activation") != "logistic":
                     raise ValueError("yolo block {}: new_coords=1 is supported only behind a conv with activation=logistic "
                                      "(block {} is {} {!r})".format(i, i - 1, head.get("type"), head.get("activation")))
+        elif kind in REORG_KINDS:
+            # [reorg] is Darknet's original (flat) layer, [reorg3d] the space-to-depth of later Darknet; the kernels compute
+            # the forward direction of either only
+            if int(blk.get("reverse", 0)) != 0:
+                raise ValueError("{} block {}: reverse={} is not supported".format(kind, i, blk["reverse"]))
+            for key in ("flatten", "extra"):
+                if int(blk.get(key, 0)) != 0:
+                    raise ValueError("{} block {}: {}={} is not supported".format(kind, i, key, blk[key]))
+            if int(blk.get("stride", 1)) < 1:
+                raise ValueError("{} block {}: stride={}".format(kind, i, blk["stride"]))
+        elif kind == "region":
+            check_region(blocks, i)
         elif kind == "shortcut":
             if "weights_type" in blk:
                 raise ValueError("shortcut block {}: weighted shortcuts (weights_type) are not supported".format(i))
@@ -157,7 +214,14 @@ def infer_shapes(blocks, net_info, height, width, pool="reference"):
             if a != b:
                 raise ValueError("shortcut block {} adds {} and {}".format(i, a, b))
             c, h, w = a
-        elif kind == "yolo":
+        elif kind in REORG_KINDS:
+            s = int(blk.get("stride", 1))
+            if h % s or w % s:
+                raise ValueError("{} block {}: stride={} does not divide the {}x{} map".format(kind, i, s, h, w))
+            if kind == "reorg" and c % (s * s):
+                raise ValueError("reorg block {}: {} channels are not a multiple of stride*stride = {}".format(i, c, s * s))
+            c, h, w = c * s * s, h // s, w // s
+        elif kind in HEAD_KINDS:
             pass
         else:
             raise ValueError("unsupported block type {!r} (block {})".format(kind, i))
@@ -190,7 +254,7 @@ def build_plan(blocks, net_info, batch, height, width, elem_size, reuse=True, fu
     readers = [[] for _ in range(n)]      # (consumer block, role)
     for i, blk in enumerate(blocks):
         kind = kinds[i]
-        if kind in ("convolutional", "maxpool", "upsample", "yolo"):
+        if kind in ("convolutional", "maxpool", "upsample") + REORG_KINDS + HEAD_KINDS:
             if i > 0:
                 readers[i - 1].append((i, "in"))
         elif kind == "route":
@@ -221,7 +285,7 @@ def build_plan(blocks, net_info, batch, height, width, elem_size, reuse=True, fu
     copies = {}             # route block -> list of (src block, Tensor dst) needing a copy op
     head_of = {}            # conv block feeding a yolo block
     for i in range(n):
-        if kinds[i] == "yolo" and kinds[i - 1] == "convolutional":
+        if kinds[i] in HEAD_KINDS and kinds[i - 1] == "convolutional":
             head_of[i - 1] = i
 
     for i, blk in enumerate(blocks):
@@ -239,7 +303,7 @@ def build_plan(blocks, net_info, batch, height, width, elem_size, reuse=True, fu
                 cj = shapes[j][0]
                 dst = Tensor(buf, off, ld, cj, h, w)
                 ok = (src not in placed and off % CH_ALIGN == 0 and src < i
-                      and kinds[src] in ("convolutional", "maxpool", "upsample", "shortcut")
+                      and kinds[src] in ("convolutional", "maxpool", "upsample", "shortcut") + REORG_KINDS
                       and src not in head_of and kinds[src] != "route")
                 if ok:
                     placed[src] = dst
@@ -260,7 +324,10 @@ def build_plan(blocks, net_info, batch, height, width, elem_size, reuse=True, fu
         m = blk["mask"]
         return m if isinstance(m, list) else [m]      # "mask=0" parses to a bare int
 
-    rows_total = sum(len(mask_of(blocks[i])) * shapes[i][1] * shapes[i][2] for i in range(n) if kinds[i] == "yolo")
+    def n_anchors(blk):
+        return int(blk.get("num", 1)) if blk["type"] == "region" else len(mask_of(blk))
+
+    rows_total = sum(n_anchors(blocks[i]) * shapes[i][1] * shapes[i][2] for i in range(n) if kinds[i] in HEAD_KINDS)
     row_offset = 0
     conv_slot = 0
     in_tensor = Tensor("input", 0, net_info["channels"], net_info["channels"], height, width)
@@ -309,6 +376,13 @@ def build_plan(blocks, net_info, batch, height, width, elem_size, reuse=True, fu
                 op["pad"] = maxpool_geometry(i, blk, op["inp"].h, op["inp"].w, pool)[2]
             ops.append(op)
             tensor_of[i] = out
+        elif kind in REORG_KINDS:
+            out = placed[i] if i in placed else own_tensor(i)
+            op = dict(kind="reorg", block=i, inp=prev_tensor(i), out=out, stride=int(blk.get("stride", 1)))
+            if kind == "reorg3d":
+                op["form3d"] = True                # the space-to-depth form (default: Darknet's original flat form)
+            ops.append(op)
+            tensor_of[i] = out
         elif kind == "shortcut":
             if i in fused_into:
                 pass                               # produced by the conv's epilogue
@@ -336,15 +410,22 @@ def build_plan(blocks, net_info, batch, height, width, elem_size, reuse=True, fu
             else:
                 for j, dst in copies[i]:
                     ops.append(dict(kind="copy", block=i, inp=tensor_of[j], out=dst))
-        elif kind == "yolo":
+        elif kind in HEAD_KINDS:
             src = tensor_of[i - 1]
             c, h, w = shapes[i]
-            na = len(mask_of(blk))
+            na = n_anchors(blk)
             if c % na != 0 or c // na <= 5:
-                raise ValueError("yolo block {}: {} channels do not split into {} anchors".format(i, c, na))
-            anchors = [blk["anchors"][m] for m in mask_of(blk)]
+                raise ValueError("{} block {}: {} channels do not split into {} anchors".format(kind, i, c, na))
+            if kind == "region":
+                # the default decode over all `num` anchors (no mask): centres, objectness and the soft-max score are what
+                # a [region] head with softmax=1 computes; its anchors, in grid cells, become pixels of the cfg's net size
+                anchors = region_anchors(blk, net_info, h, w)
+            else:
+                anchors = [blk["anchors"][m] for m in mask_of(blk)]
             op = dict(kind="yolo", block=i, inp=src, anchors=anchors, n_attr=c // na,
                       row_offset=row_offset, rows_total=rows_total)
+            if kind == "region":
+                op["region"] = True
             if float(blk.get("scale_x_y", 1)) != 1.0:
                 op["scale_x_y"] = float(blk["scale_x_y"])     # Darknet's centre stretch (default 1: the YOLOv3 decode)
             if int(blk.get("new_coords", 0)) != 0:

@@ -1,7 +1,8 @@
 """Darknet ``.weights`` stream I/O and procedural (hash-generated) weights.
 
 Stream layout consumed by the reference loader
-(/root/reference/yolov3/darknet.py:415-476): 5 x int32 header, then float32
+(/root/reference/yolov3/darknet.py:415-476): 5 x int32 header (4 x int32 in
+files of Darknet's version 0.1, whose ``seen`` counter is 32 bits), then float32
 values; per ``[convolutional]`` block in cfg order either
 ``beta, gamma, running_mean, running_var`` (each Cout values, when the block
 has a truthy ``batch_normalize``) or ``conv bias`` (Cout), followed by the conv
@@ -51,7 +52,9 @@ def conv_layout(blocks, net_info):
                 raise AssertionError(
                     "shortcut {} joins {} and {} channels".format(
                         i, cur, out_ch[i + blk["from"]]))
-        # maxpool / upsample / yolo keep the channel count
+        elif kind in ("reorg", "reorg3d"):
+            cur = cur * int(blk.get("stride", 1)) ** 2
+        # maxpool / upsample / yolo / region keep the channel count
         out_ch.append(cur)
         prev = cur
     return out_ch, convs
@@ -68,7 +71,7 @@ def stream_length(blocks, net_info):
 
 
 def read_darknet_weights(path, blocks, net_info):
-    """Read a ``.weights`` file -> (header int32[5], list of per-conv dicts).
+    """Read a ``.weights`` file -> (header int32[5], or int32[4] for a version 0.1 file, list of per-conv dicts).
 
     Each dict has ``weight`` (Cout,Cin,k,k) and either ``bn_beta, bn_gamma,
     bn_mean, bn_var`` or ``bias``.  A short file raises ``RuntimeError`` (the
@@ -76,7 +79,12 @@ def read_darknet_weights(path, blocks, net_info):
     reference does.
     """
     with open(path, "rb") as fh:
-        header = np.fromfile(fh, dtype=np.int32, count=5)
+        header = np.fromfile(fh, dtype=np.int32, count=3)
+        # major, minor, revision, then `seen`: 32 bits up to version 0.1 (the published yolov2 files), 64 bits from 0.2 on
+        if header.size == 3 and int(header[0]) * 10 + int(header[1]) < 2:
+            header = np.concatenate([header, np.fromfile(fh, dtype=np.int32, count=1)])
+        else:
+            header = np.concatenate([header, np.fromfile(fh, dtype=np.int32, count=2)])
         stream = np.fromfile(fh, dtype=np.float32)
     _, convs = conv_layout(blocks, net_info)
     pos = 0
@@ -216,15 +224,18 @@ def synth_params(blocks, net_info, seed=0, obj_bias=-3.0, calib=None,
             a = math.sqrt(3.0) / math.sqrt(fan_in)
             wgt = _uniform(seed, base + 0, co * fan_in, -a, a).reshape(co, fan_in)
             bias = _uniform(seed, base + 5, co, -0.5, 0.5)
-            # yolo head channel = anchor * (5 + classes) + attr; 3 anchors/head
-            if co % 3 == 0 and co // 3 > 5:
-                n_attr = co // 3
+            # yolo head channel = anchor * (5 + classes) + attr; 3 anchors/head, `num` of them in front of a [region] block
+            na = 3
+            if bi + 1 < len(blocks) and blocks[bi + 1]["type"] == "region":
+                na = int(blocks[bi + 1].get("num", 1))
+            if co % na == 0 and co // na > 5:
+                n_attr = co // na
                 gain = np.full(n_attr, _HEAD_GAIN_CLS, dtype=np.float32)
                 gain[0:2] = _HEAD_GAIN_XY
                 gain[2:4] = _HEAD_GAIN_WH
                 gain[4] = _HEAD_GAIN_OBJ
-                wgt = wgt * np.tile(gain, 3)[:, None]
-                for anc in range(3):
+                wgt = wgt * np.tile(gain, na)[:, None]
+                for anc in range(na):
                     o = anc * n_attr
                     bias[o + 2] -= 0.5
                     bias[o + 3] -= 0.5
