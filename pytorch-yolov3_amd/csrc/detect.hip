@@ -17,7 +17,12 @@
 //
 // Wavefront primitives: __ballot + popcount prefix sums for the ordered compactions; the NMS
 // inner loop keeps one box per lane (64 boxes per wavefront chunk), broadcasts the current
-// survivor with ds_bpermute shuffles and clears victims with a ballot mask.
+// survivor (v_readlane, ds_bpermute shuffles for int64 corners) and clears victims with a ballot mask.
+//
+// Each piece exists once: bitonic_network (the sort of detect_kernel, in LDS or global memory, and of
+// nms_float_kernel), the chunk routine of phase 4 with a Rule<DK> per suppression rule (the reference's,
+// or Darknet's iou / greedynms / diounms on float32 boxes), cxywh_to_tlbr_kernel<T>, and on the host
+// map_workspace (workspace -> DetectArgs) and launch (DK -> kernel instance) under every entry point.
 // Built with -ffp-contract=off.
 #include "common.h"
 #include "letterbox.h"
@@ -166,6 +171,108 @@ __device__ __forceinline__ bool dk_suppresses(float ax, float ay, float aw, floa
   return iou - q > thr;
 }
 
+// What phase 4 of detect_kernel needs to know about a suppression rule: the box a lane holds for one candidate, how it is
+// loaded from the candidate's position, and the pair test.  All three are called by whole wavefronts, never under a
+// lane-dependent condition: they ballot and read other lanes (a shuffle returns 0 from a lane that is switched off).
+// DK != kDkOff: Darknet's rule, one float32 centre/size box per lane, the survivor's four floats broadcast by v_readlane.
+template <int DK>
+struct Rule {
+  const float *fbox;
+  float thr, beta;
+  struct Box { f32x4 v; };
+  __device__ Rule(const DetectArgs &p, const long long *, const float *fbox_) : fbox(fbox_), thr(p.dk_thresh), beta(p.dk_beta) {}
+  __device__ __forceinline__ Box load(bool valid, const unsigned int *s_pos, int idx) const {
+    Box b = {{0.f, 0.f, 0.f, 0.f}};
+    if (valid) b.v = *reinterpret_cast<const f32x4 *>(fbox + (long long)s_pos[idx] * 4);
+    return b;
+  }
+  __device__ __forceinline__ bool narrow(const Box &, const Box &) const { return true; }
+  // does survivor lane k (wave-uniform) of chunk `a` suppress my box?
+  __device__ __forceinline__ bool suppresses(const Box &a, int k, const Box &me, bool) const {
+    return dk_suppresses<DK>(readlane_f(a.v[0], k), readlane_f(a.v[1], k), readlane_f(a.v[2], k), readlane_f(a.v[3], k),
+                             me.v[0], me.v[1], me.v[2], me.v[3], thr, beta);
+  }
+};
+
+// kDkOff: the reference's rule on int64 corners.  A lane also keeps their int32 copies and both areas, and a chunk the
+// wave-uniform "every box of it lies within +-16000" bit: two chunks that both fit are compared by the 32-bit fast test.
+template <>
+struct Rule<kDkOff> {
+  const long long *c_box;
+  double thr, thr_m;
+  struct Box {
+    long long x1, y1, x2, y2, area;
+    int ix1, iy1, ix2, iy2, iarea;
+    bool fits;
+  };
+  __device__ Rule(const DetectArgs &p, const long long *c_box_, const float *)
+      : c_box(c_box_), thr(p.iou_thresh), thr_m(fabs(p.iou_thresh) * 2.3e-16) {}
+  __device__ __forceinline__ Box load(bool valid, const unsigned int *s_pos, int idx) const {
+    Box b;
+    b.x1 = b.y1 = b.x2 = b.y2 = 0;
+    if (valid) {
+      const long long *bp = c_box + (long long)s_pos[idx] * 4;
+      b.x1 = bp[0]; b.y1 = bp[1]; b.x2 = bp[2]; b.y2 = bp[3];
+    }
+    b.area = (b.x2 - b.x1 + 1) * (b.y2 - b.y1 + 1);
+    b.fits = __ballot(box_fits_i32(b.x1, b.y1, b.x2, b.y2)) == ~0ull;
+    b.ix1 = (int)b.x1; b.iy1 = (int)b.y1; b.ix2 = (int)b.x2; b.iy2 = (int)b.y2;
+    b.iarea = (b.ix2 - b.ix1 + 1) * (b.iy2 - b.iy1 + 1);
+    return b;
+  }
+  __device__ __forceinline__ bool narrow(const Box &a, const Box &me) const { return a.fits && me.fits; }
+  __device__ __forceinline__ bool suppresses(const Box &a, int k, const Box &me, bool narrow) const {
+    if (narrow)
+      return iou_exceeds_i32(__builtin_amdgcn_readlane(a.ix1, k), __builtin_amdgcn_readlane(a.iy1, k),
+                             __builtin_amdgcn_readlane(a.ix2, k), __builtin_amdgcn_readlane(a.iy2, k),
+                             __builtin_amdgcn_readlane(a.iarea, k), me.ix1, me.iy1, me.ix2, me.iy2, me.iarea, thr, thr_m);
+    // int64 intersections and areas, IoU by float64 true division (inference.py:211-215)
+    const long long ax1 = shfl_ll(a.x1, k), ay1 = shfl_ll(a.y1, k);
+    const long long ax2 = shfl_ll(a.x2, k), ay2 = shfl_ll(a.y2, k);
+    const long long aarea = (ax2 - ax1 + 1) * (ay2 - ay1 + 1);
+    long long iw = (ax2 < me.x2 ? ax2 : me.x2) - (ax1 > me.x1 ? ax1 : me.x1) + 1;
+    long long ih = (ay2 < me.y2 ? ay2 : me.y2) - (ay1 > me.y1 ? ay1 : me.y1) + 1;
+    iw = iw > 0 ? iw : 0;
+    ih = ih > 0 ? ih : 0;
+    const long long inter = iw * ih;
+    const double iou = (double)inter / (double)(aarea + me.area - inter);
+    return iou > thr;
+  }
+};
+
+// Bitonic network over P (a power of two) slots, run by all kThreads threads: cas(i, l, up) puts slots i < l in ascending
+// order when `up`, in descending order otherwise.  Ends with every slot final and visible to the workgroup.
+template <typename CAS>
+__device__ __forceinline__ void bitonic_network(int P, CAS cas) {
+  for (int k = 2; k <= P; k <<= 1)
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      for (int i = threadIdx.x; i < P; i += kThreads) {
+        const int l = i ^ j;
+        if (l > i) cas(i, l, (i & k) == 0);
+      }
+      __syncthreads();
+    }
+}
+
+// fills key / pos (LDS or global) with the n candidates, padded to P, and sorts them by elem_less
+template <typename MK>
+__device__ __forceinline__ void sort_candidates(unsigned long long *key, unsigned int *pos, int n, int P, MK make_key) {
+  for (int i = threadIdx.x; i < P; i += kThreads) {
+    key[i] = i < n ? make_key(i) : ~0ull;
+    pos[i] = i < n ? (unsigned int)i : 0u;
+  }
+  __syncthreads();
+  bitonic_network(P, [&](int i, int l, bool up) {
+    const unsigned long long ka = key[i], kb = key[l];
+    const unsigned int pa = pos[i], pb = pos[l];
+    const bool sw = up ? elem_less(kb, pb, ka, pa) : elem_less(ka, pa, kb, pb);
+    if (sw) {
+      key[i] = kb; key[l] = ka;
+      pos[i] = pb; pos[l] = pa;
+    }
+  });
+}
+
 // block-wide ordered compaction step: returns this thread's output slot (valid when flag) and
 // adds the step's total to `running`.  Must be called by all threads.
 __device__ __forceinline__ int ordered_slot(bool flag, int &running, int *wave_tot) {
@@ -187,8 +294,9 @@ __device__ __forceinline__ int ordered_slot(bool flag, int &running, int *wave_t
   return slot;
 }
 
-// DK: kDkOff = the reference's rule on the integer corners (everything above); otherwise phase 1 also keeps every candidate's
-// float32 (x, y, w, h) and phase 4 decides survivors by Darknet's rule on them (do_chunk_dk).  Nothing else changes.
+// DK: kDkOff = the reference's rule on the integer corners; otherwise phase 1 also keeps every candidate's float32
+// (x, y, w, h) and phase 4 decides survivors by Darknet's rule on them.  Phase 4 is one chunk routine; Rule<DK> is all it
+// knows about either rule.  Nothing else changes.
 template <bool NMS_MODE, int DK = kDkOff>
 __global__ __launch_bounds__(kThreads) void detect_kernel(DetectArgs p) {
   __shared__ unsigned long long skey[kLdsSort];
@@ -313,55 +421,13 @@ __global__ __launch_bounds__(kThreads) void detect_kernel(DetectArgs p) {
     return ((unsigned long long)cu << 32) | score_desc_bits(c_prob[i]);
   };
   if (lds_sort) {
-    for (int i = tid; i < P; i += kThreads) {
-      skey[i] = i < n ? make_key(i) : ~0ull;
-      spos[i] = i < n ? (unsigned int)i : 0u;
-    }
-    __syncthreads();
-    for (int k = 2; k <= P; k <<= 1)
-      for (int j = k >> 1; j > 0; j >>= 1) {
-        for (int i = tid; i < P; i += kThreads) {
-          const int ixj = i ^ j;
-          if (ixj > i) {
-            const unsigned long long ka = skey[i], kb = skey[ixj];
-            const unsigned int pa = spos[i], pb = spos[ixj];
-            const bool up = (i & k) == 0;
-            const bool sw = up ? elem_less(kb, pb, ka, pa) : elem_less(ka, pa, kb, pb);
-            if (sw) {
-              skey[i] = kb; skey[ixj] = ka;
-              spos[i] = pb; spos[ixj] = pa;
-            }
-          }
-        }
-        __syncthreads();
-      }
+    sort_candidates(skey, spos, n, P, make_key);
     for (int i = tid; i < n; i += kThreads) {
       s_key[i] = skey[i];
       s_pos[i] = spos[i];
     }
   } else {
-    for (int i = tid; i < P; i += kThreads) {
-      s_key[i] = i < n ? make_key(i) : ~0ull;
-      s_pos[i] = i < n ? (unsigned int)i : 0u;
-    }
-    __syncthreads();
-    for (int k = 2; k <= P; k <<= 1)
-      for (int j = k >> 1; j > 0; j >>= 1) {
-        for (int i = tid; i < P; i += kThreads) {
-          const int ixj = i ^ j;
-          if (ixj > i) {
-            const unsigned long long ka = s_key[i], kb = s_key[ixj];
-            const unsigned int pa = s_pos[i], pb = s_pos[ixj];
-            const bool up = (i & k) == 0;
-            const bool sw = up ? elem_less(kb, pb, ka, pa) : elem_less(ka, pa, kb, pb);
-            if (sw) {
-              s_key[i] = kb; s_key[ixj] = ka;
-              s_pos[i] = pb; s_pos[ixj] = pa;
-            }
-          }
-        }
-        __syncthreads();
-      }
+    sort_candidates(s_key, s_pos, n, P, make_key);
   }
   if (tid == 0) { nitem_sh = 0; nflag_sh = 0; }
   for (int i = tid; i < kMaxFlags; i += kThreads) flags_sh[i] = 0;
@@ -403,105 +469,15 @@ __global__ __launch_bounds__(kThreads) void detect_kernel(DetectArgs p) {
   const int nitem = nitem_sh;
 
   // ---- phase 4: greedy NMS --------------------------------------------------------------------------
-  const double thr_m = fabs(p.iou_thresh) * 2.3e-16;
-  // one 64-candidate chunk of a class: suppress by the survivors of the earlier chunks, then greedy inside
-  auto do_chunk = [&](int start, int end, int j, int fb) {
-      const int c0 = start + 64 * j;
-      const int idx = c0 + lane;
+  const Rule<DK> rule(p, c_box, NMS_MODE ? p.in_xywh : p.c_fbox + (long long)b * R * 4);
+  // one 64-candidate chunk of a class, one box per lane: suppress by the survivors of the earlier chunks, then greedy inside.
+  // Which pair test runs (32-bit or int64 / float64 under the reference's rule) is wave-uniform and fixed per pair of chunks.
+  auto run_chunk = [&](int start, int end, int j, int fb) {
+      const int idx = start + 64 * j + lane;
       const bool valid = idx < end;
-      long long x1 = 0, y1 = 0, x2 = 0, y2 = 0;
-      if (valid) {
-        const long long *bp = c_box + (long long)s_pos[idx] * 4;
-        x1 = bp[0]; y1 = bp[1]; x2 = bp[2]; y2 = bp[3];
-      }
-      const long long area = (x2 - x1 + 1) * (y2 - y1 + 1);
-      // 32-bit fast path when every box of this chunk (and of the earlier chunk it is compared with) is small
-      const bool fits_all = __ballot(box_fits_i32(x1, y1, x2, y2)) == ~0ull;
-      const int ix1 = (int)x1, iy1 = (int)y1, ix2 = (int)x2, iy2 = (int)y2;
-      const int iarea = (ix2 - ix1 + 1) * (iy2 - iy1 + 1);
+      const auto me = rule.load(valid, s_pos, idx);
       bool dead = !valid;
       // survivors of earlier chunks of this class
-      for (int jj = 0; jj < j; ++jj) {
-        if (fb >= 0) {
-          while (__hip_atomic_load(&flags_sh[fb + jj], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) == 0)
-            __builtin_amdgcn_s_sleep(1);
-        }
-        const int p0 = start + 64 * jj;
-        unsigned long long kept = __ballot(keep[p0 + lane] != 0);
-        if (kept == 0ull) continue;
-        const long long *qp = c_box + (long long)s_pos[p0 + lane] * 4;
-        const long long qx1 = qp[0], qy1 = qp[1], qx2 = qp[2], qy2 = qp[3];
-        if (fits_all && __ballot(box_fits_i32(qx1, qy1, qx2, qy2)) == ~0ull) {
-          const int pqx1 = (int)qx1, pqy1 = (int)qy1, pqx2 = (int)qx2, pqy2 = (int)qy2;
-          const int pqarea = (pqx2 - pqx1 + 1) * (pqy2 - pqy1 + 1);
-          while (kept) {
-            const int k = __ffsll((long long)kept) - 1;
-            kept &= kept - 1ull;
-            dead = dead || iou_exceeds_i32(__builtin_amdgcn_readlane(pqx1, k), __builtin_amdgcn_readlane(pqy1, k),
-                                           __builtin_amdgcn_readlane(pqx2, k), __builtin_amdgcn_readlane(pqy2, k),
-                                           __builtin_amdgcn_readlane(pqarea, k), ix1, iy1, ix2, iy2, iarea,
-                                           p.iou_thresh, thr_m);
-          }
-          continue;
-        }
-        while (kept) {
-          const int k = __ffsll((long long)kept) - 1;
-          kept &= kept - 1ull;
-          const long long ax1 = shfl_ll(qx1, k), ay1 = shfl_ll(qy1, k);
-          const long long ax2 = shfl_ll(qx2, k), ay2 = shfl_ll(qy2, k);
-          const long long aarea = (ax2 - ax1 + 1) * (ay2 - ay1 + 1);
-          long long iw = (ax2 < x2 ? ax2 : x2) - (ax1 > x1 ? ax1 : x1) + 1;
-          long long ih = (ay2 < y2 ? ay2 : y2) - (ay1 > y1 ? ay1 : y1) + 1;
-          iw = iw > 0 ? iw : 0;
-          ih = ih > 0 ? ih : 0;
-          const long long inter = iw * ih;
-          const double iou = (double)inter / (double)(aarea + area - inter);
-          dead = dead || (iou > p.iou_thresh);
-        }
-      }
-      // greedy inside the chunk, in score order (lane order)
-      unsigned long long alive = __ballot(!dead);
-      if (fits_all) {
-        for (int k = 0; k < 64; ++k) {
-          if (!((alive >> k) & 1ull)) continue;  // wave-uniform
-          const bool hit = iou_exceeds_i32(__builtin_amdgcn_readlane(ix1, k), __builtin_amdgcn_readlane(iy1, k),
-                                           __builtin_amdgcn_readlane(ix2, k), __builtin_amdgcn_readlane(iy2, k),
-                                           __builtin_amdgcn_readlane(iarea, k), ix1, iy1, ix2, iy2, iarea,
-                                           p.iou_thresh, thr_m);
-          alive &= ~__ballot(lane > k && hit);
-        }
-      } else {
-        for (int k = 0; k < 64; ++k) {
-          if (!((alive >> k) & 1ull)) continue;  // wave-uniform
-          const long long ax1 = shfl_ll(x1, k), ay1 = shfl_ll(y1, k);
-          const long long ax2 = shfl_ll(x2, k), ay2 = shfl_ll(y2, k);
-          const long long aarea = (ax2 - ax1 + 1) * (ay2 - ay1 + 1);
-          long long iw = (ax2 < x2 ? ax2 : x2) - (ax1 > x1 ? ax1 : x1) + 1;
-          long long ih = (ay2 < y2 ? ay2 : y2) - (ay1 > y1 ? ay1 : y1) + 1;
-          iw = iw > 0 ? iw : 0;
-          ih = ih > 0 ? ih : 0;
-          const long long inter = iw * ih;
-          const double iou = (double)inter / (double)(aarea + area - inter);
-          const bool hit = lane > k && (iou > p.iou_thresh);
-          alive &= ~__ballot(hit);
-        }
-      }
-      if (valid) keep[idx] = (alive >> lane) & 1ull ? 1 : 0;
-      // publish: the flags of this chunk's survivors first, then (release) the chunk's "final" flag -- every lane
-      // stores the same word (no lane-dependent branch inside a loop that uses cross-lane reads)
-      if (fb >= 0) __hip_atomic_store(&flags_sh[fb + j], 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-      else __threadfence_block();  // later chunks of this wavefront read these flags
-  };
-  // the same chunk under Darknet's rule: one float32 centre/size box per lane, the survivor's four floats broadcast by
-  // v_readlane, victims cleared by ballot; chain, flags and publication exactly as above
-  const float *fbox = NMS_MODE ? p.in_xywh : p.c_fbox + (long long)b * R * 4;
-  auto do_chunk_dk = [&](int start, int end, int j, int fb) {
-      const int c0 = start + 64 * j;
-      const int idx = c0 + lane;
-      const bool valid = idx < end;
-      f32x4 me = {0.f, 0.f, 0.f, 0.f};
-      if (valid) me = *reinterpret_cast<const f32x4 *>(fbox + (long long)s_pos[idx] * 4);
-      bool dead = !valid;
       for (int jj = 0; jj < j; ++jj) {
         if (fb >= 0) {
           while (__hip_atomic_load(&flags_sh[fb + jj], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) == 0)
@@ -510,29 +486,28 @@ __global__ __launch_bounds__(kThreads) void detect_kernel(DetectArgs p) {
         const int p0 = start + 64 * jj;                 // an earlier chunk is full: p0 + lane < end
         unsigned long long kept = __ballot(keep[p0 + lane] != 0);
         if (kept == 0ull) continue;
-        const f32x4 q = *reinterpret_cast<const f32x4 *>(fbox + (long long)s_pos[p0 + lane] * 4);
+        const auto q = rule.load(true, s_pos, p0 + lane);
+        const bool narrow = rule.narrow(q, me);
         while (kept) {
           const int k = __ffsll((long long)kept) - 1;
           kept &= kept - 1ull;
-          const bool hit = dk_suppresses<DK>(readlane_f(q[0], k), readlane_f(q[1], k), readlane_f(q[2], k), readlane_f(q[3], k),
-                                             me[0], me[1], me[2], me[3], p.dk_thresh, p.dk_beta);
+          const bool hit = rule.suppresses(q, k, me, narrow);   // by every lane, dead ones too: the test reads other lanes
           dead = dead || hit;
         }
       }
+      // greedy inside the chunk, in score order (lane order); victims cleared by ballot
       unsigned long long alive = __ballot(!dead);
+      const bool narrow = rule.narrow(me, me);
       for (int k = 0; k < 64; ++k) {
         if (!((alive >> k) & 1ull)) continue;  // wave-uniform
-        const bool hit = dk_suppresses<DK>(readlane_f(me[0], k), readlane_f(me[1], k), readlane_f(me[2], k), readlane_f(me[3], k),
-                                           me[0], me[1], me[2], me[3], p.dk_thresh, p.dk_beta);
+        const bool hit = rule.suppresses(me, k, me, narrow);
         alive &= ~__ballot(lane > k && hit);
       }
       if (valid) keep[idx] = (alive >> lane) & 1ull ? 1 : 0;
+      // publish: the flags of this chunk's survivors first, then (release) the chunk's "final" flag -- every lane
+      // stores the same word (no lane-dependent branch inside a loop that uses cross-lane reads)
       if (fb >= 0) __hip_atomic_store(&flags_sh[fb + j], 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-      else __threadfence_block();
-  };
-  auto run_chunk = [&](int start, int end, int j, int fb) {
-    if constexpr (DK == kDkOff) do_chunk(start, end, j, fb);
-    else do_chunk_dk(start, end, j, fb);
+      else __threadfence_block();  // later chunks of this wavefront read these flags
   };
   const int wave_u = __builtin_amdgcn_readfirstlane(wave);
   for (int it = wave_u; it < nitem; it += kWaves) {
@@ -572,12 +547,21 @@ __global__ __launch_bounds__(kThreads) void detect_kernel(DetectArgs p) {
   if (tid == 0) p.det_count[b] = kept_n;
 }
 
-__global__ void cxywh_to_tlbr_kernel(const long long *in, long long *out, int n, int cols) {
+// cxywh_to_tlbr on int64, float32 or float64 rows: half a size is numpy's `wh // 2` in the array's dtype, floor(w / 2) -- an
+// arithmetic shift on integers; on floats the division by two is exact
+template <typename T>
+__device__ __forceinline__ T half_floor(T v) {
+  if constexpr (std::is_integral<T>::value) return v >> 1;
+  else return floor(v / (T)2);
+}
+
+template <typename T>
+__global__ void cxywh_to_tlbr_kernel(const T *in, T *out, int n, int cols) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
-  const long long *r = in + (long long)i * cols;
-  long long *o = out + (long long)i * cols;
-  const long long cx = r[0], cy = r[1], hw = r[2] >> 1, hh = r[3] >> 1;  // floor(w/2), floor(h/2)
+  const T *r = in + (long long)i * cols;
+  T *o = out + (long long)i * cols;
+  const T cx = r[0], cy = r[1], hw = half_floor(r[2]), hh = half_floor(r[3]);
   o[0] = cx - hw; o[1] = cy - hh; o[2] = cx + hw; o[3] = cy + hh;
   for (int c = 4; c < cols; ++c) o[c] = r[c];
 }
@@ -617,18 +601,10 @@ __global__ __launch_bounds__(kThreads) void nms_float_kernel(const F *box, const
     if (a < 0 || b < 0) return b < 0 && a >= 0;
     return nmsf_before(cls ? (int)cls[a] : 0, prob[a], a, cls ? (int)cls[b] : 0, prob[b], b);
   };
-  for (int k = 2; k <= np2; k <<= 1)
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int i = tid; i < np2; i += kThreads) {
-        const int l = i ^ j;
-        if (l > i) {
-          const int a = order[i], b = order[l];
-          const bool up = (i & k) == 0;
-          if (up ? before(b, a) : before(a, b)) { order[i] = b; order[l] = a; }
-        }
-      }
-      __syncthreads();
-    }
+  bitonic_network(np2, [&](int i, int l, bool up) {
+    const int a = order[i], b = order[l];
+    if (up ? before(b, a) : before(a, b)) { order[i] = b; order[l] = a; }
+  });
   // class segments, found by every wave on its own while it walks (all lanes read the same address: one request per wave);
   // wave w owns segments w, w + 16, ...
   int seg_index = -1;
@@ -676,18 +652,6 @@ __global__ __launch_bounds__(kThreads) void nms_float_kernel(const F *box, const
     if (flag) keep[slot] = order[i];
   }
   if (tid == 0) *keep_count = running;
-}
-
-template <typename F>
-__global__ void cxywh_to_tlbr_float_kernel(const F *in, F *out, int n, int cols) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const F *r = in + (long long)i * cols;
-  F *o = out + (long long)i * cols;
-  // numpy: wh // 2 on floats = floor(wh / 2) (division by two is exact)
-  const F cx = r[0], cy = r[1], hw = floor(r[2] / (F)2), hh = floor(r[3] / (F)2);
-  o[0] = cx - hw; o[1] = cy - hh; o[2] = cx + hw; o[3] = cy + hh;
-  for (int c = 4; c < cols; ++c) o[c] = r[c];
 }
 
 // record = 8 x int32: x1 y1 x2 y2 | score bits | class | row | 1
@@ -761,21 +725,18 @@ extern "C" size_t y3_nms_workspace_bytes(int n) {
 }
 
 namespace {
-int detect_launch(const float *d_bbox, const float *d_prob, const int64_t *d_cls, int batch, int rows, const int32_t *d_orig_hw,
-                  float prob_thresh, double iou_thresh, void *d_workspace, size_t workspace_bytes, int32_t *d_det_count,
-                  int64_t *d_det_tlbr, float *d_det_prob, int64_t *d_det_cls, int32_t *d_det_row, int lb_net_h, int lb_net_w,
-                  void *stream) {
-  Y3_REQUIRE(batch > 0 && rows > 0, "y3_detect: batch and rows must be positive");
-  Y3_REQUIRE(d_bbox && d_prob && d_cls && d_orig_hw && d_workspace && d_det_count && d_det_tlbr && d_det_prob &&
-                 d_det_cls && d_det_row, "y3_detect: null pointer argument");
+// Darknet rule, forward mode: the reference layout plus the candidates' float32 boxes
+size_t dk_fbox_offset(int batch, int rows) { return ws_layout(batch, rows).total; }
+size_t dk_ws_total(int batch, int rows) { return dk_fbox_offset(batch, rows) + align_up((size_t)batch * (size_t)rows * 4 * sizeof(float)); }
+
+// The one place that maps a workspace into DetectArgs: checks its size for `who` (the public function that was called) and
+// sets rows, rows_p2 and every workspace pointer.  fbox: the workspace also holds the float32 boxes (y3_detect_darknet).
+int map_workspace(const char *who, void *d_workspace, size_t workspace_bytes, int batch, int rows, bool fbox, DetectArgs &a) {
   const WsLayout w = ws_layout(batch, rows);
-  Y3_REQUIRE(workspace_bytes >= w.total, "y3_detect: workspace too small (%zu < %zu)", workspace_bytes, w.total);
+  const size_t need = fbox ? dk_ws_total(batch, rows) : w.total;
+  Y3_REQUIRE(workspace_bytes >= need, "%s: workspace too small (%zu < %zu)", who, workspace_bytes, need);
   char *ws = static_cast<char *>(d_workspace);
-  DetectArgs a = {};
-  a.bbox = d_bbox; a.prob = d_prob; a.cls = reinterpret_cast<const long long *>(d_cls); a.orig_hw = d_orig_hw;
-  a.lb_net_h = lb_net_h; a.lb_net_w = lb_net_w;
   a.rows = rows; a.rows_p2 = next_pow2(rows);
-  a.prob_thresh = prob_thresh; a.iou_thresh = iou_thresh;
   a.c_box = reinterpret_cast<long long *>(ws + w.box);
   a.c_prob = reinterpret_cast<float *>(ws + w.prob);
   a.c_cls = reinterpret_cast<int *>(ws + w.cls);
@@ -784,15 +745,30 @@ int detect_launch(const float *d_bbox, const float *d_prob, const int64_t *d_cls
   a.s_pos = reinterpret_cast<unsigned int *>(ws + w.pos);
   a.keep = reinterpret_cast<unsigned char *>(ws + w.keep);
   a.seg = reinterpret_cast<int *>(ws + w.seg);
-  a.det_count = d_det_count; a.det_tlbr = reinterpret_cast<long long *>(d_det_tlbr); a.det_prob = d_det_prob;
-  a.det_cls = reinterpret_cast<long long *>(d_det_cls); a.det_row = d_det_row;
-  Y3_LAUNCH(detect_kernel<false>, dim3(batch), dim3(kThreads), 0, static_cast<hipStream_t>(stream), a);
-  Y3_HIP_CHECK(hipGetLastError());
+  if (fbox) a.c_fbox = reinterpret_cast<float *>(ws + dk_fbox_offset(batch, rows));
   return Y3_OK;
 }
-// Darknet rule: the reference layout plus the candidates' float32 boxes
-size_t dk_fbox_offset(int batch, int rows) { return ws_layout(batch, rows).total; }
-size_t dk_ws_total(int batch, int rows) { return dk_fbox_offset(batch, rows) + align_up((size_t)batch * (size_t)rows * 4 * sizeof(float)); }
+
+// the arguments that y3_detect, y3_detect_letterbox and y3_detect_darknet share: checked, then put into `a`
+int forward_args(const char *who, const float *d_bbox, const float *d_prob, const int64_t *d_cls, int batch, int rows,
+                 const int32_t *d_orig_hw, float prob_thresh, double iou_thresh, const void *d_workspace, int32_t *d_det_count,
+                 int64_t *d_det_tlbr, float *d_det_prob, int64_t *d_det_cls, int32_t *d_det_row, DetectArgs &a) {
+  Y3_REQUIRE(batch > 0 && rows > 0, "%s: batch and rows must be positive", who);
+  Y3_REQUIRE(d_bbox && d_prob && d_cls && d_orig_hw && d_workspace && d_det_count && d_det_tlbr && d_det_prob &&
+                 d_det_cls && d_det_row, "%s: null pointer argument", who);
+  a.bbox = d_bbox; a.prob = d_prob; a.cls = reinterpret_cast<const long long *>(d_cls); a.orig_hw = d_orig_hw;
+  a.prob_thresh = prob_thresh; a.iou_thresh = iou_thresh;
+  a.det_count = d_det_count; a.det_tlbr = reinterpret_cast<long long *>(d_det_tlbr); a.det_prob = d_det_prob;
+  a.det_cls = reinterpret_cast<long long *>(d_det_cls); a.det_row = d_det_row;
+  return Y3_OK;
+}
+
+// caller-boxes mode (y3_nms, y3_nms_darknet): scores, classes and outputs
+void nms_args(const float *d_prob, const int64_t *d_cls, int n, int64_t *d_keep, int32_t *d_keep_count, DetectArgs &a) {
+  a.in_prob = d_prob; a.in_cls = reinterpret_cast<const long long *>(d_cls); a.n_in = n;
+  a.det_count = d_keep_count;
+  a.keep_idx = reinterpret_cast<long long *>(d_keep);
+}
 
 int dk_check(const char *who, int nms_kind, float beta_nms) {
   Y3_REQUIRE(nms_kind == Y3_NMS_IOU || nms_kind == Y3_NMS_GREEDY || nms_kind == Y3_NMS_DIOU,
@@ -801,11 +777,16 @@ int dk_check(const char *who, int nms_kind, float beta_nms) {
   return Y3_OK;
 }
 
+// dk: kDkOff, or a checked nms_kind + 1
 template <bool NMS_MODE>
-int dk_launch(const DetectArgs &a, int grid, int nms_kind, hipStream_t s) {
-  if (nms_kind == Y3_NMS_IOU) Y3_LAUNCH((detect_kernel<NMS_MODE, kDkIou>), dim3(grid), dim3(kThreads), 0, s, a);
-  else if (nms_kind == Y3_NMS_GREEDY) Y3_LAUNCH((detect_kernel<NMS_MODE, kDkGreedy>), dim3(grid), dim3(kThreads), 0, s, a);
-  else Y3_LAUNCH((detect_kernel<NMS_MODE, kDkDiou>), dim3(grid), dim3(kThreads), 0, s, a);
+int launch(const DetectArgs &a, int grid, int dk, void *stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  switch (dk) {
+    case kDkOff: Y3_LAUNCH((detect_kernel<NMS_MODE, kDkOff>), dim3(grid), dim3(kThreads), 0, s, a); break;
+    case kDkIou: Y3_LAUNCH((detect_kernel<NMS_MODE, kDkIou>), dim3(grid), dim3(kThreads), 0, s, a); break;
+    case kDkGreedy: Y3_LAUNCH((detect_kernel<NMS_MODE, kDkGreedy>), dim3(grid), dim3(kThreads), 0, s, a); break;
+    default: Y3_LAUNCH((detect_kernel<NMS_MODE, kDkDiou>), dim3(grid), dim3(kThreads), 0, s, a); break;
+  }
   Y3_HIP_CHECK(hipGetLastError());
   return Y3_OK;
 }
@@ -821,39 +802,63 @@ extern "C" size_t y3_nms_darknet_workspace_bytes(int n) {
   return ws_layout(1, n).total;
 }
 
+extern "C" int y3_detect(const float *d_bbox, const float *d_prob, const int64_t *d_cls, int batch, int rows,
+                         const int32_t *d_orig_hw, float prob_thresh, double iou_thresh, void *d_workspace,
+                         size_t workspace_bytes, int32_t *d_det_count, int64_t *d_det_tlbr, float *d_det_prob,
+                         int64_t *d_det_cls, int32_t *d_det_row, void *stream) {
+  DetectArgs a = {};
+  if (int rc = forward_args("y3_detect", d_bbox, d_prob, d_cls, batch, rows, d_orig_hw, prob_thresh, iou_thresh, d_workspace,
+                            d_det_count, d_det_tlbr, d_det_prob, d_det_cls, d_det_row, a)) return rc;
+  if (int rc = map_workspace("y3_detect", d_workspace, workspace_bytes, batch, rows, false, a)) return rc;
+  return launch<false>(a, batch, kDkOff, stream);
+}
+
+extern "C" int y3_detect_letterbox(const float *d_bbox, const float *d_prob, const int64_t *d_cls, int batch, int rows,
+                                   const int32_t *d_orig_hw, float prob_thresh, double iou_thresh, void *d_workspace,
+                                   size_t workspace_bytes, int32_t *d_det_count, int64_t *d_det_tlbr, float *d_det_prob,
+                                   int64_t *d_det_cls, int32_t *d_det_row, int net_h, int net_w, void *stream) {
+  Y3_REQUIRE(net_h > 0 && net_w > 0, "y3_detect_letterbox: network size must be positive");
+  DetectArgs a = {};
+  if (int rc = forward_args("y3_detect_letterbox", d_bbox, d_prob, d_cls, batch, rows, d_orig_hw, prob_thresh, iou_thresh,
+                            d_workspace, d_det_count, d_det_tlbr, d_det_prob, d_det_cls, d_det_row, a)) return rc;
+  if (int rc = map_workspace("y3_detect_letterbox", d_workspace, workspace_bytes, batch, rows, false, a)) return rc;
+  a.lb_net_h = net_h; a.lb_net_w = net_w;
+  return launch<false>(a, batch, kDkOff, stream);
+}
+
 extern "C" int y3_detect_darknet(const float *d_bbox, const float *d_prob, const int64_t *d_cls, int batch, int rows,
                                  const int32_t *d_orig_hw, float prob_thresh, double iou_thresh, void *d_workspace,
                                  size_t workspace_bytes, int32_t *d_det_count, int64_t *d_det_tlbr, float *d_det_prob,
                                  int64_t *d_det_cls, int32_t *d_det_row, int net_h, int net_w, int nms_kind, float beta_nms,
                                  void *stream) {
-  Y3_REQUIRE(batch > 0 && rows > 0, "y3_detect_darknet: batch and rows must be positive");
-  Y3_REQUIRE(d_bbox && d_prob && d_cls && d_orig_hw && d_workspace && d_det_count && d_det_tlbr && d_det_prob &&
-                 d_det_cls && d_det_row, "y3_detect_darknet: null pointer argument");
+  DetectArgs a = {};
+  if (int rc = forward_args("y3_detect_darknet", d_bbox, d_prob, d_cls, batch, rows, d_orig_hw, prob_thresh, iou_thresh,
+                            d_workspace, d_det_count, d_det_tlbr, d_det_prob, d_det_cls, d_det_row, a)) return rc;
   Y3_REQUIRE((net_h == 0 && net_w == 0) || (net_h > 0 && net_w > 0),
              "y3_detect_darknet: network size must be positive, or 0, 0 for frames that were not letterboxed");
   if (int rc = dk_check("y3_detect_darknet", nms_kind, beta_nms)) return rc;
-  const size_t need = dk_ws_total(batch, rows);
-  Y3_REQUIRE(workspace_bytes >= need, "y3_detect_darknet: workspace too small (%zu < %zu)", workspace_bytes, need);
-  const WsLayout w = ws_layout(batch, rows);
-  char *ws = static_cast<char *>(d_workspace);
-  DetectArgs a = {};
-  a.bbox = d_bbox; a.prob = d_prob; a.cls = reinterpret_cast<const long long *>(d_cls); a.orig_hw = d_orig_hw;
+  if (int rc = map_workspace("y3_detect_darknet", d_workspace, workspace_bytes, batch, rows, true, a)) return rc;
   a.lb_net_h = net_h; a.lb_net_w = net_w;
-  a.rows = rows; a.rows_p2 = next_pow2(rows);
-  a.prob_thresh = prob_thresh; a.iou_thresh = iou_thresh;
-  a.c_box = reinterpret_cast<long long *>(ws + w.box);
-  a.c_prob = reinterpret_cast<float *>(ws + w.prob);
-  a.c_cls = reinterpret_cast<int *>(ws + w.cls);
-  a.c_row = reinterpret_cast<int *>(ws + w.row);
-  a.s_key = reinterpret_cast<unsigned long long *>(ws + w.key);
-  a.s_pos = reinterpret_cast<unsigned int *>(ws + w.pos);
-  a.keep = reinterpret_cast<unsigned char *>(ws + w.keep);
-  a.seg = reinterpret_cast<int *>(ws + w.seg);
-  a.c_fbox = reinterpret_cast<float *>(ws + dk_fbox_offset(batch, rows));
   a.dk_thresh = (float)iou_thresh; a.dk_beta = beta_nms;
-  a.det_count = d_det_count; a.det_tlbr = reinterpret_cast<long long *>(d_det_tlbr); a.det_prob = d_det_prob;
-  a.det_cls = reinterpret_cast<long long *>(d_det_cls); a.det_row = d_det_row;
-  return dk_launch<false>(a, batch, nms_kind, static_cast<hipStream_t>(stream));
+  return launch<false>(a, batch, nms_kind + 1, stream);
+}
+
+extern "C" int y3_nms(const int64_t *d_tlbr, const float *d_prob, const int64_t *d_cls, int n, double iou_thresh,
+                      void *d_workspace, size_t workspace_bytes, int64_t *d_keep, int32_t *d_keep_count,
+                      void *stream) {
+  Y3_REQUIRE(n >= 0, "y3_nms: negative n");
+  Y3_REQUIRE(d_keep_count, "y3_nms: null d_keep_count");
+  if (n == 0) {
+    Y3_HIP_CHECK(hipMemsetAsync(d_keep_count, 0, sizeof(int32_t), static_cast<hipStream_t>(stream)));
+    return Y3_OK;
+  }
+  Y3_REQUIRE(d_tlbr && d_prob && d_workspace && d_keep, "y3_nms: null pointer argument");
+  DetectArgs a = {};
+  if (int rc = map_workspace("y3_nms", d_workspace, workspace_bytes, 1, n, false, a)) return rc;
+  nms_args(d_prob, d_cls, n, d_keep, d_keep_count, a);
+  a.in_tlbr = reinterpret_cast<const long long *>(d_tlbr);
+  a.iou_thresh = iou_thresh;
+  return launch<true>(a, 1, kDkOff, stream);
 }
 
 extern "C" int y3_nms_darknet(const float *d_xywh, const float *d_prob, const int64_t *d_cls, int n, float thresh, int nms_kind,
@@ -868,67 +873,12 @@ extern "C" int y3_nms_darknet(const float *d_xywh, const float *d_prob, const in
   }
   Y3_REQUIRE(d_xywh && d_prob && d_workspace && d_keep, "y3_nms_darknet: null pointer argument");
   Y3_REQUIRE((reinterpret_cast<uintptr_t>(d_xywh) & 15) == 0, "y3_nms_darknet: d_xywh must be 16-byte aligned");
-  const WsLayout w = ws_layout(1, n);
-  Y3_REQUIRE(workspace_bytes >= w.total, "y3_nms_darknet: workspace too small (%zu < %zu)", workspace_bytes, w.total);
-  char *ws = static_cast<char *>(d_workspace);
   DetectArgs a = {};
-  a.in_xywh = d_xywh; a.in_prob = d_prob;
-  a.in_cls = reinterpret_cast<const long long *>(d_cls); a.n_in = n;
-  a.rows = n; a.rows_p2 = next_pow2(n);
+  if (int rc = map_workspace("y3_nms_darknet", d_workspace, workspace_bytes, 1, n, false, a)) return rc;
+  nms_args(d_prob, d_cls, n, d_keep, d_keep_count, a);
+  a.in_xywh = d_xywh;
   a.dk_thresh = thresh; a.dk_beta = beta_nms;
-  a.s_key = reinterpret_cast<unsigned long long *>(ws + w.key);
-  a.s_pos = reinterpret_cast<unsigned int *>(ws + w.pos);
-  a.keep = reinterpret_cast<unsigned char *>(ws + w.keep);
-  a.seg = reinterpret_cast<int *>(ws + w.seg);
-  a.det_count = d_keep_count;
-  a.keep_idx = reinterpret_cast<long long *>(d_keep);
-  return dk_launch<true>(a, 1, nms_kind, static_cast<hipStream_t>(stream));
-}
-
-extern "C" int y3_detect(const float *d_bbox, const float *d_prob, const int64_t *d_cls, int batch, int rows,
-                         const int32_t *d_orig_hw, float prob_thresh, double iou_thresh, void *d_workspace,
-                         size_t workspace_bytes, int32_t *d_det_count, int64_t *d_det_tlbr, float *d_det_prob,
-                         int64_t *d_det_cls, int32_t *d_det_row, void *stream) {
-  return detect_launch(d_bbox, d_prob, d_cls, batch, rows, d_orig_hw, prob_thresh, iou_thresh, d_workspace, workspace_bytes,
-                       d_det_count, d_det_tlbr, d_det_prob, d_det_cls, d_det_row, 0, 0, stream);
-}
-
-extern "C" int y3_detect_letterbox(const float *d_bbox, const float *d_prob, const int64_t *d_cls, int batch, int rows,
-                                   const int32_t *d_orig_hw, float prob_thresh, double iou_thresh, void *d_workspace,
-                                   size_t workspace_bytes, int32_t *d_det_count, int64_t *d_det_tlbr, float *d_det_prob,
-                                   int64_t *d_det_cls, int32_t *d_det_row, int net_h, int net_w, void *stream) {
-  Y3_REQUIRE(net_h > 0 && net_w > 0, "y3_detect_letterbox: network size must be positive");
-  return detect_launch(d_bbox, d_prob, d_cls, batch, rows, d_orig_hw, prob_thresh, iou_thresh, d_workspace, workspace_bytes,
-                       d_det_count, d_det_tlbr, d_det_prob, d_det_cls, d_det_row, net_h, net_w, stream);
-}
-
-extern "C" int y3_nms(const int64_t *d_tlbr, const float *d_prob, const int64_t *d_cls, int n, double iou_thresh,
-                      void *d_workspace, size_t workspace_bytes, int64_t *d_keep, int32_t *d_keep_count,
-                      void *stream) {
-  Y3_REQUIRE(n >= 0, "y3_nms: negative n");
-  Y3_REQUIRE(d_keep_count, "y3_nms: null d_keep_count");
-  if (n == 0) {
-    Y3_HIP_CHECK(hipMemsetAsync(d_keep_count, 0, sizeof(int32_t), static_cast<hipStream_t>(stream)));
-    return Y3_OK;
-  }
-  Y3_REQUIRE(d_tlbr && d_prob && d_workspace && d_keep, "y3_nms: null pointer argument");
-  const WsLayout w = ws_layout(1, n);
-  Y3_REQUIRE(workspace_bytes >= w.total, "y3_nms: workspace too small (%zu < %zu)", workspace_bytes, w.total);
-  char *ws = static_cast<char *>(d_workspace);
-  DetectArgs a = {};
-  a.in_tlbr = reinterpret_cast<const long long *>(d_tlbr); a.in_prob = d_prob;
-  a.in_cls = reinterpret_cast<const long long *>(d_cls); a.n_in = n;
-  a.rows = n; a.rows_p2 = next_pow2(n);
-  a.iou_thresh = iou_thresh;
-  a.s_key = reinterpret_cast<unsigned long long *>(ws + w.key);
-  a.s_pos = reinterpret_cast<unsigned int *>(ws + w.pos);
-  a.keep = reinterpret_cast<unsigned char *>(ws + w.keep);
-  a.seg = reinterpret_cast<int *>(ws + w.seg);
-  a.det_count = d_keep_count;
-  a.keep_idx = reinterpret_cast<long long *>(d_keep);
-  Y3_LAUNCH(detect_kernel<true>, dim3(1), dim3(kThreads), 0, static_cast<hipStream_t>(stream), a);
-  Y3_HIP_CHECK(hipGetLastError());
-  return Y3_OK;
+  return launch<true>(a, 1, nms_kind + 1, stream);
 }
 
 extern "C" size_t y3_nms_float_workspace_bytes(int n) {
@@ -961,30 +911,29 @@ extern "C" int y3_nms_float(const void *d_tlbr, int box_dtype, const double *d_p
   return Y3_OK;
 }
 
+namespace {
+template <typename T>
+int cxywh_launch(const void *d_xywh, void *d_tlbr, int n, int cols, void *stream) {
+  Y3_LAUNCH(cxywh_to_tlbr_kernel<T>, dim3((n + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream),
+            static_cast<const T *>(d_xywh), static_cast<T *>(d_tlbr), n, cols);
+  Y3_HIP_CHECK(hipGetLastError());
+  return Y3_OK;
+}
+}  // namespace
+
 extern "C" int y3_cxywh_to_tlbr_float(const void *d_xywh, void *d_tlbr, int n, int cols, int dtype, void *stream) {
   Y3_REQUIRE(n >= 0 && cols >= 4, "y3_cxywh_to_tlbr_float: need n >= 0 and at least 4 columns");
   Y3_REQUIRE(dtype == Y3_F32 || dtype == Y3_F64, "y3_cxywh_to_tlbr_float: dtype must be Y3_F32 or Y3_F64");
   if (n == 0) return Y3_OK;
   Y3_REQUIRE(d_xywh && d_tlbr, "y3_cxywh_to_tlbr_float: null pointer argument");
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (dtype == Y3_F32)
-    Y3_LAUNCH(cxywh_to_tlbr_float_kernel<float>, dim3((n + 255) / 256), dim3(256), 0, s, static_cast<const float *>(d_xywh),
-                       static_cast<float *>(d_tlbr), n, cols);
-  else
-    Y3_LAUNCH(cxywh_to_tlbr_float_kernel<double>, dim3((n + 255) / 256), dim3(256), 0, s, static_cast<const double *>(d_xywh),
-                       static_cast<double *>(d_tlbr), n, cols);
-  Y3_HIP_CHECK(hipGetLastError());
-  return Y3_OK;
+  return dtype == Y3_F32 ? cxywh_launch<float>(d_xywh, d_tlbr, n, cols, stream) : cxywh_launch<double>(d_xywh, d_tlbr, n, cols, stream);
 }
 
 extern "C" int y3_cxywh_to_tlbr(const int64_t *d_xywh, int64_t *d_tlbr, int n, int cols, void *stream) {
   Y3_REQUIRE(n >= 0 && cols >= 4, "y3_cxywh_to_tlbr: need n >= 0 and at least 4 columns");
   if (n == 0) return Y3_OK;
   Y3_REQUIRE(d_xywh && d_tlbr, "y3_cxywh_to_tlbr: null pointer argument");
-  Y3_LAUNCH(cxywh_to_tlbr_kernel, dim3((n + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream),
-                     reinterpret_cast<const long long *>(d_xywh), reinterpret_cast<long long *>(d_tlbr), n, cols);
-  Y3_HIP_CHECK(hipGetLastError());
-  return Y3_OK;
+  return cxywh_launch<long long>(d_xywh, d_tlbr, n, cols, stream);
 }
 
 extern "C" int y3_pack_records(const int32_t *d_det_count, const int64_t *d_det_tlbr, const float *d_det_prob,

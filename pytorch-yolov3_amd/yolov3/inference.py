@@ -64,6 +64,25 @@ def _require_finite(arr, what):
         raise ValueError("{} holds non-finite values (NaN / inf): not supported on float boxes".format(what))
 
 
+def _run_nms(dev, ws_query, call, boxes, prob, cls):
+    """The device side that the NMS wrappers share.  Uploads ``boxes``, ``prob`` and the optional ``cls`` (host arrays that the
+    caller has validated) to ``dev``, makes the workspace that ``ws_query(n)`` asks for and the keep / count buffers, and runs
+    ``call(d_boxes, d_prob, d_cls, n, tail)`` on ``dev``: device pointers (``d_cls`` may be None) and ``tail``, the arguments
+    every NMS entry point ends with (workspace, its size, keep, count, stream).  Returns the kept indices as a list."""
+    n = boxes.shape[0]
+    d_box = torch.from_numpy(boxes).to(dev)
+    d_prob = torch.from_numpy(prob).to(dev)
+    d_cls = torch.from_numpy(cls).to(dev) if cls is not None else None
+    ws_bytes = ws_query(n)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    keep = torch.empty(n, dtype=torch.int64, device=dev)
+    count = torch.zeros(1, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        tail = (ws.data_ptr(), ws_bytes, keep.data_ptr(), count.data_ptr(), _hip.stream_ptr())
+        _hip.check(call(d_box.data_ptr(), d_prob.data_ptr(), d_cls.data_ptr() if d_cls is not None else None, n, tail))
+        return keep[:int(count.cpu()[0])].cpu().numpy().tolist()
+
+
 def cxywh_to_tlbr(bbox_xywh):
     """(n, >=4) array [cx, cy, w, h, ...] -> [x1, y1, x2, y2, ...] with ``x1 = cx - w//2`` etc. (floor division; extra
     columns pass through).  Integer pixel boxes (what ``inference()`` uses) and float32 / float64 boxes, like the reference
@@ -116,23 +135,14 @@ def non_max_suppression(bbox_tlbr, class_prob, class_idx=None, iou_thresh=0.3):
         return []
     dev = _device()
     lib = _hip.lib()
-    d_box = torch.from_numpy(boxes).to(dev)
-    d_prob = torch.from_numpy(prob).to(dev)
-    d_cls = None
+    cls = None
     if class_idx is not None:
         cls = np.ascontiguousarray(class_idx, dtype=np.int64)
         if cls.shape[0] != n:
             raise ValueError("class_idx has the wrong length")
-        d_cls = torch.from_numpy(cls).to(dev)
-    ws_bytes = lib.y3_nms_workspace_bytes(n)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    keep = torch.empty(n, dtype=torch.int64, device=dev)
-    count = torch.zeros(1, dtype=torch.int32, device=dev)
-    _hip.check(lib.y3_nms(d_box.data_ptr(), d_prob.data_ptr(), d_cls.data_ptr() if d_cls is not None else None,
-                          n, float(iou_thresh), ws.data_ptr(), ws_bytes, keep.data_ptr(), count.data_ptr(),
-                          _hip.stream_ptr()))
-    k = int(count.cpu()[0])
-    return keep[:k].cpu().numpy().tolist()
+    thr = float(iou_thresh)
+    return _run_nms(dev, lib.y3_nms_workspace_bytes,
+                    lambda box, score, cidx, n, tail: lib.y3_nms(box, score, cidx, n, thr, *tail), boxes, prob, cls)
 
 
 def non_max_suppression_darknet(bbox_xywh, class_prob, class_idx=None, thresh=0.45, nms_kind="iou", beta_nms=0.6):
@@ -172,18 +182,9 @@ def non_max_suppression_darknet(bbox_xywh, class_prob, class_idx=None, thresh=0.
     dev = _device()
     _hip.require_capabilities(_hip.CAP_NMS_DARKNET, "non_max_suppression_darknet")
     lib = _hip.lib()
-    d_box = torch.from_numpy(boxes).to(dev)
-    d_prob = torch.from_numpy(prob).to(dev)
-    d_cls = torch.from_numpy(cls).to(dev) if cls is not None else None
-    ws_bytes = lib.y3_nms_darknet_workspace_bytes(n)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    keep = torch.empty(n, dtype=torch.int64, device=dev)
-    count = torch.zeros(1, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        _hip.check(lib.y3_nms_darknet(d_box.data_ptr(), d_prob.data_ptr(), d_cls.data_ptr() if d_cls is not None else None, n,
-                                      thresh, mode[0], mode[1], ws.data_ptr(), ws_bytes, keep.data_ptr(), count.data_ptr(),
-                                      _hip.stream_ptr()))
-        return keep[:int(count.cpu()[0])].cpu().numpy().tolist()
+    return _run_nms(dev, lib.y3_nms_darknet_workspace_bytes,
+                    lambda box, score, cidx, n, tail: lib.y3_nms_darknet(box, score, cidx, n, thresh, mode[0], mode[1], *tail),
+                    boxes, prob, cls)
 
 
 def _nms_float(barr, class_prob, class_idx, iou_thresh):
@@ -196,21 +197,14 @@ def _nms_float(barr, class_prob, class_idx, iou_thresh):
         raise ValueError("bbox_tlbr and class_prob disagree on the number of boxes")
     dev = _device()
     lib = _hip.lib()
-    d_box = torch.from_numpy(boxes).to(dev)
-    d_prob = torch.from_numpy(prob).to(dev)
-    d_cls = None
+    cls = None
     if class_idx is not None:
         cls = np.ascontiguousarray(class_idx, dtype=np.int64)
         if cls.shape[0] != n:
             raise ValueError("class_idx has the wrong length")
-        d_cls = torch.from_numpy(cls).to(dev)
-    ws_bytes = lib.y3_nms_float_workspace_bytes(n)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    keep = torch.empty(n, dtype=torch.int64, device=dev)
-    count = torch.zeros(1, dtype=torch.int32, device=dev)
-    _hip.check(lib.y3_nms_float(d_box.data_ptr(), code, d_prob.data_ptr(), d_cls.data_ptr() if d_cls is not None else None, n,
-                                float(iou_thresh), ws.data_ptr(), ws_bytes, keep.data_ptr(), count.data_ptr(), _hip.stream_ptr()))
-    return keep[:int(count.cpu()[0])].cpu().numpy().tolist()
+    thr = float(iou_thresh)
+    return _run_nms(dev, lib.y3_nms_float_workspace_bytes,
+                    lambda box, score, cidx, n, tail: lib.y3_nms_float(box, code, score, cidx, n, thr, *tail), boxes, prob, cls)
 
 
 class Detector(object):
@@ -257,27 +251,28 @@ class Detector(object):
             self.orig_hw.copy_(orig_hw, non_blocking=True)
             hw = self.orig_hw
         bbox, prob, cls = out["bbox_xywh"], out["class_prob"], out["class_idx"]
-        args = (bbox.data_ptr(), prob.data_ptr(), cls.data_ptr(), self.batch, self.rows, hw.data_ptr(),
-                ctypes.c_float(prob_thresh), ctypes.c_double(iou_thresh), self.ws.data_ptr(), self.ws_bytes,
-                self.count.data_ptr(), self.tlbr.data_ptr(), self.prob.data_ptr(), self.cls.data_ptr(),
-                self.row.data_ptr())
+        lib = _hip.lib()
         if mode is not None:
             _hip.require_capabilities(_hip.CAP_NMS_DARKNET, "Detector.run(nms_kind=...)")
-            if letterbox is not None:
-                _hip.require_capabilities(_hip.CAP_LETTERBOX, "Detector.run(letterbox=...)")
-            net_h, net_w = (int(v) for v in letterbox) if letterbox is not None else (0, 0)
-            if self._ws_darknet is None:
-                nbytes = _hip.lib().y3_detect_darknet_workspace_bytes(self.batch, self.rows)
-                self._ws_darknet = (nbytes, torch.empty(nbytes, dtype=torch.uint8, device=self.device))
-            nbytes, ws = self._ws_darknet
-            args = args[:8] + (ws.data_ptr(), nbytes) + args[10:]
-            _hip.check(_hip.lib().y3_detect_darknet(*args, net_h, net_w, mode[0], ctypes.c_float(mode[1]), _hip.stream_ptr()))
-        elif letterbox is None:
-            _hip.check(_hip.lib().y3_detect(*args, _hip.stream_ptr()))
-        else:
+        if letterbox is not None:
             _hip.require_capabilities(_hip.CAP_LETTERBOX, "Detector.run(letterbox=...)")
-            net_h, net_w = (int(v) for v in letterbox)
-            _hip.check(_hip.lib().y3_detect_letterbox(*args, net_h, net_w, _hip.stream_ptr()))
+        ws, ws_bytes = self.ws, self.ws_bytes
+        if mode is not None:
+            if self._ws_darknet is None:
+                nbytes = lib.y3_detect_darknet_workspace_bytes(self.batch, self.rows)
+                self._ws_darknet = (nbytes, torch.empty(nbytes, dtype=torch.uint8, device=self.device))
+            ws_bytes, ws = self._ws_darknet
+        args = [bbox.data_ptr(), prob.data_ptr(), cls.data_ptr(), self.batch, self.rows, hw.data_ptr(),
+                ctypes.c_float(prob_thresh), ctypes.c_double(iou_thresh), ws.data_ptr(), ws_bytes,
+                self.count.data_ptr(), self.tlbr.data_ptr(), self.prob.data_ptr(), self.cls.data_ptr(),
+                self.row.data_ptr()]
+        net_h, net_w = (int(v) for v in letterbox) if letterbox is not None else (0, 0)
+        if mode is not None:
+            _hip.check(lib.y3_detect_darknet(*args, net_h, net_w, mode[0], ctypes.c_float(mode[1]), _hip.stream_ptr()))
+        elif letterbox is not None:
+            _hip.check(lib.y3_detect_letterbox(*args, net_h, net_w, _hip.stream_ptr()))
+        else:
+            _hip.check(lib.y3_detect(*args, _hip.stream_ptr()))
 
     def _run_labels(self, out, orig_hw, prob_thresh, iou_thresh, letterbox, nms_kind, beta_nms, labels, label_capacity):
         _hip.require_capabilities(_hip.CAP_MULTI_LABEL, "Detector.run(labels=...)")

@@ -75,8 +75,8 @@ def test_class_sizes_on_the_chunk_boundaries_and_signed_classes():
 # ---- (c) wide coordinates, forward mode ----------------------------------------------------------------------------------------
 def test_wide_frame_takes_the_64_bit_path_like_the_oracle():
     """A 20000 x 24000 frame: candidates on both sides of +-16000 in chunks that are narrow, wide and mixed, in every order
-    (test_detect_tail_host.py), so suppression switches between the 32-bit test and both copies of the int64 / float64 code
-    inside a class.  The same boxes on a 608 x 608 frame, where nothing is wide, are the control."""
+    (test_detect_tail_host.py), so suppression switches between the 32-bit test and the int64 / float64 test, against
+    earlier chunks and inside a chunk, inside a class.  The same boxes on a 608 x 608 frame, where nothing is wide, are the control."""
     box, prob, cls, hw = C.wide_forward()
     wide = _against_oracle((box, prob, cls, hw), C.WIDE_PROB_THRESH, C.WIDE_IOU)
     assert (np.abs(wide[0][0]) >= C.I32_LIM).any(axis=1).sum() >= 20
