@@ -296,6 +296,24 @@ class Darknet(object):
         self._plans = {}
         return self
 
+    def update_bn(self, params):
+        """New BN statistics / biases under the plans the network already holds: the folded scale and bias of every conv are
+        written into their existing device copies, which the compiled plans read at run time.  The conv weights must be the
+        installed ones (they are not uploaded again); use ``set_params`` to change them."""
+        if self._params is None or len(params) != len(self._convs):
+            raise ValueError("update_bn needs one parameter set per conv of a network that has parameters")
+        for old, new in zip(self._params, params):
+            if old["weight"].shape != new["weight"].shape or not np.array_equal(old["weight"], new["weight"]):
+                raise ValueError("update_bn does not change conv weights: call set_params")
+        self._params = params
+        for key, entry in self._dev_weights.items():
+            if key[1] == "fragment":          # the fragment-order copy of a conv's weights: weights only
+                continue
+            scale, bias = self._fold_bn(key[0])
+            entry["scale"][:scale.size].copy_(torch.from_numpy(scale))
+            entry["bias"][:bias.size].copy_(torch.from_numpy(bias))
+        return self
+
     def _fold_bn(self, slot):
         """BN(eval) as y = conv*scale + bias, float32 like torch's CPU batch_norm
         (alpha = gamma / sqrt(var + eps), beta' = beta - mean * alpha)."""

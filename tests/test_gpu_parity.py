@@ -963,20 +963,30 @@ def test_wave_specialised_igemm_is_bit_identical():
         lib.y3_set_tuning(b"auto_mask", DEFAULT_KNOBS["auto_mask"])
 
 
-def _resblock_plan(net, x, fuse, dev):
-    """1x1 (64 -> 32) + 3x3 (32 -> 64) + shortcut of yolov3's first residual block as a hand-built two-op plan."""
+def _pair_dtypes():
+    from yolov3 import _hip
+    return {"bf16": (_hip.Y3_BF16, torch.bfloat16), "fp16": (_hip.Y3_F16, torch.float16)}
+
+
+_PAIR_DTYPES = _pair_dtypes()      # storage type of the hand-built two-op plans below: (y3_op.dtype, torch dtype)
+
+
+def _resblock_plan(net, x, fuse, dev, dtype="bf16"):
+    """1x1 (64 -> 32) + 3x3 (32 -> 64) + shortcut of yolov3's first residual block as a hand-built two-op plan
+    (``dtype``: "bf16" / "fp16", the storage type of x, the weights and the output)."""
     import ctypes
     from yolov3 import _hip
     lib = _hip.lib()
     b, h, w, _ = x.shape
-    w2 = net._device_weights(2, _hip.PATH_IGEMM, "bf16", dev)
-    w3 = net._device_weights(3, _hip.PATH_IGEMM, "bf16", dev)
-    mid = torch.zeros((b, h, w, 32), dtype=torch.bfloat16, device=dev)
-    out = torch.zeros((b, h, w, 64), dtype=torch.bfloat16, device=dev)
+    c_dtype, t_dtype = _PAIR_DTYPES[dtype]
+    w2 = net._device_weights(2, _hip.PATH_IGEMM, dtype, dev)
+    w3 = net._device_weights(3, _hip.PATH_IGEMM, dtype, dev)
+    mid = torch.zeros((b, h, w, 32), dtype=t_dtype, device=dev)
+    out = torch.zeros((b, h, w, 64), dtype=t_dtype, device=dev)
     zero = torch.zeros(4096, dtype=torch.uint8, device=dev)
     ops = (_hip.Y3Op * 2)()
     for op, (wt, cin, cout, k) in zip(ops, ((w2, 64, 32, 1), (w3, 32, 64, 3))):
-        op.kind, op.dtype, op.batch = _hip.OP_CONV, _hip.Y3_BF16, b
+        op.kind, op.dtype, op.batch = _hip.OP_CONV, c_dtype, b
         op.ksize, op.stride, op.pad = k, 1, (k - 1) // 2
         op.in_c, op.out_c, op.in_ld, op.out_ld = cin, cout, cin, cout
         op.in_h = op.out_h = h
@@ -1012,20 +1022,22 @@ def test_fused_residual_block_is_bit_identical(dim, batch):
     assert torch.equal(fused, plain), float((fused.float() - plain.float()).abs().max())
 
 
-def _first_two_convs_plan(net, frames, fuse, dev):
-    """A two-op plan (stem conv + stride-2 conv of yolov3) built by hand so the second conv's output can be read."""
+def _first_two_convs_plan(net, frames, fuse, dev, dtype="bf16"):
+    """A two-op plan (stem conv + stride-2 conv of yolov3) built by hand so the second conv's output can be read
+    (``dtype``: "bf16" / "fp16", the storage type of the weights, the intermediate and the output)."""
     import ctypes
     from yolov3 import _hip
     lib = _hip.lib()
     b, h, w, _ = frames.shape
-    w0 = net._device_weights(0, _hip.PATH_STEM_MFMA, "bf16", dev)
-    w1 = net._device_weights(1, _hip.PATH_IGEMM, "bf16", dev)
-    mid = torch.zeros((b, h, w, 32), dtype=torch.bfloat16, device=dev)
-    out = torch.zeros((b, h // 2, w // 2, 64), dtype=torch.bfloat16, device=dev)
+    c_dtype, t_dtype = _PAIR_DTYPES[dtype]
+    w0 = net._device_weights(0, _hip.PATH_STEM_MFMA, dtype, dev)
+    w1 = net._device_weights(1, _hip.PATH_IGEMM, dtype, dev)
+    mid = torch.zeros((b, h, w, 32), dtype=t_dtype, device=dev)
+    out = torch.zeros((b, h // 2, w // 2, 64), dtype=t_dtype, device=dev)
     zero = torch.zeros(4096, dtype=torch.uint8, device=dev)
     ops = (_hip.Y3Op * 2)()
     for op, (wt, cin, cout, k, st) in zip(ops, ((w0, 3, 32, 3, 1), (w1, 32, 64, 3, 2))):
-        op.kind, op.dtype, op.batch = _hip.OP_CONV, _hip.Y3_BF16, b
+        op.kind, op.dtype, op.batch = _hip.OP_CONV, c_dtype, b
         op.ksize, op.stride, op.pad = k, st, 1
         op.in_c, op.out_c = cin, cout
         op.cout_pad, op.k_ld = wt["cout_pad"], wt["k_ld"]

@@ -28,11 +28,12 @@ def round_up(v, m):
     return (v + m - 1) // m * m
 
 
-def make_pair(dev, B, h, cin, cout, res, gen):
-    """Tensors + two y3_op structs of a 1x1 (cin -> 128) + 3x3 (128 -> cout) pair."""
+def make_pair(dev, B, h, cin, cout, res, gen, dtype="bf16"):
+    """Tensors + two y3_op structs of a 1x1 (cin -> 128) + 3x3 (128 -> cout) pair; dtype "bf16" / "fp16": the storage type."""
+    c_dtype, t_dtype = {"bf16": (_hip.Y3_BF16, torch.bfloat16), "fp16": (_hip.Y3_F16, torch.float16)}[dtype]
     t = {}
-    t["x"] = (torch.randn((B, h, h, cin), generator=gen) * 0.7).to(torch.bfloat16).to(dev)
-    t["mid"] = torch.zeros((B, h, h, 128), dtype=torch.bfloat16, device=dev)
+    t["x"] = (torch.randn((B, h, h, cin), generator=gen) * 0.7).to(t_dtype).to(dev)
+    t["mid"] = torch.zeros((B, h, h, 128), dtype=t_dtype, device=dev)
     t["zero"] = torch.zeros(4096, dtype=torch.uint8, device=dev)
     ops = (_hip.Y3Op * 2)()
     for n, (ci, co, k) in enumerate(((cin, 128, 1), (128, cout, 3))):
@@ -45,9 +46,9 @@ def make_pair(dev, B, h, cin, cout, res, gen):
         bi = torch.zeros(cp)
         sc[:co] = torch.rand(co, generator=gen) + 0.5
         bi[:co] = torch.rand(co, generator=gen) - 0.5
-        t["w%d" % n], t["sc%d" % n], t["bi%d" % n] = w.to(torch.bfloat16).to(dev), sc.to(dev), bi.to(dev)
+        t["w%d" % n], t["sc%d" % n], t["bi%d" % n] = w.to(t_dtype).to(dev), sc.to(dev), bi.to(dev)
         op = ops[n]
-        op.kind, op.dtype, op.batch = _hip.OP_CONV, _hip.Y3_BF16, B
+        op.kind, op.dtype, op.batch = _hip.OP_CONV, c_dtype, B
         op.ksize, op.stride, op.pad = k, 1, (k - 1) // 2
         op.in_c, op.out_c, op.in_ld, op.out_ld = ci, co, ci, co
         op.in_h = op.in_w = op.out_h = op.out_w = h
