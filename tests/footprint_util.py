@@ -220,9 +220,14 @@ def _opts():
 F32, B16, ALL = ("float32",), ("bf16", "fp16"), ("float32", "bf16", "fp16")
 
 
-def _conv(cid, family, opt, dtypes, B, h, w, cin, cout, k, s, res=False, inp="act", out_unit=None, **kw):
+def _conv(cid, family, opt, dtypes, B, h, w, cin, cout, k, s, res=False, inp="act", out_unit=None, pad=None, **kw):
+    """``pad``: None is a cfg block with ``pad=1`` ((k - 1) // 2); 0 is one that leaves the key out"""
     return dict(id=cid, group="conv", family=family, opt=opt, dtypes=dtypes, B=B, h=h, w=w, cin=cin, cout=cout, k=k, s=s,
-                res=res, inp=inp, out_unit=out_unit, **kw)
+                res=res, inp=inp, out_unit=out_unit, pad=conv_pad(k, pad), **kw)
+
+
+def conv_pad(k, pad=None):
+    return (k - 1) // 2 if pad is None else pad
 
 
 def _layer(cid, family, kind, dtypes, B, h, w, c, k=1, s=1, wide=True, dk=False, alias=False, opt="default"):
@@ -246,6 +251,18 @@ def cases():
             _conv(ver + "_64_ragged_res", fam + "_128x64", opt, ALL, 2, 15, 9, 32, 64, 3, 1, res=True),
             _conv(ver + "_32_full", fam + "_128x32", opt, ALL, 1, 16, 8, 64, 32, 1, 1, res=True),
             _conv(ver + "_32_ragged", fam + "_128x32", opt, ALL, 1, 19, 13, 16, 32, 3, 1),
+            # K-tilings and kernel geometry that only a user's own cfg reaches (igemm_ktiles: KMODE 0 when in_c is a multiple of
+            # the K-tile -- 32 float32 / 64 16-bit elements --, 2 when the K-tile is a multiple of in_c, 1 otherwise).
+            # KMODE 1, every tap but the first straddles two K-tiles, K = 216 ends inside a K-tile in every dtype
+            _conv(ver + "_k3_c24_res", fam + "_128x64", opt, ALL, 2, 15, 9, 24, 64, 3, 1, res=True),
+            _conv(ver + "_k3s2_c40", fam + "_128x128", opt, ALL, 1, 27, 21, 40, 128, 3, 2),                    # KMODE 1
+            # KMODE 2 with the 25-bit tap mask: 4 (float32) / 8 (16-bit) taps per K-tile, the last K-tile holds one tap
+            _conv(ver + "_k5_c8", fam + "_128x32", opt, ALL, 2, 13, 11, 8, 32, 5, 1),
+            _conv(ver + "_1x1_c72", fam + "_128x128", opt, ALL, 3, 13, 11, 72, 128, 1, 1),      # KMODE 1: 2.25 / 1.125 K-tiles
+            _conv(ver + "_k5s2_c64", fam + "_128x64", opt, ALL, 1, 27, 21, 64, 64, 5, 2),       # KMODE 0 with 25 taps
+            _conv(ver + "_k4s2_c16", fam + "_128x32", opt, ALL, 1, 26, 22, 16, 32, 4, 2),       # an even kernel, pad 1
+            # a 3x3 block without a pad= key: no tap is ever masked, 15 x 9 -> 13 x 7
+            _conv(ver + "_k3_pad0_c32", fam + "_128x64", opt, ALL, 2, 15, 9, 32, 64, 3, 1, pad=0),
         ]
     C += [
         # ragged channel tail: 255 float32 head channels (the head conv: bias only, float32 out).  Under the DEFAULT igemm_version
@@ -259,6 +276,20 @@ def cases():
         _conv("igemm3_128_ragged_s2", "conv_igemm3_%s_128x128", "igemm3", ALL, 2, 27, 21, 64, 128, 3, 2),
         _conv("igemm3_64_full", "conv_igemm3_%s_64x128", "igemm3_64", B16, 1, 16, 16, 256, 128, 1, 1, res=True),
         _conv("igemm3_64_ragged", "conv_igemm3_%s_64x128", "igemm3_64", B16, 3, 13, 9, 128, 256, 3, 1),
+    ]
+    for ver, opt, fam, dts in (("igemm3_128", "igemm3", "conv_igemm3_%s_128x128", ALL), ("igemm3_64", "igemm3_64", "conv_igemm3_%s_64x128", B16)):
+        C += [
+            _conv(ver + "_k3s2_c40", fam, opt, dts, 1, 27, 21, 40, 128, 3, 2),                   # KMODE 1
+            _conv(ver + "_1x1_c72", fam, opt, dts, 3, 13, 11, 72, 128, 1, 1),                    # KMODE 1
+            _conv(ver + "_k5_c16_res", fam, opt, dts, 2, 13, 11, 16, 128, 5, 1, res=True),       # KMODE 2, 25 taps
+            _conv(ver + "_k3_c160_res", fam, opt, dts, 1, 19, 19, 160, 128, 3, 1, res=True),     # KMODE 1 in 16 bits (0 in float32)
+        ]
+    C += [
+        _conv("igemm2_96_k3s2_c40", "conv_igemm2_%s_96x64", "igemm2_96", ALL, 1, 27, 21, 40, 128, 3, 2),
+        _conv("igemm2_96_k5_c16_res", "conv_igemm2_%s_96x64", "igemm2_96", ALL, 2, 13, 11, 16, 128, 5, 1, res=True),
+        # the route by which an unforced plan reaches KMODE 1: the chooser's own small-grid rule (api.hip choose_conv) sends a
+        # 160 -> 128 3x3 layer on a 19 x 19 map to the wave-specialised implicit GEMM
+        _conv("default_k3_c160", "conv_igemm3_%s_128x128", "default", B16, 1, 19, 19, 160, 128, 3, 1, res=True),
         # ---- halo-reuse strip kernels (conv_halo.hip): 192- / 256-pixel strips of whole rows x 128 channels; float32 too
         _conv("halo192_full", "conv_halo_ws_%s_192x128", "halo192", ALL, 2, 24, 16, 128, 128, 3, 1, res=True, out_unit=8),
         _conv("halo192_ragged", "conv_halo_ws_%s_192x128", "halo192", ALL, 3, 19, 13, 128, 256, 3, 1, out_unit=8),
@@ -304,6 +335,17 @@ def cases():
         _conv("stem_mfma_full", "conv_stem_mfma_u8_%s", "default", B16, 2, 32, 32, 3, 32, 3, 1, inp="u8"),
         _conv("stem_mfma_ragged", "conv_stem_mfma_u8_%s", "default", B16, 3, 29, 21, 3, 32, 3, 1, inp="u8"),
         _conv("stem_mfma_ragged_16ch", "conv_stem_mfma_u8_%s", "default", B16, 1, 45, 37, 3, 16, 3, 1, inp="u8"),
+        # ---- the direct fallback (conv_small.hip conv_direct_kernel, one thread per output element): what api.hip conv_path gives
+        # a conv on activations that the implicit GEMMs decline (in_c no multiple of the 16-byte chunk, size > 5, out_ld % 4 != 0)
+        # and a network-input conv that is not 3 channels x 3x3.  No shipped cfg reaches it
+        _conv("direct_odd_cin_res", "conv_direct_%s", "default", ALL, 2, 13, 11, 13, 24, 3, 1, res=True),
+        _conv("direct_odd_both_s2", "conv_direct_%s", "default", ALL, 3, 19, 13, 21, 13, 3, 2),
+        _conv("direct_k7_s2", "conv_direct_%s", "default", ALL, 1, 19, 13, 16, 32, 7, 2),
+        _conv("direct_f32_logits", "conv_direct_%s", "default", ALL, 2, 7, 5, 21, 18, 1, 1, out_f32=True, leaky=False),
+        _conv("direct_nchw_k5_s2", "conv_direct_%s", "default", ALL, 2, 21, 17, 3, 16, 5, 2, inp="nchw"),
+        _conv("direct_nchw_grey", "conv_direct_%s", "default", ALL, 2, 16, 16, 1, 16, 3, 1, inp="nchw"),
+        _conv("direct_u8_k5", "conv_direct_%s", "default", ALL, 2, 21, 17, 3, 16, 5, 1, inp="u8"),
+        _conv("direct_u8_grey_s2", "conv_direct_%s", "default", ALL, 2, 22, 18, 1, 16, 3, 2, inp="u8"),
     ]
     # ---- fused groups, laid out as the plan lays them: private intermediate, input and output are slices
     C += [
@@ -356,7 +398,7 @@ DENSE_ONLY = {}
 
 # kernel names the choosers can produce that no plan of the shipped cfgs under kernel_choice_util.OPTION_SETS reaches, so
 # tests/golden/kernel_choice.json does not hold them: covered here all the same
-NOT_IN_FIXTURE = ("add_%s", "copy_%s", "maxpool_dk_%s", "maxpool_spp_pyramid_dk_%s")
+NOT_IN_FIXTURE = ("add_%s", "copy_%s", "maxpool_dk_%s", "maxpool_spp_pyramid_dk_%s", "conv_direct_%s")
 
 
 def case_ids():
@@ -414,9 +456,9 @@ def _conv_weights(prefix, dtype, cin, cout, k, path, operands):
     return cp, k_ld
 
 
-def _set_conv(op, dtype, B, h, w, cin, cout, k, s, flags):
+def _set_conv(op, dtype, B, h, w, cin, cout, k, s, flags, pad=None):
     H = _H()
-    pad = (k - 1) // 2
+    pad = conv_pad(k, pad)
     op.kind, op.dtype, op.flags, op.batch = H.OP_CONV, DT_CODE[dtype], flags, B
     op.in_h, op.in_w, op.in_c = h, w, cin
     op.out_h, op.out_w, op.out_c = (h + 2 * pad - k) // s + 1, (w + 2 * pad - k) // s + 1, cout
@@ -469,18 +511,18 @@ def build(case, dtype, mode, opt, base=None):
             flags |= H.F_PLAN_INPUT | H.F_IN_NCHW_F32
         if case["res"]:
             flags |= H.F_RESIDUAL
-        _set_conv(op, dtype, B, h, w, cin, cout, k, s, flags)
+        _set_conv(op, dtype, B, h, w, cin, cout, k, s, flags, case["pad"])
         Po = B * op.out_h * op.out_w
         ptrs = []
         if case["inp"] == "act":
             x = _act(used, "input", "in", dtype, P, cin, mode, unit, 0)
             ptrs.append((0, "d_in", "input", 0))
         elif case["inp"] == "u8":
-            x = _flat("input", "in", "u8", P * 3, 3)
+            x = _flat("input", "in", "u8", P * cin, cin)
         else:
-            x = _flat("input", "in", "float32", P * 3, 3)
+            x = _flat("input", "in", "float32", P * cin, cin)
         operands.append(x)
-        op.in_ld = x.ld if case["inp"] == "act" else 3
+        op.in_ld = x.ld if case["inp"] == "act" else cin
         ofmt = "float32" if out_f32 else dtype
         ounit = case["out_unit"] or (4 if out_f32 else unit)
         o = _act(used, "output", "out", dtype, Po, cout, mode, ounit, 1, fmt=ofmt)

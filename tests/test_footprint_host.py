@@ -38,8 +38,9 @@ def test_every_case_gets_the_family_it_claims(mode):
 
 
 def test_table_reaches_every_family_of_the_kernel_choice_fixture():
-    """Exact names (dtype included): what the table reaches == the fixture's kernel names + the four layer kernels no shipped
-    cfg's plan holds.  No skip list: removing a row of the table that is a family's only one fails here."""
+    """Exact names (dtype included): what the table reaches == the fixture's kernel names + the five kernels no shipped cfg's
+    plan holds (add, copy, maxpool_dk, maxpool_spp_pyramid_dk, conv_direct).  No skip list: removing a row of the table that
+    is a family's only one fails here."""
     reached = {fu.family_name(c, d) for c in fu.cases() for d in c["dtypes"]}
     fixture = _fixture_families()
     extra = {f % t for f in fu.NOT_IN_FIXTURE for t in ("f32", "bf16", "f16")}
@@ -59,13 +60,34 @@ def test_every_family_has_a_full_and_a_ragged_case_and_both_shortcut_forms():
     # the conv families that take a shortcut operand (their choosers accept Y3_F_RESIDUAL) have a case with one
     for fam in ("conv_igemm_%s_128x128", "conv_igemm2_%s_128x128", "conv_igemm2_%s_96x64", "conv_igemm3_%s_128x128",
                 "conv_igemm3_%s_64x128", "conv_halo_ws_%s_192x128", "conv_halo_ws_%s_256x128", "conv_halo_dw_%s_192x256",
-                "conv_patch_wsp_%s_8x32x128", "conv_dw48_k1_%s", "conv_dw48_k3_%s", "conv_block_fused_%s_x128"):
+                "conv_patch_wsp_%s_8x32x128", "conv_dw48_k1_%s", "conv_dw48_k3_%s", "conv_block_fused_%s_x128", "conv_direct_%s"):
         assert any(c.get("res") for c in by_family[fam]), fam
     # shapes stay at or below 16 x 76 x 76 x 512
     for c in fu.cases():
         assert c["B"] <= 16 and c["h"] * c["w"] <= 76 * 76 and max(c.get("cin", 0), c.get("cout", 0), c.get("c", 0)) <= 512, c["id"]
         # only the patch kernel's maps are wider than 76 (its chooser asks rows of more than 128 px)
         assert max(c["h"], c["w"]) <= 76 or c["family"].startswith("conv_patch_wsp"), c["id"]
+
+
+def _kmode(case, dtype):
+    """(K-tiling mode, whether the last K-tile is partial): csrc/conv_igemm.hip igemm_ktiles restated"""
+    bke = 128 // fu.ES[dtype]                                   # elements of one K-tile
+    mode = 0 if case["cin"] % bke == 0 else (2 if bke % case["cin"] == 0 else 1)
+    return mode, (case["k"] ** 2 * case["cin"]) % bke != 0
+
+
+def test_k_tilings_of_the_table():
+    """every implicit-GEMM version runs every K-tiling in every element type: one tap per K-tile (0), per-chunk taps (1),
+    several whole taps per K-tile (2); a 5x5 (25-bit tap mask); a last K-tile that K ends inside of"""
+    for dtype in fu.ALL:
+        for version in ("conv_igemm_%s_", "conv_igemm2_%s_", "conv_igemm3_%s_"):
+            cs = [c for c in fu.cases() if c["group"] == "conv" and c["family"].startswith(version) and dtype in c["dtypes"]]
+            modes = [_kmode(c, dtype) for c in cs]
+            assert {m for m, _ in modes} == {0, 1, 2}, (dtype, version, sorted({m for m, _ in modes}))
+            assert any(c["k"] == 5 for c in cs), (dtype, version, "no 5x5")
+            assert any(partial for _, partial in modes), (dtype, version, "no partial last K-tile")
+            # the modes that can end inside a K-tile each do so once
+            assert {m for m, partial in modes if partial} == {1, 2}, (dtype, version)
 
 
 def test_no_family_is_dense_only():

@@ -8,6 +8,9 @@ exactly; mish and logistic must land on a storage value that a float32 result wi
 A conv that reads a non-finite activation has a NaN accumulator (0 * inf), so every conv block of the family network is
 checked in a forward of its own: the complete list in that block, finite-only lists in the blocks before it.  The plan is
 built once per test; between forwards only the device copies of scale and bias change (Darknet.update_bn).
+
+The family network has no channel count off the 16-byte chunk, so it never reaches the direct fallback: ``conv_direct_*`` gets
+the whole list in a one-op plan of its own (test_direct_conv_epilogue), with a shortcut operand and with float32 output too.
 """
 import ctypes
 
@@ -393,3 +396,82 @@ def test_shortcut_operand_non_finite(dtype, act):
     lo, hi, isnan = E.expect(act, dtype, t2, r2)
     assert isnan[0] and isnan[2] and np.isinf(lo[4])
     _gate(_nchw(out), lo, hi, isnan, "%s %s non-finite shortcut operand" % (name, act), tags, t2)
+
+
+# ---- the direct fallback --------------------------------------------------------------------------------------------------
+# conv_direct_kernel (csrc/conv_small.hip) narrows through y3_from_float<T> on a path of its own, and the family network never
+# reaches it (no odd channel count): a one-op plan through the C ABI, 1x1 conv 13 -> 128 channels on a 2 x 5 x 7 map, zero
+# weights and a finite input, so the pre-activation of channel c is +0 * scale[c] + bias[c] = the planted t[c]; the -0 entry
+# gets scale -1 (+0 * -1 = -0, and -0 + -0 = -0), every other entry scale +1.
+DIRECT_DTYPES = {"float32": (_hip.Y3_F32, torch.float32, "f32"), "bf16": (_hip.Y3_BF16, torch.bfloat16, "bf16"),
+                 "fp16": (_hip.Y3_F16, torch.float16, "f16")}
+ACT_FLAG = {"linear": 0, "leaky": _hip.F_LEAKY, "mish": _hip.F_MISH, "logistic": _hip.F_LOGISTIC}
+DIRECT_SHAPE = (2, 5, 7, 13, 128)          # B, h, w, cin, cout
+
+
+def _direct_conv(dtype, act, t, tags, r=None, out_f32=False):
+    """(stored output as (B, C, H, W) float32 on the device, kernel name) of the one-op plan with pre-activations ``t`` (one
+    per channel), shortcut operand ``r`` per channel or None, and float32 output from 16-bit storage with ``out_f32``"""
+    _hip.require_gpu()
+    lib = _hip.lib()
+    B, h, w, cin, cout = DIRECT_SHAPE
+    code, tdt, _ = DIRECT_DTYPES[dtype]
+    es = 4 if dtype == "float32" else 2
+    k_ld = -(-cin // (128 // es)) * (128 // es)
+    dev = torch.device("cuda:0")
+    x = (torch.rand((B, h, w, cin), generator=torch.Generator().manual_seed(13)) - 0.5).to(tdt).to(dev)
+    wgt = torch.zeros((cout, k_ld), dtype=tdt, device=dev)
+    neg = np.asarray([g == E.NEG_SCALE_TAG for g in tags]) & (E.bits(t) == 0x80000000)
+    scale = torch.from_numpy(np.where(neg, -1.0, 1.0).astype(np.float32)).to(dev)
+    bias = torch.from_numpy(E.f32(t).copy()).to(dev)
+    out = torch.full((B, h, w, cout), 7.0, dtype=torch.float32 if out_f32 else tdt, device=dev)
+    zero = torch.zeros(4096, dtype=torch.uint8, device=dev)
+    op = _hip.Y3Op()
+    op.kind, op.dtype, op.batch, op.block_idx = _hip.OP_CONV, code, B, 1
+    op.flags = ACT_FLAG[act] | (_hip.F_OUT_F32 if out_f32 else 0) | (_hip.F_RESIDUAL if r is not None else 0)
+    op.in_h, op.in_w, op.in_c, op.in_ld = h, w, cin, cin
+    op.out_h, op.out_w, op.out_c, op.out_ld = h, w, cout, cout
+    op.ksize, op.stride, op.pad = 1, 1, 0
+    op.cout_pad, op.k_ld = cout, k_ld
+    op.d_in, op.d_out = x.data_ptr(), out.data_ptr()
+    op.d_weight, op.d_scale, op.d_bias = wgt.data_ptr(), scale.data_ptr(), bias.data_ptr()
+    if r is not None:
+        res = torch.from_numpy(E.f32(r).copy()).to(tdt).to(dev).view(1, 1, 1, -1).expand(B, h, w, cout).contiguous()
+        op.d_res, op.res_ld = res.data_ptr(), cout
+    ops = (_hip.Y3Op * 1)(op)
+    handle = ctypes.c_void_p()
+    _hip.check(lib.y3_plan_create_ex(ops, 1, zero.data_ptr(), None, ctypes.byref(handle)))
+    try:
+        name = lib.y3_plan_op_kernel(handle, 0).decode()
+        _hip.check(lib.y3_plan_run(handle, x.data_ptr(), _hip.stream_ptr()))
+        torch.cuda.synchronize()
+    finally:
+        lib.y3_plan_destroy(handle)
+    return out.float().permute(0, 3, 1, 2).contiguous(), name
+
+
+@pytest.mark.parametrize("act", E.ACTS)
+@pytest.mark.parametrize("dtype", E.DTYPES)
+def test_direct_conv_epilogue(dtype, act):
+    want_name = "conv_direct_" + DIRECT_DTYPES[dtype][2]
+    t, idx = E.padded(act)
+    tags = [E.cases(act)[i].tag for i in idx]
+    assert E.NEG_SCALE_TAG in tags and len(t) == DIRECT_SHAPE[4]
+    got, name = _direct_conv(dtype, act, t, tags)
+    assert name == want_name, name
+    _gate(got, *E.expect(act, dtype, t), "%s %s %s" % (name, dtype, act), tags, t)
+    if dtype != "float32":
+        # Y3_F_OUT_F32: the value stored is the float32 result, not narrowed
+        got, name = _direct_conv(dtype, act, t, tags, out_f32=True)
+        assert name == want_name, name
+        _gate(got, *E.expect(act, "float32", t), "%s %s %s, float32 out" % (name, dtype, act), tags, t)
+    if act in ("linear", "leaky"):
+        # the shortcut operand is added in float32 before the one store (`v += res`): one rounding of the sum
+        r = _operand(DIRECT_SHAPE[4], 13, dtype)
+        ts, stags = E.shortcut_cases(act, dtype, r, 13)
+        got, name = _direct_conv(dtype, act, ts, stags, r=r)
+        assert name == want_name, name
+        _gate(got, *E.expect(act, dtype, ts, r, fused=True), "%s %s %s + shortcut" % (name, dtype, act), stags, ts)
+        # (float32 storage has no tie and no witness of a second rounding: E.shortcut_cases plants those as "plain")
+        kinds = {"shortcut: inexact", "shortcut: cancel", "shortcut: inf", "shortcut: nan"}
+        assert set(stags) >= kinds | (set() if dtype == "float32" else {"shortcut: witness", "shortcut: tie"}), sorted(set(stags))

@@ -10,6 +10,12 @@ the case table).  Per case, through the C ABI and under one option set, with the
   aliasing      the in-place add (d_out == d_in) and the fused blocks whose shortcut operand is the group's input run in that
                 strided layout too.
 
+The table holds every kernel the shipped cfgs' plans reach (tests/golden/kernel_choice.json) and the conv code only a user's own
+cfg reaches: the direct fallback ``conv_direct_*`` in each of its input forms (activations, float NCHW, uint8 frames; odd
+channel counts, 7x7, one input channel, float32 store from 16-bit storage), and on all three implicit-GEMM versions the
+per-chunk (KMODE 1) and several-taps (KMODE 2) K-tilings, 5x5 and even kernels and a 3x3 without padding.
+``test_implicit_gemm_versions_sum_in_one_k_order`` holds the versions to one another bit for bit on those K-tilings.
+
 Guards lie inside the allocation: a stray access is recorded, never a fault.  The reference has no counterpart of these
 layouts (the reference's yolov3/darknet.py:366-399 allocates a tensor per block).  Need an MI355X: -m gpu."""
 import ctypes
@@ -63,11 +69,11 @@ def _make_data(case, dtype, lay, paths):
         if o.name in ("input", "input/output", "residual"):
             c = o.slices[0][1]
             if o.fmt == "u8":
-                t = torch.randint(0, 256, (B, h, w, 3), generator=gen, dtype=torch.uint8)
+                t = torch.randint(0, 256, (B, h, w, case.get("cin", 3)), generator=gen, dtype=torch.uint8)
                 ref["frames"] = t.numpy()
                 data[o.name] = [t.reshape(1, -1)]
             elif case["group"] == "conv" and case["inp"] == "nchw":
-                t = torch.rand((B, 3, h, w), generator=gen).to(tdt).float()      # (storage-exact values, held as float32)
+                t = torch.rand((B, case["cin"], h, w), generator=gen).to(tdt).float()      # (storage-exact values, held as float32)
                 ref["x"] = t
                 data[o.name] = [t.reshape(1, -1)]
             else:
@@ -113,7 +119,8 @@ def _make_data(case, dtype, lay, paths):
             p = {"weight": wt.numpy(), "bn_gamma": gamma.numpy(), "bn_beta": beta.numpy(),
                  "bn_mean": np.zeros(cout, dtype=np.float32), "bn_var": var}
         data[prefix + "scale"], data[prefix + "bias"] = [sc.reshape(1, -1)], [bi.reshape(1, -1)]
-        ref["convs"].append(dict(p=p, k=k, s=s, leaky=leaky))
+        ref["convs"].append(dict(p=p, k=k, s=s, leaky=leaky, pad=case.get("pad", fu.conv_pad(k))))
+    ref["path"] = paths[0]
     return data, ref
 
 
@@ -189,18 +196,21 @@ def _nchw(t, B, h, w):
 
 def _check_dense_against_oracle(case, dtype, outs, ref, lay):
     from oracle import darknet_oracle as orc
+    from yolov3 import _hip as H
     g = case["group"]
     B, h, w = case["B"], case["h"], case["w"]
     emulate = EMULATE.get(dtype)
     acc = "f64" if dtype == "float32" else "f32"
 
     def conv(x, cv):
-        return orc.conv_block(x, cv["p"], cv["s"], (cv["k"] - 1) // 2, cv["leaky"], round_weights=emulate, accumulate=acc)
+        return orc.conv_block(x, cv["p"], cv["s"], cv["pad"], cv["leaky"], round_weights=emulate, accumulate=acc)
 
     def x_of():
         if "frames" in ref:
             x = torch.from_numpy(orc.frames_to_input(list(ref["frames"])))
-            return orc.storage_round(emulate)(x) if emulate else x
+            # the MFMA stem stores byte / 255 in the storage type before it multiplies; the VALU stem and conv_direct read the
+            # bytes themselves and multiply byte / 255 in float32 by the (storage-type) weights: no rounding of the input
+            return orc.storage_round(emulate)(x) if emulate and ref["path"] == H.PATH_STEM_MFMA else x
         return ref["x"] if ref["x"].dim() == 4 else _nchw(ref["x"], B, h, w)
 
     if g in ("conv", "stem_pair", "resblock", "block"):
@@ -321,6 +331,43 @@ def test_kernel_touches_exactly_its_operands(cid):
         for key in dense:
             assert torch.equal(strided[key], dense[key]), "%s: %d bytes of the strided, poisoned run differ from the dense run" % (
                 key, int((strided[key] != dense[key]).sum()))
+
+
+# ------------------------------------------------------------------------------------------------ one K order
+# csrc/api.hip choose_conv: "Which kernel runs changes speed only: every MFMA conv kernel sums in the same K order".
+# tests/test_gpu_parity.py::test_kernel_choice_does_not_change_a_bit holds that on the shipped shapes, all of them one tap per
+# K-tile; here the per-chunk (KMODE 1) and several-taps (KMODE 2) K-tilings of the three implicit-GEMM versions, each shape run
+# dense under several option sets on the SAME data (the case of the table that gives the shape seeds it).
+
+K_ORDER_FAMILY = {"igemm1": "conv_igemm_%s_128x{bn}", "igemm2_noshrink": "conv_igemm2_%s_128x{bn}", "igemm3": "conv_igemm3_%s_128x128",
+                  "igemm2_96": "conv_igemm2_%s_96x64", "igemm3_64": "conv_igemm3_%s_64x128"}
+# (case of the table that gives shape and data, option sets; igemm3_64 has 16-bit tiles only)
+K_ORDER_SHAPES = [("igemm1_k3s2_c40", ("igemm1", "igemm2_noshrink", "igemm3", "igemm2_96", "igemm3_64")),
+                  ("igemm1_1x1_c72", ("igemm1", "igemm2_noshrink", "igemm3", "igemm2_96", "igemm3_64")),
+                  ("igemm3_128_k5_c16_res", ("igemm3", "igemm2_96", "igemm3_64")),
+                  ("igemm1_k3_c24_res", ("igemm1", "igemm2_noshrink"))]
+
+
+@pytest.mark.parametrize("dtype", fu.ALL)
+@pytest.mark.parametrize("cid,opts", K_ORDER_SHAPES, ids=["k3s2_c40", "1x1_c72", "k5_c16_res", "k3_c24_res"])
+def test_implicit_gemm_versions_sum_in_one_k_order(cid, opts, dtype):
+    from yolov3 import _hip
+    _hip.require_gpu()
+    base = fu.case_by_id(cid)
+    first = None
+    for opt in opts:
+        if opt == "igemm3_64" and dtype == "float32":
+            continue
+        family = K_ORDER_FAMILY[opt].format(bn=128 if base["cout"] > 64 else 64)
+        outs, msg, names, _, _ = _run(dict(base, opt=opt, family=family), dtype, "dense")
+        assert names[0] == family % fu.TAG[dtype], (opt, names)
+        assert msg is None, "%s: %s" % (opt, msg)
+        if first is None:
+            first = (opt, names[0], outs)
+            continue
+        differ = int((outs["output/0"] != first[2]["output/0"]).sum())
+        assert differ == 0, "%s %s: %d bytes of %s (%s) differ from %s (%s)" % (
+            cid, dtype, differ, names[0], opt, first[1], first[0])
 
 
 # ------------------------------------------------------------------------------------------------ the other entry points
