@@ -239,6 +239,7 @@ int y3_abi_version(void);
 #define Y3_CAP_MULTI_LABEL 256u /* y3_expand_labels and its workspace query   */
 #define Y3_CAP_PREPROCESS_DARKNET 512u /* y3_preprocess_darknet_f32            */
 #define Y3_CAP_REORG 1024u     /* Y3_OP_REORG and Y3_F_REORG_3D              */
+#define Y3_CAP_LAUNCH_LOG 2048u /* y3_debug_launch_log_begin, y3_debug_launch_log_end */
 uint32_t y3_capabilities(void);
 const char *y3_last_error(void);
 /* number of visible HIP devices whose arch is gfx950 (0 on a CPU-only machine) */
@@ -288,6 +289,17 @@ int y3_conv_make_fragment_weights(const y3_op *op, void *d_dst, void *stream);
  * "fuse_head", "fuse_spp", "decode_lanes", "fuse_block").  Plans created afterwards without explicit options pick it up; existing
  * plans keep the options they were created with.                                                                  */
 int y3_set_tuning(const char *key, int value);
+
+/* Launch log (tests and tools only; host code, the kernels are the same): between the two calls every kernel the CALLING
+ * THREAD launches through this library is recorded by its code-object symbol name, the mangled name the `.name` field of the
+ * AMDGPU metadata holds (e.g. _Z16conv_dw48_kernelIDF16bLi3ELi2ELi2ELi1EEv...), in launch order, one name per line.  A replayed
+ * hipGraph (use_graph) launches nothing through the library and logs nothing.  y3_debug_launch_log_begin fails when the thread
+ * has a log already.  y3_debug_launch_log_end copies the NUL-terminated text into `names` and ends the log; *needed (may be
+ * NULL) receives the bytes the text takes, NUL included.  With names == NULL or capacity < *needed it returns Y3_ERR_INVALID
+ * and the log stays open -- the size query -- so the caller asks, allocates and calls again.  A launch whose name the runtime
+ * could not give is logged as "?" and makes the ending call return Y3_ERR_INVALID after it has copied the text.       */
+int y3_debug_launch_log_begin(void);
+int y3_debug_launch_log_end(char *names, size_t capacity, size_t *needed);
 
 /* single op (unit tests): same dispatch as inside a plan */
 int y3_op_run(const y3_op *op, const void *d_input, const void *d_zero, void *stream);

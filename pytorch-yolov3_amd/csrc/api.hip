@@ -5,6 +5,7 @@
 
 #include <atomic>
 #include <new>
+#include <string>
 #include <vector>
 
 #include "common.h"
@@ -19,8 +20,28 @@ thread_local char g_err[512] = "";
 static y3_options g_y3_defaults = {/*auto_mask*/ (int32_t)Y3_AM_DEFAULT, /*unused0*/ 0, /*igemm_version*/ 2, /*igemm_ns*/ 2,
                                    /*igemm_bm*/ 0, /*use_graph*/ 0, /*fuse_stem*/ 1, /*fuse_head*/ 1, /*fuse_spp*/ 1,
                                    /*decode_lanes*/ 4, /*fuse_block*/ 0, {0, 0, 0, 0, 0}};
-static thread_local Y3KernelTimer *tl_y3_timer = nullptr;
-Y3KernelTimer *y3_kernel_timer() { return tl_y3_timer; }
+static thread_local Y3LaunchHooks tl_y3_hooks = {nullptr, nullptr};
+Y3LaunchHooks *y3_launch_hooks() { return &tl_y3_hooks; }
+// The launch log of one thread: newline-separated symbol names in launch order.  A launch whose name the runtime cannot
+// give is recorded as "?" and makes y3_debug_launch_log_end fail: a census must never miss a kernel quietly.
+struct Y3LaunchLog {
+  std::string names;
+  bool unnamed = false;
+};
+void y3_launch_log_append(Y3LaunchLog *log, const void *host_function, hipStream_t stream) {
+  const char *name = hipKernelNameRefByPtr(host_function, stream);
+  if (!name || !*name) {
+    hipFunction_t f = nullptr;
+    if (hipGetFuncBySymbol(&f, host_function) == hipSuccess && f) name = hipKernelNameRef(f);
+    else (void)hipGetLastError();
+  }
+  if (!name || !*name) {
+    name = "?";
+    log->unnamed = true;
+  }
+  log->names += name;
+  log->names += '\n';
+}
 // y3_set_tuning("debug", v): exists in DIAGNOSTIC builds only (`make variant FLAGS=-DY3_X_...`, `make stamps`); the product
 // library rejects the key, so a benchmark line can never come from kernels that skip work
 #if defined(Y3_X_NOEPI) || defined(Y3_X_S2BOUND) || defined(Y3_X_DEBUG) || defined(Y3_STAMPS)
@@ -257,7 +278,30 @@ int y3_abi_version(void) { return Y3_ABI_VERSION; }
 
 uint32_t y3_capabilities(void) {
   return Y3_CAP_MISH | Y3_CAP_SCALE_X_Y | Y3_CAP_LOGISTIC | Y3_CAP_NEW_COORDS | Y3_CAP_LETTERBOX | Y3_CAP_POOL_DARKNET |
-         Y3_CAP_NMS_DARKNET | Y3_CAP_SCORES_DARKNET | Y3_CAP_MULTI_LABEL | Y3_CAP_PREPROCESS_DARKNET | Y3_CAP_REORG;
+         Y3_CAP_NMS_DARKNET | Y3_CAP_SCORES_DARKNET | Y3_CAP_MULTI_LABEL | Y3_CAP_PREPROCESS_DARKNET | Y3_CAP_REORG |
+         Y3_CAP_LAUNCH_LOG;
+}
+
+int y3_debug_launch_log_begin(void) {
+  Y3_REQUIRE(!tl_y3_hooks.log, "y3_debug_launch_log_begin: this thread has a launch log already");
+  tl_y3_hooks.log = new (std::nothrow) Y3LaunchLog;
+  Y3_REQUIRE(tl_y3_hooks.log, "y3_debug_launch_log_begin: out of memory");
+  return Y3_OK;
+}
+
+int y3_debug_launch_log_end(char *names, size_t capacity, size_t *needed) {
+  Y3LaunchLog *log = tl_y3_hooks.log;
+  Y3_REQUIRE(log, "y3_debug_launch_log_end: this thread has no launch log");
+  const size_t n = log->names.size() + 1;
+  if (needed) *needed = n;
+  // too small a buffer is the size query: the log stays open (and goes on recording) until a call that can take it
+  Y3_REQUIRE(names && capacity >= n, "y3_debug_launch_log_end: the log needs %zu bytes, the buffer has %zu", n, capacity);
+  memcpy(names, log->names.c_str(), n);
+  const bool unnamed = log->unnamed;
+  tl_y3_hooks.log = nullptr;
+  delete log;
+  Y3_REQUIRE(!unnamed, "y3_debug_launch_log_end: the runtime gave no name for a launched kernel (logged as \"?\")");
+  return Y3_OK;
 }
 
 const char *y3_last_error(void) { return g_err; }
@@ -455,13 +499,13 @@ int y3_plan_run_profiled(y3_plan *plan, const void *d_input, void *stream, float
   Y3KernelTimer timer = {plan->kstart.data(), plan->kstop.data(), 0, (int)cap};
   std::vector<int> first(n + 1, 0);
   int rc = Y3_OK;
-  tl_y3_timer = &timer;
+  tl_y3_hooks.timer = &timer;
   for (size_t i = 0; i < n && rc == Y3_OK; ++i) {
     first[i] = timer.n;
     rc = run_op(plan, i, d_input, s);
   }
   first[n] = timer.n;
-  tl_y3_timer = nullptr;
+  tl_y3_hooks.timer = nullptr;
   if (rc != Y3_OK) return rc;
   Y3_HIP_CHECK(hipStreamSynchronize(s));
   for (size_t i = 0; i < n; ++i) {

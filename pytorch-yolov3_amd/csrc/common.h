@@ -69,10 +69,21 @@ struct Y3KernelTimer {
   hipEvent_t *start, *stop;
   int n, cap;
 };
-Y3KernelTimer *y3_kernel_timer();
+// The launch log (y3_debug_launch_log_begin / _end, api.hip): while the calling thread has one, Y3_LAUNCH appends the kernel's
+// code-object symbol name -- the mangled name in the `.name` field of the AMDGPU metadata -- before it launches.  Host code
+// only.  Timer and log share one thread-local pair, so a launch with neither pays the one thread-local access it always paid.
+struct Y3LaunchLog;
+struct Y3LaunchHooks {
+  Y3KernelTimer *timer;
+  Y3LaunchLog *log;
+};
+Y3LaunchHooks *y3_launch_hooks();
+void y3_launch_log_append(Y3LaunchLog *log, const void *host_function, hipStream_t stream);
 #define Y3_LAUNCH(kernel, grid, block, lds, stream, ...)                                                             \
   do {                                                                                                               \
-    Y3KernelTimer *_kt = y3_kernel_timer();                                                                          \
+    const Y3LaunchHooks *_hk = y3_launch_hooks();                                                                    \
+    if (_hk->log) y3_launch_log_append(_hk->log, reinterpret_cast<const void *>(kernel), stream);                    \
+    Y3KernelTimer *_kt = _hk->timer;                                                                                 \
     if (_kt && _kt->n < _kt->cap) {                                                                                  \
       hipExtLaunchKernelGGL(kernel, grid, block, lds, stream, _kt->start[_kt->n], _kt->stop[_kt->n], 0, __VA_ARGS__); \
       ++_kt->n;                                                                                                      \

@@ -38,6 +38,7 @@ F_MISH, F_LOGISTIC, F_NEW_COORDS, F_POOL_DARKNET, F_SCORES_DARKNET, F_REORG_3D =
 # y3_capabilities() bits: what the loaded library computes beyond ABI 6 as first released
 CAP_MISH, CAP_SCALE_X_Y, CAP_LOGISTIC, CAP_NEW_COORDS, CAP_LETTERBOX, CAP_POOL_DARKNET = 1, 2, 4, 8, 16, 32
 CAP_NMS_DARKNET, CAP_SCORES_DARKNET, CAP_MULTI_LABEL, CAP_PREPROCESS_DARKNET, CAP_REORG = 64, 128, 256, 512, 1024
+CAP_LAUNCH_LOG = 2048
 # Darknet's suppression measures (include/yolov3_hip.h: Y3_NMS_*), by the cfg's spelling of `nms_kind`
 NMS_IOU, NMS_GREEDY, NMS_DIOU = 0, 1, 2
 NMS_KINDS = {"iou": NMS_IOU, "greedynms": NMS_GREEDY, "diounms": NMS_DIOU}
@@ -131,6 +132,8 @@ PROTOTYPES = {
     "y3_conv_fragment_weight_bytes": (ctypes.c_size_t, [ctypes.POINTER(Y3Op), ctypes.POINTER(Y3Options)]),
     "y3_conv_make_fragment_weights": (ctypes.c_int, [ctypes.POINTER(Y3Op), ctypes.c_void_p, ctypes.c_void_p]),
     "y3_set_tuning": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_int]),
+    "y3_debug_launch_log_begin": (ctypes.c_int, []),
+    "y3_debug_launch_log_end": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]),
     "y3_op_run": (ctypes.c_int, [ctypes.POINTER(Y3Op), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "y3_detect_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
     "y3_detect": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
@@ -184,7 +187,8 @@ PROTOTYPES = {
 # symbols a library of ABI 6 built before they were added lacks: asked for through capabilities()
 _OPTIONAL = ("y3_capabilities", "y3_detect_letterbox", "y3_letterbox_geometry", "y3_letterbox_u8",
              "y3_detect_darknet_workspace_bytes", "y3_detect_darknet", "y3_nms_darknet_workspace_bytes", "y3_nms_darknet",
-             "y3_expand_labels_workspace_bytes", "y3_expand_labels", "y3_preprocess_darknet_f32")
+             "y3_expand_labels_workspace_bytes", "y3_expand_labels", "y3_preprocess_darknet_f32",
+             "y3_debug_launch_log_begin", "y3_debug_launch_log_end")
 
 
 class HipLibraryError(RuntimeError):
@@ -279,6 +283,33 @@ def nms_mode(nms_kind, beta_nms=0.6):
     if not (beta > 0.0 and beta != float("inf")):
         raise ValueError("beta_nms must be finite and > 0 (as float32), got {!r}".format(beta_nms))
     return NMS_KINDS[nms_kind], beta
+
+
+class launch_log:
+    """``with launch_log() as log:`` records the code-object symbol name of every kernel this thread launches through the
+    library inside the block (``y3_debug_launch_log_begin`` / ``_end``); afterwards ``log.names`` is the list in launch order
+    and ``log.symbols`` the sorted set.  Tests and tools only."""
+
+    def __init__(self):
+        self.names, self.symbols = [], []
+
+    def __enter__(self):
+        if not capabilities() & CAP_LAUNCH_LOG:
+            raise HipLibraryError("the loaded libyolov3_hip.so has no launch log (rebuild: make -C pytorch-yolov3_amd/csrc)")
+        check(lib().y3_debug_launch_log_begin())
+        return self
+
+    def __exit__(self, *exc):
+        handle = lib()
+        need = ctypes.c_size_t(0)
+        handle.y3_debug_launch_log_end(None, 0, ctypes.byref(need))          # the size query: fails by design, fills `need`
+        buf = ctypes.create_string_buffer(need.value)
+        rc = handle.y3_debug_launch_log_end(buf, need.value, None)
+        self.names = buf.value.decode().split()
+        self.symbols = sorted(set(self.names))
+        if exc[0] is None:
+            check(rc)
+        return False
 
 
 def options(**overrides):

@@ -201,6 +201,8 @@ def _opts():
         igemm2_96=dict(auto_mask=0, igemm_bm=96),
         igemm3=dict(auto_mask=0, igemm_version=3),
         igemm3_64=dict(auto_mask=0, igemm_version=3, igemm_bm=64),
+        igemm3_ns4=dict(auto_mask=0, igemm_version=3, igemm_ns=4),
+        igemm3_64_ns4=dict(auto_mask=0, igemm_version=3, igemm_bm=64, igemm_ns=4),
         halo192=dict(auto_mask=halo),
         halo256=dict(auto_mask=halo | H.AM_HALO_TILE256),
         halo_dw=dict(auto_mask=halo | H.AM_HALO_DW_ALWAYS),
@@ -209,6 +211,7 @@ def _opts():
         dw1x1=dict(auto_mask=H.AM_1X1_DW),
         dw48=dict(auto_mask=H.AM_SMALL_DW | H.AM_SMALL_DW_ALWAYS),
         default={},
+        stem_phased=dict(fuse_stem=2),
         fuse_block=dict(fuse_block=2),
         head_tiled=dict(fuse_head=2),
         head48=dict(fuse_head=3),
@@ -238,7 +241,13 @@ def _layer(cid, family, kind, dtypes, B, h, w, c, k=1, s=1, wide=True, dk=False,
 def cases():
     """Every case: at least a full-tile and a ragged shape per family (the last pixel tile partial, the map not square where
     the family allows it), with and without the shortcut operand where the family takes one.  ``family`` is the kernel name
-    with %s for the dtype tag.  Shapes stay at or below 16 x 76 x 76 x 512."""
+    with %s for the dtype tag.  Shapes stay at or below 16 x 76 x 76 x 512.
+
+    Below the family name the library is compiled by INSTANCE (the y3_ints lists of the .hip files): the rows marked
+    "instance" are there for one compiled device function that no other row launches (tests/kernel_census.py has the proof that
+    none is left out).  A row with ``nkt`` is for a direct-weights instance of that K depth, which dictates its channel count,
+    in_c = 64 x nkt per halo image: the only rows that may exceed 512 channels.  ``wide_map``: the two-image stride-2 form of
+    conv_dw48 at 256 channels, whose halo image outgrows LDS only on rows of 124 pixels and more."""
     C = []
     # ---- implicit GEMMs (conv_igemm.hip).  Tile widths follow Cout (128 / 64 / 32); version 2 shrinks them on small grids
     # unless AM_NO_BN_SHRINK; pixel tiles are 128 (96, 64): "full" shapes have B*Ho*Wo a multiple of the tile
@@ -290,6 +299,19 @@ def cases():
         # the route by which an unforced plan reaches KMODE 1: the chooser's own small-grid rule (api.hip choose_conv) sends a
         # 160 -> 128 3x3 layer on a 19 x 19 map to the wave-specialised implicit GEMM
         _conv("default_k3_c160", "conv_igemm3_%s_128x128", "default", B16, 1, 19, 19, 160, 128, 3, 1, res=True),
+        # instances: the LDS-DMA kernel's K-tilings on the tiles the rows above leave out (KMODE 2 at 128 x 128 and, in float32, at
+        # 128 x 64; KMODE 1 at 128 x 32) ...
+        _conv("igemm2_128_k3_c16", "conv_igemm2_%s_128x128", "igemm2_noshrink", ALL, 2, 13, 11, 16, 128, 3, 1, res=True),
+        _conv("igemm2_64_k3_c16", "conv_igemm2_%s_128x64", "igemm2_noshrink", ALL, 1, 19, 13, 16, 64, 3, 1),
+        _conv("igemm2_32_k3_c24", "conv_igemm2_%s_128x32", "igemm2_noshrink", ALL, 2, 15, 9, 24, 32, 3, 1, res=True),
+        # ... and the wave-specialised kernel with FOUR LDS stages (igemm_ns = 4; every row above runs the default three), each
+        # K-tiling on both tiles
+        _conv("igemm3_128_ns4_full", "conv_igemm3_%s_128x128", "igemm3_ns4", ALL, 2, 16, 16, 128, 128, 3, 1, res=True),
+        _conv("igemm3_128_ns4_k3s2_c40", "conv_igemm3_%s_128x128", "igemm3_ns4", ALL, 1, 27, 21, 40, 128, 3, 2),
+        _conv("igemm3_128_ns4_k5_c16_res", "conv_igemm3_%s_128x128", "igemm3_ns4", ALL, 2, 13, 11, 16, 128, 5, 1, res=True),
+        _conv("igemm3_64_ns4_ragged", "conv_igemm3_%s_64x128", "igemm3_64_ns4", B16, 3, 13, 9, 128, 256, 3, 1),
+        _conv("igemm3_64_ns4_1x1_c72", "conv_igemm3_%s_64x128", "igemm3_64_ns4", B16, 3, 13, 11, 72, 128, 1, 1),
+        _conv("igemm3_64_ns4_k5_c16_res", "conv_igemm3_%s_64x128", "igemm3_64_ns4", B16, 2, 13, 11, 16, 128, 5, 1, res=True),
         # ---- halo-reuse strip kernels (conv_halo.hip): 192- / 256-pixel strips of whole rows x 128 channels; float32 too
         _conv("halo192_full", "conv_halo_ws_%s_192x128", "halo192", ALL, 2, 24, 16, 128, 128, 3, 1, res=True, out_unit=8),
         _conv("halo192_ragged", "conv_halo_ws_%s_192x128", "halo192", ALL, 3, 19, 13, 128, 256, 3, 1, out_unit=8),
@@ -297,10 +319,15 @@ def cases():
         _conv("halo256_full", "conv_halo_ws_%s_256x128", "halo256", ALL, 2, 16, 16, 128, 128, 3, 1, res=True, out_unit=8),
         _conv("halo256_ragged", "conv_halo_ws_%s_256x128", "halo256", ALL, 3, 19, 13, 128, 256, 3, 1, out_unit=8),
         _conv("halo256_ragged_76", "conv_halo_ws_%s_256x128", "halo256", ALL, 1, 76, 52, 128, 128, 3, 1, res=True, out_unit=8),
+        # instance: rows of 63 px and more leave the 256-pixel tile THREE weight slots (conv_halo.hip launch_conv_halo: na > 12)
+        _conv("halo256_ring3_w76", "conv_halo_ws_%s_256x128", "halo256", ALL, 1, 26, 76, 128, 128, 3, 1, res=True, out_unit=8),
         # direct-weights strip kernel: 192 pixels x 256 channels, fragment-order weights
         _conv("halo_dw_full", "conv_halo_dw_%s_192x256", "halo_dw", B16, 2, 24, 16, 128, 256, 3, 1, res=True),
         _conv("halo_dw_ragged", "conv_halo_dw_%s_192x256", "halo_dw", B16, 3, 19, 13, 256, 512, 3, 1),
         _conv("halo_dw_ragged_res", "conv_halo_dw_%s_192x256", "halo_dw", B16, 2, 38, 26, 128, 256, 3, 1, res=True),
+        # instances: five halo passes per chunk (rows of 31 .. 62 px) and six (63 .. 94); the rows above have four
+        _conv("halo_dw_na5_w38", "conv_halo_dw_%s_192x256", "halo_dw", B16, 1, 19, 38, 128, 256, 3, 1, res=True),
+        _conv("halo_dw_na6_w76", "conv_halo_dw_%s_192x256", "halo_dw", B16, 1, 13, 76, 128, 256, 3, 1),
         # 2-D patch kernel: 8 x 32 output tiles; its chooser asks rows wider than 128 px (api.hip: `w > 128`), so these maps are
         # wide and low: h * w stays below 76 * 76
         _conv("patch_full", "conv_patch_wsp_%s_8x32x128", "patch", ALL, 1, 16, 160, 64, 128, 3, 1, res=True, out_unit=8),
@@ -317,6 +344,15 @@ def cases():
         _conv("dw1x1_96_ragged", "conv1x1_dw_%s_96x256", "dw1x1", B16, 16, 38, 37, 512, 256, 1, 1),
         _conv("dw1x1_48_full", "conv1x1_dw_%s_48x256", "dw1x1", B16, 8, 24, 16, 512, 256, 1, 1),
         _conv("dw1x1_48_ragged", "conv1x1_dw_%s_48x256", "dw1x1", B16, 9, 19, 19, 512, 256, 1, 1),
+        # instances: the K depths 4, 6 and 12 at both tile heights and 16 at 48 pixels (the rows above: 8), on the maps of the rows
+        # above (768 channels: on the fewest 96-pixel tiles the chooser takes, 197)
+        _conv("dw1x1_96_c256", "conv1x1_dw_%s_96x256", "dw1x1", B16, 16, 38, 37, 256, 256, 1, 1, nkt=4),
+        _conv("dw1x1_96_c384", "conv1x1_dw_%s_96x256", "dw1x1", B16, 16, 38, 37, 384, 256, 1, 1, nkt=6),
+        _conv("dw1x1_96_c768", "conv1x1_dw_%s_96x256", "dw1x1", B16, 16, 38, 31, 768, 256, 1, 1, nkt=12),
+        _conv("dw1x1_48_c256", "conv1x1_dw_%s_48x256", "dw1x1", B16, 9, 19, 19, 256, 256, 1, 1, nkt=4),
+        _conv("dw1x1_48_c384", "conv1x1_dw_%s_48x256", "dw1x1", B16, 9, 19, 19, 384, 256, 1, 1, nkt=6),
+        _conv("dw1x1_48_c768", "conv1x1_dw_%s_48x256", "dw1x1", B16, 9, 19, 19, 768, 256, 1, 1, nkt=12),
+        _conv("dw1x1_48_c1024", "conv1x1_dw_%s_48x256", "dw1x1", B16, 9, 19, 19, 1024, 256, 1, 1, nkt=16),
         # ---- small-grid direct-weights kernel (conv_dw48.hip): 48-pixel tiles, one frame at a time
         _conv("dw48_k1_full", "conv_dw48_k1_%s", "dw48", B16, 1, 24, 16, 256, 128, 1, 1, res=True),
         _conv("dw48_k1_ragged", "conv_dw48_k1_%s", "dw48", B16, 2, 19, 13, 512, 256, 1, 1),
@@ -326,6 +362,17 @@ def cases():
         _conv("dw48_k3s2_full", "conv_dw48_k3s2_%s", "dw48", B16, 1, 48, 32, 128, 256, 3, 2),
         _conv("dw48_k3s2_ragged", "conv_dw48_k3s2_%s", "dw48", B16, 2, 38, 26, 256, 512, 3, 2),
         _conv("dw48_k3s2_ragged_1frame", "conv_dw48_k3s2_%s", "dw48", B16, 1, 38, 22, 256, 512, 3, 2),
+        # instances: 1x1 with 2, 6, 12 and 16 K-steps (the rows above: 4 and 8); 3x3 with 8; stride 2 with one K-step (64 channels)
+        # and as two halo images of half the channels each, 4 K-steps per image (512 channels on any map) and 2 (256 channels,
+        # where one image of all channels outgrows LDS: 124 px and wider)
+        _conv("dw48_k1_c128_res", "conv_dw48_k1_%s", "dw48", B16, 1, 19, 13, 128, 128, 1, 1, res=True, nkt=2),
+        _conv("dw48_k1_c384", "conv_dw48_k1_%s", "dw48", B16, 2, 13, 11, 384, 256, 1, 1, nkt=6),
+        _conv("dw48_k1_c768", "conv_dw48_k1_%s", "dw48", B16, 1, 19, 13, 768, 256, 1, 1, nkt=12),
+        _conv("dw48_k1_c1024_res", "conv_dw48_k1_%s", "dw48", B16, 2, 13, 11, 1024, 128, 1, 1, res=True, nkt=16),
+        _conv("dw48_k3_c512_res", "conv_dw48_k3_%s", "dw48", B16, 1, 19, 13, 512, 256, 3, 1, res=True, nkt=8),
+        _conv("dw48_k3s2_c64", "conv_dw48_k3s2_%s", "dw48", B16, 1, 38, 26, 64, 128, 3, 2, nkt=1),
+        _conv("dw48_k3s2_c512_two_images", "conv_dw48_k3s2_%s", "dw48", B16, 1, 26, 22, 512, 256, 3, 2, nkt=4),
+        _conv("dw48_k3s2_c256_two_images", "conv_dw48_k3s2_%s", "dw48", B16, 1, 6, 126, 256, 128, 3, 2, nkt=2, wide_map=True),
         # ---- stems (conv_small.hip): the network input is a whole dense tensor by definition (no pixel stride), so only the
         # output is a slice; the input is an exact-size body between guards (uint8 frames: guards 0x00 and 0xFF)
         _conv("stem_nchw_full", "conv_stem3x3_nchw_%s", "default", ALL, 2, 32, 32, 3, 32, 3, 1, inp="nchw"),
@@ -335,6 +382,10 @@ def cases():
         _conv("stem_mfma_full", "conv_stem_mfma_u8_%s", "default", B16, 2, 32, 32, 3, 32, 3, 1, inp="u8"),
         _conv("stem_mfma_ragged", "conv_stem_mfma_u8_%s", "default", B16, 3, 29, 21, 3, 32, 3, 1, inp="u8"),
         _conv("stem_mfma_ragged_16ch", "conv_stem_mfma_u8_%s", "default", B16, 1, 45, 37, 3, 16, 3, 1, inp="u8"),
+        # instance: uint8 frames into a 16-bit network where the MFMA stem declines (stride 2; more than 32 output channels): the
+        # VALU stem kernel with 16-bit stores.  No shipped cfg reaches it
+        _conv("stem_u8_16bit_s2", "conv_stem3x3_u8_%s", "default", B16, 2, 32, 32, 3, 32, 3, 2, inp="u8"),
+        _conv("stem_u8_16bit_c48", "conv_stem3x3_u8_%s", "default", B16, 3, 29, 21, 3, 48, 3, 1, inp="u8"),
         # ---- the direct fallback (conv_small.hip conv_direct_kernel, one thread per output element): what api.hip conv_path gives
         # a conv on activations that the implicit GEMMs decline (in_c no multiple of the 16-byte chunk, size > 5, out_ld % 4 != 0)
         # and a network-input conv that is not 3 channels x 3x3.  No shipped cfg reaches it
@@ -351,6 +402,9 @@ def cases():
     C += [
         dict(id="stem_s2_full", group="stem_pair", family="conv_stem_s2_fused_u8_%s", opt="default", dtypes=B16, B=2, h=64, w=64),
         dict(id="stem_s2_ragged", group="stem_pair", family="conv_stem_s2_fused_u8_%s", opt="default", dtypes=B16, B=3, h=45, w=37),
+        # instance: the phase-by-phase form of the fused stem pair (fuse_stem = 2), one name with the pipelined form
+        dict(id="stem_s2_phased_full", group="stem_pair", family="conv_stem_s2_fused_u8_%s", opt="stem_phased", dtypes=B16, B=2, h=64, w=64),
+        dict(id="stem_s2_phased_ragged", group="stem_pair", family="conv_stem_s2_fused_u8_%s", opt="stem_phased", dtypes=B16, B=3, h=45, w=37),
         # the shortcut operand of the fused residual block IS the group's input (always: the chooser requires it)
         dict(id="resblock_full", group="resblock", family="conv_resblock_fused_%s_64_32_64", opt="default", dtypes=B16, B=2, h=32, w=32),
         dict(id="resblock_ragged", group="resblock", family="conv_resblock_fused_%s_64_32_64", opt="default", dtypes=B16, B=3, h=29, w=21),
@@ -363,6 +417,8 @@ def cases():
         dict(id="head48_ragged", group="head", family="conv_head_decode_dw_%s_48x256", opt="head48", dtypes=B16, B=3, h=19, w=13, cin=512),
         dict(id="head96_full", group="head", family="conv_head_decode_dw_%s_96x256", opt="head96", dtypes=B16, B=2, h=12, w=12, cin=256),
         dict(id="head96_ragged", group="head", family="conv_head_decode_dw_%s_96x256", opt="head96", dtypes=B16, B=3, h=19, w=13, cin=512),
+        # instance: sixteen K-steps (48-pixel tiles only: conv_1x1.hip dw_head_bm)
+        dict(id="head48_c1024", group="head", family="conv_head_decode_dw_%s_48x256", opt="head48", dtypes=B16, B=1, h=13, w=11, cin=1024, nkt=16),
     ]
     # ---- layer kernels (layers.hip): the wide form (16-byte vectors) and the element-wise form, which is chosen when in_c or a
     # stride is not a multiple of the vector width
@@ -378,6 +434,13 @@ def cases():
             _layer("add_inplace_" + tag, "add_%s", "add", ALL, 3, 19, 13, c, wide=wide, alias=True),
             _layer("copy_" + tag, "copy_%s", "copy", ALL, 3, 19, 13, c, wide=wide),
         ]
+    # Darknet's [reorg] (layers.hip reorg_kernel: one instance per element size), the flat form and the space-to-depth form
+    C += [
+        dict(id="reorg_full", group="reorg", family="reorg_%s", opt="default", dtypes=ALL, B=2, h=16, w=16, c=64, s=2, form3d=False),
+        dict(id="reorg_ragged", group="reorg", family="reorg_%s", opt="default", dtypes=ALL, B=3, h=14, w=10, c=12, s=2, form3d=False),
+        dict(id="reorg3d_full", group="reorg", family="reorg3d_%s", opt="default", dtypes=ALL, B=2, h=16, w=16, c=64, s=2, form3d=True),
+        dict(id="reorg3d_ragged", group="reorg", family="reorg3d_%s", opt="default", dtypes=ALL, B=3, h=15, w=9, c=13, s=3, form3d=True),
+    ]
     C += [
         dict(id="spp_full", group="spp", family="maxpool_spp_pyramid_%s", opt="default", dtypes=ALL, B=2, h=16, w=16, c=64, dk=False),
         dict(id="spp_ragged", group="spp", family="maxpool_spp_pyramid_%s", opt="default", dtypes=ALL, B=3, h=19, w=13, c=48, dk=False),
@@ -398,7 +461,9 @@ DENSE_ONLY = {}
 
 # kernel names the choosers can produce that no plan of the shipped cfgs under kernel_choice_util.OPTION_SETS reaches, so
 # tests/golden/kernel_choice.json does not hold them: covered here all the same
-NOT_IN_FIXTURE = ("add_%s", "copy_%s", "maxpool_dk_%s", "maxpool_spp_pyramid_dk_%s", "conv_direct_%s")
+# (an entry without %s is one name: the float32 VALU stem on uint8 frames IS in the fixture, its 16-bit forms are not)
+NOT_IN_FIXTURE = ("add_%s", "copy_%s", "maxpool_dk_%s", "maxpool_spp_pyramid_dk_%s", "conv_direct_%s", "reorg_%s", "reorg3d_%s",
+                  "conv_stem3x3_u8_bf16", "conv_stem3x3_u8_f16")
 
 
 def case_ids():
@@ -658,6 +723,21 @@ def build(case, dtype, mode, opt, base=None):
             op.res_ld = r.ld
             ptrs.append((0, "d_res", "residual", 0))
         return finish(ops, ptrs) + (None,)
+
+    if g == "reorg":
+        c, st = case["c"], case["s"]
+        co = c * st * st
+        ops = (H.Y3Op * 1)()
+        op = ops[0]
+        op.kind, op.dtype, op.batch, op.stride = H.OP_REORG, DT_CODE[dtype], B, st
+        op.flags = H.F_REORG_3D if case["form3d"] else 0
+        op.in_h, op.in_w, op.in_c, op.out_h, op.out_w, op.out_c = h, w, c, h // st, w // st, co
+        # (an element-wise kernel: strides are multiples of nothing, as for the element-wise layer forms)
+        x = _act(used, "input", "in", dtype, P, c, mode, 1, 0)
+        o = _act(used, "output", "out", dtype, B * op.out_h * op.out_w, co, mode, 1, 1)
+        operands += [x, o]
+        op.in_ld, op.out_ld = x.ld, o.ld
+        return finish(ops, [(0, "d_in", "input", 0), (0, "d_out", "output", 0)]) + (None,)
 
     if g == "spp":
         c = case["c"]

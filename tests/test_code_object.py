@@ -111,3 +111,82 @@ def test_device_code_hash_does_not_depend_on_the_build_directory(tmp_path):
     assert bench.device_code_sha256(objs[0]) == bench.device_code_sha256(objs[1])
     # ... and it is a hash of the kernels: another source gives another value
     assert bench.device_code_sha256(objs[0]) != bench.device_code_sha256(LIB)
+
+
+# ---- the census of compiled instances (tests/kernel_census.py) ---------------------------------------------------------------
+
+def _census():
+    import kernel_census as census
+    if not os.path.exists(census.FIXTURE):
+        pytest.fail("tests/golden/kernel_instances.json is missing (tools/make_kernel_instances.py writes it on an MI355X)")
+    return census, census.load()
+
+
+def test_every_compiled_kernel_is_launched_by_a_footprint_case_or_provably_by_nothing(kernels):
+    """Coverage: every ``.name`` of the library's code objects is in the union of the fixture's ``footprint`` map -- a one-op
+    test with the oracle gate, the strided / poisoned run and the byte-for-byte footprint check launched it on an MI355X --
+    or in ``kernel_census.UNREACHABLE`` with the chooser condition that excludes it.  Never both: no recorded GPU test
+    launches an UNREACHABLE symbol."""
+    census, fixture = _census()
+    library = {k[".name"] for k in kernels}
+    t = census.totals(fixture, library)
+    print("kernel census: %(symbols)d symbols, %(covered)d covered by footprint cases, %(unreachable)d unreachable" % t)
+    rep = census.report(fixture, library)
+    bad = [m for m in census.failures(fixture, library) if "footprint case" in m or "UNREACHABLE that" in m]
+    assert not rep["uncovered"] and not rep["unreachable_but_launched"], "\n".join(bad)
+    assert t["covered"] + t["unreachable"] == t["symbols"]
+    for sym, reason in census.UNREACHABLE.items():
+        assert ".hip:" in reason, "UNREACHABLE[%s] names no chooser line" % sym
+
+
+def test_census_names_no_kernel_the_library_lacks(kernels):
+    """Stale check: every symbol named in the fixture or in UNREACHABLE exists in the library (a removed or renamed instance
+    must leave the record too)."""
+    census, fixture = _census()
+    library = {k[".name"] for k in kernels}
+    assert not census.report(fixture, library)["stale"], "\n".join(m for m in census.failures(fixture, library) if "does not hold" in m)
+    assert set(fixture) == {"footprint", "contention"} and fixture["footprint"] and fixture["contention"]
+    for table in fixture.values():
+        for key, syms in table.items():
+            assert syms == sorted(set(syms)) and syms, key
+
+
+def test_every_run_ahead_instance_runs_beside_the_copy_kernel(kernels):
+    """Contention: every instance of the register-destination run-ahead families -- conv1x1_dw_kernel with both HEAD values,
+    conv_dw48_kernel, conv_halo_dw_kernel: the kernels whose template parameter sets their wait counts -- is in the union of
+    the fixture's ``contention`` map, or UNREACHABLE."""
+    census, fixture = _census()
+    library = {k[".name"] for k in kernels}
+    t = census.totals(fixture, library)
+    print("kernel census: %(run_ahead)d run-ahead instances, %(under_contention)d under contention" % t)
+    assert t["run_ahead"] >= 2 * (9 + 5 + 14 + 3), t          # (both 16-bit types of the y3_ints lists as they stand)
+    assert not census.report(fixture, library)["not_under_contention"], "\n".join(
+        m for m in census.failures(fixture, library) if "contention case" in m)
+
+
+def test_launch_log_entry_points_and_names(kernels):
+    """``y3_debug_launch_log_begin`` / ``_end`` without a GPU: one log per thread, the size query leaves the log open, and the name
+    logged for a launch is a ``.name`` of the code objects -- the log is written BEFORE the launch, which here fails for want of
+    a device."""
+    import ctypes
+
+    import torch
+    from yolov3 import _hip
+    lib = _hip.lib()
+    assert _hip.capabilities() & _hip.CAP_LAUNCH_LOG == 2048
+    assert lib.y3_debug_launch_log_end(None, 0, None) != 0 and b"no launch log" in lib.y3_last_error()
+    assert lib.y3_debug_launch_log_begin() == 0
+    assert lib.y3_debug_launch_log_begin() != 0 and b"already" in lib.y3_last_error()
+    need = ctypes.c_size_t(99)
+    assert lib.y3_debug_launch_log_end(None, 0, ctypes.byref(need)) != 0 and need.value == 1      # the size query: an empty log
+    buf = ctypes.create_string_buffer(b"x" * 8, 8)
+    assert lib.y3_debug_launch_log_end(buf, 8, None) == 0 and buf.value == b""
+    assert lib.y3_debug_launch_log_end(buf, 8, None) != 0                                         # ended
+    if torch.cuda.is_available():
+        pytest.skip("fake device addresses must never reach a library that can see a GPU (the GPU tests take real logs)")
+    with _hip.launch_log() as log:
+        assert lib.y3_cxywh_to_tlbr(1 << 44, 1 << 45, 4, 4, None) != 0                            # no device: the launch fails
+        assert lib.y3_cxywh_to_tlbr_float(1 << 44, 1 << 45, 4, 4, _hip.Y3_F64, None) != 0
+    names = {k[".name"] for k in kernels}
+    assert len(log.names) == 2 and log.symbols == sorted(set(log.names)) and set(log.names) <= names, log.names
+    assert all("cxywh_to_tlbr_kernel" in n for n in log.names)

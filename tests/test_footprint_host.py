@@ -38,12 +38,12 @@ def test_every_case_gets_the_family_it_claims(mode):
 
 
 def test_table_reaches_every_family_of_the_kernel_choice_fixture():
-    """Exact names (dtype included): what the table reaches == the fixture's kernel names + the five kernels no shipped cfg's
-    plan holds (add, copy, maxpool_dk, maxpool_spp_pyramid_dk, conv_direct).  No skip list: removing a row of the table that
-    is a family's only one fails here."""
+    """Exact names (dtype included): what the table reaches == the fixture's kernel names + the kernels no shipped cfg's plan
+    under the fixture's option sets holds (add, copy, maxpool_dk, maxpool_spp_pyramid_dk, conv_direct, the two reorg forms,
+    the VALU stem with 16-bit stores).  No skip list: removing a row of the table that is a family's only one fails here."""
     reached = {fu.family_name(c, d) for c in fu.cases() for d in c["dtypes"]}
     fixture = _fixture_families()
-    extra = {f % t for f in fu.NOT_IN_FIXTURE for t in ("f32", "bf16", "f16")}
+    extra = {f % t if "%s" in f else f for f in fu.NOT_IN_FIXTURE for t in ("f32", "bf16", "f16")}
     assert not (extra & fixture), "a kernel listed as absent from the fixture is in it: %s" % sorted(extra & fixture)
     assert fixture - reached == set(), "families without a footprint case: %s" % sorted(fixture - reached)
     assert reached - fixture == extra, "cases for kernels neither in the fixture nor declared: %s" % sorted(reached - fixture - extra)
@@ -62,11 +62,21 @@ def test_every_family_has_a_full_and_a_ragged_case_and_both_shortcut_forms():
                 "conv_igemm3_%s_64x128", "conv_halo_ws_%s_192x128", "conv_halo_ws_%s_256x128", "conv_halo_dw_%s_192x256",
                 "conv_patch_wsp_%s_8x32x128", "conv_dw48_k1_%s", "conv_dw48_k3_%s", "conv_block_fused_%s_x128", "conv_direct_%s"):
         assert any(c.get("res") for c in by_family[fam]), fam
-    # shapes stay at or below 16 x 76 x 76 x 512
+    # shapes stay at or below 16 x 76 x 76 x 512 ...
     for c in fu.cases():
-        assert c["B"] <= 16 and c["h"] * c["w"] <= 76 * 76 and max(c.get("cin", 0), c.get("cout", 0), c.get("c", 0)) <= 512, c["id"]
-        # only the patch kernel's maps are wider than 76 (its chooser asks rows of more than 128 px)
-        assert max(c["h"], c["w"]) <= 76 or c["family"].startswith("conv_patch_wsp"), c["id"]
+        assert c["B"] <= 16 and c["h"] * c["w"] <= 76 * 76 and max(c.get("cout", 0), c.get("c", 0)) <= 512, c["id"]
+        # ... but for the input channels of a row that is there for ONE compiled K depth of a direct-weights kernel, which are
+        # then exactly what that instance dictates: 64 x nkt per halo image (the stride-2 kernel's two-image form: twice that),
+        # on the smallest grid its chooser takes: at most half the elements of a tensor at the limit
+        if c.get("cin", 0) > 512:
+            assert c.get("nkt") in (12, 16) and c["cin"] == 64 * c["nkt"] and c["h"] * c["w"] <= 38 * 38, c["id"]
+            assert c["B"] * c["h"] * c["w"] * c["cin"] <= 16 * 76 * 76 * 512 // 2, c["id"]
+        if "nkt" in c:
+            assert c["cin"] in (64 * c["nkt"], 128 * c["nkt"]) and (c["cin"] == 64 * c["nkt"] or "two_images" in c["id"]), c["id"]
+        # only the patch kernel's maps are wider than 76 (its chooser asks rows of more than 128 px), and the one row of the
+        # stride-2 kernel's two-image form at 256 channels (conv_dw48.hip dw48_shape: one image of all channels must outgrow LDS)
+        assert max(c["h"], c["w"]) <= 76 or c["family"].startswith("conv_patch_wsp") or c.get("wide_map"), c["id"]
+    assert [c["id"] for c in fu.cases() if c.get("wide_map")] == ["dw48_k3s2_c256_two_images"]
 
 
 def _kmode(case, dtype):

@@ -7,7 +7,9 @@ Why: the waits are hand-counted.  Alone, loads land in issue order and early; un
 direct-weights kernel that showed as a fault (round 5), in an LDS-DMA kernel it would be a SILENTLY wrong tile, which no
 oracle comparison of a kernel running alone can see.  Each case: a single-op plan (two ops for the fused block) through the C
 ABI, its output alone, then 20 x [y3_copy_bytes of 17.7 MB from pinned host memory on stream A, 6 launches on stream B], bit-equal
-every fifth round.  These kernels replace /root/reference/yolov3/darknet.py:244-257 (+ the shortcut at :376-379).
+every fifth round.  The run-ahead families are compiled per K depth, each depth with its own wait counts: the quiet run of every
+case is taken with the library's launch log and must launch the instance tests/golden/kernel_instances.json records for it, and
+tests/test_code_object.py proves that every such instance has a case here.  These kernels replace /root/reference/yolov3/darknet.py:244-257 (+ the shortcut at :376-379).
 Need an MI355X: -m gpu."""
 import ctypes
 import os
@@ -20,7 +22,10 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 
 pytestmark = pytest.mark.gpu
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
 TDT = {"bf16": torch.bfloat16, "fp16": torch.float16}
+RECORDING = False      # the census tool sets it: record the launch sets, 0 contended rounds, no comparison with the fixture
 
 
 def _conv_op(dev, gen, dtype, B, h, cin, cout, k, stride, res):
@@ -54,16 +59,29 @@ def _conv_op(dev, gen, dtype, B, h, cin, cout, k, stride, res):
     return op, keep, out
 
 
-def _beside_a_copy(handle, out, rounds=20, launches=6, more=()):
-    """`out` (and the tensors in `more`) after launches beside the copy kernel == after a launch alone."""
+LAUNCHED = {}          # census key -> the sorted symbol set of the case's quiet run (tools/make_kernel_instances.py reads it)
+
+
+def _beside_a_copy(handle, out, key, rounds=20, launches=6, more=()):
+    """`out` (and the tensors in `more`) after launches beside the copy kernel == after a launch alone, and the quiet launch ran
+    the compiled instance(s) recorded as `key` (the log is on for that run only)."""
     from yolov3 import _hip
     lib = _hip.lib()
     dev = out.device
-    _hip.check(lib.y3_plan_run(handle, None, None))
+    with _hip.launch_log() as log:
+        _hip.check(lib.y3_plan_run(handle, None, None))
     torch.cuda.synchronize()
+    LAUNCHED[key] = log.symbols
+    if not RECORDING:
+        import kernel_census as census
+        want = census.load()["contention"].get(key)
+        assert want is not None, "tests/golden/kernel_instances.json has no contention entry %r: run tools/make_kernel_instances.py" % key
+        assert log.symbols == want, (key, log.symbols, want)
     alone = out.clone()
     alone_more = [t.clone() for t in more]
     assert torch.isfinite(alone.float()).all() and float(alone.float().abs().max()) > 0
+    if RECORDING:
+        return
     out.zero_()
     for t in more:
         t.zero_()
@@ -114,6 +132,14 @@ def _cases():
         ("dw1x1_96", "conv1x1_dw_%s_96x256", dict(auto_mask=H.AM_1X1_DW), 16, 38, 512, 256, 1, 1, False),
         ("dw1x1_48", "conv1x1_dw_%s_48x256", dict(auto_mask=H.AM_1X1_DW), 16, 19, 1024, 512, 1, 1, False),
         ("dw1x1_96_k768", "conv1x1_dw_%s_96x256", dict(auto_mask=H.AM_1X1_DW), 16, 38, 768, 256, 1, 1, False),
+        # ... each K depth is an instance of its own (DEPTH = min(NKT, 4) loads ahead, the wait counts follow from it): 4 and 6
+        # K-steps at 96 pixels, 4, 6, 8 and 12 at 48 (19^2 x 16 frames: 121 tiles, too few for the 96-pixel form)
+        ("dw1x1_96_k256", "conv1x1_dw_%s_96x256", dict(auto_mask=H.AM_1X1_DW), 16, 38, 256, 256, 1, 1, False),
+        ("dw1x1_96_k384", "conv1x1_dw_%s_96x256", dict(auto_mask=H.AM_1X1_DW), 16, 38, 384, 256, 1, 1, False),
+        ("dw1x1_48_k256", "conv1x1_dw_%s_48x256", dict(auto_mask=H.AM_1X1_DW), 16, 19, 256, 256, 1, 1, False),
+        ("dw1x1_48_k384", "conv1x1_dw_%s_48x256", dict(auto_mask=H.AM_1X1_DW), 16, 19, 384, 256, 1, 1, False),
+        ("dw1x1_48_k512", "conv1x1_dw_%s_48x256", dict(auto_mask=H.AM_1X1_DW), 16, 19, 512, 256, 1, 1, False),
+        ("dw1x1_48_k768", "conv1x1_dw_%s_48x256", dict(auto_mask=H.AM_1X1_DW), 16, 19, 768, 256, 1, 1, False),
         # small-grid direct-weights kernel (round 6): 1 .. 8 waves per workgroup, run-ahead weight loads behind the halo's LDS-DMA
         ("dw48_k3_76", "conv_dw48_k3_%s", dict(auto_mask=H.AM_SMALL_DW), 1, 76, 128, 256, 3, 1, True),
         ("dw48_k3_19", "conv_dw48_k3_%s", dict(auto_mask=H.AM_SMALL_DW), 2, 19, 512, 1024, 3, 1, True),
@@ -121,6 +147,23 @@ def _cases():
         # ... its stride-2 form (four parity planes; 512 channels as two LDS images, re-staged by helper and computing waves in the K loop)
         ("dw48_k3s2_76", "conv_dw48_k3s2_%s", dict(auto_mask=H.AM_SMALL_DW), 1, 76, 256, 512, 3, 2, False),
         ("dw48_k3s2_38", "conv_dw48_k3s2_%s", dict(auto_mask=H.AM_SMALL_DW), 2, 38, 512, 1024, 3, 2, False),
+        # ... and its other K depths per halo image, one frame each: 3x3 with 4 K-steps; 1x1 with 2, 4, 6, 12 and 16; stride 2 with
+        # ONE and two (the shallow pipelines: all of an image's weights in flight at once) and as two images of two K-steps (256
+        # channels on rows of 124 px and more, where one image of all channels outgrows LDS)
+        ("dw48_k3_38_k256", "conv_dw48_k3_%s", dict(auto_mask=H.AM_SMALL_DW), 1, 38, 256, 512, 3, 1, True),
+        ("dw48_k1_38_k128", "conv_dw48_k1_%s", dict(auto_mask=H.AM_SMALL_DW), 1, 38, 128, 256, 1, 1, False),
+        ("dw48_k1_38_k256", "conv_dw48_k1_%s", dict(auto_mask=H.AM_SMALL_DW), 1, 38, 256, 256, 1, 1, True),
+        ("dw48_k1_38_k384", "conv_dw48_k1_%s", dict(auto_mask=H.AM_SMALL_DW), 1, 38, 384, 256, 1, 1, False),
+        ("dw48_k1_38_k768", "conv_dw48_k1_%s", dict(auto_mask=H.AM_SMALL_DW), 1, 38, 768, 256, 1, 1, False),
+        ("dw48_k1_38_k1024", "conv_dw48_k1_%s", dict(auto_mask=H.AM_SMALL_DW), 1, 38, 1024, 256, 1, 1, False),
+        ("dw48_k3s2_76_k64", "conv_dw48_k3s2_%s", dict(auto_mask=H.AM_SMALL_DW), 1, 76, 64, 128, 3, 2, False),
+        ("dw48_k3s2_76_k128", "conv_dw48_k3s2_%s", dict(auto_mask=H.AM_SMALL_DW), 1, 76, 128, 256, 3, 2, False),
+        ("dw48_k3s2_128_k256_two_images", "conv_dw48_k3s2_%s", dict(auto_mask=H.AM_SMALL_DW), 1, 128, 256, 128, 3, 2, False),
+        # direct-weights strip kernel: run-ahead weight loads behind the halo's LDS-DMA, four, five and six halo passes per chunk
+        # (rows of 19, 38 and 76 px)
+        ("halo_dw_19_na4", "conv_halo_dw_%s_192x256", dict(auto_mask=halo | H.AM_HALO_DW_ALWAYS), 4, 19, 256, 512, 3, 1, True),
+        ("halo_dw_38_na5", "conv_halo_dw_%s_192x256", dict(auto_mask=halo | H.AM_HALO_DW_ALWAYS), 2, 38, 128, 256, 3, 1, True),
+        ("halo_dw_76_na6", "conv_halo_dw_%s_192x256", dict(auto_mask=halo | H.AM_HALO_DW_ALWAYS), 1, 76, 128, 256, 3, 1, False),
         # persistent 2-D patch kernel (rows wider than 128 px)
         ("patch_152", "conv_patch_wsp_%s_8x32x128", dict(auto_mask=halo | H.AM_PATCH_WIDE), 16, 152, 64, 128, 3, 1, True),
     ]
@@ -150,7 +193,7 @@ def test_counted_wait_kernel_beside_a_copy_kernel(case, dtype):
     try:
         want = kernel % {"bf16": "bf16", "fp16": "f16"}[dtype]
         assert lib.y3_plan_op_kernel(handle, 0).decode() == want, (lib.y3_plan_op_kernel(handle, 0).decode(), want)
-        _beside_a_copy(handle, out)
+        _beside_a_copy(handle, out, "%s-%s" % (case, dtype))
     finally:
         lib.y3_plan_destroy(handle)
 
@@ -169,17 +212,22 @@ def test_fused_bottleneck_block_beside_a_copy_kernel(res):
     handle = bb.make_plan(ops, t["zero"], out, fuse_block=2)
     try:
         assert lib.y3_plan_op_kernel(handle, 0).decode() == "conv_block_fused_bf16_x128"
-        _beside_a_copy(handle, out)
+        _beside_a_copy(handle, out, "block_fused_%s-bf16" % ("res" if res else "nores"))
     finally:
         lib.y3_plan_destroy(handle)
 
 
-@pytest.mark.parametrize("dtype", ["bf16", "fp16"])
-@pytest.mark.parametrize("mode,kernel,B,h,cin", [
+HEADS = [
     (2, "conv_head_decode_%s_64x256", 16, 38, 512),            # tiled head kernel: LDS-DMA double buffer
     (4, "conv_head_decode_dw_%s_96x256", 16, 38, 512),         # direct-weights head kernel (round 6): run-ahead weight loads, 96-pixel tiles
     (1, "conv_head_decode_dw_%s_48x256", 16, 19, 1024),        # ... 48-pixel tiles (the default), sixteen K-steps
-    (1, "conv_head_decode_dw_%s_48x256", 1, 76, 256)])         # ... one frame
+    (1, "conv_head_decode_dw_%s_48x256", 1, 76, 256),          # ... one frame, four K-steps
+    (3, "conv_head_decode_dw_%s_48x256", 4, 38, 512),          # ... eight K-steps at 48 pixels
+    (4, "conv_head_decode_dw_%s_96x256", 4, 38, 256)]          # ... four K-steps at 96 pixels
+
+
+@pytest.mark.parametrize("dtype", ["bf16", "fp16"])
+@pytest.mark.parametrize("mode,kernel,B,h,cin", HEADS)
 def test_head_kernels_beside_a_copy_kernel(mode, kernel, B, h, cin, dtype):
     """The fused detection-head kernels (1x1 conv + YOLO decode in one launch; /root/reference/yolov3/darknet.py:244-257 + :86-116):
     boxes, scores and classes beside a copy kernel == alone."""
@@ -214,6 +262,6 @@ def test_head_kernels_beside_a_copy_kernel(mode, kernel, B, h, cin, dtype):
     try:
         want = kernel % {"bf16": "bf16", "fp16": "f16"}[dtype]
         assert lib.y3_plan_op_kernel(handle, 0).decode() == want, (lib.y3_plan_op_kernel(handle, 0).decode(), want)
-        _beside_a_copy(handle, bbox, more=(prob, cls))
+        _beside_a_copy(handle, bbox, "head_mode%d_%dx%dx%d-%s" % (mode, B, h, cin, dtype), more=(prob, cls))
     finally:
         lib.y3_plan_destroy(handle)

@@ -79,8 +79,11 @@ def test_more_frames_than_one_launch_takes_and_a_striding_grid():
 BATCH = [(40, 100), (90, 60), (33, 70), (7, 5)]
 
 
+MIXED_NETS = [(33, 70), (32, 48)]
+
+
 @pytest.mark.parametrize("letterbox", [False, True])
-@pytest.mark.parametrize("net", [(33, 70), (32, 48)])
+@pytest.mark.parametrize("net", MIXED_NETS)
 def test_mixed_batch_in_one_launch_stays_inside_its_output(net, letterbox):
     """four frames of different sizes, one call; the output lies between guards filled with a byte pattern and is itself
     pre-filled with NaN: the guards must stay as they are and no NaN may be left"""
@@ -99,9 +102,12 @@ def test_mixed_batch_in_one_launch_stays_inside_its_output(net, letterbox):
     torch.cuda.synchronize()
     before = alloc.clone()
     assert bool(torch.isnan(fu.read_slice(before, out, 0, torch.float32)).all())
-    _hip.check(_hip.lib().y3_preprocess_darknet_f32(descs, len(frames), out.ptr(alloc.data_ptr()), net[0], net[1],
-                                                    1 if letterbox else 0, None))
+    import test_gpu_footprint as TF                      # (the launch census: tests/kernel_census.py)
+    del TF.LAUNCHED[:]
+    TF._logged(lambda: _hip.check(_hip.lib().y3_preprocess_darknet_f32(descs, len(frames), out.ptr(alloc.data_ptr()), net[0], net[1],
+                                                                       1 if letterbox else 0, None)))
     torch.cuda.synchronize()
+    TF._assert_census("y3_preprocess_darknet_f32")
     msg = fu.footprint_violations(before, alloc, lay)
     assert msg is None, msg
     got = fu.read_slice(alloc, out, 0, torch.float32).reshape(len(frames), 3, net[0], net[1]).cpu()

@@ -16,6 +16,11 @@ channel counts, 7x7, one input channel, float32 store from 16-bit storage), and 
 per-chunk (KMODE 1) and several-taps (KMODE 2) K-tilings, 5x5 and even kernels and a 3x3 without padding.
 ``test_implicit_gemm_versions_sum_in_one_k_order`` holds the versions to one another bit for bit on those K-tilings.
 
+Below the family name the library is compiled by instance: every run here is taken with the library's launch log, and the set
+of code-object symbols it launched must equal the record of tests/golden/kernel_instances.json for that case
+(tests/kernel_census.py; tools/make_kernel_instances.py writes the record, tests/test_code_object.py proves that it leaves no
+compiled kernel out).
+
 Guards lie inside the allocation: a stray access is recorded, never a fault.  The reference has no counterpart of these
 layouts (the reference's yolov3/darknet.py:366-399 allocates a tensor per block).  Need an MI355X: -m gpu."""
 import ctypes
@@ -124,6 +129,43 @@ def _make_data(case, dtype, lay, paths):
     return data, ref
 
 
+# ------------------------------------------------------------------------------------------------ the launch census
+
+RECORD = None          # tools/make_kernel_instances.py sets it to {}: _assert_census then records instead of comparing
+FRAGMENT_LAUNCHED = []  # ... and of every y3_conv_make_fragment_weights call inside ``_run``
+LAUNCHED = []          # the sorted symbol set of every logged call since a test (or the census tool) last cleared it
+
+
+def _logged(call):
+    """``call()`` under the library's launch log; what it launched is appended to LAUNCHED"""
+    from yolov3 import _hip as H
+    with H.launch_log() as log:
+        out = call()
+    LAUNCHED.append(log.symbols)
+    return out
+
+
+def _assert_census(key, table="footprint"):
+    """every logged call since the last clear launched exactly the symbols recorded for ``key``; clears the list"""
+    import kernel_census as census
+    if RECORD is not None:
+        assert LAUNCHED and all(got == LAUNCHED[0] for got in LAUNCHED), (key, LAUNCHED)
+        assert RECORD.setdefault(key, LAUNCHED[0]) == LAUNCHED[0], key
+        del LAUNCHED[:]
+        return
+    want = census.load()[table].get(key)
+    assert want is not None, "tests/golden/kernel_instances.json has no %s entry %r: run tools/make_kernel_instances.py" % (table, key)
+    assert LAUNCHED, key
+    names = census.demangle(set(want).union(*LAUNCHED))
+    for got in LAUNCHED:
+        assert got == want, "%s launched\n  %s\nrecorded\n  %s" % (key, "\n  ".join(names[s] for s in got),
+                                                                 "\n  ".join(names[s] for s in want))
+    del LAUNCHED[:]
+
+
+FRAGMENT_KEY = "y3_conv_make_fragment_weights"
+
+
 # ------------------------------------------------------------------------------------------------ one run
 
 def _run(case, dtype, mode, u8_guard=0, opt_name=None):
@@ -147,8 +189,10 @@ def _run(case, dtype, mode, u8_guard=0, opt_name=None):
     # fragment-order weight copies: made by the library into their operand, which is all that call may write
     for i, name in frag.items():
         before = alloc.clone()
-        H.check(lib.y3_conv_make_fragment_weights(ctypes.byref(ops[i]), ctypes.c_void_p(ops[i].d_weight_frag), None))
+        with H.launch_log() as flog:
+            H.check(lib.y3_conv_make_fragment_weights(ctypes.byref(ops[i]), ctypes.c_void_p(ops[i].d_weight_frag), None))
         torch.cuda.synchronize()
+        FRAGMENT_LAUNCHED.append(flog.symbols)
         lay[name].side = "scratch"
         msg = fu.footprint_violations(before, alloc, lay)
         lay[name].side = "in"
@@ -159,7 +203,7 @@ def _run(case, dtype, mode, u8_guard=0, opt_name=None):
         names = [lib.y3_plan_op_kernel(handle, i).decode() for i in range(len(ops))]
         before = alloc.clone()
         d_input = lay["input"].ptr(base) if lay.has("input") else None
-        H.check(lib.y3_plan_run(handle, d_input, None))
+        _logged(lambda: H.check(lib.y3_plan_run(handle, d_input, None)))
         torch.cuda.synchronize()
     finally:
         lib.y3_plan_destroy(handle)
@@ -258,6 +302,13 @@ def _check_dense_against_oracle(case, dtype, outs, ref, lay):
         got = _nchw(_typed(outs, key, dtype), B, want.shape[2], want.shape[3])
         assert torch.equal(got, want), "%s: %d values differ from the oracle" % (case["id"], int((got != want).sum()))
         return
+    if g == "reorg":
+        import yolov2_restate as R2
+        x = _nchw(ref["x"], B, h, w)
+        want = torch.from_numpy(R2.reorg(x.numpy(), case["s"], case["form3d"]))
+        got = _nchw(_typed(outs, "output/0", dtype), B, want.shape[2], want.shape[3])
+        assert torch.equal(got, want), "%s: %d values differ from Darknet's loop" % (case["id"], int((got != want).sum()))
+        return
     if g == "spp":
         x = _nchw(ref["x"], B, h, w)
         for i, k in enumerate((5, 9, 13)):
@@ -271,7 +322,9 @@ def _check_dense_against_oracle(case, dtype, outs, ref, lay):
         return
     if g == "head":
         # the gate the suite holds the fused head kernels to (tests/test_gpu_parity.py): the two separate kernels, bit for bit
+        held = list(LAUNCHED)
         plain, msg, names, _, _ = _run(case, dtype, "dense", opt_name="head_unfused")
+        LAUNCHED[:] = held                                    # (the two separate kernels are not this case's launch set)
         assert msg is None, msg
         assert names[0].startswith("conv_igemm_") and names[1] == "yolo_decode_f32", names
         for key in ("bbox/0", "prob/0", "cls/0"):
@@ -315,6 +368,7 @@ def test_kernel_touches_exactly_its_operands(cid):
     cname, dtype = cid.rsplit("-", 1)
     case = fu.case_by_id(cname)
     want = fu.family_name(case, dtype)
+    del LAUNCHED[:], FRAGMENT_LAUNCHED[:]
     dense, msg, names, ref, lay = _run(case, dtype, "dense")
     assert names[0] == want, (names, want)
     assert msg is None, "dense run: " + msg
@@ -331,6 +385,12 @@ def test_kernel_touches_exactly_its_operands(cid):
         for key in dense:
             assert torch.equal(strided[key], dense[key]), "%s: %d bytes of the strided, poisoned run differ from the dense run" % (
                 key, int((strided[key] != dense[key]).sum()))
+    # the dense run and every strided run launched exactly the compiled instance(s) recorded for this case
+    assert len(LAUNCHED) == (3 if u8 else 2)
+    _assert_census(cid)
+    if FRAGMENT_LAUNCHED:
+        LAUNCHED[:] = FRAGMENT_LAUNCHED
+        _assert_census(FRAGMENT_KEY)
 
 
 # ------------------------------------------------------------------------------------------------ one K order
@@ -355,6 +415,7 @@ def test_implicit_gemm_versions_sum_in_one_k_order(cid, opts, dtype):
     _hip.require_gpu()
     base = fu.case_by_id(cid)
     first = None
+    del LAUNCHED[:]
     for opt in opts:
         if opt == "igemm3_64" and dtype == "float32":
             continue
@@ -390,7 +451,7 @@ def _guarded(bufs, call, poisoned):
     fu.fill(alloc, lay, data, poisoned=poisoned, u8_guard=0xFF if poisoned else 0)
     torch.cuda.synchronize()
     before = alloc.clone()
-    call({o.name: o.ptr(base) for o in ops})
+    _logged(lambda: call({o.name: o.ptr(base) for o in ops}))
     torch.cuda.synchronize()
     msg = fu.footprint_violations(before, alloc, lay)
     assert msg is None, ("poisoned guards: " if poisoned else "zero guards: ") + msg
@@ -411,19 +472,23 @@ def _unguarded(bufs, call):
             t[name] = torch.full((n * es,), 0x7F if side == "out" else 0xFF, dtype=torch.uint8, device=dev)
         assert t[name].numel() == n * es and t[name].data_ptr() % 16 == 0, name
     torch.cuda.synchronize()
-    call({name: v.data_ptr() for name, v in t.items()})
+    _logged(lambda: call({name: v.data_ptr() for name, v in t.items()}))
     torch.cuda.synchronize()
     return {name: t[name].reshape(1, -1).cpu() for name, side, _, _, _ in bufs if side == "out"}
 
 
-def _both(bufs, call):
-    """outputs of the unguarded call, after the two guarded calls have been held to it byte for byte"""
+def _both(bufs, call, key):
+    """outputs of the unguarded call, after the two guarded calls have been held to it byte for byte and all three to the
+    launch set recorded as ``key``"""
+    del LAUNCHED[:]
     free = _unguarded(bufs, call)
     for what, poisoned in (("zero guards", False), ("poisoned guards", True)):
         got = _guarded(bufs, call, poisoned)
         for k in free:
             assert torch.equal(free[k], got[k]), "%s: %d bytes differ between the unguarded call and the call between %s" % (
                 k, int((free[k] != got[k]).sum()), what)
+    assert len(LAUNCHED) == 3
+    _assert_census(key)
     return free
 
 
@@ -477,7 +542,7 @@ def test_detectors_stay_inside_exact_size_workspace_and_outputs(which):
     box, prob, cls, hw = _detect_inputs()
     b, rows = prob.shape
     ws = int((lib.y3_detect_darknet_workspace_bytes if which.startswith("darknet") else lib.y3_detect_workspace_bytes)(b, rows))
-    outs = _both(_detect_bufs(ws, box, prob, cls, hw), _detect_call(which, b, rows, ws))
+    outs = _both(_detect_bufs(ws, box, prob, cls, hw), _detect_call(which, b, rows, ws), "detect-" + which)
     count = outs["det_count"].view(torch.int32).flatten().tolist()
     assert count[0] == 0 and 0 < count[1] <= 12 and count[2] > 0 and count[3] > 0, count
     assert int((prob[2] >= np.float32(0.1)).sum()) > 4096
@@ -486,7 +551,10 @@ def test_detectors_stay_inside_exact_size_workspace_and_outputs(which):
 NMS = ["int64", "float32", "float64", "darknet_iou", "darknet_greedynms", "darknet_diounms"]
 
 
-@pytest.mark.parametrize("n", [1, 300, 5000])
+NMS_SIZES = [1, 300, 5000]
+
+
+@pytest.mark.parametrize("n", NMS_SIZES)
 @pytest.mark.parametrize("which", NMS)
 def test_nms_entry_points_stay_inside_exact_size_workspace_and_outputs(which, n):
     import darknet_nms_restate as R
@@ -523,7 +591,7 @@ def test_nms_entry_points_stay_inside_exact_size_workspace_and_outputs(which, n)
         else:
             H.check(lib.y3_nms_float(p["tlbr"], H.Y3_F64 if which == "float64" else H.Y3_F32, p["prob"], p["cls"], n, 0.3,
                                      p["workspace"], ws, p["keep"], p["keep_count"], None))
-    outs = _both(bufs, call)
+    outs = _both(bufs, call, "nms-%s-%d" % (which, n))
     kept = int(outs["keep_count"].view(torch.int32)[0])
     assert 1 <= kept <= n
     if which.startswith("darknet"):         # the values: Darknet's rule as tests/darknet_nms_restate.py states it
@@ -544,7 +612,7 @@ def test_pack_records_stays_inside_exact_size_buffers():
     box, prob, cls, hw = _detect_inputs()
     b, rows = prob.shape
     ws = int(lib.y3_detect_workspace_bytes(b, rows))
-    det = _both(_detect_bufs(ws, box, prob, cls, hw), _detect_call("detect", b, rows, ws))
+    det = _both(_detect_bufs(ws, box, prob, cls, hw), _detect_call("detect", b, rows, ws), "detect-detect")
     kmax = 7
     V = lambda k, dt: det[k].contiguous().view(dt).flatten()
     bufs = [("det_count", "in", "i32", b, V("det_count", torch.int32)), ("det_tlbr", "in", "i64", b * rows * 4, V("det_tlbr", torch.int64)),
@@ -555,12 +623,15 @@ def test_pack_records_stays_inside_exact_size_buffers():
     def call(p):
         H.check(lib.y3_pack_records(p["det_count"], p["det_tlbr"], p["det_prob"], p["det_cls"], p["det_row"], b, rows, kmax,
                                     p["records"], p["rec_count"], None))
-    outs = _both(bufs, call)
+    outs = _both(bufs, call, "y3_pack_records")
     rc = outs["rec_count"].view(torch.int32).flatten().tolist()
     assert rc == V("det_count", torch.int32).tolist() and rc[0] == 0 and rc[2] > kmax
 
 
-@pytest.mark.parametrize("src,dst", [((37, 53), (29, 41)), ((21, 35), (45, 77)), ((3, 5), (7, 11))])
+RESIZES = [((37, 53), (29, 41)), ((21, 35), (45, 77)), ((3, 5), (7, 11))]
+
+
+@pytest.mark.parametrize("src,dst", RESIZES)
 def test_resize_stays_inside_exact_size_frames(src, dst):
     """odd sizes: 5883 -> 3567, 2205 -> 10395 and 45 -> 231 bytes, none a multiple of 16"""
     from yolov3 import _hip as H
@@ -576,7 +647,7 @@ def test_resize_stays_inside_exact_size_frames(src, dst):
 
     def call(p):
         H.check(lib.y3_resize_bilinear_u8(p["src"], sh, sw, p["dst"], dh, dw, p["ytab"], p["xtab"], None))
-    outs = _both(bufs, call)
+    outs = _both(bufs, call, "y3_resize_bilinear_u8-%dx%d-%dx%d" % (sh, sw, dh, dw))
     want = P.resize_bilinear_u8(frame, dh, dw)
     assert np.array_equal(outs["dst"].numpy().reshape(dh, dw, 3), want)
 
@@ -606,13 +677,16 @@ def test_letterbox_stays_inside_exact_size_frames():
             descs[i].d_src, descs[i].src_h, descs[i].src_w = p["src%d" % i], f.shape[0], f.shape[1]
             descs[i].d_ytab, descs[i].d_xtab = p["ytab%d" % i], p["xtab%d" % i]
         H.check(lib.y3_letterbox_u8(descs, len(frames), p["dst"], net_h, net_w, 128, None))
-    outs = _both(bufs, call)
+    outs = _both(bufs, call, "y3_letterbox_u8")
     got = outs["dst"].numpy().reshape(len(frames), net_h, net_w, 3)
     for i, f in enumerate(frames):
         assert np.array_equal(got[i], P.letterbox_u8(f, net_h, net_w, 128)), i
 
 
-@pytest.mark.parametrize("nbytes", [1, 15, 100003, 1 << 20])
+COPY_SIZES = [1, 15, 100003, 1 << 20]
+
+
+@pytest.mark.parametrize("nbytes", COPY_SIZES)
 def test_copy_bytes_stays_inside_exact_size_buffers(nbytes):
     from yolov3 import _hip as H
     H.require_gpu()
@@ -622,5 +696,38 @@ def test_copy_bytes_stays_inside_exact_size_buffers(nbytes):
 
     def call(p):
         H.check(lib.y3_copy_bytes(p["src"], p["dst"], nbytes, 8, None))
-    outs = _both(bufs, call)
+    outs = _both(bufs, call, "y3_copy_bytes-%d" % nbytes)
     assert torch.equal(outs["dst"].flatten(), src)
+
+
+CXYWH = ["int64", "float32", "float64"]
+
+
+@pytest.mark.parametrize("which", CXYWH)
+def test_cxywh_to_tlbr_stays_inside_exact_size_rows(which):
+    """y3_cxywh_to_tlbr / y3_cxywh_to_tlbr_float (the reference's cxywh_to_tlbr, inference.py:269-283) on 1000 rows of 6 columns,
+    more than one block and a partial last one: tl = c - floor(wh / 2), br = c + floor(wh / 2) in the rows' own type, exactly;
+    the columns past the fourth are copied as they are"""
+    from yolov3 import _hip as H
+    H.require_gpu()
+    lib = H.lib()
+    n, cols = 1000, 6
+    rng = np.random.default_rng(11)
+    ndt = {"int64": np.int64, "float32": np.float32, "float64": np.float64}[which]
+    fmt = {"int64": "i64", "float32": "float32", "float64": "f64"}[which]
+    xywh = rng.uniform(-50.0, 700.0, (n, cols))
+    xywh[:, 2:4] = rng.uniform(-20.0, 300.0, (n, 2))               # (negative sizes: floor, not truncation)
+    xywh = (np.floor(xywh * 4) / 4 if which != "int64" else np.floor(xywh)).astype(ndt)      # (quarters: exact in float32)
+    bufs = [("xywh", "in", fmt, n * cols, torch.from_numpy(xywh)), ("tlbr", "out", fmt, n * cols, None)]
+
+    def call(p):
+        if which == "int64":
+            H.check(lib.y3_cxywh_to_tlbr(p["xywh"], p["tlbr"], n, cols, None))
+        else:
+            H.check(lib.y3_cxywh_to_tlbr_float(p["xywh"], p["tlbr"], n, cols, H.Y3_F64 if which == "float64" else H.Y3_F32, None))
+    outs = _both(bufs, call, "y3_cxywh_to_tlbr-" + which)
+    tdt = {"int64": torch.int64, "float32": torch.float32, "float64": torch.float64}[which]
+    got = outs["tlbr"].contiguous().view(tdt).reshape(n, cols).numpy()
+    half = xywh[:, 2:4] // 2 if which == "int64" else np.floor(xywh[:, 2:4] / ndt(2))
+    assert np.array_equal(got[:, 0:2], xywh[:, 0:2] - half) and np.array_equal(got[:, 2:4], xywh[:, 0:2] + half)
+    assert np.array_equal(got[:, 4:], xywh[:, 4:])                       # the columns past the fourth are copied
