@@ -175,12 +175,36 @@ int check_flags(const y3_op &op) {
   return Y3_OK;
 }
 
-// what one op runs on its own under options `o`
+// The size limits of every op kind (checked for every op of a plan, the ones a fused step absorbs included, before any chooser
+// sees it).  Byte addresses are 64-bit in every kernel, but the tiled kernels keep the PIXEL index of a tile in an int or a
+// uint32_t (`m = m0 + ...`, the magic-number divisions by __umulhi: common.h y3_fast_div, exact below 2^31), a tile reaches up
+// to 256 pixels past the tensor's last pixel, and the choosers themselves form batch x height x width in int.  So both pixel
+// counts stay one widest tile below 2^31; and the grid of the smallest tile any kernel has (16 pixels x 32 channels bounds
+// them all from above) stays an int.  The table is in DESIGN.md section 1.
+constexpr long long kY3MaxPixels = (1ll << 31) - 1 - 256;
+int check_size(const y3_op &op) {
+  const long long in_px = (long long)op.batch * op.in_h * op.in_w, out_px = (long long)op.batch * op.out_h * op.out_w;
+  Y3_REQUIRE(in_px <= kY3MaxPixels, "op for block %d: %lld input pixels (%d x %d x %d); the limit is %lld (2^31 less one 256-pixel tile)",
+             op.block_idx, in_px, op.batch, op.in_h, op.in_w, kY3MaxPixels);
+  Y3_REQUIRE(out_px <= kY3MaxPixels, "op for block %d: %lld output pixels (%d x %d x %d); the limit is %lld (2^31 less one 256-pixel tile)",
+             op.block_idx, out_px, op.batch, op.out_h, op.out_w, kY3MaxPixels);
+  const long long tiles = (out_px / 16 + 1) * (op.out_c / 32 + 1);
+  Y3_REQUIRE(tiles < (1ll << 31), "op for block %d: %lld output pixels x %d channels need %lld tiles of 16 x 32; the limit is 2^31 - 1",
+             op.block_idx, out_px, op.out_c, tiles);
+  return Y3_OK;
+}
+
+// grid x block of what a step launches (y3_step.threads, filled by its chooser from the launcher's own grid): fewer than 2^32
+int check_launch(const y3_op &op, const y3_step &st) {
+  Y3_REQUIRE(st.threads <= kY3MaxThreads, "op for block %d: %s would be a launch of %lld threads; the limit is %lld (2^32 less one workgroup)",
+             op.block_idx, st.name, st.threads, kY3MaxThreads);
+  return Y3_OK;
+}
+
+// what one op runs on its own under options `o` (the op has passed check_flags and check_size)
 int choose_op(const y3_op &op, const y3_options &o, y3_step &st) {
   Y3_REQUIRE(op.dtype == Y3_F32 || op.dtype == Y3_BF16 || op.dtype == Y3_F16, "op for block %d: unknown dtype %d", op.block_idx, op.dtype);
   Y3_REQUIRE(op.batch > 0 && op.in_h > 0 && op.in_w > 0 && op.in_c > 0, "op for block %d: empty input shape", op.block_idx);
-  const int rc = check_flags(op);
-  if (rc != Y3_OK) return rc;
   switch (op.kind) {
     case Y3_OP_CONV: return choose_conv(op, o, st);
     case Y3_OP_MAXPOOL: case Y3_OP_UPSAMPLE: case Y3_OP_ADD: case Y3_OP_COPY: return y3_choose_layer(op, st);
@@ -330,6 +354,7 @@ size_t y3_conv_fragment_weight_bytes(const y3_op *op, const y3_options *options)
   y3_step st;
   // (a detection-head conv is chosen for together with the YOLO op behind it, at plan creation: asked about by its shape here)
   if (o.fuse_head && y3_conv_head_dw_fits(*op, o)) return y3_conv_halo_dw_weight_bytes(*op);
+  if (check_flags(*op) != Y3_OK || check_size(*op) != Y3_OK) return 0;
   return choose_op(*op, o, st) == Y3_OK && st.frag ? y3_conv_halo_dw_weight_bytes(*op) : 0;
 }
 
@@ -365,6 +390,7 @@ int y3_plan_create_ex(const y3_op *ops, int n_ops, const void *d_zero, const y3_
   for (int i = 0; i < n_ops; ++i) {
     y3_step &st = p->steps[i];
     int rc = check_flags(q[i]);
+    if (rc == Y3_OK) rc = check_size(q[i]);
     if (rc != Y3_OK) {
       y3_plan_destroy(p);
       return rc;
@@ -386,6 +412,7 @@ int y3_plan_create_ex(const y3_op *ops, int n_ops, const void *d_zero, const y3_
     }
     const int absorbed = st.fuse == y3_fuse::none ? 0 : (st.fuse == y3_fuse::spp ? 2 : 1);
     if (rc == Y3_OK) rc = check_activation(q + i, absorbed + 1, st);
+    if (rc == Y3_OK) rc = check_launch(q[i], st);
     if (rc != Y3_OK) {
       y3_plan_destroy(p);
       return rc;
@@ -607,7 +634,10 @@ int y3_op_run(const y3_op *op, const void *d_input, const void *d_zero, void *st
   const void *in = (op->flags & Y3_F_PLAN_INPUT) ? d_input : op->d_in;
   int rc = check_pointers(*op, in);
   y3_step st;
+  if (rc == Y3_OK) rc = check_flags(*op);
+  if (rc == Y3_OK) rc = check_size(*op);
   if (rc == Y3_OK) rc = choose_op(*op, g_y3_defaults, st);
+  if (rc == Y3_OK) rc = check_launch(*op, st);
   if (rc != Y3_OK) return rc;
   st.frag_w = op->d_weight_frag;
   if (!st.frag || st.frag_w) return st.launch(op, st, in, d_zero, s);

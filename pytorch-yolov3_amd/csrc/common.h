@@ -147,6 +147,10 @@ static inline int y3_by_dtype16(int dtype, F &&f) {   // kernels that exist for 
   return dtype == Y3_F16 ? f(f16_t{}) : f(bf16_t{});
 }
 static inline int y3_ceil_div(int a, int b) { return (a + b - 1) / b; }
+// A launch holds fewer than 2^32 threads (grid x block): every chooser records what its launcher will launch in y3_step.threads,
+// and plan creation refuses a step past the limit (api.hip check_launch)
+constexpr long long kY3MaxThreads = ((1ll << 32) - 1) / 256 * 256;
+static inline long long y3_ceil_div64(long long a, long long b) { return (a + b - 1) / b; }
 // n / d == (umulhi(n, mul) + n) >> sh for 0 <= n < 2^31 (round-up method, d >= 1)
 static inline void y3_fast_div(uint32_t d, uint32_t &mul, uint32_t &sh) {
   if (d <= 1) { mul = 0; sh = 0; return; }
@@ -431,6 +435,7 @@ struct y3_step {
   // per workgroup; decode lanes per box; block-fused tile; pipelined (or phase-by-phase) stem pair
   int version = 0, ns = 0, bm = 0, bn = 0, waves = 0, lanes = 0, tw = 0, th = 0;
   bool pipelined = false;
+  long long threads = 0;          // grid x block of the launch (0: a persistent grid of at most one workgroup per CU or so)
   bool frag = false;              // reads the fragment-order copy of ops[0]'s weights (y3_conv_halo_dw_make_weights) ...
   const void *frag_w = nullptr;   // ... this one (never null at launch)
 };

@@ -536,6 +536,7 @@ int y3_choose_conv1x1_dw(const y3_op &op, y3_step &st) {
   st.bm = dw1x1_bm(op);
   Y3_REQUIRE(st.bm != 0, "conv block %d: not a shape for the direct-weights 1x1 kernel", op.block_idx);
   st.launch = launch_conv1x1_dw;
+  st.threads = y3_ceil_div64((long long)op.batch * op.in_h * op.in_w, st.bm) * (op.out_c / 256) * 512;
   st.name = st.bm == 96 ? Y3_KNAME(op.dtype, "conv1x1_dw_", "_96x256") : Y3_KNAME(op.dtype, "conv1x1_dw_", "_48x256");
   st.frag = true;
   return Y3_OK;
@@ -548,6 +549,7 @@ bool y3_conv_head_dw_fits(const y3_op &op0, const y3_options &o) { return dw_hea
 void y3_choose_conv_head_decode_dw(const y3_op &op0, const y3_options &o, y3_step &st) {
   st.bm = dw_head_bm(op0, o);
   st.launch = launch_head_decode_dw;
+  st.threads = y3_ceil_div64((long long)op0.batch * op0.out_h * op0.out_w, st.bm ? st.bm : 48) * 512;
   st.name = st.bm == 96 ? Y3_KNAME(op0.dtype, "conv_head_decode_dw_", "_96x256") : Y3_KNAME(op0.dtype, "conv_head_decode_dw_", "_48x256");
   st.frag = true;
 }

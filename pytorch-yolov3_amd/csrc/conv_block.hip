@@ -495,6 +495,7 @@ bool y3_choose_conv_block_fused(const y3_op &op0, const y3_op &op1, const y3_opt
   st.tw = tw;
   st.th = th;
   st.launch = launch_block_fused;
+  st.threads = (long long)y3_ceil_div(op0.in_w, tw) * y3_ceil_div(op0.in_h, th) * op0.batch * kNT;
   st.name = Y3_KNAME(op0.dtype, "conv_block_fused_", "_x128");
   return true;
 }

@@ -422,6 +422,7 @@ int y3_choose_conv_dw48(const y3_op &op, const y3_options &o, y3_step &st) {
   st.waves = dw48_waves_for(op, o);
   Y3_REQUIRE(st.waves != 0, "conv block %d: not a shape for the small-grid direct-weights kernel", op.block_idx);
   st.launch = launch_dw48;
+  st.threads = y3_ceil_div64((long long)op.batch * op.out_h * op.out_w, 48) * (op.out_c / (32 * st.waves)) * (Y3_DW48_HELPERS ? 512 : 64 * st.waves);
   st.name = op.ksize == 3 ? (op.stride == 2 ? Y3_KNAME(op.dtype, "conv_dw48_k3s2_", "") : Y3_KNAME(op.dtype, "conv_dw48_k3_", ""))
                           : Y3_KNAME(op.dtype, "conv_dw48_k1_", "");
   st.frag = true;

@@ -935,6 +935,8 @@ bool y3_choose_conv_fused_stem_s2(const y3_op &op0, const y3_op &op1, const y3_o
   if (op1.d_in != op0.d_out || op1.in_h != op0.out_h || op1.in_w != op0.out_w || op1.batch != op0.batch) return false;
   if (op1.k_ld < 288 || op1.cout_pad < 64) return false;
   if (op1.out_h != (op1.in_h + 2 - 3) / 2 + 1 || op1.out_w != (op1.in_w + 2 - 3) / 2 + 1) return false;
+  // 32-bit lane offsets from a tile's 64-bit base: up to kIR rows of W * 3 bytes in, 16 pixels of out_ld elements out
+  if ((long long)kIR * op0.in_w * 3 >= (1ll << 31) || op1.out_ld >= (1 << 24)) return false;
   st.launch = launch_stem_s2;
   st.name = op0.dtype == Y3_F16 ? "conv_stem_s2_fused_u8_f16" : "conv_stem_s2_fused_u8_bf16";
   st.pipelined = o.fuse_stem != 2;                      // fuse_stem 2: the phase-by-phase kernel (A/B)
@@ -982,6 +984,8 @@ bool y3_choose_conv_fused_resblock(const y3_op &op0, const y3_op &op1, const y3_
   if (op0.out_h != op0.in_h || op0.out_w != op0.in_w || op1.out_h != op1.in_h || op1.out_w != op1.in_w) return false;
   if (op0.in_ld % 8 != 0 || op1.out_ld % 8 != 0 || op0.in_ld < 64 || op1.out_ld < 64) return false;
   if (op0.k_ld < 64 || op1.k_ld < 288 || op0.cout_pad < 32 || op1.cout_pad < 64) return false;
+  // 32-bit lane offsets from a tile's 64-bit base: kRT + 2 rows of W pixels of x, kRT rows of the output
+  if ((long long)(kRT + 2) * op0.in_w * (op0.in_ld > op1.out_ld ? op0.in_ld : op1.out_ld) * 2 >= (1ll << 32)) return false;
   st.launch = launch_resblock;
   st.name = Y3_KNAME(op0.dtype, "conv_resblock_fused_", "_64_32_64");
   return true;

@@ -1422,6 +1422,7 @@ int y3_choose_conv_halo_dw(const y3_op &op, y3_step &st) {
   Y3_REQUIRE(y3_conv_halo_dw_fits(op), "conv block %d: shape not supported by the direct-weights halo kernel", op.block_idx);
   Y3_REQUIRE((long long)op.batch * op.in_h * op.in_w < (1ll << 31), "conv block %d: too many pixels for the 32-bit tile index", op.block_idx);
   st.launch = launch_conv_halo_dw;
+  st.threads = y3_ceil_div64((long long)op.batch * op.in_h * op.in_w, DW_BM) * (op.out_c / 256) * 512;
   st.name = Y3_KNAME(op.dtype, "conv_halo_dw_", "_192x256");
   st.frag = true;
   return Y3_OK;
@@ -1502,6 +1503,7 @@ int y3_choose_conv_halo(const y3_op &op, const y3_options &o, y3_step &st) {
   const int mi = halo_tile_fragments(op.batch * op.in_h * op.in_w, op.out_c / 128, op.in_c / (128 / es), y3_device_cus(), o);
   st.launch = launch_conv_halo;
   st.bm = 64 * mi;
+  st.threads = y3_ceil_div64((long long)op.batch * op.in_h * op.in_w, st.bm) * (op.out_c / 128) * 768;
   st.name = mi == 3 ? Y3_KNAME(op.dtype, "conv_halo_ws_", "_192x128") : Y3_KNAME(op.dtype, "conv_halo_ws_", "_256x128");
   return Y3_OK;
 }

@@ -1037,6 +1037,11 @@ int y3_choose_conv_igemm(const y3_op &op, const y3_options &o, y3_step &st, int 
   st.launch = launch_conv_igemm;
   st.ns = ns;
   st.bm = 128;
+  // grid x block of the launch (launch_cfg / launch_cfg2 / launch_cfg3): 256 threads per tile, 512 on the wave-specialised kernel
+  auto done = [&]() {
+    st.threads = y3_ceil_div64(M, st.bm) * y3_ceil_div(op.out_c, st.bn) * (st.version == 3 ? 512 : 256);
+    return Y3_OK;
+  };
   // channel-tile width follows Cout so narrow layers do not multiply zero padding ...
   int bn = op.out_c > 64 ? 128 : (op.out_c > 32 ? 64 : 32);
   // ... and shrinks while the grid would leave most CUs without a workgroup (small maps / small batches: 13^2 x 8 frames
@@ -1052,13 +1057,13 @@ int y3_choose_conv_igemm(const y3_op &op, const y3_options &o, y3_step &st, int 
     st.version = 1;
     st.name = bn == 128 ? Y3_KNAME(dt, "conv_igemm_", "_128x128")
                         : (bn == 64 ? Y3_KNAME(dt, "conv_igemm_", "_128x64") : Y3_KNAME(dt, "conv_igemm_", "_128x32"));
-    return Y3_OK;
+    return done();
   }
   if (version == 3 && bn == 128 && !(op.flags & Y3_F_OUT_F32)) {
     st.version = 3;
     st.bm = bm_knob == 64 && bf ? 64 : 128;   // 64-pixel tiles: twice the workgroups, two per CU at 3 stages
     st.name = st.bm == 64 ? Y3_KNAME(dt, "conv_igemm3_", "_64x128") : Y3_KNAME(dt, "conv_igemm3_", "_128x128");
-    return Y3_OK;
+    return done();
   }
   st.version = 2;
   // 96 x 64 tiles where they fit the chip in ONE round of equal workgroups and the tile above does not: yolov3-tiny's big
@@ -1074,12 +1079,12 @@ int y3_choose_conv_igemm(const y3_op &op, const y3_options &o, y3_step &st, int 
       st.bm = 96;
       st.bn = 64;
       st.name = Y3_KNAME(dt, "conv_igemm2_", "_96x64");
-      return Y3_OK;
+      return done();
     }
   }
   st.name = bn == 128 ? Y3_KNAME(dt, "conv_igemm2_", "_128x128")
                       : (bn == 64 ? Y3_KNAME(dt, "conv_igemm2_", "_128x64") : Y3_KNAME(dt, "conv_igemm2_", "_128x32"));
-  return Y3_OK;
+  return done();
 }
 
 Y3_STAMP_READER(y3_debug_stamps_igemm)
@@ -1107,6 +1112,7 @@ bool y3_choose_conv_head_decode(const y3_op &op0, const y3_op &op1, const y3_opt
   } else {
     st.launch = launch_head_decode;
     st.name = Y3_KNAME(op0.dtype, "conv_head_decode_", "_64x256");
+    st.threads = y3_ceil_div64((long long)op0.batch * op0.out_h * op0.out_w, 64) * 256;
   }
   return true;
 }

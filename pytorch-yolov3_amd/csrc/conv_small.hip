@@ -297,6 +297,7 @@ int y3_choose_conv_small(const y3_op &op, y3_step &st) {
   Y3_REQUIRE(!(op.flags & Y3_F_RESIDUAL), "conv block %d: stem kernel has no residual input", op.block_idx);
   const int odt = (op.flags & Y3_F_OUT_F32) ? Y3_F32 : op.dtype;
   st.launch = launch_conv_small;
+  st.threads = y3_ceil_div64((long long)op.batch * op.out_h * op.out_w, 256) * 256;
   st.name = (op.flags & Y3_F_IN_NHWC_U8BGR) ? Y3_KNAME(odt, "conv_stem3x3_u8_", "") : Y3_KNAME(odt, "conv_stem3x3_nchw_", "");
   return Y3_OK;
 }
@@ -327,6 +328,7 @@ static int launch_conv_stem_mfma(const y3_op *ops, const y3_step &, const void *
 int y3_choose_conv_stem_mfma(const y3_op &op, y3_step &st) {
   Y3_REQUIRE(y3_conv_stem_mfma_supported(op), "conv block %d: not a shape for the MFMA stem", op.block_idx);
   st.launch = launch_conv_stem_mfma;
+  st.threads = (long long)y3_ceil_div(op.in_w, kStemTW) * y3_ceil_div(op.in_h, kStemTH) * op.batch * 256;
   st.name = op.dtype == Y3_F16 ? "conv_stem_mfma_u8_f16" : "conv_stem_mfma_u8_bf16";
   return Y3_OK;
 }
@@ -350,6 +352,7 @@ static int launch_conv_direct(const y3_op *ops, const y3_step &, const void *d_i
 int y3_choose_conv_direct(const y3_op &op, y3_step &st) {
   Y3_REQUIRE(op.k_ld >= op.ksize * op.ksize * op.in_c, "conv block %d: k_ld too small", op.block_idx);
   st.launch = launch_conv_direct;
+  st.threads = y3_ceil_div64((long long)op.batch * op.out_h * op.out_w * op.out_c, 256) * 256;   // one thread per output element
   st.name = Y3_KNAME(op.dtype, "conv_direct_", "");
   return Y3_OK;
 }

@@ -183,6 +183,18 @@ void launch_one(Which w, const LayerArgs &a, hipStream_t s) {
   }
 }
 
+// the wide form (one 16-byte channel chunk per thread) or the element-wise one: decided at launch, from the op and its input
+bool layer_is_wide(const y3_op &op, const void *d_in) {
+  const int vec = 16 / y3_elem_size(op.dtype);
+  bool wide = op.in_c % vec == 0 && op.in_ld % vec == 0 && op.out_ld % vec == 0 &&
+              ((uintptr_t)d_in % 16 == 0) && ((uintptr_t)op.d_out % 16 == 0);
+  if (op.kind == Y3_OP_ADD) wide = wide && op.res_ld % vec == 0 && ((uintptr_t)op.d_res % 16 == 0);
+  return wide;
+}
+long long layer_threads(const y3_op &op, bool wide) {
+  return (long long)op.batch * op.out_h * op.out_w * (wide ? op.in_c / (16 / y3_elem_size(op.dtype)) : op.in_c);
+}
+
 int launch_layer(const y3_op *ops, const y3_step &, const void *d_in, const void *, hipStream_t s) {
   const y3_op &op = ops[0];
   const Which w = op.kind == Y3_OP_MAXPOOL ? ((op.flags & Y3_F_POOL_DARKNET) ? MAXPOOL_DK : MAXPOOL) : op.kind == Y3_OP_UPSAMPLE ? UPSAMPLE : op.kind == Y3_OP_ADD ? ADD : COPY;
@@ -195,12 +207,9 @@ int launch_layer(const y3_op *ops, const y3_step &, const void *d_in, const void
   a.k = op.ksize; a.stride = op.stride;
   a.zero_pad = (op.ksize > 1 && op.stride == 1) ? 1 : 0;
   a.pad_lo = op.pad / 2;
-  const int es = y3_elem_size(op.dtype);
-  const int vec = 16 / es;
-  bool wide = op.in_c % vec == 0 && op.in_ld % vec == 0 && op.out_ld % vec == 0 &&
-              ((uintptr_t)d_in % 16 == 0) && ((uintptr_t)op.d_out % 16 == 0);
-  if (w == ADD) wide = wide && op.res_ld % vec == 0 && ((uintptr_t)op.d_res % 16 == 0);
-  a.total = (long long)op.batch * op.out_h * op.out_w * (wide ? op.in_c / vec : op.in_c);
+  const bool wide = layer_is_wide(op, d_in);
+  a.total = layer_threads(op, wide);
+  Y3_REQUIRE(a.total <= kY3MaxThreads, "block %d: a launch of %lld threads; the limit is %lld", op.block_idx, a.total, kY3MaxThreads);
   return y3_by_dtype(op.dtype, [&](auto tag) {
     typedef decltype(tag) T;
     if (wide) launch_one<T, 16 / sizeof(T)>(w, a, s); else launch_one<T, 1>(w, a, s);
@@ -213,6 +222,9 @@ int launch_layer(const y3_op *ops, const y3_step &, const void *d_in, const void
 
 int y3_choose_layer(const y3_op &op, y3_step &st) {
   Y3_REQUIRE(op.in_c == op.out_c, "block %d: channel count changes in a pool/upsample/add/copy op", op.block_idx);
+  // one thread per 16-byte chunk or per element of the output (an op that reads the plan's input: its address is not known yet
+  // and is taken as aligned; launch_layer checks what it really launches)
+  st.threads = y3_ceil_div64(layer_threads(op, layer_is_wide(op, (op.flags & Y3_F_PLAN_INPUT) ? nullptr : op.d_in)), 256) * 256;
   st.launch = launch_layer;
   switch (op.kind) {
     case Y3_OP_MAXPOOL:
@@ -339,6 +351,7 @@ int y3_choose_reorg(const y3_op &op, y3_step &st) {
   Y3_REQUIRE((long long)op.in_c * op.in_h * op.in_w < (1ll << 31), "reorg block %d: a frame of %d x %d x %d elements is too large",
              op.block_idx, op.in_c, op.in_h, op.in_w);
   st.launch = launch_reorg;
+  st.threads = y3_ceil_div64((long long)op.batch * op.out_h * op.out_w * op.out_c, 256) * 256;   // one thread per output element
   st.name = (op.flags & Y3_F_REORG_3D) ? Y3_KNAME(op.dtype, "reorg3d_", "") : Y3_KNAME(op.dtype, "reorg_", "");
   return Y3_OK;
 }
@@ -484,6 +497,9 @@ bool y3_choose_maxpool_spp(const y3_op &a, const y3_op &b, const y3_op &c, y3_st
     if (q->out_h != q->in_h || q->out_w != q->in_w || q->out_c != q->in_c) return false;
   }
   if (seen != 7 || spp_lds_bytes(a) > 64 * 1024) return false;
+  // one workgroup of 256 threads per frame and 32-byte channel group; past the launch limit: three single pools
+  st.threads = (long long)a.batch * (a.in_c * y3_elem_size(a.dtype) / 32) * 256;
+  if (st.threads > kY3MaxThreads) { st.threads = 0; return false; }
   st.launch = launch_maxpool_spp;
   st.name = (a.flags & Y3_F_POOL_DARKNET) ? Y3_KNAME(a.dtype, "maxpool_spp_pyramid_dk_", "") : Y3_KNAME(a.dtype, "maxpool_spp_pyramid_", "");
   return true;

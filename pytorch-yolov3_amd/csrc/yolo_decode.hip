@@ -190,5 +190,6 @@ int y3_choose_yolo(const y3_op &op, const y3_options &o, y3_step &st) {
   st.name = "yolo_decode_f32";
   // bf16 networks (throughput mode) take the four-lanes-per-box form; float32 networks keep the sequential class loop
   st.lanes = y3_is16(op.dtype) && o.decode_lanes != 1 ? 4 : 1;
+  st.threads = y3_ceil_div64((long long)op.batch * op.in_h * op.in_w, kPix) * (st.lanes == 1 ? 256 : 384);
   return Y3_OK;
 }

@@ -141,6 +141,8 @@ def fill(alloc, layout, data, poisoned, u8_guard=0):
                     sl.copy_(_bytes_tensor(NAN_BYTES[o.fmt], o.pixels * c * o.es, dev).view(o.pixels, c * o.es))
                 else:
                     sl.fill_(0x7F)                   # integer outputs: a value no kernel here writes (0x7F7F... )
+            elif o.side == "pad":
+                pass                                 # (the pad of the big-operand layouts: it keeps the fill around it)
             else:
                 sl.fill_(0xFF if poisoned else 0)    # scratch / workspace: no kernel may rely on what it finds there
 
@@ -530,10 +532,11 @@ def _set_conv(op, dtype, B, h, w, cin, cout, k, s, flags, pad=None):
     op.ksize, op.stride, op.pad = k, s, pad
 
 
-def build(case, dtype, mode, opt, base=None):
+def build(case, dtype, mode, opt, base=None, lead=()):
     """(ops, layout, n_frag) of ``case`` in layout ``mode`` ("dense", "strided"; the aliasing cases alias in both); ``base``: the allocation's device
     address, or None for fake addresses (the chooser only decides).  ``n_frag``: {op index: operand name} of fragment-order
-    weight copies to make with y3_conv_make_fragment_weights before the run."""
+    weight copies to make with y3_conv_make_fragment_weights before the run.  ``lead``: operands laid out before the case's own
+    (the pad of the big-operand layouts)."""
     H = _H()
     lib = H.lib()
     es = ES[dtype]
@@ -554,7 +557,7 @@ def build(case, dtype, mode, opt, base=None):
                 operands.append(_flat(frag[i], "in", dtype, n // es))
             else:
                 del frag[i]
-        lay = Layout(operands + [zero])
+        lay = Layout(list(lead) + operands + [zero])
         b = base if base is not None else (1 << 44)
         for i, field, name, k in ptrs:
             setattr(ops[i], field, lay[name].ptr(b, k))
@@ -674,7 +677,8 @@ def build(case, dtype, mode, opt, base=None):
         ops[1].in_ld = mid.ld
         ptrs.append((1, "d_in", mid.name, 0))
         Po = B * ops[1].out_h * ops[1].out_w
-        o = _act(used, "output", "out", dtype, Po, shp[1][1], mode, unit, 1)
+        # (``same_ld``: the output gets the input's stride -- big_cases(): both operands of the fused block one frame below 2^32 bytes)
+        o = _act(set() if case.get("same_ld") else used, "output", "out", dtype, Po, shp[1][1], mode, unit, 0 if case.get("same_ld") else 1)
         operands.append(o)
         ops[1].out_ld = o.ld
         ptrs.append((1, "d_out", "output", 0))
@@ -786,7 +790,7 @@ def build(case, dtype, mode, opt, base=None):
         operands += [x, Operand("bbox", "out", "float32", B, total * 4, [(off * 4, rows * 4)], tile_elems=4),
                      Operand("prob", "out", "float32", B, total, [(off, rows)], tile_elems=1),
                      Operand("cls", "out", "i64", B, total, [(off, rows)], tile_elems=1)]
-        lay = Layout(operands + [zero])
+        lay = Layout(list(lead) + operands + [zero])
         b = base if base is not None else (1 << 44)
         yo.d_in = lay["input"].ptr(b)
         # d_bbox / d_prob / d_cls are the bases of the WHOLE outputs: the op adds row_offset itself
@@ -809,3 +813,254 @@ def chosen(case, dtype, mode, base=None):
         return [lib.y3_plan_op_kernel(handle, i).decode() for i in range(len(ops))], lay
     finally:
         lib.y3_plan_destroy(handle)
+
+
+# ------------------------------------------------------------------------------------------------ operands past 4 GiB
+# tests/test_big_operands_host.py (no GPU) and tests/test_gpu_big_operands.py: every kernel family on operands whose byte
+# offsets pass 2^32, and the refusal of ops of 2^31 pixels.  The rows are NOT census cases: cases() stays as it is.
+
+SPAN = 1 << 32
+PAD_BYTES = 1 << 32            # in front of the first operand: a 32-bit wrap or a sign-extended offset lands inside the allocation
+MAX_PIXELS = (1 << 31) - 1 - TILE_PIXELS     # csrc/api.hip check_size: both pixel counts of every op, one widest tile below 2^31
+MAX_THREADS = ((1 << 32) - 1) // 256 * 256   # csrc/common.h kY3MaxThreads: grid x block of any one launch (api.hip check_launch)
+
+# One row per kernel family, from the family's ragged row of cases() (same channels, kernel, stride, shortcut form, option set
+# and map; the batch comes from big_batch).  Families without a row called "ragged" give the row named here: the direct
+# fallback its stride-2 row with odd channel counts on both sides, the layer kernels their wide (16-byte vector) rows, the
+# 16-bit VALU stem its 48-channel row.  Maps are odd x odd, so a frame's byte size divides neither 2^31 nor 2^32 and a wrapped
+# address lands mid-frame -- but where the op itself demands even sides: the stride-2 conv_dw48 (dw48_shape: in_h % 2 == 0)
+# and the flat reorg at stride 2 keep their even maps (38 x 26, 14 x 10), whose OUTPUT maps are odd (19 x 13, 7 x 5) and whose frame
+# sizes have odd factors too; the stride-2 max-pool is moved from 26 x 22 to 27 x 23.
+_BIG_ROWS = (
+    ("igemm1_128_ragged", {}), ("igemm1_64_ragged_res", {}), ("igemm1_32_ragged", {}),
+    ("igemm2_128_ragged", {}), ("igemm2_64_ragged_res", {}), ("igemm2_32_ragged", {}), ("igemm2_96_ragged", {}),
+    ("igemm3_128_ragged", {}), ("igemm3_64_ragged", {}),
+    ("halo256_ragged", {}), ("halo_dw_ragged", {}), ("patch_ragged", {}),
+    ("wres_128_ragged", {}), ("wres_64_ragged", {}),
+    ("dw48_k1_ragged", {}), ("dw48_k3_ragged", {}), ("dw48_k3s2_ragged", {}),
+    ("stem_nchw_ragged", {}), ("stem_u8_f32_ragged", {}), ("stem_u8_16bit_c48", {}), ("stem_mfma_ragged", {}),
+    ("direct_odd_both_s2", {}),
+    ("stem_s2_ragged", {}), ("resblock_ragged", {}),
+    # the fused block keeps 32-bit byte offsets and diverts at 2^32 bytes (conv_block.hip y3_choose_conv_block_fused): its row has
+    # x and z at ONE stride, both within one frame below 2^32 bytes
+    ("block_ragged_res", {"same_ld": True}),
+    ("head_tiled_ragged", {}), ("head48_ragged", {}), ("head96_ragged", {}),
+    ("maxpool_s2_wide", {"h": 27, "w": 23}), ("maxpool_dk_s2_wide", {}), ("upsample_wide", {}), ("add_wide", {}), ("copy_wide", {}),
+    ("reorg_ragged", {}), ("reorg3d_ragged", {}), ("spp_ragged", {}), ("spp_dk_ragged", {}), ("yolo_wide_stride", {}),
+)
+
+# Families whose own chooser rule bounds the grid, so that no operand of theirs comes near 2^31 bytes: no GPU row, the host test
+# proves the bound on the row named here.  conv1x1_dw: one round of workgroups (conv_1x1.hip dw1x1_bm: at most one 96- or
+# 48-pixel tile per CU).  conv_halo_ws 192 x 128: the 192-pixel tile is taken only while it saves rounds of workgroups
+# (conv_halo.hip halo_tile_fragments: cost = rounds x time per tile, and a 192-pixel tile takes at least 0.8 of a 256-pixel
+# tile's time, so from about ten rounds on -- rounds(192) / rounds(256) -> 4 / 3 -- the 256-pixel tile always wins).
+# (The stride-2 conv_dw48 and the 256-pixel and direct-weights halo kernels are NOT bounded: row width, LDS and even sides limit
+# the map, nothing limits the batch under the option sets that force them.  They have rows above.)
+BIG_BOUNDED = {"conv1x1_dw_%s_96x256": "dw1x1_96_ragged", "conv1x1_dw_%s_48x256": "dw1x1_48_ragged",
+               "conv_halo_ws_%s_192x128": "halo192_ragged"}
+
+
+def big_cases():
+    rows = []
+    for src, over in _BIG_ROWS:
+        c = dict(case_by_id(src))
+        c.update(over)
+        c["src"] = src
+        c["dtypes"] = tuple(d for d in c["dtypes"] if d != "fp16")     # (fp16 shares the ES = 2 address code with bf16)
+        rows.append(c)
+    return rows
+
+
+def big_case_ids():
+    return [(c["id"], d) for c in big_cases() for d in c["dtypes"]]
+
+
+def big_row(cid):
+    return next(c for c in big_cases() if c["id"] == cid)
+
+
+def _is_frames_input(case):
+    """the op reads the network input (uint8 frames / float NCHW): a dense tensor a few bytes per pixel"""
+    return case["group"] == "stem_pair" or (case["group"] == "conv" and case["inp"] != "act")
+
+
+def span_operands(case, lay):
+    """the activation operands of ``lay`` that big_batch holds past 2^32 bytes: every one, but the network-input forms (there
+    the output), and the input alone of the ops whose outputs are detections (the decode, the fused heads)"""
+    g = case["group"]
+    if g in ("yolo", "head"):
+        return [lay["input"]]
+    names = ("input", "output", "residual", "concat", "input/output")
+    return [o for o in lay.operands if o.name in names and not (o.name == "input" and _is_frames_input(case))]
+
+
+def frame_pixels(case, dtype):
+    """the largest pixel count per frame among the inputs and outputs of the case's ops"""
+    ops, _, _, _ = build(dict(case, B=3), dtype, "strided", _H().options(**_opts()[case["opt"]]))
+    return max(max(op.in_h * op.in_w, op.out_h * op.out_w) for op in ops)
+
+
+def big_batch(case, dtype):
+    """frames that put every operand of span_operands more than 2^32 bytes plus one frame long (the fused block: the largest batch
+    that keeps x and z below 2^32 bytes)"""
+    _, lay, _, _ = build(dict(case, B=3), dtype, "strided", _H().options(**_opts()[case["opt"]]))
+    frames = [o.body_bytes // 3 for o in span_operands(case, lay)]
+    assert frames and all(f * 3 == o.body_bytes for f, o in zip(frames, span_operands(case, lay)))
+    if case["group"] == "block":
+        assert len(set(frames)) == 1, frames
+        return (SPAN - 1) // frames[0]
+    return max((SPAN + f) // f + 1 for f in frames)
+
+
+def big_case(row, dtype):
+    return dict(row, B=big_batch(row, dtype))
+
+
+def pad_operand():
+    return Operand("pad", "pad", "u8", 1, PAD_BYTES, [(0, PAD_BYTES)], tile_elems=1)
+
+
+# ---- the checker (torch, any device; nothing here allocates a temporary of the allocation's size)
+
+CHUNK = 1 << 28
+
+
+def _first_difference(before, after, lo, hi, chunk=CHUNK):
+    """None, or the (first 100000) offsets in [lo, hi) where the two byte tensors differ"""
+    for a in range(lo, hi, chunk):
+        b = min(hi, a + chunk)
+        if not torch.equal(before[a:b], after[a:b]):
+            return (torch.nonzero(before[a:b] != after[a:b]).flatten()[:100000] + a).cpu().numpy()
+    return None
+
+
+def region_violations(before, after, layout, chunk=CHUNK):
+    """footprint_violations region by region: the pad, every guard, the body of every read-only operand and the margins of
+    every written one must be byte for byte what they were.  None, or describe()'s message for the first region that is not."""
+    for o in layout.operands:
+        regions = [(o.front, o.body), (o.body + o.body_bytes, o.end)]
+        if o.side in ("in", "pad"):
+            regions.insert(1, (o.body, o.body + o.body_bytes))
+        for lo, hi in regions:
+            offs = _first_difference(before, after, lo, hi, chunk)
+            if offs is not None:
+                return describe(offs, layout)
+        if o.side not in ("out", "inout"):
+            continue
+        row = o.ld * o.es
+        cols, at = [], 0                                   # byte columns of a pixel outside every slice
+        for c0, c in o.slices:
+            if c0 * o.es > at:
+                cols.append((at, c0 * o.es))
+            at = (c0 + c) * o.es
+        if at < row:
+            cols.append((at, row))
+        step = max(1, chunk // row)
+        for p0 in range(0, o.pixels if cols else 0, step):
+            p1 = min(o.pixels, p0 + step)
+            bb = before[o.body + p0 * row:o.body + p1 * row].view(-1, row)
+            ab = after[o.body + p0 * row:o.body + p1 * row].view(-1, row)
+            for lo, hi in cols:
+                if not torch.equal(bb[:, lo:hi], ab[:, lo:hi]):
+                    ix = torch.nonzero(bb[:, lo:hi] != ab[:, lo:hi])[:100000]
+                    offs = (o.body + (ix[:, 0] + p0) * row + ix[:, 1] + lo).cpu().numpy()
+                    return describe(offs, layout)
+    return None
+
+
+def _frames(t, n_frames):
+    assert t.numel() % n_frames == 0, (tuple(t.shape), n_frames)
+    return t.reshape(n_frames, -1)
+
+
+def frame_violations(t, n_frames, base=None, chunk=CHUNK):
+    """``t``: one written slice as bytes (read_slice's (pixels, bytes)); frame b is its b-th of ``n_frames`` equal parts.  None, or a
+    message naming the first frame that is not, byte for byte, frame b % 3 of ``base`` ((3, frame bytes); default: the tensor's
+    own first three frames) -- position independence: the inputs' frame b is their frame b % 3."""
+    f = _frames(t, n_frames)
+    base = f[:3] if base is None else base.to(f.device).reshape(3, -1)
+    assert base.shape[1] == f.shape[1], (tuple(base.shape), tuple(f.shape))
+    step = max(3, chunk // f.shape[1] // 3 * 3)
+    for f0 in range(0, n_frames, step):
+        x = f[f0:f0 + step]
+        want = base.repeat(x.shape[0] // 3 + 1, 1)[:x.shape[0]]
+        if torch.equal(x, want):
+            continue
+        bad = torch.nonzero((x != want).any(1)).flatten()
+        b = int(bad[0])
+        where = torch.nonzero(x[b] != want[b]).flatten()
+        return "frame %d differs from frame %d (%d %% 3) in %d of %d bytes, first at byte %d of the frame; %d frames of %d .. %d differ" % (
+            f0 + b, (f0 + b) % 3, f0 + b, where.numel(), f.shape[1], int(where[0]), bad.numel(), f0, f0 + x.shape[0] - 1)
+    return None
+
+
+def nan_violations(t, n_frames, fmt, chunk=CHUNK):
+    """None, or a message naming the first frame of the slice ``t`` (bytes) that holds a NaN of storage type ``fmt``: an element
+    left at its prefill, or computed from a byte the op does not own"""
+    if fmt not in NAN_BYTES:
+        return None
+    f = _frames(t, n_frames)
+    step = max(1, chunk // f.shape[1])
+    for f0 in range(0, n_frames, step):
+        nan = torch.isnan(f[f0:f0 + step].contiguous().view(TORCH_DT[fmt]))
+        if bool(nan.any()):
+            b = int(torch.nonzero(nan.any(1)).flatten()[0])
+            return "frame %d holds NaN: %d of its %d elements never written or poisoned" % (f0 + b, int(nan[b].sum()), nan.shape[1])
+    return None
+
+
+def launch_threads(case, dtype, B):
+    """grid x block of the launch of ``case`` at batch ``B``, restated from the launchers of csrc/*.hip (None: a persistent grid of
+    about one workgroup per CU, or the fused block, which its 2^32-byte rule bounds first).  A launch holds fewer than 2^32
+    threads: MAX_THREADS (csrc/api.hip check_launch)."""
+    H = _H()
+    ops, _, _, _ = build(dict(case, B=3), dtype, "strided", H.options(**_opts()[case["opt"]]))
+    op = ops[0]
+    cd = lambda a, b: -(-a // b)
+    P, Po, es = B * op.in_h * op.in_w, B * op.out_h * op.out_w, ES[dtype]
+    fam, cout = case["family"], op.out_c
+    if fam.startswith("conv_igemm"):                    # conv_igemm.hip launch_cfg / 2 / 3: 256 threads a tile, version 3 512
+        bm, bn = (int(x) for x in fam.rsplit("_", 1)[1].split("x"))
+        return cd(Po, bm) * cd(cout, bn) * (512 if fam.startswith("conv_igemm3") else 256)
+    if fam.startswith("conv_halo_ws"):
+        return cd(P, int(fam.rsplit("_", 1)[1].split("x")[0])) * (cout // 128) * 768
+    if fam.startswith("conv_halo_dw"):
+        return cd(P, 192) * (cout // 256) * 512
+    if fam.startswith("conv1x1_dw"):
+        return cd(P, int(fam.rsplit("_", 1)[1].split("x")[0])) * (cout // 256) * 512
+    if fam.startswith("conv_dw48"):                     # under SMALL_DW_ALWAYS: the widest workgroup the channel count allows
+        nw = next(n for n in (8, 4, 2, 1) if cout % (32 * n) == 0)
+        return cd(Po, 48) * (cout // (32 * nw)) * 512
+    if fam.startswith("conv_stem3x3"):
+        return cd(Po, 256) * 256
+    if fam.startswith("conv_stem_mfma"):
+        return cd(op.in_w, 32) * cd(op.in_h, 8) * B * 256
+    if fam.startswith("conv_direct"):
+        return cd(Po * cout, 256) * 256
+    if fam.startswith("conv_head_decode_dw"):
+        return cd(P, int(fam.rsplit("_", 1)[1].split("x")[0])) * 512
+    if fam.startswith("conv_head_decode"):
+        return cd(P, 64) * 256
+    if case["group"] == "layer":
+        return cd(Po * (op.in_c // (16 // es) if case["wide"] else op.in_c), 256) * 256
+    if case["group"] == "reorg":
+        return cd(Po * cout, 256) * 256
+    if case["group"] == "spp":
+        return B * (op.in_c * es // 32) * 256
+    if case["group"] == "yolo":
+        return cd(P, 32) * (256 if dtype == "float32" else 384)
+    assert fam.split("_%s")[0] in ("conv_patch_wsp", "conv1x1_wres", "conv_stem_s2_fused_u8", "conv_resblock_fused", "conv_block_fused"), fam
+    return None
+
+
+def largest_batch(case, dtype):
+    """(the largest batch plan creation takes for ``case``, what refuses the next one: "pixels" or "threads")"""
+    fp = frame_pixels(case, dtype)
+    ok = MAX_PIXELS // fp
+    if (launch_threads(case, dtype, ok) or 0) <= MAX_THREADS:
+        return ok, "pixels"
+    lo, hi = 1, ok                                      # threads grow with the batch
+    while lo < hi:
+        mid = (lo + hi + 1) // 2
+        lo, hi = (mid, hi) if launch_threads(case, dtype, mid) <= MAX_THREADS else (lo, mid - 1)
+    return lo, "threads"
