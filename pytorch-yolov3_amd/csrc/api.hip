@@ -42,9 +42,9 @@ void y3_launch_log_append(Y3LaunchLog *log, const void *host_function, hipStream
   log->names += name;
   log->names += '\n';
 }
-// y3_set_tuning("debug", v): exists in DIAGNOSTIC builds only (`make variant FLAGS=-DY3_X_...`, `make stamps`); the product
+// y3_set_tuning("debug", v): exists in DIAGNOSTIC builds only (`make variant FLAGS=-DY3_DEBUG_KEY ...`, `make stamps`); the product
 // library rejects the key, so a benchmark line can never come from kernels that skip work
-#if defined(Y3_X_NOEPI) || defined(Y3_X_S2BOUND) || defined(Y3_X_DEBUG) || defined(Y3_STAMPS)
+#if defined(Y3_DEBUG_KEY) || defined(Y3_STAMPS)
 #define Y3_HAS_DEBUG_KEY 1
 static int g_y3_debug = 0;
 int y3_debug_flags() { return g_y3_debug; }

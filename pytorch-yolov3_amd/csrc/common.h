@@ -35,7 +35,8 @@ typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 #endif
 #define Y3_LEAKY_SLOPE 0.1f
 
-// diagnostic builds only (y3_set_tuning("debug", v)): 0 in the product
+// diagnostic builds only (y3_set_tuning("debug", v)): 0 in the product.  The hook of timing experiments (a launcher passes it to its
+// kernel as a flag bit); the experiments that read it are measured and removed (profiles/), so nothing reads it at present
 int y3_debug_flags();
 // CU count of the current device (api.hip); the choosers' grid-size heuristics scale with it
 int y3_device_cus();

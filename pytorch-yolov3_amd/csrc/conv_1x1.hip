@@ -17,10 +17,8 @@
 // Geometry: BM = 128 pixels, BN = 128 (K <= 256) or 64 (K <= 512) channels, 4 MFMA waves (2 x 2, wave tile 64 x BN/2)
 // + 4 loader waves, LDS = K*BN*2 (weights) + 128*BN*2 (park) + 4 x 16 KiB (ring) <= 160 KiB, one workgroup per CU.
 // Workgroup b owns channel tile b % n_tiles and the pixel tiles (b / n_tiles) + j * (grid / n_tiles).
-#include <type_traits>
-#include <utility>
-
 #include "common.h"
+#include "conv_device.h"
 #include "decode_core.h"
 
 namespace {
@@ -38,14 +36,6 @@ struct WresArgs {
   int m_tiles;     // ceil(M / 128)
   uint32_t flags;
 };
-
-typedef __attribute__((address_space(3))) void lds_void;
-typedef const __attribute__((address_space(1))) void gbl_void;
-
-template <int N>
-__device__ __forceinline__ void wres_wait_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 
 template <typename T, int BN>
 __global__ __launch_bounds__(512, 2) void conv1x1_wres_kernel(WresArgs p) {
@@ -111,7 +101,7 @@ __global__ __launch_bounds__(512, 2) void conv1x1_wres_kernel(WresArgs p) {
     }
     int kt = 0;
     for (int s = 0; s < total; ++s) {
-      wres_wait_vmcnt<(NS - 2) * A_CH>();            // K-tile s (and the weights before it) landed; NS - 2 tiles in flight
+      y3_wait_vmcnt<(NS - 2) * A_CH>();              // K-tile s (and the weights before it) landed; NS - 2 tiles in flight
       __builtin_amdgcn_s_barrier();                  // B(s): tile s visible, slot of tile s - 1 free
       issue(stage);
       stage = stage + 1 == NS ? 0 : stage + 1;
@@ -120,7 +110,7 @@ __global__ __launch_bounds__(512, 2) void conv1x1_wres_kernel(WresArgs p) {
         __builtin_amdgcn_s_barrier();                // P: the MFMA waves have parked the finished tile
       }
     }
-    wres_wait_vmcnt<0>();
+    y3_wait_vmcnt<0>();
     return;
   }
 
@@ -135,7 +125,7 @@ __global__ __launch_bounds__(512, 2) void conv1x1_wres_kernel(WresArgs p) {
     sc[ni] = *reinterpret_cast<const f32x4 *>(p.scale + c);
     bi[ni] = *reinterpret_cast<const f32x4 *>(p.bias + c);
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // nothing of this wave is in flight inside the loop
+  y3_wait_vmcnt<0>();                                // nothing of this wave is in flight inside the loop
   int stage = 0;
   for (int j = 0; j < my_tiles; ++j) {
     f32x4 acc[MI][NI];
@@ -228,20 +218,6 @@ struct DwArgs {
 };
 static_assert(offsetof(DwArgs, dec) == 104 && sizeof(DwArgs) == 224, "kernel argument layout");
 
-template <int V>
-struct StepC { static constexpr int value = V; };
-template <int... I, typename F>
-__device__ __forceinline__ void static_for_impl(std::integer_sequence<int, I...>, F &&f) { (f(StepC<I>{}), ...); }
-template <int N, typename F>
-__device__ __forceinline__ void static_for(F &&f) { static_for_impl(std::make_integer_sequence<int, N>{}, f); }
-
-// s_waitcnt vmcnt(N) that NAMES the four registers it waits for (see dw_wait_vm in conv_halo.hip): the tie keeps the compiler
-// from moving their uses above the wait and from re-using them while the load is in flight
-template <int N>
-__device__ __forceinline__ void dw1_wait_vm(u32x4 (&w)[2][2]) {
-  asm volatile("s_waitcnt vmcnt(%4)" : "+v"(w[0][0]), "+v"(w[0][1]), "+v"(w[1][0]), "+v"(w[1][1]) : "n"(N) : "memory");
-}
-
 // HEAD = true: the detection-head conv (bias, linear or logistic, <= 256 logits per pixel = ONE channel tile) + YOLOLayer decode
 // (/root/reference/yolov3/darknet.py:86-116) in one launch: after the K loop the float32 logits (sum * scale + bias, one fused rounding
 // -- the arithmetic of the tiled head kernel, conv_igemm.hip) are parked in the LDS the activation tile no longer needs, rows of
@@ -303,7 +279,7 @@ __global__ __launch_bounds__(512, 2) void conv1x1_dw_kernel(DwArgs p) {
 #pragma unroll
     for (int ni = 0; ni < NI; ++ni) acc[mi][ni] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4 * (DEPTH - 1)) : "memory");   // the tile (this wave's pieces) and step 0's weights landed
+  y3_wait_vmcnt<4 * (DEPTH - 1)>();                   // the tile (this wave's pieces) and step 0's weights landed
   __builtin_amdgcn_s_barrier();                       // ... everyone's pieces: the only barrier of the kernel
   if (wave >= 4) __builtin_amdgcn_s_setprio(1);       // the younger wave of each SIMD (see conv_halo_ws_kernel)
 
@@ -330,11 +306,11 @@ __global__ __launch_bounds__(512, 2) void conv1x1_dw_kernel(DwArgs p) {
     }
   };
   read_x(0, 0, xf[0]);
-  static_for<NKT>([&](auto ktc) {
+  y3_static_for<NKT>([&](auto ktc) {
     constexpr int kt = decltype(ktc)::value, slot = kt % DEPTH;
     // in flight behind step kt's four loads: those of steps kt + 1 .. min(kt + DEPTH, NKT) - 1
     constexpr int younger = 4 * ((kt + DEPTH < NKT ? kt + DEPTH : NKT) - kt - 1);
-    dw1_wait_vm<younger>(wf[slot]);
+    y3_wait_vmcnt_for<younger>(wf[slot]);
     __builtin_amdgcn_sched_barrier(0);
     read_x(kt, 1, xf[1]);
     mma(xf[0], wf[slot][0]);

@@ -40,12 +40,9 @@
 // then see eight consecutive keys with alternating row parity whatever TW is, i.e. conflict-free ds_read_b128
 // (MI355X_MICROARCH.md, LDS; measured SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE = 3 %, all from the mid image's writes).
 #include "common.h"
-#include <type_traits>
+#include "conv_device.h"
 
 namespace {
-
-typedef __attribute__((address_space(3))) void lds_void;
-typedef const __attribute__((address_space(1))) void gbl_void;
 
 constexpr int kHaloRows = 448;                  // patch rows a workgroup can hold (28 fragments)
 constexpr int kPlane = kHaloRows * 128;         // one x buffer / one mid plane: 57344 bytes
@@ -71,10 +68,6 @@ struct BlockArgs {
   uint32_t inv_pw, inv_tw;   // n / d == (n * inv) >> 16 for n < 512 (d = TW + 2, TW)
 };
 
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 __device__ __forceinline__ uint32_t lane32(uint32_t v) {
   asm volatile("" : "+v"(v));
   return v;
@@ -145,8 +138,8 @@ __global__ __launch_bounds__(kNT) void conv_block_fused_kernel(BlockArgs p) {
   };
   // at most n loads of this wave still in flight (n = whole sub-chunks: 5 loads each in waves 0-3, 4 in waves 4-7)
   auto wait_chunks = [&](int n) {
-    if (n_ax == kAX) { if (n >= 2) wait_vm<10>(); else if (n == 1) wait_vm<5>(); else wait_vm<0>(); }
-    else { if (n >= 2) wait_vm<8>(); else if (n == 1) wait_vm<4>(); else wait_vm<0>(); }
+    if (n_ax == kAX) { if (n >= 2) y3_wait_vmcnt<10>(); else if (n == 1) y3_wait_vmcnt<5>(); else y3_wait_vmcnt<0>(); }
+    else { if (n >= 2) y3_wait_vmcnt<8>(); else if (n == 1) y3_wait_vmcnt<4>(); else y3_wait_vmcnt<0>(); }
   };
 
   Y3_STAMP_DECL
@@ -397,9 +390,9 @@ __global__ __launch_bounds__(kNT) void conv_block_fused_kernel(BlockArgs p) {
       // fly") would rest on how many stores the wave really issued -- they are predicated per lane, a wave whose pixels are
       // all outside the frame issues none -- and was right only because the compiler's waits on the scale / bias loads, which
       // return in order behind the weight pieces, happened to cover them.  One full drain per 18 K-steps instead.
-      wait_vm<0>();
+      y3_wait_vmcnt<0>();
     } else {
-      wait_vm<0>();                                   // weights(it + 2) (and everything older) landed: ready for B(it + 1)
+      y3_wait_vmcnt<0>();                             // weights(it + 2) (and everything older) landed: ready for B(it + 1)
     }
     Y3_STAMP(6);
     np = np1; c = c1; tap = tap1; slot = slot1;

@@ -17,14 +17,10 @@
 //   * the K loop is FULLY unrolled (Cin / 64 is a template parameter): chunk outermost, tap innermost, K-halves in order -- the order of
 //     every other MFMA conv kernel: same bits;
 //   * epilogue in registers: a lane holds eight consecutive channels of its pixel -> one 16-byte shortcut load, one 16-byte store.
-#include <utility>
-
 #include "common.h"
+#include "conv_device.h"
 
 namespace {
-
-typedef __attribute__((address_space(3))) void lds_void;
-typedef const __attribute__((address_space(1))) void gbl_void;
 
 struct Dw48Args {
   const char *in;
@@ -46,24 +42,9 @@ struct Dw48Args {
 };
 
 template <int V>
-struct HalfC { static constexpr int value = V; };
-template <int... I, typename F>
-__device__ __forceinline__ void dw48_for_impl(std::integer_sequence<int, I...>, F &&f) { (f(HalfC<I>{}), ...); }
-template <int N, typename F>
-__device__ __forceinline__ void dw48_for(F &&f) { dw48_for_impl(std::make_integer_sequence<int, N>{}, f); }
-
-// s_waitcnt vmcnt(N) that NAMES the two registers it waits for (see dw_wait_vm in conv_halo.hip)
-template <int N>
-__device__ __forceinline__ void dw48_wait_vm(u32x4 (&w)[2]) {
-  asm volatile("s_waitcnt vmcnt(%2)" : "+v"(w[0]), "+v"(w[1]) : "n"(N) : "memory");
-}
-
-#ifndef Y3_DW48_DEPTH
-#define Y3_DW48_DEPTH 8
-#endif
-#ifndef Y3_DW48_HELPERS
-#define Y3_DW48_HELPERS 1                              // 0: a workgroup has only its computing waves (A/B)
-#endif
+using HalfC = std::integral_constant<int, V>;          // a half-step (32 K-elements) as a compile-time constant
+// Tried and removed (profiles/r06_conv_dw48.txt): weight prefetch depths of 6 / 12 / 16 half-steps instead of 8 (no difference; 24
+// spills), and workgroups of the computing waves alone, without the helper waves that only stage the halo image (slower).
 
 // Stride 2 (ST = 2, 3x3, even input maps): the same kernel over FOUR PARITY PLANES of the input.  With iy = 2 oy - 1 + ky and
 // ix = 2 ox - 1 + kx every tap reads one of  EE = in[2i][2j],  EO = in[2i][2j+1],  OE = in[2i+1][2j],  OO = in[2i+1][2j+1],  and each
@@ -85,7 +66,7 @@ __global__ __launch_bounds__(512) void conv_dw48_kernel(Dw48Args p) {
   constexpr int S = NKT * TAPS * 2;                    // half-steps (32 K-elements each) per image: NH x S make the whole sum
   // half-steps of weight fragments in flight (2 loads of 1 KiB per wave each).  Only 2-8 waves run on a CU here and a half-step is six
   // MFMAs (96 cycles): six half-steps in flight covered a quarter of an L2 round trip (19^2 x 1 frame: 19.9 us for 6.6 us of MFMA work)
-  constexpr int DEPTH = S < Y3_DW48_DEPTH ? S : Y3_DW48_DEPTH;
+  constexpr int DEPTH = S < 8 ? S : 8;
   extern __shared__ __attribute__((aligned(16))) char smem[];
 
   const int tid = threadIdx.x;
@@ -152,7 +133,7 @@ __global__ __launch_bounds__(512) void conv_dw48_kernel(Dw48Args p) {
     for (int h = 0; h < NH; ++h) {
       if (h > 0) __builtin_amdgcn_s_barrier();
       stage(h);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      y3_wait_vmcnt<0>();
       __builtin_amdgcn_s_barrier();
     }
     return;
@@ -168,7 +149,7 @@ __global__ __launch_bounds__(512) void conv_dw48_kernel(Dw48Args p) {
     asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(w[0]) : "v"(voff), "s"(b0));
     asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(w[1]) : "v"(voff), "s"(b1));
   };
-  dw48_for<DEPTH>([&](auto sc) { load_w(sc, wf[decltype(sc)::value]); });
+  y3_static_for<DEPTH>([&](auto sc) { load_w(sc, wf[decltype(sc)::value]); });
 
   // ---- fragment addresses, once per workgroup: tap (ky, kx) of this lane's pixel mi * 16 + fr is halo row mi * 16 + fr + ky W + kx; a
   // border tap (zero padding, row wrap of the raster strip) is redirected to the zero row here, so that the K loop's per-half-step
@@ -229,15 +210,15 @@ __global__ __launch_bounds__(512) void conv_dw48_kernel(Dw48Args p) {
       for (int ni = 0; ni < NI; ++ni) acc[mi][ni] = y3_mfma16<T>(w[ni], x[mi], acc[mi][ni]);
   };
   auto run_image = [&]() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * (DEPTH - 1)) : "memory");   // this wave's halo pieces and half-step 0's weights landed
+    y3_wait_vmcnt<2 * (DEPTH - 1)>();                  // this wave's halo pieces and half-step 0's weights landed
     __builtin_amdgcn_s_barrier();                      // ... everyone's pieces: the only barrier of the K loop (per image)
     read_x(HalfC<0>{}, xf[0]);
     if constexpr (S > 1) read_x(HalfC<1>{}, xf[1]);
-    dw48_for<S>([&](auto sc) {
+    y3_static_for<S>([&](auto sc) {
       constexpr int s = decltype(sc)::value, slot = s % DEPTH;
       // in flight behind half-step s's two loads: those of half-steps s + 1 .. min(s + DEPTH, S) - 1
       constexpr int younger = 2 * ((s + DEPTH < S ? s + DEPTH : S) - s - 1);
-      dw48_wait_vm<younger>(wf[slot]);
+      y3_wait_vmcnt_for<younger>(wf[slot]);
       __builtin_amdgcn_sched_barrier(0);
       if constexpr (s + 2 < S) read_x(HalfC<s + 2>{}, xf[(s + 2) % 3]);
       mma(xf[s % 3], wf[slot]);
@@ -270,7 +251,7 @@ __global__ __launch_bounds__(512) void conv_dw48_kernel(Dw48Args p) {
         stage(h + 1);
         asm volatile("" ::: "memory");
         w_img = w_lane + (uint32_t)(((h + 1) * NKT * 2) << 10);
-        dw48_for<DEPTH>([&](auto sc) { load_w(sc, wf[decltype(sc)::value]); });
+        y3_static_for<DEPTH>([&](auto sc) { load_w(sc, wf[decltype(sc)::value]); });
       }
     }
   }
@@ -398,7 +379,7 @@ int launch_dw48(const y3_op *ops, const y3_step &step, const void *d_in, const v
   a.flags = op.flags;
   const int nkt = sh.cin_img / 64;
   const size_t lds = (size_t)(a.hr + 1) * sh.cin_img * 2 + 1024;   // (+ the tail of the last 1-KiB piece)
-  const dim3 grid(y3_ceil_div(a.M, 48) * a.n_ctiles), block(Y3_DW48_HELPERS ? 512 : 64 * nw);
+  const dim3 grid(y3_ceil_div(a.M, 48) * a.n_ctiles), block(512);
   return y3_by_dtype16(op.dtype, [&](auto tag) {
     typedef decltype(tag) T;
     if (op.ksize == 3 && op.stride == 1)
@@ -422,7 +403,7 @@ int y3_choose_conv_dw48(const y3_op &op, const y3_options &o, y3_step &st) {
   st.waves = dw48_waves_for(op, o);
   Y3_REQUIRE(st.waves != 0, "conv block %d: not a shape for the small-grid direct-weights kernel", op.block_idx);
   st.launch = launch_dw48;
-  st.threads = y3_ceil_div64((long long)op.batch * op.out_h * op.out_w, 48) * (op.out_c / (32 * st.waves)) * (Y3_DW48_HELPERS ? 512 : 64 * st.waves);
+  st.threads = y3_ceil_div64((long long)op.batch * op.out_h * op.out_w, 48) * (op.out_c / (32 * st.waves)) * 512;
   st.name = op.ksize == 3 ? (op.stride == 2 ? Y3_KNAME(op.dtype, "conv_dw48_k3s2_", "") : Y3_KNAME(op.dtype, "conv_dw48_k3_", ""))
                           : Y3_KNAME(op.dtype, "conv_dw48_k1_", "");
   st.frag = true;

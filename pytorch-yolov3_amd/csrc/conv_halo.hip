@@ -23,8 +23,10 @@
 // every wave loads and computes in lock step, ping-pong wave groups, 32-channel chunks with a deeper ring
 // (profiles/r01_convbench_*.txt); two workgroups per CU with 128 x 128 tiles (profiles/HISTORY.md 3.1c); two persistent forms of
 // the strip kernel, the second with the epilogue in registers and the finished tile drained by the loader waves
-// (profiles/r03b_persistent_halo_wsq_investigation.txt).
+// (profiles/r03b_persistent_halo_wsq_investigation.txt).  Timing-only experiments, removed as well: every other first-round
+// workgroup starting half a tile period late (profiles/r04s_fill_path.txt, item 4), the patch kernel without its epilogue.
 #include "common.h"
+#include "conv_device.h"
 
 namespace {
 
@@ -51,39 +53,8 @@ struct HaloArgs {
   uint32_t flags;
 };
 
-template <typename T>
-struct MmaH {   // bf16 / IEEE half: one v_mfma_f32_16x16x32 per 64-byte K-half
-  static __device__ __forceinline__ void run(f32x4 &acc, const u32x4 &w, const u32x4 &x) { acc = y3_mfma16<T>(w, x, acc); }
-};
-template <>
-struct MmaH<float> {
-  static __device__ __forceinline__ void run(f32x4 &acc, const u32x4 &w, const u32x4 &x) {
-    const f32x4 wf = __builtin_bit_cast(f32x4, w), xf = __builtin_bit_cast(f32x4, x);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[j], xf[j], acc, 0, 0, 0);
-  }
-};
-
-typedef __attribute__((address_space(3))) void lds_void;
-typedef const __attribute__((address_space(1))) void gbl_void;
-
 template <int V>
-struct TapC { static constexpr int value = V; };
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-  if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  else if constexpr (N == 1) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
-  else if constexpr (N == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-  else if constexpr (N == 3) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-  else if constexpr (N == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-  else asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt_n() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
+using TapC = std::integral_constant<int, V>;   // a filter tap as a compile-time constant
 
 // ------------------------------------------------------------------------------------------------
 // Wave-specialised variant (BM = 256, BN = 128): 8 consumer waves (wave tile 64 x 64, two per SIMD) that only
@@ -118,13 +89,6 @@ __global__ __launch_bounds__(768, 3) void conv_halo_ws_kernel(HaloArgs p) {
   char *sB = smem;                                    // [NSB][BN][128]
   char *sA = smem + NSB * B_BYTES;                    // [2][hr_pad][128]
 
-#ifdef Y3_X_STAGGER
-  // timing experiment: every other first-round workgroup of an XCD starts half a tile period late, so that the CUs' prologues
-  // and epilogues (bursts of memory traffic) no longer coincide
-  if ((p.flags & 0x40000000u) && blockIdx.x < 256 && ((blockIdx.x >> 3) & 1)) {
-    __builtin_amdgcn_s_sleep(127); __builtin_amdgcn_s_sleep(127);
-  }
-#endif
   Y3_STAMP_DECL
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -220,8 +184,8 @@ __global__ __launch_bounds__(768, 3) void conv_halo_ws_kernel(HaloArgs p) {
       // youngest halo slices in flight (they are not needed before the next chunk, and a slice issued at step s is
       // covered by the wait of step s+1): only the weights' landing sits on the barrier's critical path.
       // (guaranteed landed at B(it): the weights issued D steps ago; halo slices issued D + 1 or more steps ago)
-      if (D == 2) { if (it == 0) wait_vmcnt<NBL>(); else if (it == 1) wait_vmcnt_n<PER>(); else wait_vmcnt_n<PER + HPS>(); }
-      else { if (it == 0) wait_vmcnt<0>(); else wait_vmcnt_n<HPS>(); }
+      if (D == 2) { if (it == 0) y3_wait_vmcnt<(NBL < 5 ? NBL : 5)>(); else if (it == 1) y3_wait_vmcnt<PER>(); else y3_wait_vmcnt<PER + HPS>(); }
+      else { if (it == 0) y3_wait_vmcnt<0>(); else y3_wait_vmcnt<HPS>(); }
       Y3_COARSE(3);
       __builtin_amdgcn_s_barrier();
       Y3_COARSE(4);
@@ -244,7 +208,7 @@ __global__ __launch_bounds__(768, 3) void conv_halo_ws_kernel(HaloArgs p) {
       if (++tap == 9) { tap = 0; ++chunk; }
       Y3_COARSE(5);
     }
-    wait_vmcnt<0>();                                  // the tail's dummy loads must not land on the output tile
+    y3_wait_vmcnt<0>();                               // the tail's dummy loads must not land on the output tile
 #if defined(Y3_STAMPS) && !defined(Y3_STAMPS_FINE) && !defined(Y3_STAMPS_CLOCK)
     if (tid == NC) for (int _i = 3; _i < 7; ++_i) atomicAdd(&g_y3_stamps[_i], _st_acc[_i]);
 #endif
@@ -378,7 +342,7 @@ __global__ __launch_bounds__(768, 3) void conv_halo_ws_kernel(HaloArgs p) {
 #pragma unroll
       for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
-        for (int ni = 0; ni < NI; ++ni) MmaH<T>::run(acc[mi][ni], wf[ni], xf[mi]);
+        for (int ni = 0; ni < NI; ++ni) Mma<T>::run(acc[mi][ni], wf[ni], xf[mi]);
     };
     auto interleave = [&]() {
 #pragma unroll
@@ -575,13 +539,7 @@ __global__ __launch_bounds__(768, 3) void conv_halo_ws_kernel(HaloArgs p) {
         for (int r = 0; r < 4; ++r) { v[r] += r0[r]; v[4 + r] += r1[r]; }
       }
     }
-    T *op = reinterpret_cast<T *>(p.out) + (long long)m * p.out_ld + co;
-    if constexpr (sizeof(T) == 2) {
-      *reinterpret_cast<u32x4 *>(op) = y3_pack8<T>(v);
-    } else {
-      *reinterpret_cast<f32x4 *>(op) = f32x4{v[0], v[1], v[2], v[3]};
-      *reinterpret_cast<f32x4 *>(op + 4) = f32x4{v[4], v[5], v[6], v[7]};
-    }
+    y3_store8(reinterpret_cast<T *>(p.out) + (long long)m * p.out_ld + co, v);
   }
   Y3_CLK_TAIL();
 }
@@ -686,8 +644,8 @@ __global__ __launch_bounds__(768, 3) void conv_patch_wsp_kernel(HaloArgs p, int 
 #pragma unroll 1
       for (int it = 0; it < nit; ++it) {
         // weights first, halo slices after: the counted wait leaves the youngest halo slices in flight (see above)
-        if (D == 2) { if (gstep == 0) wait_vmcnt<NBL>(); else if (gstep == 1) wait_vmcnt_n<PER>(); else wait_vmcnt_n<PER + HPS>(); }
-        else { if (gstep == 0) wait_vmcnt<0>(); else wait_vmcnt_n<HPS>(); }
+        if (D == 2) { if (gstep == 0) y3_wait_vmcnt<(NBL < 5 ? NBL : 5)>(); else if (gstep == 1) y3_wait_vmcnt<PER>(); else y3_wait_vmcnt<PER + HPS>(); }
+        else { if (gstep == 0) y3_wait_vmcnt<0>(); else y3_wait_vmcnt<HPS>(); }
         ++gstep;
         __builtin_amdgcn_s_barrier();
         // weight tile D + 1 steps ahead: this tile's, the next tile's, or (nothing left) the last one again
@@ -708,7 +666,7 @@ __global__ __launch_bounds__(768, 3) void conv_patch_wsp_kernel(HaloArgs p, int 
       }
       __builtin_amdgcn_s_barrier();                    // E: consumers are done with the last chunk's halo buffer
     }
-    wait_vmcnt<0>();
+    y3_wait_vmcnt<0>();
     return;
   }
 
@@ -756,7 +714,7 @@ __global__ __launch_bounds__(768, 3) void conv_patch_wsp_kernel(HaloArgs p, int 
 #pragma unroll
       for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
-        for (int ni = 0; ni < NI; ++ni) MmaH<T>::run(acc[mi][ni], wf[ni], xf[mi]);
+        for (int ni = 0; ni < NI; ++ni) Mma<T>::run(acc[mi][ni], wf[ni], xf[mi]);
     };
     auto interleave = [&]() {
 #pragma unroll
@@ -797,16 +755,6 @@ __global__ __launch_bounds__(768, 3) void conv_patch_wsp_kernel(HaloArgs p, int 
       ring = ring_n;
     }
     __builtin_amdgcn_s_barrier();                      // E: every consumer is done reading the last chunk's halo
-#ifdef Y3_X_NOEPI
-    // timing-only experiment (y3_set_tuning("debug", 1) in this diagnostic build): no epilogue at all (results wrong)
-    if (p.flags & 0x40000000u) {
-#pragma unroll
-      for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < NI; ++ni) asm volatile("" ::"v"(acc[mi][ni]));
-      continue;
-    }
-#endif
     // ---- epilogue, per wave: 16 pixels x 64 channels at a time through a private 4 KiB slice of that buffer ----
     float *sC = reinterpret_cast<float *>(sA + ((gchunk + 1) & 1) * p.a_bytes) + wave * 1024;
     const int oc = lane & 7;                           // 8-channel group of this lane's write-out items
@@ -868,13 +816,7 @@ __global__ __launch_bounds__(768, 3) void conv_patch_wsp_kernel(HaloArgs p, int 
               for (int q = 0; q < 4; ++q) { v[q] += resf[AHEAD ? (mi & 1) : 0][r][0][q]; v[4 + q] += resf[AHEAD ? (mi & 1) : 0][r][1][q]; }
             }
           }
-          T *op = reinterpret_cast<T *>(p.out) + (long long)m * p.out_ld + co;
-          if constexpr (sizeof(T) == 2) {
-            *reinterpret_cast<u32x4 *>(op) = y3_pack8<T>(v);
-          } else {
-            *reinterpret_cast<f32x4 *>(op) = f32x4{v[0], v[1], v[2], v[3]};
-            *reinterpret_cast<f32x4 *>(op + 4) = f32x4{v[4], v[5], v[6], v[7]};
-          }
+          y3_store8(reinterpret_cast<T *>(p.out) + (long long)m * p.out_ld + co, v);
         }
       }
       __builtin_amdgcn_s_waitcnt(0xC07F);              // reads done before the next group overwrites the slice
@@ -895,33 +837,16 @@ __global__ __launch_bounds__(768, 3) void conv_patch_wsp_kernel(HaloArgs p, int 
 // and at most one 1-KiB LDS-DMA piece of the next chunk's halo.  Same K order (chunk outermost, tap innermost, K-halves
 // in order) as every other MFMA conv kernel here: same bits.  Development, measurements and the one hard bug
 // (inline-asm loads the compiler cannot see in flight): profiles/r05s_halo_dw.txt.
-// dw_wait_vm: s_waitcnt vmcnt(N) that NAMES the four registers it waits for -- the tie is what keeps the compiler from
-// moving their uses above the wait, and from re-using them while the load is in flight.
-// Y3_DW_EPI: the kernel's write-out.  0 = two channel halves of 128, each parked in LDS as float32 and written out by all
-// threads (round 5).  1 = straight from the accumulators: the fragment-order copy of the weights carries y3_pair_perm'd rows,
-// so a lane holds eight consecutive channels of its pixel per fragment pair -- scale / bias / LeakyReLU / shortcut / rounding
-// in registers, one 16-byte store per pair; no LDS, no barrier, waves finish independently.  2 = the same arithmetic in
-// registers, the ROUNDED tile (192 x 256 x 2 bytes) parked in LDS once and written out as whole 512-byte pixel rows.
-// Same arithmetic per value in all three: same bits.
-#ifndef Y3_DW_EPI
-#define Y3_DW_EPI 0
-#endif
-// Y3_DW_SMASK: 1 = border-tap masks as wave-wide lane masks in scalar registers (one v_cndmask per select, as in
-// conv_halo_ws_kernel); 0 = nine tap bits per fragment in vector registers (round 5)
-#ifndef Y3_DW_SMASK
-#define Y3_DW_SMASK 1
-#endif
-
+// Write-out: two channel halves of 128, each parked in LDS as float32 and written out by all threads.  Tried in round 6 and
+// removed (profiles/r06_dw_epilogue.txt): the epilogue straight from the accumulators (a lane holds eight consecutive channels per
+// fragment pair: no LDS, no barrier) and the same with the ROUNDED tile parked in LDS and written as whole 512-byte pixel rows --
+// same bits, 2-4.5 % slower with a shortcut operand, level to +2.6 % without; border-tap masks as nine tap bits per fragment in vector
+// registers (round 5) instead of the wave-wide lane masks in scalar registers of conv_halo_ws_kernel (0.3-0.9 % slower).
 // Tried in round 6 and removed (profiles/r06_dw_epilogue.txt): THREE halo buffers with the images of chunks 0, 1 and 2 all issued in
 // the prologue and chunk c + 2 fetched during chunk c (EXEC-masked inline-asm LDS-DMA, so that a 128-channel layer issues none
 // from inside its K loop and a 256-channel layer one chunk's worth instead of three).  -8 % at 38^2, -12 % at 76^2, -5 % end to
 // end: all 256 CUs start together and the prologue's burst (144 instead of 48 KiB per CU) is memory-bound; the loads of the
 // second K-step cannot complete before it (vmcnt retires in order).  Spread over the K loop the same bytes cost less.
-template <int N, typename V>
-__device__ __forceinline__ void dw_wait_vm(V (&w)[4]) {
-  asm volatile("s_waitcnt vmcnt(%4)" : "+v"(w[0]), "+v"(w[1]), "+v"(w[2]), "+v"(w[3]) : "n"(N) : "memory");
-}
-
 template <typename T, int NA>
 __global__ __launch_bounds__(512, 2) void conv_halo_dw_kernel(HaloArgs p) {
   static_assert(sizeof(T) == 2 && NA >= 4 && NA <= 6, "16-bit storage modes only; 4 .. 6 halo passes per chunk");
@@ -990,9 +915,7 @@ __global__ __launch_bounds__(512, 2) void conv_halo_dw_kernel(HaloArgs p) {
   };
 
   // ---- pixel fragments ----
-  // border-tap masks of the wave's six fragments: lane masks in scalar registers (Y3_DW_SMASK) or nine tap bits per fragment,
-  // three fragments per vector register
-  [[maybe_unused]] uint32_t tm[(MI + 2) / 3] = {};
+  // border-tap masks of the wave's six fragments: lane masks in scalar registers
   unsigned long long mk_top[MI], mk_bot[MI], mk_left[MI], mk_right[MI];
 #pragma unroll
   for (int mi = 0; mi < MI; ++mi) {
@@ -1001,16 +924,10 @@ __global__ __launch_bounds__(512, 2) void conv_halo_dw_kernel(HaloArgs p) {
     const uint32_t r = m - img * (uint32_t)p.HW;
     const uint32_t oy = (__umulhi(r, p.mul_w) + r) >> p.sh_w;
     const uint32_t ox = r - oy * (uint32_t)p.W;
-#if Y3_DW_SMASK
     mk_top[mi] = __builtin_amdgcn_ballot_w64(oy >= 1u);
     mk_bot[mi] = __builtin_amdgcn_ballot_w64(oy + 1u < (uint32_t)p.H);
     mk_left[mi] = __builtin_amdgcn_ballot_w64(ox >= 1u);
     mk_right[mi] = __builtin_amdgcn_ballot_w64(ox + 1u < (uint32_t)p.W);
-#else
-    const uint32_t vx = (ox >= 1u ? 1u : 0u) | 2u | (ox + 1u < (uint32_t)p.W ? 4u : 0u);
-    const uint32_t t9 = (oy >= 1u ? vx : 0u) | (vx << 3) | (oy + 1u < (uint32_t)p.H ? vx << 6 : 0u);
-    tm[mi / 3] |= t9 << (9 * (mi % 3));
-#endif
   }
   typedef const __attribute__((address_space(3))) u32x4 lds_u32x4;
   const int sA_lds = (int)(size_t)(lds_void *)sA;
@@ -1028,15 +945,11 @@ __global__ __launch_bounds__(512, 2) void conv_halo_dw_kernel(HaloArgs p) {
     for (int mi = 0; mi < MI; ++mi) {
       int off = ap + mi * 2048;
       if constexpr (tap != 4) {
-#if Y3_DW_SMASK
         unsigned long long ok = ky == 0 ? mk_top[mi] : (ky == 2 ? mk_bot[mi] : ~0ull);
         if constexpr (kx == 0) ok &= mk_left[mi];
         if constexpr (kx == 2) ok &= mk_right[mi];
         const int real = off;
         asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(off) : "v"(zoff), "v"(real), "s"(ok));
-#else
-        off = ((tm[mi / 3] >> (9 * (mi % 3) + tap)) & 1u) ? off : zoff;
-#endif
       }
       sel[mi] = off;
     }
@@ -1058,7 +971,7 @@ __global__ __launch_bounds__(512, 2) void conv_halo_dw_kernel(HaloArgs p) {
   for (int pass = 0; pass < p.na; ++pass) issue_halo_pass(0, pass, true);
   load_w0(wf[0], b_voff);
   load_w1(wf[2], b_voff);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  y3_wait_vmcnt<0>();
   __builtin_amdgcn_s_barrier();
   if (wave >= 4) __builtin_amdgcn_s_setprio(1);       // the younger wave of each SIMD (see conv_halo_ws_kernel)
   frag_addrs(TapC<0>{}, 0);
@@ -1083,14 +996,14 @@ __global__ __launch_bounds__(512, 2) void conv_halo_dw_kernel(HaloArgs p) {
     if constexpr (tap < NA) issue_halo_pass(chunk + 1, tap, chunk + 1 < p.nchunks);
     // younger than wf[S]'s loads: 4 loads of the previous step + 4 of this one for certain, up to two halo pieces maybe --
     // the count that is always safe is 8
-    dw_wait_vm<8>(wf[S]);
+    y3_wait_vmcnt_for<8>(wf[S]);
     mma_half(xf, 0, wf[S]);
     read_half(xf, 0, 64);
     mma_half(xf, MH, wf[S]);
     read_half(xf, MH, 64);
     __builtin_amdgcn_sched_barrier(0);
     load_w1(wf[S], voff_n);
-    dw_wait_vm<8>(wf[(S + 2) % 3]);                   // younger for certain: 4 + 4 loads of this step
+    y3_wait_vmcnt_for<8>(wf[(S + 2) % 3]);            // younger for certain: 4 + 4 loads of this step
     mma_half(xf, 0, wf[(S + 2) % 3]);
     if constexpr (tap == 8) {
       // chunk boundary: the next step reads the other halo buffer.  Its pieces (the youngest was issued before the last
@@ -1098,7 +1011,7 @@ __global__ __launch_bounds__(512, 2) void conv_halo_dw_kernel(HaloArgs p) {
       // is done with the buffer that the next chunk's pieces will overwrite -- EXCEPT the second half of this K-half's
       // fragments, which are in registers already
       mma_half(xf, MH, wf[(S + 2) % 3]);
-      asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+      y3_wait_vmcnt<4>();
       __builtin_amdgcn_s_barrier();
       frag_addrs(TapC<tap_n>{}, (chunk_n & 1) * p.a_bytes);
       read_half(xf, 0, 0);
@@ -1122,71 +1035,12 @@ __global__ __launch_bounds__(512, 2) void conv_halo_dw_kernel(HaloArgs p) {
   // below the compiler considers their destination registers free from here on and may place the epilogue's pointer arithmetic
   // in them BEFORE the wait -- a load that lands late (memory contention: another kernel beside this one) then overwrites an
   // address, and the epilogue reads from nowhere (HSA_STATUS_ERROR_MEMORY_APERTURE_VIOLATION; profiles/r05s_halo_dw.txt).
-  dw_wait_vm<0>(wf[0]);
-  dw_wait_vm<0>(wf[1]);
-  dw_wait_vm<0>(wf[2]);
+  y3_wait_vmcnt_for<0>(wf[0]);
+  y3_wait_vmcnt_for<0>(wf[1]);
+  y3_wait_vmcnt_for<0>(wf[2]);
 
   const int act = y3_act(p.flags);
   const bool has_res = p.flags & Y3_F_RESIDUAL;
-#if Y3_DW_EPI != 0
-  // ---- epilogue in registers (Y3_DW_EPI 1 / 2).  The weight rows were laid out with y3_pair_perm: after both fragments of a
-  // pair (ni = 2 pr, 2 pr + 1) lane (fr, fq) holds channels  n0 + wn * 64 + pr * 32 + 8 fq .. + 7  of pixel  m0 + wm * 96 +
-  // mi * 16 + fr.  All twelve shortcut loads of the wave (16 bytes each, the registers of the weight / pixel fragments are
-  // free now) go out first, then per pair: scale / bias, LeakyReLU, + shortcut, round, store.
-  {
-    constexpr int NP = NI / 2;
-    const int co0 = n0 + wn * 64 + fq * 8;
-    const int mrow = m0 + wm * WM + fr;
-    u32x4 resv[NP][MI];
-    if (has_res) {
-#pragma unroll
-      for (int pr = 0; pr < NP; ++pr)
-#pragma unroll
-        for (int mi = 0; mi < MI; ++mi) {
-          const int m = mrow + mi * 16;
-          const char *rp = p.res + ((long long)m * p.res_ld + co0 + pr * 32) * ES;
-          resv[pr][mi] = m < p.M ? *reinterpret_cast<const u32x4 *>(rp) : u32x4{0u, 0u, 0u, 0u};
-        }
-    }
-#if Y3_DW_EPI == 2
-    __builtin_amdgcn_s_waitcnt(0xC07F);
-    __builtin_amdgcn_s_barrier();                     // nobody reads the halo any more: LDS holds the rounded output tile
-    char *sO = smem;                                  // [192 pixels][512 bytes], 16-byte pieces XOR-swizzled by pixel
-#endif
-#pragma unroll
-    for (int pr = 0; pr < NP; ++pr) {
-      const int co = co0 + pr * 32;
-      const f32x4 sc_lo = *reinterpret_cast<const f32x4 *>(p.scale + co), sc_hi = *reinterpret_cast<const f32x4 *>(p.scale + co + 4);
-      const f32x4 bi_lo = *reinterpret_cast<const f32x4 *>(p.bias + co), bi_hi = *reinterpret_cast<const f32x4 *>(p.bias + co + 4);
-#pragma unroll
-      for (int mi = 0; mi < MI; ++mi) {
-        const int m = mrow + mi * 16;
-        float v[8];
-        y3_bn_act8(v, acc[mi][2 * pr], acc[mi][2 * pr + 1], sc_lo, sc_hi, bi_lo, bi_hi, act);
-        if (has_res) y3_add8<T>(v, resv[pr][mi]);
-        const u32x4 o = y3_pack8<T>(v);
-#if Y3_DW_EPI == 1
-        if (m < p.M) *reinterpret_cast<u32x4 *>(reinterpret_cast<T *>(p.out) + (long long)m * p.out_ld + co) = o;
-#else
-        const int pl = wm * WM + mi * 16 + fr;        // piece index inside the pixel's 512 bytes: (channel - n0) / 8
-        *reinterpret_cast<u32x4 *>(sO + pl * 512 + ((((co - n0) >> 3) ^ (pl & 31)) << 4)) = o;
-#endif
-      }
-    }
-#if Y3_DW_EPI == 2
-    __syncthreads();
-    // 512 threads x 16 bytes = 16 pixel rows of 512 bytes per pass: every wave writes 2 KiB of consecutive output bytes
-    const int piece = tid & 31;
-#pragma unroll
-    for (int j = 0; j < BM / 16; ++j) {
-      const int pl = (tid >> 5) + j * 16;
-      const int m = m0 + pl;
-      const u32x4 o = *reinterpret_cast<const u32x4 *>(sO + pl * 512 + ((piece ^ (pl & 31)) << 4));
-      if (m < p.M) *reinterpret_cast<u32x4 *>(reinterpret_cast<T *>(p.out) + (long long)m * p.out_ld + n0 + piece * 8) = o;
-    }
-#endif
-  }
-#else
   // ---- epilogue: two channel halves of 128; the four waves that own a half park it, all 512 threads write it out.  A half's
   // scale / bias / shortcut reads are issued one stage ahead: the first half's before the barrier that ends the K loop, the
   // second half's before the first half's write-out (all at once, before the loop's end, they cost 48 registers: spills) ----
@@ -1241,12 +1095,10 @@ __global__ __launch_bounds__(512, 2) void conv_halo_dw_kernel(HaloArgs p) {
       float v[8];
       y3_bn_act8(v, lo, hi, sc_lo[h], sc_hi[h], bi_lo[h], bi_hi[h], act);
       if (has_res) y3_add8<T>(v, resv[h][j]);
-      T *op = reinterpret_cast<T *>(p.out) + (long long)m * p.out_ld + co;
-      *reinterpret_cast<u32x4 *>(op) = y3_pack8<T>(v);
+      y3_store8(reinterpret_cast<T *>(p.out) + (long long)m * p.out_ld + co, v);
     }
     if (h == 0) __syncthreads();                      // the first half is out of LDS before the second is parked
   }
-#endif
 }
 
 // HaloArgs of a 3x3 stride-1 conv with `wgt` as its weights and tile_n output channels per tile: all but the tile geometry,
@@ -1442,7 +1294,6 @@ bool y3_conv_patch_fits(const y3_op &op) {
 static int launch_conv_patch(const y3_op *ops, const y3_step &, const void *d_in, const void *d_zero, hipStream_t s) {
   const y3_op &op = ops[0];
   HaloArgs a = halo_args(op, op.d_weight, d_in, d_zero, 128);
-  a.flags |= y3_debug_flags() ? 0x40000000u : 0u;
   constexpr int TY = 8, TX = 32, PROWS = (TY + 2) * (TX + 2);
   static_assert(PROWS <= 12 * 32, "all patch slices must be out by tap 5 (4-slot ring)");
   a.na = y3_ceil_div(PROWS, 32);
@@ -1467,7 +1318,6 @@ int y3_choose_conv_patch(const y3_op &op, y3_step &st) {
 static int launch_conv_halo(const y3_op *ops, const y3_step &st, const void *d_in, const void *d_zero, hipStream_t s) {
   const y3_op &op = ops[0];
   HaloArgs a = halo_args(op, op.d_weight, d_in, d_zero, 128);
-  a.flags |= y3_debug_flags() ? 0x40000000u : 0u;
   const int mi = st.bm / 64;
   const int bm = 64 * mi;
   a.hr = bm + 2 * a.W + 2;

@@ -20,6 +20,7 @@
 #include <string.h>
 
 #include "common.h"
+#include "conv_device.h"
 #include "decode_core.h"
 
 namespace {
@@ -48,26 +49,6 @@ struct IgemmArgs {
   Y3DecodeArgs dec;
 };
 static_assert(offsetof(IgemmArgs, dec) == 168 && sizeof(IgemmArgs) == 288, "kernel argument layout");
-
-template <typename T>
-struct Mma {
-  // 16-bit element types (bf16, IEEE half): one 128-byte K-tile = 64 elements = 2 MFMA k-steps of 32; a lane's 16-byte
-  // chunk = 8 k values
-  static __device__ __forceinline__ void run(f32x4 &acc, const u32x4 &w, const u32x4 &x) { acc = y3_mfma16<T>(w, x, acc); }
-};
-
-template <>
-struct Mma<float> {
-  // one 128-byte K-tile = 32 floats = 2 groups of 16; lane (r, q) holds floats 4q..4q+3 of the
-  // group for row r.  MFMA j consumes element j of every lane: it sums k in {j, 4+j, 8+j, 12+j};
-  // the same permutation is applied to both operands, so the four MFMAs cover the group.
-  static __device__ __forceinline__ void run(f32x4 &acc, const u32x4 &w, const u32x4 &x) {
-    const f32x4 wf = __builtin_bit_cast(f32x4, w), xf = __builtin_bit_cast(f32x4, x);
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[j], xf[j], acc, 0, 0, 0);
-  }
-};
 
 template <typename TO>
 __device__ __forceinline__ void store4(char *dst, const float v[4], int nvalid) {
@@ -172,12 +153,7 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(IgemmArgs p) {
       const bool in_k = ke < p.K;
 #pragma unroll
       for (int i = 0; i < A_CH; ++i) {
-        bool ok = in_k && ((a_taps[i] >> tap) & 1u);
-#ifdef Y3_X_S2BOUND
-        // timing-only bound for a staged-once stride-2 kernel (`make variant NAME=s2bound FLAGS=-DY3_X_S2BOUND`, debug = 1):
-        // only tap 0 of a stride-2 layer fetches pixels, the other eight read the zero page (results wrong)
-        if ((p.flags & 0x40000000u) && p.stride == 2 && tap != 0) ok = false;
-#endif
+        const bool ok = in_k && ((a_taps[i] >> tap) & 1u);
         const char *src = ok ? a_base[i] + tap_off : p.zero;
         a_reg[i] = *reinterpret_cast<const u32x4 *>(src);
       }
@@ -283,7 +259,8 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(IgemmArgs p) {
 // KMODE 0: Cin % BKE == 0 (one tap per K-tile)   1: any Cin % CE == 0 (per-chunk tap, slow)
 //       2: BKE % Cin == 0, Cin < BKE (several whole taps per K-tile, e.g. Cin = 32 with bf16)
 // (Measured and removed: a register-staged single-stage form, 64-byte K rows for three workgroups per CU, and a
-// 256x128 eight-wave tile -- all within +-8 % of this one, none better: profiles/r01_convbench_variants.txt.)
+// 256x128 eight-wave tile -- all within +-8 % of this one, none better: profiles/r01_convbench_variants.txt.  A timing-only
+// bound for staging a stride-2 layer's pixels once, taps 1..8 reading the zero page or not issued: profiles/r04p_stride2_bound.txt.)
 template <typename T, int BM, int BN, int WAVES_M, int WAVES_N, int KMODE, bool DECODE = false>
 __global__ __launch_bounds__(64 * WAVES_M * WAVES_N) void conv_igemm2_kernel(IgemmArgs p) {
   constexpr int RB = 128;                            // bytes of K per tile row
@@ -365,9 +342,6 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N) void conv_igemm2_kernel(Ige
     cc = kc - tl * cpt;
   }
 
-  typedef __attribute__((address_space(3))) void lds_void;
-  typedef const __attribute__((address_space(1))) void gbl_void;
-
   // source address of this thread's i-th A chunk of K-tile kt (zero page for padding / tail rows)
   auto a_sources = [&](int kt, const char *(&src)[A_CH]) {
     long long tap_off;
@@ -403,11 +377,6 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N) void conv_igemm2_kernel(Ige
     char *sB = sA + BM * RB;
     const char *src[A_CH];
     a_sources(kt, src);
-#ifdef Y3_X_S2BOUND
-    // debug = 2: the pixel loads of taps 1..8 are not even issued (this kernel waits vmcnt(0) per K-tile: any count is safe)
-    const bool skip_a = (p.flags & 0x80000000u) && p.stride == 2 && KMODE == 0 && (kt % p.n_taps) != 0;
-    if (!skip_a)
-#endif
 #pragma unroll
     for (int i = 0; i < A_CH; ++i)
       __builtin_amdgcn_global_load_lds((gbl_void *)src[i], (lds_void *)(sA + wave * 1024 + i * (NT * 16)), 16, 0, Y3_AUX_A);
@@ -469,7 +438,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N) void conv_igemm2_kernel(Ige
   issue(0, 0);
   for (int kt = 0; kt < p.n_ktiles; ++kt) {
     const int cur = kt & 1;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // tile kt has landed (this wave's pieces)
+    y3_wait_vmcnt<0>();                                // tile kt has landed (this wave's pieces)
     __syncthreads();                                   // ... everyone's; stage cur^1 is free again
     if (kt == 0) Y3_STAMP(1);
     if (kt + 1 < p.n_ktiles) issue(kt + 1, cur ^ 1);
@@ -595,11 +564,6 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N) void conv_igemm2_kernel(Ige
 // roles takes the DMA issue out of the MFMA waves' instruction stream; the SIMD's other wave keeps the
 // matrix pipe busy meanwhile.  NS LDS stages (3: 96 KiB, one workgroup per CU, two tiles in flight; 4: 128 KiB);
 // one raw barrier per K-step pairs "tile kt has landed" with "stage kt-1 is free".
-template <int N>
-__device__ __forceinline__ void igemm_wait_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
 template <typename T, int BM, int BN, int WAVES_M, int WAVES_N, int KMODE, int NS>
 __global__ __launch_bounds__(128 * WAVES_M * WAVES_N,
                              NS * (BM + BN) * 128 <= 80 * 1024 ? (WAVES_M * WAVES_N) : (WAVES_M * WAVES_N) / 2)
@@ -635,9 +599,6 @@ void conv_igemm3_kernel(IgemmArgs p) {
   const int m0 = (p.n_major ? tile % p.m_tiles : tile / p.n_tiles) * BM;
   const int n0 = (p.n_major ? tile / p.m_tiles : tile % p.n_tiles) * BN;
   const int n_kt = p.n_ktiles;
-
-  typedef __attribute__((address_space(3))) void lds_void;
-  typedef const __attribute__((address_space(1))) void gbl_void;
 
   f32x4 acc[MI][NI];
 #pragma unroll
@@ -719,12 +680,7 @@ void conv_igemm3_kernel(IgemmArgs p) {
       char *sB = sA + BM * RB;
 #pragma unroll
       for (int i = 0; i < A_CH; ++i) {
-        bool ok = in_k && ((a_taps[i] >> tap) & 1u);
-#ifdef Y3_X_S2BOUND
-        // timing-only bound for a staged-once stride-2 kernel (`make variant NAME=s2bound FLAGS=-DY3_X_S2BOUND`, debug = 1):
-        // only tap 0 of a stride-2 layer fetches pixels, the other eight read the zero page (results wrong)
-        if ((p.flags & 0x40000000u) && p.stride == 2 && tap != 0) ok = false;
-#endif
+        const bool ok = in_k && ((a_taps[i] >> tap) & 1u);
         const char *src = ok ? a_base[i] + tap_off : p.zero;
         __builtin_amdgcn_global_load_lds((gbl_void *)src, (lds_void *)(sA + lwave * 1024 + i * (NC * 16)), 16, 0, Y3_AUX_A);
       }
@@ -740,9 +696,9 @@ void conv_igemm3_kernel(IgemmArgs p) {
     Y3_STAMP(6);
     for (int kt = 0; kt < n_kt; ++kt) {
       // tiles issued so far: 0 .. min(kt + NS - 2, n_kt - 1); tile kt must have landed
-      if (NS > 2 && kt + NS - 2 < n_kt) igemm_wait_vmcnt<(NS - 2) * PER>();
-      else if (NS > 3 && kt + NS - 3 < n_kt) igemm_wait_vmcnt<(NS > 3 ? NS - 3 : 0) * PER>();
-      else igemm_wait_vmcnt<0>();
+      if (NS > 2 && kt + NS - 2 < n_kt) y3_wait_vmcnt<(NS - 2) * PER>();
+      else if (NS > 3 && kt + NS - 3 < n_kt) y3_wait_vmcnt<(NS > 3 ? NS - 3 : 0) * PER>();
+      else y3_wait_vmcnt<0>();
       Y3_STAMP(3);
       __builtin_amdgcn_s_barrier();                   // tile kt visible to the consumers; stage of tile kt-1 free
       Y3_STAMP(4);
@@ -989,7 +945,7 @@ static int launch_conv_igemm(const y3_op *ops, const y3_step &st, const void *d_
   // split (yolov3-tiny's 13^2 layers at batch 8: 18.9 MB of float32 weights against 2.8 MB of input -- 45 MB of traffic per
   // launch for 16 MB algorithmic before this, profiles/r03_traffic.json).  Placement only: results do not change.
   a.n_major = (double)op.out_c * a.K > (double)op.batch * op.in_h * op.in_w * op.in_c ? 1 : 0;
-  a.flags = op.flags | (y3_debug_flags() ? 0x40000000u : 0u) | (y3_debug_flags() == 2 ? 0x80000000u : 0u);
+  a.flags = op.flags;
   y3_fast_div((uint32_t)a.HoWo, a.mul_hw, a.sh_hw);
   y3_fast_div((uint32_t)a.Wo, a.mul_w, a.sh_w);
   const int tile = igemm_tile(st.bm, st.bn);
