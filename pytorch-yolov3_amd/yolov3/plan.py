@@ -181,6 +181,36 @@ def check_blocks(blocks):
                     i, blk["activation"]))
 
 
+def check_head_readers(blocks, readers, elem_size):
+    """Refuse, naming both blocks, a graph that reads a detection head in a form nothing here computes.  ``readers[i]``: the
+    (consumer block, role) pairs of block i's output.
+
+    * Any reader of a [yolo] / [region] block's output, in every storage mode: in Darknet that is the activated tensor; the
+      decode kernels write boxes only, and the planner's alias of the block would hand the reader the raw logits.
+    * In the 16-bit modes (``elem_size != 4``) the logits of a head conv are float32 and, with the head fused into the decode
+      kernel, never reach memory; every other tensor is 16-bit.  So a second reader of a head conv (a route, a shortcut's
+      ``from``) would misread them, and a head behind anything but a conv would decode 16-bit elements as float32, past the
+      end of their buffer."""
+    kinds = [b["type"] for b in blocks]
+    for i, kind in enumerate(kinds):
+        if kind not in HEAD_KINDS:
+            continue
+        for r, _ in readers[i]:
+            raise ValueError("{} block {}: block {} ({}) reads its output: the activated output of a detection head is not "
+                             "computed (only its boxes are)".format(kind, i, r, kinds[r]))
+        if elem_size == 4 or i == 0:
+            continue
+        if kinds[i - 1] != "convolutional":
+            raise ValueError("{} block {}: block {} in front of it is a [{}], not a conv: in the 16-bit modes the decode reads "
+                             "float32 logits, which only a conv directly in front of the head stores (float32 runs this "
+                             "graph)".format(kind, i, i - 1, kinds[i - 1]))
+        for r, _ in readers[i - 1]:
+            if r != i:
+                raise ValueError("conv block {}: block {} ({}) reads the logits of the head conv of {} block {}: in the 16-bit "
+                                 "modes they are float32 and may never reach memory (float32 runs this graph)".format(
+                                     i - 1, r, kinds[r], kind, i))
+
+
 def infer_shapes(blocks, net_info, height, width, pool="reference"):
     """(C,H,W) of every block output for an input of size (height,width); conv arithmetic
     as torch.nn.Conv2d / MaxPool2d / Upsample compute it, max-pools by Darknet's size formula with ``pool="darknet"``."""
@@ -263,6 +293,8 @@ def build_plan(blocks, net_info, batch, height, width, elem_size, reuse=True, fu
         elif kind == "shortcut":
             readers[i - 1].append((i, "sc_prev"))
             readers[i + blk["from"]].append((i, "sc_from"))
+
+    check_head_readers(blocks, readers, elem_size)
 
     # ---- shortcut fusion: conv (i-1) + shortcut (i) when nobody else reads conv i-1 -------
     fused_into = {}      # shortcut block -> conv block
