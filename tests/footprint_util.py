@@ -243,7 +243,8 @@ def _layer(cid, family, kind, dtypes, B, h, w, c, k=1, s=1, wide=True, dk=False,
 def cases():
     """Every case: at least a full-tile and a ragged shape per family (the last pixel tile partial, the map not square where
     the family allows it), with and without the shortcut operand where the family takes one.  ``family`` is the kernel name
-    with %s for the dtype tag.  Shapes stay at or below 16 x 76 x 76 x 512.
+    with %s for the dtype tag.  Shapes stay at or below 16 x 76 x 76 x 512.  The rows of ``tiny_cases()`` follow them: every
+    family once more on maps of one pixel a side.
 
     Below the family name the library is compiled by INSTANCE (the y3_ints lists of the .hip files): the rows marked
     "instance" are there for one compiled device function that no other row launches (tests/kernel_census.py has the proof that
@@ -453,7 +454,123 @@ def cases():
         dict(id="yolo_wide_stride", group="yolo", family="yolo_decode_f32", opt="default", dtypes=ALL, B=3, h=7, w=9, n_anchor=3, ncls=80, ld=268, c0=4),
         dict(id="yolo_few_classes", group="yolo", family="yolo_decode_f32", opt="default", dtypes=ALL, B=2, h=5, w=6, n_anchor=2, ncls=7, ld=36, c0=4),
     ]
+    return C + tiny_cases()
+
+
+# ------------------------------------------------------------------------------------------------ degenerate maps
+# Every family once more on maps of one pixel a side: every pixel is a border pixel on two or four sides, a pixel tile holds
+# many whole frames and ends inside one, a halo row is W + 1 = 2 pixels and wraps through several frames, a 13-wide pool window
+# has one tap inside the image.  Three shapes per family, named by the OUTPUT map; a stride-2 family reads the input that gives it:
+TINY_SHAPES = (("dot", 37, 1, 1), ("row", 5, 1, 5), ("column", 5, 5, 1))
+
+
+def _tiny_dw1x1_batch(bm, h, w):
+    """conv1x1_dw takes grids of ONE round of workgroups (conv_1x1.hip dw1x1_bm: 48-pixel tiles for 64 .. 191 of them, 96-pixel
+    tiles from 192 tiles on): the smallest batch of an h x w map that reaches the tile height, one more frame where that would be
+    whole tiles, so that the last tile is partial"""
+    pixels = {48: 64 * 48, 96: 192 * 96}[bm] + 1
+    return -(-pixels // (h * w)) + 1
+
+
+def tiny_cases():
+    """Channel counts are the smallest each family takes (the K depths and widths of the rows of cases()); batches are 37 / 5 / 5 but
+    for conv1x1_dw, whose chooser wants one round of workgroups (``_tiny_dw1x1_batch``).  Every family of cases() has the three
+    rows, the two below excepted.
+
+    Declined (family, shape) pairs, which have NO row (``TINY_DECLINED``; tests/test_footprint_host.py
+    test_tiny_rows_cover_every_family_or_a_declined_entry proves each entry through plan creation):
+
+    =========================  =========  =================================================================  ========================
+    family                     shapes     the chooser line that declines                                     plan creation gives the
+                                                                                                             op to
+    =========================  =========  =================================================================  ========================
+    conv_patch_wsp_*_8x32x128  all three  csrc/api.hip choose_conv: ``w > 128`` -- the 2-D patch kernel is   conv_igemm2_*_128x32
+                                          for rows wider than any strip tile                                 (three workgroups of a
+                                                                                                             128-wide tile idle)
+    conv_block_fused_*_x128    all three  csrc/conv_block.hip choose_tile: ``if (tw > W || th < 4)           the pair as two launches:
+                                          continue`` -- rectangles are 8 .. 24 pixels wide and at least 4    conv_dw48_k1_*, then
+                                          high, so a map under 8 x 4 has no tile                             conv_dw48_k3_*
+    =========================  =========  =================================================================  ========================
+    """
+    C = []
+
+    def conv(name, family, opt, dtypes, cin, cout, k, s=1, res=False, **kw):
+        for tag, B, h, w in TINY_SHAPES:
+            C.append(_conv("tiny_%s_%s" % (name, tag), family, opt, dtypes, B, h * s, w * s, cin, cout, k, s, res=res, tiny=tag, **kw))
+
+    conv("igemm1_128", "conv_igemm_%s_128x128", "igemm1", ALL, 64, 128, 3, res=True)
+    conv("igemm1_64", "conv_igemm_%s_128x64", "igemm1", ALL, 32, 64, 3, res=True)
+    conv("igemm1_32_k1", "conv_igemm_%s_128x32", "igemm1", ALL, 64, 32, 1)
+    conv("igemm2_64", "conv_igemm2_%s_128x64", "igemm2_noshrink", ALL, 32, 64, 3, res=True)
+    conv("igemm2_128", "conv_igemm2_%s_128x128", "igemm2_noshrink", ALL, 64, 128, 3, res=True)
+    conv("igemm2_32", "conv_igemm2_%s_128x32", "igemm2_noshrink", ALL, 16, 32, 3, res=True)
+    conv("igemm2_96", "conv_igemm2_%s_96x64", "igemm2_96", ALL, 128, 128, 3, res=True)
+    conv("igemm3_128", "conv_igemm3_%s_128x128", "igemm3", ALL, 128, 128, 3, res=True)
+    conv("igemm3_128_s2", "conv_igemm3_%s_128x128", "igemm3", ALL, 64, 128, 3, s=2)
+    conv("igemm3_64", "conv_igemm3_%s_64x128", "igemm3_64", B16, 128, 128, 3, res=True)
+    conv("halo192", "conv_halo_ws_%s_192x128", "halo192", ALL, 128, 128, 3, res=True, out_unit=8)
+    conv("halo256", "conv_halo_ws_%s_256x128", "halo256", ALL, 128, 128, 3, res=True, out_unit=8)
+    conv("halo_dw", "conv_halo_dw_%s_192x256", "halo_dw", B16, 128, 256, 3, res=True)
+    conv("wres_128", "conv1x1_wres_%s_128x128", "wres", B16, 256, 128, 1)
+    conv("wres_64", "conv1x1_wres_%s_128x64", "wres", B16, 128, 64, 1)
+    conv("dw48_k1", "conv_dw48_k1_%s", "dw48", B16, 128, 128, 1, res=True, nkt=2)
+    conv("dw48_k3", "conv_dw48_k3_%s", "dw48", B16, 128, 256, 3, res=True)
+    conv("dw48_k3s2", "conv_dw48_k3s2_%s", "dw48", B16, 64, 128, 3, s=2, nkt=1)
+    conv("direct", "conv_direct_%s", "default", ALL, 13, 24, 3, res=True)
+    conv("direct_s2", "conv_direct_%s", "default", ALL, 21, 13, 3, s=2)
+    conv("direct_f32_logits", "conv_direct_%s", "default", ALL, 21, 18, 1, out_f32=True, leaky=False)
+    conv("direct_nchw_grey", "conv_direct_%s", "default", ALL, 1, 16, 3, inp="nchw")
+    conv("direct_u8_k5", "conv_direct_%s", "default", ALL, 3, 16, 5, inp="u8")
+    # the stems on a network input of one pixel a side (no shipped cfg: the planner takes such an input all the same)
+    conv("stem_nchw", "conv_stem3x3_nchw_%s", "default", ALL, 3, 16, 3, inp="nchw")
+    conv("stem_u8_f32", "conv_stem3x3_u8_%s", "default", F32, 3, 16, 3, inp="u8")
+    conv("stem_mfma", "conv_stem_mfma_u8_%s", "default", B16, 3, 16, 3, inp="u8")
+    conv("stem_u8_16bit_s2", "conv_stem3x3_u8_%s", "default", B16, 3, 32, 3, s=2, inp="u8")
+    for bm in (48, 96):
+        for tag, _, h, w in TINY_SHAPES:
+            C.append(_conv("tiny_dw1x1_%d_%s" % (bm, tag), "conv1x1_dw_%%s_%dx256" % bm, "dw1x1", B16, _tiny_dw1x1_batch(bm, h, w), h, w,
+                           256, 256, 1, 1, nkt=4, tiny=tag))
+    for tag, B, h, w in TINY_SHAPES:
+        C += [
+            # the fused stem pair ends in a stride-2 conv: 2 x 2, 2 x 10 and 10 x 2 frames
+            dict(id="tiny_stem_s2_" + tag, group="stem_pair", family="conv_stem_s2_fused_u8_%s", opt="default", dtypes=B16, B=B, h=2 * h, w=2 * w, tiny=tag),
+            dict(id="tiny_stem_s2_phased_" + tag, group="stem_pair", family="conv_stem_s2_fused_u8_%s", opt="stem_phased", dtypes=B16, B=B, h=2 * h, w=2 * w, tiny=tag),
+            dict(id="tiny_resblock_" + tag, group="resblock", family="conv_resblock_fused_%s_64_32_64", opt="default", dtypes=B16, B=B, h=h, w=w, tiny=tag),
+            dict(id="tiny_head_tiled_" + tag, group="head", family="conv_head_decode_%s_64x256", opt="head_tiled", dtypes=B16, B=B, h=h, w=w, cin=192, tiny=tag),
+            dict(id="tiny_head48_" + tag, group="head", family="conv_head_decode_dw_%s_48x256", opt="head48", dtypes=B16, B=B, h=h, w=w, cin=256, tiny=tag),
+            dict(id="tiny_head96_" + tag, group="head", family="conv_head_decode_dw_%s_96x256", opt="head96", dtypes=B16, B=B, h=h, w=w, cin=256, tiny=tag),
+        ]
+        for wide, form, c in ((True, "wide", 64), (False, "elem", 13)):
+            t = "_%s_%s" % (form, tag)
+            C += [
+                dict(_layer("tiny_maxpool_s1" + t, "maxpool_%s", "maxpool", ALL, B, h, w, c, k=2, s=1, wide=wide), tiny=tag),
+                dict(_layer("tiny_maxpool_s2" + t, "maxpool_%s", "maxpool", ALL, B, 2 * h, 2 * w, c, k=2, s=2, wide=wide), tiny=tag),
+                dict(_layer("tiny_maxpool_dk_s1" + t, "maxpool_dk_%s", "maxpool", ALL, B, h, w, c, k=5, s=1, wide=wide, dk=True), tiny=tag),
+                dict(_layer("tiny_maxpool_dk_s2" + t, "maxpool_dk_%s", "maxpool", ALL, B, 2 * h, 2 * w, c, k=2, s=2, wide=wide, dk=True), tiny=tag),
+                dict(_layer("tiny_upsample" + t, "upsample_%s", "upsample", ALL, B, h, w, c, s=2, wide=wide), tiny=tag),
+                dict(_layer("tiny_add" + t, "add_%s", "add", ALL, B, h, w, c, wide=wide), tiny=tag),
+                dict(_layer("tiny_add_inplace" + t, "add_%s", "add", ALL, B, h, w, c, wide=wide, alias=True), tiny=tag),
+                dict(_layer("tiny_copy" + t, "copy_%s", "copy", ALL, B, h, w, c, wide=wide), tiny=tag),
+            ]
+        C += [
+            # reorg reads the multiples of its stride that give the shape: 2 x 2, 2 x 10, 10 x 2 (flat form), 3 x 3, 3 x 15, 15 x 3
+            dict(id="tiny_reorg_" + tag, group="reorg", family="reorg_%s", opt="default", dtypes=ALL, B=B, h=2 * h, w=2 * w, c=12, s=2, form3d=False, tiny=tag),
+            dict(id="tiny_reorg3d_" + tag, group="reorg", family="reorg3d_%s", opt="default", dtypes=ALL, B=B, h=3 * h, w=3 * w, c=13, s=3, form3d=True, tiny=tag),
+            dict(id="tiny_spp_" + tag, group="spp", family="maxpool_spp_pyramid_%s", opt="default", dtypes=ALL, B=B, h=h, w=w, c=48, dk=False, tiny=tag),
+            dict(id="tiny_spp_dk_" + tag, group="spp", family="maxpool_spp_pyramid_dk_%s", opt="default", dtypes=ALL, B=B, h=h, w=w, c=48, dk=True, tiny=tag),
+            # the pixel stride wider than the channels: 255 channels at 268, from channel 4
+            dict(id="tiny_yolo_wide_stride_" + tag, group="yolo", family="yolo_decode_f32", opt="default", dtypes=ALL, B=B, h=h, w=w, n_anchor=3, ncls=80, ld=268, c0=4, tiny=tag),
+            dict(id="tiny_yolo_few_classes_" + tag, group="yolo", family="yolo_decode_f32", opt="default", dtypes=ALL, B=B, h=h, w=w, n_anchor=2, ncls=7, ld=36, c0=4, tiny=tag),
+        ]
     return C
+
+
+# family -> (the row of cases() whose channels, kernel and option set force the family everywhere else, the kernels plan creation
+# gives the op(s) to on each of TINY_SHAPES instead): the table of tiny_cases()
+TINY_DECLINED = {
+    "conv_patch_wsp_%s_8x32x128": ("patch_full", ("conv_igemm2_%s_128x32",)),
+    "conv_block_fused_%s_x128": ("block_full_res", ("conv_dw48_k1_%s", "conv_dw48_k3_%s")),
+}
 
 
 # Families whose chooser declines every strided operand: none, every chooser takes pixel strides (the strided half of

@@ -77,9 +77,9 @@ class _Fake:
         return a
 
 
-def build_ops(model, dim, dtype, batch, input_mode, opt):
+def build_ops(model, dim, dtype, batch, input_mode, opt, width=None):
     """the ops of one plan (a ctypes array) as Darknet._compile_on_device builds them, and the fragment-weight bytes of each
-    conv (None for other ops) asked under ``opt``"""
+    conv (None for other ops) asked under ``opt``.  The input is ``dim`` x ``dim``, or ``dim`` high and ``width`` wide."""
     lib = _hip.lib()
     blocks, net_info = parse_config(os.path.join(MODEL_DIR, model + ".cfg"))
     for i, blk in enumerate(blocks):            # absolute route indices (Darknet.__init__)
@@ -87,7 +87,7 @@ def build_ops(model, dim, dtype, batch, input_mode, opt):
             blk["layers"] = [j if j >= 0 else i + j for j in blk["layers"]]
     _, convs = conv_layout(blocks, net_info)
     c_dtype, es = DTYPES[dtype][0], DTYPES[dtype][1]
-    desc = build_plan(blocks, net_info, batch, dim, dim, es, reuse=True, fuse=True)
+    desc = build_plan(blocks, net_info, batch, dim, width or dim, es, reuse=True, fuse=True)
     fake = _Fake()
     base = fake(desc["arena_bytes"])
 
@@ -174,18 +174,19 @@ def build_ops(model, dim, dtype, batch, input_mode, opt):
     return ops, frag, fake
 
 
-def plan_choice(model, dim, dtype, batch, input_mode, overrides):
-    """{"kernel": [y3_plan_op_kernel per op], "frag": [y3_conv_fragment_weight_bytes per op, None for non-convs]}"""
+def plan_choice(model, dim, dtype, batch, input_mode, overrides, width=None):
+    """{"kernel": [y3_plan_op_kernel per op], "frag": [y3_conv_fragment_weight_bytes per op, None for non-convs], "map": [(in_h, in_w)
+    per op]}"""
     lib = _hip.lib()
     opt = _hip.options(**overrides)
-    ops, frag, fake = build_ops(model, dim, dtype, batch, input_mode, opt)
+    ops, frag, fake = build_ops(model, dim, dtype, batch, input_mode, opt, width)
     handle = ctypes.c_void_p()
     _hip.check(lib.y3_plan_create_ex(ops, len(ops), fake(4096), ctypes.byref(opt), ctypes.byref(handle)))
     try:
         kernels = [lib.y3_plan_op_kernel(handle, i).decode() for i in range(len(ops))]
     finally:
         lib.y3_plan_destroy(handle)
-    return {"kernel": kernels, "frag": frag}
+    return {"kernel": kernels, "frag": frag, "map": [(ops[i].in_h, ops[i].in_w) for i in range(len(ops))]}
 
 
 def all_choices():

@@ -2,6 +2,7 @@
 chooser with fake addresses (``y3_plan_create_ex`` only decides, as in tests/kernel_choice_util.py) and get the family the
 case claims; the table reaches every kernel name of tests/golden/kernel_choice.json; guards, margins and alignment of every
 layout meet the conditions a GPU run of the cases relies on."""
+import ctypes
 import json
 
 import pytest
@@ -64,7 +65,10 @@ def test_every_family_has_a_full_and_a_ragged_case_and_both_shortcut_forms():
         assert any(c.get("res") for c in by_family[fam]), fam
     # shapes stay at or below 16 x 76 x 76 x 512 ...
     for c in fu.cases():
-        assert c["B"] <= 16 and c["h"] * c["w"] <= 76 * 76 and max(c.get("cout", 0), c.get("c", 0)) <= 512, c["id"]
+        # (a row on a map of one pixel a side has a batch of its own, 37 or 5 -- conv1x1_dw: what fills one round of workgroups --,
+        # and stays below 16 x 76 x 76 PIXELS all the same)
+        assert c["B"] <= 16 or (c.get("tiny") and min(c["h"], c["w"]) <= 3 and c["B"] * c["h"] * c["w"] <= 16 * 76 * 76), c["id"]
+        assert c["h"] * c["w"] <= 76 * 76 and max(c.get("cout", 0), c.get("c", 0)) <= 512, c["id"]
         # ... but for the input channels of a row that is there for ONE compiled K depth of a direct-weights kernel, which are
         # then exactly what that instance dictates: 64 x nkt per halo image (the stride-2 kernel's two-image form: twice that),
         # on the smallest grid its chooser takes: at most half the elements of a tensor at the limit
@@ -77,6 +81,51 @@ def test_every_family_has_a_full_and_a_ragged_case_and_both_shortcut_forms():
         # stride-2 kernel's two-image form at 256 channels (conv_dw48.hip dw48_shape: one image of all channels must outgrow LDS)
         assert max(c["h"], c["w"]) <= 76 or c["family"].startswith("conv_patch_wsp") or c.get("wide_map"), c["id"]
     assert [c["id"] for c in fu.cases() if c.get("wide_map")] == ["dw48_k3s2_c256_two_images"]
+
+
+def test_tiny_rows_cover_every_family_or_a_declined_entry():
+    """every family of the table has a "dot", a "row" and a "column" row (footprint_util.tiny_cases), or an entry in
+    TINY_DECLINED -- and then plan creation, under the option set that forces the family on its other rows, gives each of the
+    three shapes to the kernels the entry names"""
+    _no_gpu()
+    H = fu._H()
+    lib = H.lib()
+    tags = [t for t, _, _, _ in fu.TINY_SHAPES]
+    by_family = {}
+    for c in fu.cases():
+        by_family.setdefault(c["family"], []).append(c.get("tiny"))
+    for fam, have in by_family.items():
+        if fam in fu.TINY_DECLINED:
+            assert not any(have), fam + ": rows AND a declined entry"
+            continue
+        for t in tags:
+            assert t in have, "%s has no %r row" % (fam, t)
+    # output maps of the rows are what their names say
+    for c in fu.tiny_cases():
+        for dtype in c["dtypes"]:
+            ops, _, _, _ = fu.build(c, dtype, "dense", H.options(**fu._opts()[c["opt"]]))
+            last = ops[len(ops) - 1]
+            out = (last.out_h, last.out_w) if last.kind != H.OP_YOLO else (last.in_h, last.in_w)
+            if c["group"] == "layer" and c["kind"] == "upsample":
+                out = (last.in_h, last.in_w)                  # (named by its input: 1 x 1 to 2 x 2)
+            want = {t: (h, w) for t, _, h, w in fu.TINY_SHAPES}[c["tiny"]]
+            assert out == want, (c["id"], out, want)
+    for fam, (src, goes_to) in fu.TINY_DECLINED.items():
+        for tag, B, h, w in fu.TINY_SHAPES:
+            case = dict(fu.case_by_id(src), B=B, h=h, w=w)
+            for dtype in case["dtypes"]:
+                opt = H.options(**fu._opts()[case["opt"]])
+                ops, lay, _, _ = fu.build(case, dtype, "strided", opt)
+                for i in range(len(ops)):                     # (whatever reads fragment-order weights gets a fake copy: decide only)
+                    if ops[i].kind == H.OP_CONV and not ops[i].d_weight_frag:
+                        ops[i].d_weight_frag = (1 << 45) + (i << 32)
+                handle = ctypes.c_void_p()
+                H.check(lib.y3_plan_create_ex(ops, len(ops), lay["zero page"].ptr(1 << 44), ctypes.byref(opt), ctypes.byref(handle)))
+                try:
+                    names = tuple(lib.y3_plan_op_kernel(handle, i).decode() for i in range(len(ops)))
+                finally:
+                    lib.y3_plan_destroy(handle)
+                assert names == tuple(g % fu.TAG[dtype] for g in goes_to), (fam, tag, dtype, names)
 
 
 def _kmode(case, dtype):

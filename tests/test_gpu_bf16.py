@@ -59,6 +59,12 @@ def _net(model, mode="bf16", **kw):
     return net.eval()
 
 
+def _net_f32(model, mode, **kw):
+    net = yolov3.Darknet(MODELS[model], device="cuda", dtype="float32", **kw)
+    net.load_weights(golden_weights_path(model))
+    return net.eval()
+
+
 def _bf16_ulp(r, mode="bf16"):
     """Spacing of the storage type's values at the (storage-valued) tensor r: 2^(exponent - 7) for bf16, 2^(exponent - 10)
     for fp16 (not below its subnormal spacing 2^-24)."""
@@ -101,15 +107,34 @@ def _close_bf16(got, want, what, slack=None, mode="bf16"):
     return frac
 
 
-def _teacher_forced(model, frames, expect_kernels=(), options=None, mode="bf16", frames_checked=None):
+F32_BLOCK_TOL = dict(rtol=1e-4, atol=2e-5)      # per block in float32 (tests/test_gpu_parity.py test_mini_every_block_fp32)
+
+
+def _close_f32(got, want, what):
+    """float32 storage: a block against the same block computed from the SAME input with float64 accumulation"""
+    np.testing.assert_allclose(got.numpy(), want.numpy(), err_msg=what, **F32_BLOCK_TOL)
+    return 0.0                                  # (no share to report: float32 values differ in their last bits everywhere)
+
+
+def _teacher_forced(model, frames, expect_kernels=(), options=None, mode="bf16", frames_checked=None, expect_pairs=()):
     """``frames_checked``: the frames of the batch whose blocks are compared with the oracle (the product runs the WHOLE batch, so the plan
-    and every kernel's grid are the batch's; the CPU oracle, 95 % of this test's time at batch 16, emulates only these).  None = all."""
-    rnd, emulate = MODES[mode]["rnd"], MODES[mode]["emulate"]
-    expect_kernels = tuple(k.replace("bf16", MODES[mode]["tag"]) for k in expect_kernels)
-    net = _net(model, mode, keep_all=True, fuse=True, options=options)
+    and every kernel's grid are the batch's; the CPU oracle, 95 % of this test's time at batch 16, emulates only these).  None = all.
+
+    ``mode`` "float32": the same walk with float32 storage -- no rounding, every conv against the oracle's conv of the product's own
+    input accumulated in float64, at ``F32_BLOCK_TOL``; the logits are in memory and are compared too.
+    ``expect_pairs``: (kernel, (input map height, width)) pairs the plan that ran must hold (tests/tiny_maps_util.py)."""
+    f32 = mode == "float32"
+    rnd, emulate = ((lambda t: t), None) if f32 else (MODES[mode]["rnd"], MODES[mode]["emulate"])
+    acc = "f64" if f32 else "f32"
+    expect_kernels = tuple(k if f32 else k.replace("bf16", MODES[mode]["tag"]) for k in expect_kernels)
+    net = (_net_f32 if f32 else _net)(model, mode, keep_all=True, fuse=True, options=options)
     out = net.forward_frames(frames)
     torch.cuda.synchronize()
     report = net.plan_report()
+    if expect_pairs:
+        import tiny_maps_util
+        got_pairs = tiny_maps_util.net_pairs(net, keep=lambda m: True)
+        assert set(expect_pairs) <= got_pairs, "not in the plan that ran: %s" % sorted(set(expect_pairs) - got_pairs)
     kernel_of = {}
     for r in report:
         kernel_of.setdefault(r["block"], []).append(r["kernel"])
@@ -131,7 +156,12 @@ def _teacher_forced(model, frames, expect_kernels=(), options=None, mode="bf16",
         k = blk["size"]
         pad = (k - 1) // 2 if "pad" in blk else 0
         return orc.conv_block(x, ref.params[ref._conv_slot[i]], blk["stride"], pad, blk["activation"] == "leaky",
-                              round_weights=emulate)
+                              round_weights=emulate, accumulate=acc)
+
+    def close(got, want, what, slack=None):
+        if f32:
+            return _close_f32(got, want, what)
+        return _close_bf16(got, rnd(want), what, slack, mode)
 
     def fused_away(i):
         return kernel_of.get(i, [""])[0].startswith("(fused")
@@ -146,6 +176,7 @@ def _teacher_forced(model, frames, expect_kernels=(), options=None, mode="bf16",
                 continue                                   # first half of a fused pair: checked with its second half
             slack = None
             if fused_away(i) and blocks[i - 1]["type"] == "convolutional":
+                assert not f32, what
                 mid = conv(i - 1, hip(i - 2))              # the pair's intermediate tensor lives in LDS as bf16
                 x = rnd(mid)
                 p2 = ref.params[ref._conv_slot[i]]
@@ -159,19 +190,20 @@ def _teacher_forced(model, frames, expect_kernels=(), options=None, mode="bf16",
             nxt = blocks[i + 1]["type"] if i + 1 < len(blocks) else None
             if nxt == "yolo":
                 heads.append((i + 1, y))                   # float32 logits: checked through the decode below
+                if f32:                                    # ... and, in memory in a float32 plan, as they are
+                    close(hip(i), y, what)
                 continue
             if not rounds[i]:                              # conv + shortcut in one epilogue, one rounding of the sum
                 sc = i + 1
                 y = y + hip(sc + blocks[sc]["from"])
-                worst_frac = max(worst_frac, _close_bf16(hip(sc), rnd(y), what + " + shortcut", slack, mode))
+                worst_frac = max(worst_frac, close(hip(sc), y, what + " + shortcut", slack))
             else:
-                worst_frac = max(worst_frac, _close_bf16(hip(i), rnd(y), what, slack, mode))
+                worst_frac = max(worst_frac, close(hip(i), y, what, slack))
             checked += 1
         elif kind == "shortcut":
             if not rounds[i - 1]:
                 continue                                   # checked with its conv
-            want = rnd(hip(i - 1) + hip(i + blk["from"]))
-            _close_bf16(hip(i), want, what, None, mode)
+            close(hip(i), hip(i - 1) + hip(i + blk["from"]), what)
             checked += 1
         elif kind == "maxpool":
             assert torch.equal(hip(i), orc.maxpool(hip(i - 1), blk["size"], blk["stride"])), what
@@ -206,6 +238,13 @@ def _teacher_forced(model, frames, expect_kernels=(), options=None, mode="bf16",
         row += n
         checked += 1
     assert row == pr.shape[1]
+    if f32:
+        # the network outputs against the oracle in free run (tests/test_gpu_parity.py
+        # test_yolov3_float32_matches_oracle_at_other_input_sizes, its tolerances)
+        want = ref.forward(x_net)
+        np.testing.assert_allclose(bb.numpy(), want["bbox_xywh"].numpy(), rtol=1e-4, atol=1e-3)
+        np.testing.assert_allclose(pr.numpy(), want["class_prob"].numpy(), atol=1e-3)
+        assert (ci.numpy() == want["class_idx"].numpy()).mean() > 0.999
     return checked, worst_frac, names
 
 
@@ -260,15 +299,17 @@ def test_bf16_every_block_teacher_forced(model, h, w, batch, options, kernels):
     _every_block(model, h, w, batch, options, kernels, "bf16")
 
 
-def _every_block(model, h, w, batch, options, kernels, mode):
+def _every_block(model, h, w, batch, options, kernels, mode, pairs=(), frames_checked=None):
     frames = synth_frames(1000 + h + w + batch, batch, h, w)
     if (h, w) == (608, 608):
         frames[0] = resize_bilinear_u8(load_jpeg_bgr("000000035279.jpg"), h, w)
     # batches of 8 / 16: the first, a middle and the last frame against the oracle (tiles of the raster strips straddle frames; that every
     # frame of a full-size batch equals the same frame alone is test_frames_are_independent_at_full_size's job)
-    some = (0, batch // 2, batch - 1) if batch >= 8 else None
-    checked, frac, names = _teacher_forced(model, frames, kernels, options=options, mode=mode, frames_checked=some)
+    some = frames_checked or ((0, batch // 2, batch - 1) if batch >= 8 else None)
+    checked, frac, names = _teacher_forced(model, frames, kernels, options=options, mode=mode, frames_checked=some, expect_pairs=pairs)
     print("%s %s %dx%d b%d %s: %d blocks checked, worst mismatch share %.4f" % (mode, model, h, w, batch, options, checked, frac))
+    if pairs:
+        print("    on these maps: %s" % ", ".join("%s %dx%d" % (k, m[0], m[1]) for k, m in sorted(pairs)))
     assert checked >= (20 if model == "yolov3-tiny" else 75)      # 107 blocks, 23 convs checked with their shortcut, 3 yolo
 
 

@@ -270,7 +270,17 @@ def test_default_is_the_reference_pool(model):
 
 @pytest.mark.parametrize("model", ["yolov3-spp", "yolov3-tiny", "yolov4", "yolov4-tiny", "yolov4-csp"])
 def test_float32_network_matches_restatement_with_darknet_pools(model):
-    dim = DIMS[model]
+    _float32_network_matches_restatement(model, DIMS[model])
+
+
+@pytest.mark.parametrize("model", ["yolov3-spp", "yolov3-tiny"])
+def test_float32_network_matches_restatement_with_darknet_pools_at_32_pixels(model):
+    """1 x 1, 2 x 2 and 4 x 4 maps: the centred 13-window has one tap inside a 1 x 1 map (yolov3-spp), and yolov3-tiny's last
+    stride-2 pool goes from 2 x 2 to 1 x 1 and its size-2 stride-1 pool runs on that one pixel"""
+    _float32_network_matches_restatement(model, 32)
+
+
+def _float32_network_matches_restatement(model, dim):
     net = _net(model, "float32", pool="darknet")
     cls = DP.NewCoordsRestatement if model == "yolov4-csp" else DP.Restatement
     ref = cls(_cfg(model), _params(model))

@@ -511,10 +511,10 @@ def test_nms_large_matches_oracle(n, ncls):
 
 
 @pytest.mark.parametrize("model,dim,batch", [(m, d, b) for m in ("yolov3", "yolov3-tiny", "yolov3-spp")
-                                             for d in (320, 416, 608) for b in (1, 2)])
+                                             for d in (32, 64, 320, 416, 608) for b in (1, 2)])
 def test_shape_sweep_bf16(model, dim, batch):
     """The reference's own 18-case smoke sweep (tests/test_darknet.py:10-27), plus shape asserts; bf16 at batch 1, fp16 at
-    batch 2 (the two 16-bit modes share every kernel template)."""
+    batch 2 (the two 16-bit modes share every kernel template).  32 and 64 pixels: detection scales of 1 x 1 and 2 x 2 cells."""
     net = _net(model, dtype="bf16" if batch == 1 else "fp16")
     x = torch.rand(batch, 3, dim, dim, generator=torch.Generator().manual_seed(dim + batch))
     out = net.forward(x)

@@ -106,6 +106,20 @@ def _ulp_close(got, want, what):
 
 @pytest.mark.parametrize("dtype", ["float32", "bf16", "fp16"])
 def test_mish_on_every_conv_family(tmp_path, dtype):
+    _mish_on_the_family_network(tmp_path, dtype, FAMILY_DIM, True)
+
+
+@pytest.mark.parametrize("dim", [32, 4])
+@pytest.mark.parametrize("dtype", ["float32", "bf16", "fp16"])
+def test_mish_on_small_maps(tmp_path, dtype, dim):
+    """The same network, runs and gates at a 32-pixel input (maps of 32, 16 and 8 pixels: the network's stride is 4) and at a
+    4-pixel one, whose maps are 4 x 4, 2 x 2 and 1 x 1: mish, the fused shortcut and the scale_x_y head on one cell.  Which
+    kernel takes a layer differs from the 288-pixel run's (no map is wide enough for the patch kernel), so the list of families
+    is not asked for here: tests/test_gpu_tiny_maps.py and the footprint rows hold kernels to maps."""
+    _mish_on_the_family_network(tmp_path, dtype, dim, False)
+
+
+def _mish_on_the_family_network(tmp_path, dtype, dim, every_family):
     cfg = _write(tmp_path, FAMILY_CFG, "family.cfg")
     params = _params(cfg)
     ref = R.Restatement(cfg, params)
@@ -113,7 +127,7 @@ def test_mish_on_every_conv_family(tmp_path, dtype):
     rounds = ref.rounding_points()
     seen = set()
     for name, options, batch in FAMILY_RUNS:
-        frames = synth_frames(500 + batch, batch, FAMILY_DIM, FAMILY_DIM)
+        frames = synth_frames(500 + batch, batch, dim, dim)
         net = _net(cfg, dtype, params, options)
         out = _run(net, frames, dtype == "float32")
         report = net.plan_report()
@@ -189,6 +203,8 @@ def test_mish_on_every_conv_family(tmp_path, dtype):
         torch.testing.assert_close(out["bbox_xywh"][sel].cpu(), box, rtol=2e-4, atol=2e-5, msg=lambda m: what + ": " + m)
         torch.testing.assert_close(out["class_prob"][sel].cpu(), prob, rtol=5e-4, atol=2e-5, msg=lambda m: what + ": " + m)
         del net
+    if not every_family:
+        return
     want = FAMILIES_32 if dtype == "float32" else tuple(f.replace("bf16", MODES[dtype]["tag"]) for f in FAMILIES_16)
     missing = [f for f in want if not any(f in k for k in seen)]
     assert not missing, "kernel families not exercised: %s (seen %s)" % (missing, sorted(seen))
