@@ -194,10 +194,11 @@ int check_size(const y3_op &op) {
   return Y3_OK;
 }
 
-// grid x block of what a step launches (y3_step.threads, filled by its chooser from the launcher's own grid): fewer than 2^32
+// grid x block of what a step launches (the grid and block its chooser recorded, which its launcher launches): fewer than 2^32
 int check_launch(const y3_op &op, const y3_step &st) {
-  Y3_REQUIRE(st.threads <= kY3MaxThreads, "op for block %d: %s would be a launch of %lld threads; the limit is %lld (2^32 less one workgroup)",
-             op.block_idx, st.name, st.threads, kY3MaxThreads);
+  const long long threads = st.dims.grid * st.dims.block;
+  Y3_REQUIRE(threads <= kY3MaxThreads, "op for block %d: %s would be a launch of %lld threads; the limit is %lld (2^32 less one workgroup)",
+             op.block_idx, st.name, threads, kY3MaxThreads);
   return Y3_OK;
 }
 

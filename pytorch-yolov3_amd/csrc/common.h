@@ -93,6 +93,14 @@ void y3_launch_log_append(Y3LaunchLog *log, const void *host_function, hipStream
     }                                                                                                                \
   } while (0)
 
+// What a launch is made of: workgroups (64-bit, so that plan creation can refuse a grid no launch holds), threads per workgroup,
+// dynamic LDS bytes.  A chooser records them in its y3_step; the launcher launches exactly that.
+struct y3_dims {
+  long long grid = 0;
+  int block = 0;
+  size_t lds = 0;
+};
+
 // Launches one kernel instance through Y3_LAUNCH and checks the launch.  Dynamic LDS over 64 KiB needs the instance's limit
 // raised first; the attribute is per device, so it is set on the instance's first such launch on each device (one lock and
 // state per instance: the statics of this template).  Launches within 64 KiB take no lock.
@@ -114,6 +122,10 @@ int y3_launch(dim3 grid, dim3 block, size_t lds, hipStream_t s, const A &...args
   Y3_LAUNCH(Kernel, grid, block, lds, s, args...);
   Y3_HIP_CHECK(hipGetLastError());
   return Y3_OK;
+}
+template <auto Kernel, typename... A>
+int y3_launch(const y3_dims &d, hipStream_t s, const A &...args) {
+  return y3_launch<Kernel>(dim3((unsigned)d.grid), dim3(d.block), d.lds, s, args...);
 }
 
 // The instantiated values of one template parameter of a kernel family: the chooser asks has(v), the launcher pick(v, f),
@@ -148,8 +160,8 @@ static inline int y3_by_dtype16(int dtype, F &&f) {   // kernels that exist for 
   return dtype == Y3_F16 ? f(f16_t{}) : f(bf16_t{});
 }
 static inline int y3_ceil_div(int a, int b) { return (a + b - 1) / b; }
-// A launch holds fewer than 2^32 threads (grid x block): every chooser records what its launcher will launch in y3_step.threads,
-// and plan creation refuses a step past the limit (api.hip check_launch)
+// A launch holds fewer than 2^32 threads (grid x block): plan creation refuses a step whose recorded launch (y3_step.dims) is past
+// the limit (api.hip check_launch)
 constexpr long long kY3MaxThreads = ((1ll << 32) - 1) / 256 * 256;
 static inline long long y3_ceil_div64(long long a, long long b) { return (a + b - 1) / b; }
 // n / d == (umulhi(n, mul) + n) >> sh for 0 <= n < 2^31 (round-up method, d >= 1)
@@ -415,6 +427,11 @@ __device__ __forceinline__ unsigned long long y3_now_real() {
 // ---- plan steps ----------------------------------------------------------------------------------------------------------
 // What one step of a plan (a single op, or a fused group led by its first op) launches: decided once, when the plan is created,
 // from the op(s) and the plan's options (api.hip: choose_conv and the choosers below); the launcher only launches what it records.
+// Each kernel family has ONE geometry function in its .hip file (op, variant -> the launch, the derived values of its kernel
+// arguments, whether the shape fits): its `fits` predicate, its chooser and its args builder read that and nothing restates it.
+// Every refusal that depends on the op and the step alone is the chooser's; a launcher builds the arguments, picks the instance from
+// the recorded template values (each one has()-checked by the chooser) and launches `dims`.  The one exception is launch_layer
+// (layers.hip), whose form depends on a run-time address.
 enum class y3_fuse : uint8_t {
   none,         // one op
   into_prev,    // nothing: launched by an earlier step
@@ -431,12 +448,13 @@ struct y3_step {
   y3_fuse fuse = y3_fuse::none;
   y3_launcher launch = nullptr;
   const char *name = "";
-  // variant parameters, each launcher reading its own: implicit GEMM version / pipeline stages / pixel x channel tile; the halo
-  // kernel's pixel tile (192 / 256); the 1x1-dw and head-dw tile height (bm); the weights-resident channel tile (bn); dw48 waves
-  // per workgroup; decode lanes per box; block-fused tile; pipelined (or phase-by-phase) stem pair
+  // variant parameters (template values), each launcher reading its own: implicit GEMM version / pipeline stages / pixel x channel
+  // tile; the halo kernel's pixel tile (192 / 256) and weight-ring slots (ns); the 1x1-dw and head-dw tile height (bm); the
+  // weights-resident channel tile (bn); dw48 waves per workgroup; decode lanes per box; block-fused tile; pipelined (or
+  // phase-by-phase) stem pair
   int version = 0, ns = 0, bm = 0, bn = 0, waves = 0, lanes = 0, tw = 0, th = 0;
   bool pipelined = false;
-  long long threads = 0;          // grid x block of the launch (0: a persistent grid of at most one workgroup per CU or so)
+  y3_dims dims;                   // the launch itself (a persistent kernel's grid is an ordinary small grid)
   bool frag = false;              // reads the fragment-order copy of ops[0]'s weights (y3_conv_halo_dw_make_weights) ...
   const void *frag_w = nullptr;   // ... this one (never null at launch)
 };

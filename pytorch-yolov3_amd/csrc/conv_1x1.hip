@@ -374,20 +374,38 @@ using DwBm = y3_ints<96, 48>;
 template <int BM> using Dw1Nkt = std::conditional_t<BM == 96, y3_ints<4, 6, 8, 12>, y3_ints<4, 6, 8, 12, 16>>;
 template <int BM> using DwHeadNkt = std::conditional_t<BM == 96, y3_ints<4, 8>, y3_ints<4, 8, 16>>;
 
+// Geometry of the direct-weights kernel at bm-pixel tiles, the plain 1x1 form (256-channel tiles) or the detection-head form
+// (head: one channel tile; the logit tile of bm x 260 floats is parked in the activation tile's LDS).  fits: the (bm, nkt)
+// instance exists and the tile of bm pixels x all of Cin fits LDS.
+struct DwGeom { bool fits; int M, nkt, n_tiles; y3_dims dims; };
+DwGeom dw_geom(const y3_op &op, int bm, bool head) {
+  DwGeom g;
+  g.M = head ? op.batch * op.out_h * op.out_w : op.batch * op.in_h * op.in_w;
+  g.nkt = op.in_c / 64;
+  g.n_tiles = head ? 1 : op.out_c / 256;
+  const size_t tile = (size_t)bm * op.in_c * 2, logits = (size_t)bm * 260 * 4;
+  g.dims.lds = head && logits > tile ? logits : tile;
+  const bool inst = bm == 96 ? (head ? DwHeadNkt<96>::has(g.nkt) : Dw1Nkt<96>::has(g.nkt))
+                             : (head ? DwHeadNkt<48>::has(g.nkt) : Dw1Nkt<48>::has(g.nkt));
+  g.fits = DwBm::has(bm) && inst && g.dims.lds <= 144 * 1024;
+  g.dims.grid = y3_ceil_div64(g.M, bm) * g.n_tiles;
+  g.dims.block = 512;
+  return g;
+}
+
 // tile height of the direct-weights 1x1 kernel for this op (96 / 48), or 0 when it does not take it
 int dw1x1_bm(const y3_op &op) {
   if (op.kind != Y3_OP_CONV || !y3_is16(op.dtype) || op.ksize != 1 || op.stride != 1 || op.pad != 0) return 0;
   if (op.flags & (Y3_F_RESIDUAL | Y3_F_OUT_F32 | Y3_F_IN_NCHW_F32 | Y3_F_IN_NHWC_U8BGR | Y3_F_PLAN_INPUT)) return 0;
   if (op.out_c % 256 != 0 || op.in_ld % 8 != 0 || op.out_ld % 8 != 0 || op.k_ld % 32 != 0 || op.k_ld < op.in_c || op.cout_pad % 32 != 0) return 0;
-  const int nkt = op.in_c / 64;
   if (op.in_c % 128 != 0) return 0;
-  const int M = op.batch * op.in_h * op.in_w, n_cu = y3_device_cus(), nt = op.out_c / 256;
+  const DwGeom g96 = dw_geom(op, 96, false), g48 = dw_geom(op, 48, false);
+  const int n_cu = y3_device_cus();
   // one round of workgroups: 96-pixel tiles where they already give every CU (nearly) one, else 48-pixel tiles -- down to a
   // quarter of the CUs (512 -> 256 at 19^2 x 16 frames: 121 tiles, 5.8 against 8.1-8.9 us on the implicit GEMMs, whose eight
   // K-steps each wait out an L2 round trip whatever the grid; 38^2 x 8 frames 6.6 against 8.7-11.2: profiles/r06_conv1x1_dw.txt); smaller grids (one frame at a time) stay on the tiled kernels
-  const long long t96 = (long long)y3_ceil_div(M, 96) * nt, t48 = (long long)y3_ceil_div(M, 48) * nt;
-  if (Dw1Nkt<96>::has(nkt) && op.in_c * 2 * 96 <= 144 * 1024 && t96 <= n_cu && 4 * t96 >= 3 * n_cu) return 96;
-  if (Dw1Nkt<48>::has(nkt) && op.in_c * 2 * 48 <= 144 * 1024 && t48 <= n_cu && 4 * t48 >= n_cu) return 48;
+  if (g96.fits && g96.dims.grid <= n_cu && 4 * g96.dims.grid >= 3 * n_cu) return 96;
+  if (g48.fits && g48.dims.grid <= n_cu && 4 * g48.dims.grid >= n_cu) return 48;
   return 0;
 }
 
@@ -401,11 +419,10 @@ int dw_head_bm(const y3_op &op, const y3_options &o) {
   if (op.kind != Y3_OP_CONV || !y3_is16(op.dtype) || op.ksize != 1 || op.stride != 1 || op.pad != 0 || !(op.flags & Y3_F_OUT_F32)) return 0;
   if (op.flags & (Y3_F_LEAKY | Y3_F_MISH | Y3_F_RESIDUAL | Y3_F_IN_NCHW_F32 | Y3_F_IN_NHWC_U8BGR | Y3_F_PLAN_INPUT)) return 0;   // (logistic: new_coords heads)
   if (op.out_c > 256 || op.cout_pad < 256 || op.cout_pad % 32 != 0 || op.in_ld % 8 != 0 || op.k_ld % 32 != 0 || op.k_ld < op.in_c) return 0;
-  const int nkt = op.in_c / 64;
-  if (op.in_c % 128 != 0 || !DwHeadNkt<48>::has(nkt)) return 0;
-  const long long M = (long long)op.batch * op.in_h * op.in_w;
-  if (M >= (1ll << 31)) return 0;
-  return mode == 4 && DwHeadNkt<96>::has(nkt) ? 96 : 48;   // (96 pixels x 1024 channels would be 192 KiB)
+  // (asked about a conv's shape before plan creation's size check as well: y3_conv_fragment_weight_bytes)
+  if ((long long)op.batch * op.in_h * op.in_w >= (1ll << 31) || (long long)op.batch * op.out_h * op.out_w >= (1ll << 31)) return 0;
+  if (op.in_c % 128 != 0 || !dw_geom(op, 48, true).fits) return 0;
+  return mode == 4 && dw_geom(op, 96, true).fits ? 96 : 48;   // (96 pixels x 1024 channels would be 192 KiB)
 }
 
 using WresBn = y3_ints<128, 64>;   // channel tiles of the weights-resident kernel
@@ -416,58 +433,73 @@ int wres_bn(const y3_op &op) {
   return 0;
 }
 
-int launch_conv1x1_dw(const y3_op *ops, const y3_step &st, const void *d_in, const void *d_zero, hipStream_t s) {
-  const y3_op &op = ops[0];
-  const int bm = st.bm;
+// Geometry of the weights-resident kernel: 128-pixel x bn-channel tiles, the whole weight panel of a channel tile in LDS, and a
+// PERSISTENT grid: one workgroup per CU (of the device current at plan creation), a whole number of them per channel tile (at
+// least one each: more channel tiles than CUs just means more than one workgroup per CU in turn), never more than tiles.  A
+// workgroup strides over its channel tile's pixel tiles by gridDim / n_tiles, so the grid is placement only.
+struct WresGeom { bool fits; int bn, n_kt, n_tiles, m_tiles; y3_dims dims; };
+WresGeom wres_geom(const y3_op &op) {
+  WresGeom g = {};
+  g.bn = wres_bn(op);
+  if (!WresBn::has(g.bn)) return g;
+  g.n_kt = op.in_c / 64;
+  g.n_tiles = op.out_c / g.bn;
+  g.m_tiles = (int)y3_ceil_div64((long long)op.batch * op.in_h * op.in_w, 128);
+  g.dims.lds = (size_t)g.n_kt * g.bn * 128 + (size_t)128 * g.bn * 2 + (size_t)4 * 128 * 128;
+  g.fits = g.dims.lds <= 160 * 1024;
+  const int n_cu = y3_device_cus();
+  g.dims.grid = g.n_tiles > n_cu ? g.n_tiles : n_cu - n_cu % g.n_tiles;
+  const long long tiles = (long long)g.m_tiles * g.n_tiles;
+  if (g.dims.grid > tiles) g.dims.grid = tiles;
+  g.dims.block = 512;
+  return g;
+}
+
+// DwArgs of 1x1 conv `op` with geometry g; `yolo`: the detection-head form, which writes no conv output and decodes its logits for
+// the YOLO op `yolo`
+DwArgs dw_args(const y3_op &op, const void *d_in, const y3_step &st, const void *d_zero, const DwGeom &g, const y3_op *yolo = nullptr) {
   DwArgs a;
   a.in = static_cast<const char *>(d_in);
   a.wgt = static_cast<const char *>(st.frag_w);
   a.scale = op.d_scale; a.bias = op.d_bias;
-  a.out = static_cast<char *>(op.d_out);
+  a.out = yolo ? nullptr : static_cast<char *>(op.d_out);
   a.zero = static_cast<const char *>(d_zero);
-  a.M = op.batch * op.in_h * op.in_w;
+  a.M = g.M;
   a.in_ld = op.in_ld; a.out_ld = op.out_ld; a.k_ld = op.k_ld;
-  a.n_tiles = op.out_c / 256;
+  a.n_tiles = g.n_tiles;
   a.flags = op.flags;
-  const int nkt = op.in_c / 64;
+  if (yolo) {
+    a.Ho = op.out_h; a.Wo = op.out_w; a.HoWo = op.out_h * op.out_w;
+    y3_fast_div((uint32_t)a.HoWo, a.mul_hw, a.sh_hw);
+    y3_fast_div((uint32_t)a.Wo, a.mul_w, a.sh_w);
+    a.dec = y3_decode_args(*yolo);
+  }
+  return a;
+}
+
+int launch_conv1x1_dw(const y3_op *ops, const y3_step &st, const void *d_in, const void *d_zero, hipStream_t s) {
+  const y3_op &op = ops[0];
+  const DwGeom g = dw_geom(op, st.bm, false);
+  const DwArgs a = dw_args(op, d_in, st, d_zero, g);
   return y3_by_dtype16(op.dtype, [&](auto tag) {
     typedef decltype(tag) T;
-    const size_t lds = (size_t)bm * op.in_c * 2;
-    const dim3 grid(y3_ceil_div(a.M, bm) * a.n_tiles);
-    return DwBm::pick(bm, [&](auto m) {
-      return Dw1Nkt<m.value>::pick(nkt, [&](auto k) {
-        return y3_launch<conv1x1_dw_kernel<T, m.value, k.value>>(grid, dim3(512), lds, s, a);
+    return DwBm::pick(st.bm, [&](auto m) {
+      return Dw1Nkt<m.value>::pick(g.nkt, [&](auto k) {
+        return y3_launch<conv1x1_dw_kernel<T, m.value, k.value>>(st.dims, s, a);
       });
     });
   });
 }
 
 int launch_head_decode_dw(const y3_op *ops, const y3_step &st, const void *, const void *d_zero, hipStream_t s) {
-  const y3_op &op0 = ops[0], &op1 = ops[1];
-  const int bm = st.bm;
-  DwArgs a;
-  a.in = static_cast<const char *>(op0.d_in);
-  a.wgt = static_cast<const char *>(st.frag_w);
-  a.scale = op0.d_scale; a.bias = op0.d_bias;
-  a.out = nullptr;
-  a.zero = static_cast<const char *>(d_zero);
-  a.Ho = op0.out_h; a.Wo = op0.out_w; a.HoWo = op0.out_h * op0.out_w;
-  a.M = op0.batch * a.HoWo;
-  a.in_ld = op0.in_ld; a.out_ld = op0.out_ld; a.k_ld = op0.k_ld;
-  a.n_tiles = 1;
-  a.flags = op0.flags;
-  y3_fast_div((uint32_t)a.HoWo, a.mul_hw, a.sh_hw);
-  y3_fast_div((uint32_t)a.Wo, a.mul_w, a.sh_w);
-  a.dec = y3_decode_args(op1);
-  const int nkt = op0.in_c / 64;
+  const y3_op &op0 = ops[0];
+  const DwGeom g = dw_geom(op0, st.bm, true);
+  const DwArgs a = dw_args(op0, op0.d_in, st, d_zero, g, &ops[1]);
   return y3_by_dtype16(op0.dtype, [&](auto tag) {
     typedef decltype(tag) T;
-    const size_t tile = (size_t)bm * op0.in_c * 2, logits = (size_t)bm * 260 * 4;
-    const size_t lds = tile > logits ? tile : logits;
-    const dim3 grid(y3_ceil_div(a.M, bm));
-    return DwBm::pick(bm, [&](auto m) {
-      return DwHeadNkt<m.value>::pick(nkt, [&](auto k) {
-        return y3_launch<conv1x1_dw_kernel<T, m.value, k.value, true>>(grid, dim3(512), lds, s, a);
+    return DwBm::pick(st.bm, [&](auto m) {
+      return DwHeadNkt<m.value>::pick(g.nkt, [&](auto k) {
+        return y3_launch<conv1x1_dw_kernel<T, m.value, k.value, true>>(st.dims, s, a);
       });
     });
   });
@@ -475,7 +507,7 @@ int launch_head_decode_dw(const y3_op *ops, const y3_step &st, const void *, con
 
 int launch_conv1x1_wres(const y3_op *ops, const y3_step &st, const void *d_in, const void *d_zero, hipStream_t s) {
   const y3_op &op = ops[0];
-  const int bn = st.bn;
+  const WresGeom g = wres_geom(op);
   WresArgs a;
   a.in = static_cast<const char *>(d_in);
   a.wgt = static_cast<const char *>(op.d_weight);
@@ -484,21 +516,10 @@ int launch_conv1x1_wres(const y3_op *ops, const y3_step &st, const void *d_in, c
   a.zero = static_cast<const char *>(d_zero);
   a.M = op.batch * op.in_h * op.in_w;
   a.Cin = op.in_c; a.in_ld = op.in_ld; a.Cout = op.out_c; a.out_ld = op.out_ld; a.k_ld = op.k_ld;
-  a.n_kt = op.in_c / 64;
-  a.n_tiles = op.out_c / bn;
-  a.m_tiles = y3_ceil_div(a.M, 128);
+  a.n_kt = g.n_kt; a.n_tiles = g.n_tiles; a.m_tiles = g.m_tiles;
   a.flags = op.flags;
   return y3_by_dtype16(op.dtype, [&](auto tag) {
-    typedef decltype(tag) T;
-    const size_t lds = (size_t)a.n_kt * bn * 128 + (size_t)128 * bn * 2 + (size_t)4 * 128 * 128;
-    Y3_REQUIRE(lds <= 160 * 1024, "conv block %d: weight panel does not fit LDS", op.block_idx);
-    // one workgroup per CU, a whole number of them per channel tile (at least one each: more channel tiles than CUs just
-    // means more than one workgroup per CU in turn)
-    const int n_cu = y3_device_cus();
-    int grid = a.n_tiles > n_cu ? a.n_tiles : n_cu - n_cu % a.n_tiles;
-    const long long tiles = (long long)a.m_tiles * a.n_tiles;
-    if (grid > tiles) grid = (int)tiles;
-    return WresBn::pick(bn, [&](auto n) { return y3_launch<conv1x1_wres_kernel<T, n.value>>(dim3(grid), dim3(512), lds, s, a); });
+    return WresBn::pick(st.bn, [&](auto n) { return y3_launch<conv1x1_wres_kernel<decltype(tag), n.value>>(st.dims, s, a); });
   });
 }
 
@@ -509,23 +530,23 @@ int launch_conv1x1_wres(const y3_op *ops, const y3_step &st, const void *d_in, c
 bool y3_conv1x1_dw_pays(const y3_op &op) { return dw1x1_bm(op) != 0; }
 
 int y3_choose_conv1x1_dw(const y3_op &op, y3_step &st) {
-  st.bm = dw1x1_bm(op);
+  st.bm = dw1x1_bm(op);   // (a tile height whose geometry fits: its (bm, nkt) instance exists)
   Y3_REQUIRE(st.bm != 0, "conv block %d: not a shape for the direct-weights 1x1 kernel", op.block_idx);
   st.launch = launch_conv1x1_dw;
-  st.threads = y3_ceil_div64((long long)op.batch * op.in_h * op.in_w, st.bm) * (op.out_c / 256) * 512;
+  st.dims = dw_geom(op, st.bm, false).dims;
   st.name = st.bm == 96 ? Y3_KNAME(op.dtype, "conv1x1_dw_", "_96x256") : Y3_KNAME(op.dtype, "conv1x1_dw_", "_48x256");
   st.frag = true;
   return Y3_OK;
 }
 
 // detection-head conv + YOLO decode on the direct-weights 1x1 kernel (op0: the head conv, op1: the Y3_OP_YOLO op reading it; the pair
-// has passed the checks of y3_choose_conv_head_decode)
+// has passed the checks of y3_choose_conv_head_decode and y3_conv_head_dw_fits)
 bool y3_conv_head_dw_fits(const y3_op &op0, const y3_options &o) { return dw_head_bm(op0, o) != 0; }
 
 void y3_choose_conv_head_decode_dw(const y3_op &op0, const y3_options &o, y3_step &st) {
   st.bm = dw_head_bm(op0, o);
   st.launch = launch_head_decode_dw;
-  st.threads = y3_ceil_div64((long long)op0.batch * op0.out_h * op0.out_w, st.bm ? st.bm : 48) * 512;
+  st.dims = dw_geom(op0, st.bm, true).dims;
   st.name = st.bm == 96 ? Y3_KNAME(op0.dtype, "conv_head_decode_dw_", "_96x256") : Y3_KNAME(op0.dtype, "conv_head_decode_dw_", "_48x256");
   st.frag = true;
 }
@@ -551,8 +572,11 @@ bool y3_conv1x1_wres_pays(const y3_op &op) {
 
 int y3_choose_conv1x1_wres(const y3_op &op, y3_step &st) {
   Y3_REQUIRE(y3_conv1x1_wres_supported(op), "conv block %d: not a shape for the weights-resident 1x1 kernel", op.block_idx);
-  st.bn = wres_bn(op);
+  const WresGeom g = wres_geom(op);
+  Y3_REQUIRE(g.fits, "conv block %d: weight panel does not fit LDS", op.block_idx);
+  st.bn = g.bn;
   st.launch = launch_conv1x1_wres;
+  st.dims = g.dims;
   st.name = st.bn == 128 ? Y3_KNAME(op.dtype, "conv1x1_wres_", "_128x128") : Y3_KNAME(op.dtype, "conv1x1_wres_", "_128x64");
   return Y3_OK;
 }

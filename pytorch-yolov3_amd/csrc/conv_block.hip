@@ -424,8 +424,19 @@ bool choose_tile(int H, int W, int batch, int n_cu, int &TW, int &TH, double &ef
   return true;
 }
 
+// Geometry of the kernel on tw x th rectangles: one workgroup of kNT threads and kBlockLds bytes per rectangle
+struct BlockGeom { int tiles_x, tiles_y; long long grid; };
+BlockGeom block_geom(const y3_op &op0, int tw, int th) {
+  BlockGeom g;
+  g.tiles_x = y3_ceil_div(op0.in_w, tw);
+  g.tiles_y = y3_ceil_div(op0.in_h, th);
+  g.grid = (long long)g.tiles_x * g.tiles_y * op0.batch;
+  return g;
+}
+
 int launch_block_fused(const y3_op *ops, const y3_step &st, const void *, const void *, hipStream_t s) {
   const y3_op &op0 = ops[0], &op1 = ops[1];
+  const BlockGeom g = block_geom(op0, st.tw, st.th);
   BlockArgs a;
   a.x = static_cast<const char *>(op0.d_in);
   a.H = op0.in_h; a.W = op0.in_w; a.x_ld = op0.in_ld; a.ns = op0.in_c / 64;
@@ -437,14 +448,11 @@ int launch_block_fused(const y3_op *ops, const y3_step &st, const void *, const 
   a.leaky3 = (op1.flags & Y3_F_LEAKY) ? 1 : 0;
   a.TW = st.tw;
   a.TH = st.th;
+  a.tiles_x = g.tiles_x; a.tiles_y = g.tiles_y;
+  a.inv_pw = (65536u + (uint32_t)(a.TW + 2) - 1u) / (uint32_t)(a.TW + 2);
+  a.inv_tw = (65536u + (uint32_t)a.TW - 1u) / (uint32_t)a.TW;
   return y3_by_dtype16(op0.dtype, [&](auto tag) {
-    typedef decltype(tag) T;
-    a.tiles_x = y3_ceil_div(a.W, a.TW);
-    a.tiles_y = y3_ceil_div(a.H, a.TH);
-    a.inv_pw = (65536u + (uint32_t)(a.TW + 2) - 1u) / (uint32_t)(a.TW + 2);
-    a.inv_tw = (65536u + (uint32_t)a.TW - 1u) / (uint32_t)a.TW;
-    const int grid = a.tiles_x * a.tiles_y * op0.batch;
-    return y3_launch<conv_block_fused_kernel<T>>(dim3(grid), dim3(kNT), kBlockLds, s, a);
+    return y3_launch<conv_block_fused_kernel<decltype(tag)>>(st.dims, s, a);
   });
 }
 
@@ -488,7 +496,7 @@ bool y3_choose_conv_block_fused(const y3_op &op0, const y3_op &op1, const y3_opt
   st.tw = tw;
   st.th = th;
   st.launch = launch_block_fused;
-  st.threads = (long long)y3_ceil_div(op0.in_w, tw) * y3_ceil_div(op0.in_h, th) * op0.batch * kNT;
+  st.dims = {block_geom(op0, tw, th).grid, kNT, kBlockLds};
   st.name = Y3_KNAME(op0.dtype, "conv_block_fused_", "_x128");
   return true;
 }

@@ -286,10 +286,12 @@ using Dw48NktK1 = y3_ints<2, 4, 6, 8, 12, 16>;
 using Dw48NktS2 = y3_ints<1, 2, 4>;
 using Dw48NktS2Halves = y3_ints<2, 4>;
 
-// Shape of the halo image(s) for an op: rows that hold pixels, channels per image, images (NH); rows = 0: not a shape of this kernel
-struct Dw48Shape { int rows, cin_img, nh; };
-Dw48Shape dw48_shape(const y3_op &op) {
-  Dw48Shape z = {0, 0, 0};
+// Geometry of the kernel for an op.  Shape of the halo image(s): rows that hold pixels, channels per image, images (NH), K-steps per
+// image, LDS bytes; rows = 0: not a shape of this kernel.  The launch with nw waves (32-channel tiles) per workgroup: 48-pixel
+// tiles (m_tiles) x channel tiles of 32 nw (n_ctiles; nw = 0, the shape asked about alone: none), 512 threads.
+struct Dw48Shape { int rows, cin_img, nh, nkt, m_tiles, n_ctiles; y3_dims dims; };
+Dw48Shape dw48_shape(const y3_op &op, int nw = 0) {
+  Dw48Shape z = {};
   if (op.kind != Y3_OP_CONV || !y3_is16(op.dtype)) return z;
   const bool k1 = op.ksize == 1 && op.pad == 0 && op.stride == 1, k3 = op.ksize == 3 && op.pad == 1 && op.stride == 1;
   const bool k3s2 = op.ksize == 3 && op.pad == 1 && op.stride == 2 && op.in_h % 2 == 0 && op.in_w % 2 == 0;
@@ -298,17 +300,21 @@ Dw48Shape dw48_shape(const y3_op &op) {
   if (op.out_c % 32 != 0 || op.cout_pad % 32 != 0 || op.in_ld % 8 != 0 || op.out_ld % 8 != 0 || op.k_ld % 32 != 0) return z;
   if ((op.flags & Y3_F_RESIDUAL) && op.res_ld % 8 != 0) return z;
   if ((op.in_c % 128 != 0 && !(k3s2 && op.in_c == 64)) || op.k_ld < op.ksize * op.ksize * op.in_c) return z;
-  Dw48Shape sh;
+  Dw48Shape sh = {};
   sh.rows = k1 ? 48 : (k3 ? 48 + 2 * op.in_w + 2 : 194 + 2 * op.out_w);
   sh.cin_img = op.in_c;
   sh.nh = 1;
   // stride 2: four input pixels per output pixel -- when all channels do not fit, two images of half the channels one after the other
   if (k3s2 && (long long)(sh.rows + 1) * sh.cin_img * 2 + 1024 > 160 * 1024 && sh.cin_img % 256 == 0) { sh.cin_img /= 2; sh.nh = 2; }
-  if ((long long)(sh.rows + 1) * sh.cin_img * 2 + 1024 > 160 * 1024) return z;
-  const int nkt = sh.cin_img / 64;
-  const bool inst = k1 ? Dw48NktK1::has(nkt) : (k3 ? Dw48NktK3::has(nkt) : (sh.nh == 1 ? Dw48NktS2::has(nkt) : Dw48NktS2Halves::has(nkt)));
+  sh.dims.lds = (size_t)(sh.rows + 1) * sh.cin_img * 2 + 1024;   // (+ the tail of the last 1-KiB piece)
+  if (sh.dims.lds > 160 * 1024) return z;
+  sh.nkt = sh.cin_img / 64;
+  const bool inst = k1 ? Dw48NktK1::has(sh.nkt) : (k3 ? Dw48NktK3::has(sh.nkt) : (sh.nh == 1 ? Dw48NktS2::has(sh.nkt) : Dw48NktS2Halves::has(sh.nkt)));
   if (!inst) return z;
-  if ((long long)op.batch * op.out_h * op.out_w >= (1ll << 31)) return z;
+  sh.m_tiles = (int)y3_ceil_div64((long long)op.batch * op.out_h * op.out_w, 48);
+  sh.n_ctiles = nw ? op.out_c / (32 * nw) : 0;
+  sh.dims.grid = (long long)sh.m_tiles * sh.n_ctiles;
+  sh.dims.block = 512;
   return sh;
 }
 
@@ -318,8 +324,7 @@ Dw48Shape dw48_shape(const y3_op &op) {
 int dw48_waves(const y3_op &op, int grid) {
   const Dw48Shape sh = dw48_shape(op);
   if (sh.rows == 0) return 0;
-  const long long M = (long long)op.batch * op.out_h * op.out_w;
-  const long long mt = (M + 47) / 48;
+  const long long mt = sh.m_tiles;
   const int n_cu = y3_device_cus();
   int widest = 0;
   for (int nw = 8; nw >= 1 && !widest; nw >>= 1)
@@ -357,6 +362,7 @@ int dw48_waves_for(const y3_op &op, const y3_options &o) {
 int launch_dw48(const y3_op *ops, const y3_step &step, const void *d_in, const void *d_zero, hipStream_t s) {
   const y3_op &op = ops[0];
   const int nw = step.waves;
+  const Dw48Shape sh = dw48_shape(op, nw);
   Dw48Args a;
   a.in = static_cast<const char *>(d_in);
   a.wgt = static_cast<const char *>(step.frag_w);
@@ -368,27 +374,24 @@ int launch_dw48(const y3_op *ops, const y3_step &step, const void *d_in, const v
   a.in_h = op.in_h; a.in_w = op.in_w;
   a.M = op.batch * a.HW;
   a.in_ld = op.in_ld; a.out_ld = op.out_ld; a.res_ld = op.res_ld; a.k_ld = op.k_ld;
-  a.n_ctiles = op.out_c / (32 * nw);
+  a.n_ctiles = sh.n_ctiles;
   a.nwc = nw;
-  a.m_tiles = y3_ceil_div(a.M, 48);
+  a.m_tiles = sh.m_tiles;
   a.m_inner = (double)op.ksize * op.ksize * op.in_c * op.out_c > (double)op.batch * op.in_h * op.in_w * op.in_c;   // weights outweigh the activations
-  const Dw48Shape sh = dw48_shape(op);
   a.hr = sh.rows;
   y3_fast_div((uint32_t)a.HW, a.mul_hw, a.sh_hw);
   y3_fast_div((uint32_t)a.W, a.mul_w, a.sh_w);
   a.flags = op.flags;
-  const int nkt = sh.cin_img / 64;
-  const size_t lds = (size_t)(a.hr + 1) * sh.cin_img * 2 + 1024;   // (+ the tail of the last 1-KiB piece)
-  const dim3 grid(y3_ceil_div(a.M, 48) * a.n_ctiles), block(512);
+  const int nkt = sh.nkt;
   return y3_by_dtype16(op.dtype, [&](auto tag) {
     typedef decltype(tag) T;
     if (op.ksize == 3 && op.stride == 1)
-      return Dw48NktK3::pick(nkt, [&](auto k) { return y3_launch<conv_dw48_kernel<T, 3, k.value>>(grid, block, lds, s, a); });
+      return Dw48NktK3::pick(nkt, [&](auto k) { return y3_launch<conv_dw48_kernel<T, 3, k.value>>(step.dims, s, a); });
     if (op.ksize == 1)
-      return Dw48NktK1::pick(nkt, [&](auto k) { return y3_launch<conv_dw48_kernel<T, 1, k.value>>(grid, block, lds, s, a); });
+      return Dw48NktK1::pick(nkt, [&](auto k) { return y3_launch<conv_dw48_kernel<T, 1, k.value>>(step.dims, s, a); });
     if (sh.nh == 1)
-      return Dw48NktS2::pick(nkt, [&](auto k) { return y3_launch<conv_dw48_kernel<T, 3, k.value, 2, 1>>(grid, block, lds, s, a); });
-    return Dw48NktS2Halves::pick(nkt, [&](auto k) { return y3_launch<conv_dw48_kernel<T, 3, k.value, 2, 2>>(grid, block, lds, s, a); });
+      return Dw48NktS2::pick(nkt, [&](auto k) { return y3_launch<conv_dw48_kernel<T, 3, k.value, 2, 1>>(step.dims, s, a); });
+    return Dw48NktS2Halves::pick(nkt, [&](auto k) { return y3_launch<conv_dw48_kernel<T, 3, k.value, 2, 2>>(step.dims, s, a); });
   });
 }
 
@@ -403,7 +406,7 @@ int y3_choose_conv_dw48(const y3_op &op, const y3_options &o, y3_step &st) {
   st.waves = dw48_waves_for(op, o);
   Y3_REQUIRE(st.waves != 0, "conv block %d: not a shape for the small-grid direct-weights kernel", op.block_idx);
   st.launch = launch_dw48;
-  st.threads = y3_ceil_div64((long long)op.batch * op.out_h * op.out_w, 48) * (op.out_c / (32 * st.waves)) * 512;
+  st.dims = dw48_shape(op, st.waves).dims;   // (a shape of the kernel: its nkt is an instance of its form)
   st.name = op.ksize == 3 ? (op.stride == 2 ? Y3_KNAME(op.dtype, "conv_dw48_k3s2_", "") : Y3_KNAME(op.dtype, "conv_dw48_k3_", ""))
                           : Y3_KNAME(op.dtype, "conv_dw48_k1_", "");
   st.frag = true;

@@ -921,7 +921,25 @@ __global__ __launch_bounds__(kThreads) void conv_resblock_fused_kernel(ResArgs<T
 
 
 static int launch_stem_s2(const y3_op *ops, const y3_step &st, const void *d_in, const void *, hipStream_t s);
-static int launch_resblock(const y3_op *ops, const y3_step &, const void *, const void *, hipStream_t s);
+static int launch_resblock(const y3_op *ops, const y3_step &st, const void *, const void *, hipStream_t s);
+
+// Geometry of the two fused kernels: a tile list of tw x th output pixels per frame, and a PERSISTENT grid of one workgroup per CU
+// (of the device current at plan creation) or per tile.  Both kernels stride over the tile list by gridDim, so the grid is
+// placement only.
+struct FusedGeom { int tiles_x, tiles_y, n_tiles; long long grid; };
+static FusedGeom fused_geom(int out_w, int out_h, int batch, int tw, int th) {
+  FusedGeom g;
+  g.tiles_x = y3_ceil_div(out_w, tw);
+  g.tiles_y = y3_ceil_div(out_h, th);
+  g.n_tiles = g.tiles_x * g.tiles_y * batch;
+  const int n_cu = y3_device_cus();
+  g.grid = g.n_tiles < n_cu ? g.n_tiles : n_cu;
+  return g;
+}
+static FusedGeom stem_s2_geom(const y3_op &op1, bool pipelined) {
+  return fused_geom(op1.out_w, op1.out_h, op1.batch, pipelined ? kPX : kTO, pipelined ? kPY : kTO);
+}
+static FusedGeom resblock_geom(const y3_op &op0) { return fused_geom(op0.in_w, op0.in_h, op0.batch, kRT, kRT); }
 
 // op0: the MFMA stem conv (uint8 frames, 3 -> 32, bf16 out); op1: 3x3 stride-2 conv 32 -> 64 reading ONLY op0's output
 bool y3_choose_conv_fused_stem_s2(const y3_op &op0, const y3_op &op1, const y3_options &o, y3_step &st) {
@@ -940,6 +958,7 @@ bool y3_choose_conv_fused_stem_s2(const y3_op &op0, const y3_op &op1, const y3_o
   st.launch = launch_stem_s2;
   st.name = op0.dtype == Y3_F16 ? "conv_stem_s2_fused_u8_f16" : "conv_stem_s2_fused_u8_bf16";
   st.pipelined = o.fuse_stem != 2;                      // fuse_stem 2: the phase-by-phase kernel (A/B)
+  st.dims = {stem_s2_geom(op1, st.pipelined).grid, st.pipelined ? 1024 : kThreads, (size_t)(st.pipelined ? kPLds : kLds)};
   return true;
 }
 
@@ -958,13 +977,10 @@ static int launch_stem_s2(const y3_op *ops, const y3_step &st, const void *d_in,
     a.out = static_cast<T *>(op1.d_out);
     a.out_ld = op1.out_ld; a.Ho = op1.out_h; a.Wo = op1.out_w;
     a.dbg = 0;
-    const bool pipelined = st.pipelined;
-    a.tiles_x = y3_ceil_div(a.Wo, pipelined ? kPX : kTO);
-    a.tiles_y = y3_ceil_div(a.Ho, pipelined ? kPY : kTO);
-    a.n_tiles = a.tiles_x * a.tiles_y * a.batch;
-    const int n_cu = y3_device_cus(), grid = a.n_tiles < n_cu ? a.n_tiles : n_cu;
-    if (!pipelined) return y3_launch<conv_stem_s2_fused_kernel<T>>(dim3(grid), dim3(kThreads), kLds, s, a);
-    return y3_launch<conv_stem_s2_ws_kernel<T, 4>>(dim3(grid), dim3(1024), kPLds, s, a);
+    const FusedGeom g = stem_s2_geom(op1, st.pipelined);
+    a.tiles_x = g.tiles_x; a.tiles_y = g.tiles_y; a.n_tiles = g.n_tiles;
+    if (!st.pipelined) return y3_launch<conv_stem_s2_fused_kernel<T>>(st.dims, s, a);
+    return y3_launch<conv_stem_s2_ws_kernel<T, 4>>(st.dims, s, a);
   });
 }
 
@@ -987,11 +1003,12 @@ bool y3_choose_conv_fused_resblock(const y3_op &op0, const y3_op &op1, const y3_
   // 32-bit lane offsets from a tile's 64-bit base: kRT + 2 rows of W pixels of x, kRT rows of the output
   if ((long long)(kRT + 2) * op0.in_w * (op0.in_ld > op1.out_ld ? op0.in_ld : op1.out_ld) * 2 >= (1ll << 32)) return false;
   st.launch = launch_resblock;
+  st.dims = {resblock_geom(op0).grid, kThreads, kRLds};
   st.name = Y3_KNAME(op0.dtype, "conv_resblock_fused_", "_64_32_64");
   return true;
 }
 
-static int launch_resblock(const y3_op *ops, const y3_step &, const void *, const void *, hipStream_t s) {
+static int launch_resblock(const y3_op *ops, const y3_step &st, const void *, const void *, hipStream_t s) {
   const y3_op &op0 = ops[0], &op1 = ops[1];
   return y3_by_dtype16(op0.dtype, [&](auto tag) {
     typedef decltype(tag) T;
@@ -1002,11 +1019,9 @@ static int launch_resblock(const y3_op *ops, const y3_step &, const void *, cons
     a.w3 = static_cast<const T *>(op1.d_weight); a.k_ld3 = op1.k_ld; a.sc3 = op1.d_scale; a.bi3 = op1.d_bias;
     a.out = static_cast<T *>(op1.d_out);
     a.out_ld = op1.out_ld;
-    a.tiles_x = y3_ceil_div(a.W, kRT);
-    a.tiles_y = y3_ceil_div(a.H, kRT);
-    a.n_tiles = a.tiles_x * a.tiles_y * a.batch;
-    const int n_cu = y3_device_cus(), grid = a.n_tiles < n_cu ? a.n_tiles : n_cu;
-    return y3_launch<conv_resblock_fused_kernel<T>>(dim3(grid), dim3(kThreads), kRLds, s, a);
+    const FusedGeom g = resblock_geom(op0);
+    a.tiles_x = g.tiles_x; a.tiles_y = g.tiles_y; a.n_tiles = g.n_tiles;
+    return y3_launch<conv_resblock_fused_kernel<T>>(st.dims, s, a);
   });
 }
 

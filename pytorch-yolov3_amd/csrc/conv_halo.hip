@@ -1101,31 +1101,6 @@ __global__ __launch_bounds__(512, 2) void conv_halo_dw_kernel(HaloArgs p) {
   }
 }
 
-// HaloArgs of a 3x3 stride-1 conv with `wgt` as its weights and tile_n output channels per tile: all but the tile geometry,
-// which each launcher sets
-HaloArgs halo_args(const y3_op &op, const void *wgt, const void *d_in, const void *d_zero, int tile_n) {
-  HaloArgs a;
-  a.in = static_cast<const char *>(d_in);
-  a.wgt = static_cast<const char *>(wgt);
-  a.scale = op.d_scale; a.bias = op.d_bias;
-  a.res = static_cast<const char *>(op.d_res);
-  a.out = static_cast<char *>(op.d_out);
-  a.zero = static_cast<const char *>(d_zero);
-  a.H = op.in_h; a.W = op.in_w; a.Cin = op.in_c; a.in_ld = op.in_ld;
-  a.Cout = op.out_c; a.out_ld = op.out_ld; a.res_ld = op.res_ld;
-  a.HW = op.in_h * op.in_w;
-  a.M = op.batch * a.HW;
-  a.k_ld = op.k_ld;
-  a.nchunks = op.in_c / (128 / y3_elem_size(op.dtype));
-  a.n_tiles = op.out_c / tile_n;
-  a.hr = a.hr_pad = a.na = a.a_bytes = 0;
-  a.ngrp_w = a.n_tiles; a.m_tiles = 0;
-  y3_fast_div((uint32_t)a.HW, a.mul_hw, a.sh_hw);
-  y3_fast_div((uint32_t)a.W, a.mul_w, a.sh_w);
-  a.flags = op.flags;
-  return a;
-}
-
 // Tile order and HBM traffic of the strip kernels: the ngrp_w for a.  Each XCD (own L2) gets one contiguous run of tile ids.
 // With all channel tiles innermost (ngrp_w = n_tiles) a run covers a few pixel tiles x ALL weight panels: every XCD fetches
 // the whole weight matrix -- fine while the input outweighs it (76^2, 38^2), 75 MB of extra fetches per launch at 19^2
@@ -1142,6 +1117,41 @@ int halo_tile_groups(const HaloArgs &a) {
     if (pn == 1 || cost < 0.9 * best_cost) { best = pn; best_cost = cost; }
   }
   return a.n_tiles / best;
+}
+
+// Geometry of one launch of a kernel of this file (halo_strip_geom, patch_geom below): the launch the chooser records, the
+// derived HaloArgs fields, and whether the shape fits
+struct HaloGeom {
+  bool fits;
+  int hr, na, hr_pad, a_bytes;   // the HaloArgs fields of these names
+  int m_tiles, nsb;              // strip kernels: pixel tiles (0: the patch kernel); wave-specialised kernel: weight-ring slots
+  int tiles, tiles_x, tiles_y;   // patch kernel: its tile list
+  y3_dims dims;
+};
+
+// HaloArgs of a 3x3 stride-1 conv with `wgt` as its weights, tile_n output channels per tile and the geometry g
+HaloArgs halo_args(const y3_op &op, const void *wgt, const void *d_in, const void *d_zero, int tile_n, const HaloGeom &g) {
+  HaloArgs a;
+  a.in = static_cast<const char *>(d_in);
+  a.wgt = static_cast<const char *>(wgt);
+  a.scale = op.d_scale; a.bias = op.d_bias;
+  a.res = static_cast<const char *>(op.d_res);
+  a.out = static_cast<char *>(op.d_out);
+  a.zero = static_cast<const char *>(d_zero);
+  a.H = op.in_h; a.W = op.in_w; a.Cin = op.in_c; a.in_ld = op.in_ld;
+  a.Cout = op.out_c; a.out_ld = op.out_ld; a.res_ld = op.res_ld;
+  a.HW = op.in_h * op.in_w;
+  a.M = op.batch * a.HW;
+  a.k_ld = op.k_ld;
+  a.nchunks = op.in_c / (128 / y3_elem_size(op.dtype));
+  a.n_tiles = op.out_c / tile_n;
+  a.hr = g.hr; a.hr_pad = g.hr_pad; a.na = g.na; a.a_bytes = g.a_bytes;
+  a.m_tiles = g.m_tiles;
+  a.ngrp_w = g.m_tiles ? halo_tile_groups(a) : a.n_tiles;
+  y3_fast_div((uint32_t)a.HW, a.mul_hw, a.sh_hw);
+  y3_fast_div((uint32_t)a.W, a.mul_w, a.sh_w);
+  a.flags = op.flags;
+  return a;
 }
 
 // 192-pixel tiles (MI = 3) when they finish sooner than 256-pixel tiles: rounds of workgroups (one per CU) x per-tile
@@ -1190,34 +1200,81 @@ using HaloWsMi = y3_ints<4, 3>;
 using HaloWsNsb = y3_ints<3, 4>;
 using HaloDwNa = y3_ints<4, 5, 6>;
 
-}  // namespace
+// The strip kernels at bm-pixel tiles: the wave-specialised one (128-channel tiles, 32 halo rows per loader pass, 768 threads) or
+// the direct-weights one (dw: 256-channel tiles, 64 rows per pass, 512 threads).  The halo image of bm + 2W + 2 pixel rows and
+// two zero rows (hr is even: rows hr, hr + 1 = one 256-byte bank row), padded to whole passes, is held twice; the finished
+// float32 tile is parked in the same LDS.
+HaloGeom halo_strip_geom(const y3_op &op, bool dw, int bm) {
+  HaloGeom g = {};
+  const int rpp = dw ? 64 : 32;
+  g.hr = bm + 2 * op.in_w + 2;
+  g.na = y3_ceil_div(g.hr + 2, rpp);
+  g.hr_pad = g.na * rpp;
+  g.a_bytes = g.hr_pad * 128;
+  const size_t park = (size_t)bm * 128 * 4;
+  if (dw) {
+    g.dims.lds = (size_t)2 * g.a_bytes > park ? (size_t)2 * g.a_bytes : park;
+    g.fits = HaloDwNa::has(g.na) && g.dims.lds <= 160 * 1024;
+  } else {
+    // four weight slots, or three: the next chunk's halo goes out two passes per K-step and must be older than the last loads
+    // allowed in flight, i.e. all real halo slices out by tap 5 (4 slots) / 6 (3 slots)
+    for (int c = 4; c >= 3 && !g.nsb; --c) {
+      if (g.na > (c == 4 ? 12 : 14)) continue;
+      g.dims.lds = (size_t)c * 128 * 128 + (size_t)2 * g.a_bytes;
+      if (g.dims.lds < park) g.dims.lds = park;
+      if (g.dims.lds <= 160 * 1024) g.nsb = c;
+    }
+    g.fits = g.nsb != 0;
+  }
+  g.m_tiles = (int)y3_ceil_div64((long long)op.batch * op.in_h * op.in_w, bm);
+  g.dims.grid = (long long)g.m_tiles * (op.out_c / (dw ? 256 : 128));
+  g.dims.block = dw ? 512 : 768;
+  return g;
+}
 
-bool y3_conv_halo_eligible(const y3_op &op) {
+// The patch kernel: 8 x 32 output tiles, four weight slots, a PERSISTENT grid of one workgroup per CU (of the device current at
+// plan creation) or per tile.  The kernel strides over its tile list by gridDim, so the grid is placement only.
+HaloGeom patch_geom(const y3_op &op) {
+  constexpr int TY = 8, TX = 32, PROWS = (TY + 2) * (TX + 2);
+  static_assert(PROWS <= 12 * 32, "all patch slices must be out by tap 5 (4-slot ring)");
+  HaloGeom g = {};
+  g.fits = true;
+  g.na = y3_ceil_div(PROWS, 32);
+  g.hr_pad = g.na * 32;
+  g.a_bytes = g.hr_pad * 128;
+  g.dims.lds = (size_t)4 * 128 * 128 + (size_t)2 * g.a_bytes;
+  g.tiles_x = y3_ceil_div(op.in_w, TX);
+  g.tiles_y = y3_ceil_div(op.in_h, TY);
+  g.tiles = g.tiles_x * g.tiles_y * op.batch * (op.out_c / 128);
+  const int n_cu = y3_device_cus();
+  g.dims.grid = g.tiles < n_cu ? g.tiles : n_cu;
+  g.dims.block = 768;
+  return g;
+}
+
+// the layer class of this file: 3x3 stride 1 pad 1, NHWC in and out in the op's element type, whole 128-byte channel chunks
+// (at least min_chunks of them), Cout a multiple of 128
+bool halo_eligible(const y3_op &op, int min_chunks) {
   const int es = y3_elem_size(op.dtype);
   const int bke = 128 / es;
   if (op.ksize != 3 || op.stride != 1 || op.pad != 1) return false;
   if (op.flags & (Y3_F_OUT_F32 | Y3_F_IN_NCHW_F32 | Y3_F_IN_NHWC_U8BGR)) return false;
-  if (op.in_c % bke != 0 || op.in_c / bke < 2) return false;
+  if (op.in_c % bke != 0 || op.in_c / bke < min_chunks) return false;
   if (op.out_c % 128 != 0 || op.out_ld % 8 != 0 || op.in_ld % (16 / es) != 0) return false;
   if ((op.flags & Y3_F_RESIDUAL) && op.res_ld % 8 != 0) return false;
-  if (op.k_ld < 9 * op.in_c) return false;
-  return true;
+  return op.k_ld >= 9 * op.in_c;
 }
 
-// additionally the halo image must fit: 2 x (258 + 2W rows, padded to 32) x 128 B + 3 weight slots <= 160 KiB, and all
-// real halo slices must be out by tap 6 of the previous chunk (<= 14 passes of 32 rows)
-bool y3_conv_halo_ws_fits(const y3_op &op) {
-  if (!y3_conv_halo_eligible(op)) return false;
-  const int na = y3_ceil_div(256 + 2 * op.in_w + 4, 32);
-  return na <= 14 && (size_t)3 * 128 * 128 + (size_t)2 * na * 32 * 128 <= 160 * 1024;
-}
+}  // namespace
+
+// additionally the halo image of a 256-pixel tile must fit LDS, with three weight slots at least (rows of up to 94 pixels)
+bool y3_conv_halo_ws_fits(const y3_op &op) { return halo_eligible(op, 2) && halo_strip_geom(op, false, 256).fits; }
 
 // direct-weights strip kernel (round 5): 16-bit modes, Cout a multiple of 256, rows of up to 94 pixels (four to six 64-row halo
 // passes per chunk: the maps the wave-specialised kernel takes)
 bool y3_conv_halo_dw_fits(const y3_op &op) {
-  if (!y3_conv_halo_eligible(op) || !y3_is16(op.dtype) || op.out_c % 256 != 0 || op.cout_pad % 32 != 0 || op.k_ld % 32 != 0) return false;
-  const int na = y3_ceil_div(DW_BM + 2 * op.in_w + 4, 64);
-  return HaloDwNa::has(na) && y3_conv_halo_ws_fits(op);
+  if (!y3_is16(op.dtype) || op.out_c % 256 != 0 || op.cout_pad % 32 != 0 || op.k_ld % 32 != 0) return false;
+  return y3_conv_halo_ws_fits(op) && halo_strip_geom(op, true, DW_BM).fits;
 }
 
 // Where it is the better kernel.  Per workgroup the two strip kernels do the same work per cycle (PMC, profiles/r05s: 64 % of
@@ -1252,95 +1309,53 @@ int y3_conv_halo_dw_make_weights(const y3_op &op, void *dst, hipStream_t s) {
 
 static int launch_conv_halo_dw(const y3_op *ops, const y3_step &st, const void *d_in, const void *d_zero, hipStream_t s) {
   const y3_op &op = ops[0];
-  HaloArgs a = halo_args(op, st.frag_w, d_in, d_zero, 256);
-  a.hr = DW_BM + 2 * a.W + 2;
-  a.na = y3_ceil_div(a.hr + 2, 64);                   // + the two zero rows
-  a.hr_pad = a.na * 64;
-  a.a_bytes = a.hr_pad * 128;
-  size_t lds = (size_t)2 * a.a_bytes;
-  if (lds < (size_t)DW_BM * 128 * 4) lds = (size_t)DW_BM * 128 * 4;
-  Y3_REQUIRE(HaloDwNa::has(a.na) && lds <= 160 * 1024, "direct-weights halo kernel: row width %d does not fit", a.W);
-  a.m_tiles = y3_ceil_div(a.M, DW_BM);
-  a.ngrp_w = halo_tile_groups(a);
-  const dim3 grid(a.m_tiles * a.n_tiles);
+  const HaloGeom g = halo_strip_geom(op, true, DW_BM);
+  const HaloArgs a = halo_args(op, st.frag_w, d_in, d_zero, 256, g);
   return y3_by_dtype16(op.dtype, [&](auto tag) {
-    return HaloDwNa::pick(a.na, [&](auto na) {
-      return y3_launch<conv_halo_dw_kernel<decltype(tag), na.value>>(grid, dim3(512), lds, s, a);
+    return HaloDwNa::pick(g.na, [&](auto na) {
+      return y3_launch<conv_halo_dw_kernel<decltype(tag), na.value>>(st.dims, s, a);
     });
   });
 }
 
 int y3_choose_conv_halo_dw(const y3_op &op, y3_step &st) {
   Y3_REQUIRE(y3_conv_halo_dw_fits(op), "conv block %d: shape not supported by the direct-weights halo kernel", op.block_idx);
-  Y3_REQUIRE((long long)op.batch * op.in_h * op.in_w < (1ll << 31), "conv block %d: too many pixels for the 32-bit tile index", op.block_idx);
+  const HaloGeom g = halo_strip_geom(op, true, DW_BM);   // (its na is an instance: g.fits)
+  Y3_REQUIRE(g.fits, "direct-weights halo kernel: row width %d does not fit", op.in_w);
   st.launch = launch_conv_halo_dw;
-  st.threads = y3_ceil_div64((long long)op.batch * op.in_h * op.in_w, DW_BM) * (op.out_c / 256) * 512;
+  st.dims = g.dims;
   st.name = Y3_KNAME(op.dtype, "conv_halo_dw_", "_192x256");
   st.frag = true;
   return Y3_OK;
 }
 
 // 2-D patch kernel: same layer class, any number (>= 1) of channel chunks, any row width
-bool y3_conv_patch_fits(const y3_op &op) {
-  const int es = y3_elem_size(op.dtype);
-  const int bke = 128 / es;
-  if (op.ksize != 3 || op.stride != 1 || op.pad != 1) return false;
-  if (op.flags & (Y3_F_OUT_F32 | Y3_F_IN_NCHW_F32 | Y3_F_IN_NHWC_U8BGR)) return false;
-  if (op.in_c % bke != 0 || op.out_c % 128 != 0 || op.out_ld % 8 != 0 || op.in_ld % (16 / es) != 0) return false;
-  if ((op.flags & Y3_F_RESIDUAL) && op.res_ld % 8 != 0) return false;
-  return op.k_ld >= 9 * op.in_c;
-}
+bool y3_conv_patch_fits(const y3_op &op) { return halo_eligible(op, 1); }
 
-static int launch_conv_patch(const y3_op *ops, const y3_step &, const void *d_in, const void *d_zero, hipStream_t s) {
+static int launch_conv_patch(const y3_op *ops, const y3_step &st, const void *d_in, const void *d_zero, hipStream_t s) {
   const y3_op &op = ops[0];
-  HaloArgs a = halo_args(op, op.d_weight, d_in, d_zero, 128);
-  constexpr int TY = 8, TX = 32, PROWS = (TY + 2) * (TX + 2);
-  static_assert(PROWS <= 12 * 32, "all patch slices must be out by tap 5 (4-slot ring)");
-  a.na = y3_ceil_div(PROWS, 32);
-  a.hr_pad = a.na * 32;
-  a.a_bytes = a.hr_pad * 128;
-  const size_t lds = (size_t)4 * 128 * 128 + (size_t)2 * a.a_bytes;
-  const int tiles_x = y3_ceil_div(a.W, TX), tiles_y = y3_ceil_div(a.H, TY);
-  const int tiles = tiles_x * tiles_y * (a.M / a.HW) * a.n_tiles, n_cu = y3_device_cus();
-  const dim3 grid(tiles < n_cu ? tiles : n_cu);
+  const HaloGeom g = patch_geom(op);
+  const HaloArgs a = halo_args(op, op.d_weight, d_in, d_zero, 128, g);
   return y3_by_dtype(op.dtype, [&](auto tag) {
-    return y3_launch<conv_patch_wsp_kernel<decltype(tag), 4>>(grid, dim3(768), lds, s, a, tiles, tiles_x, tiles_y);
+    return y3_launch<conv_patch_wsp_kernel<decltype(tag), 4>>(st.dims, s, a, g.tiles, g.tiles_x, g.tiles_y);
   });
 }
 
 int y3_choose_conv_patch(const y3_op &op, y3_step &st) {
   Y3_REQUIRE(y3_conv_patch_fits(op), "conv block %d: shape not supported by the patch kernel", op.block_idx);
   st.launch = launch_conv_patch;
+  st.dims = patch_geom(op).dims;
   st.name = Y3_KNAME(op.dtype, "conv_patch_wsp_", "_8x32x128");
   return Y3_OK;
 }
 
 static int launch_conv_halo(const y3_op *ops, const y3_step &st, const void *d_in, const void *d_zero, hipStream_t s) {
   const y3_op &op = ops[0];
-  HaloArgs a = halo_args(op, op.d_weight, d_in, d_zero, 128);
-  const int mi = st.bm / 64;
-  const int bm = 64 * mi;
-  a.hr = bm + 2 * a.W + 2;
-  a.na = y3_ceil_div(a.hr + 2, 32);                   // + the two zero rows (hr is even: rows hr, hr + 1 = one 256-byte bank row)
-  a.hr_pad = a.na * 32;
-  a.a_bytes = a.hr_pad * 128;
-  // the next chunk's halo goes out two passes per K-step and must be older than the last loads allowed in flight
-  int nsb = 0;
-  size_t lds = 0;
-  for (int c = 4; c >= 3; --c) {
-    if (a.na > (c == 4 ? 12 : 14)) continue;   // all real halo slices out by tap 5 (4 slots) / 6 (3 slots)
-    lds = (size_t)c * 128 * 128 + (size_t)2 * a.a_bytes;
-    if (lds < (size_t)bm * 128 * 4) lds = (size_t)bm * 128 * 4;
-    if (lds <= 160 * 1024) { nsb = c; break; }
-  }
-  Y3_REQUIRE(nsb != 0, "wave-specialised halo kernel: row width %d does not fit", a.W);
-  a.m_tiles = y3_ceil_div(a.M, bm);
-  a.ngrp_w = halo_tile_groups(a);
-  const dim3 grid(a.m_tiles * a.n_tiles);
+  const HaloArgs a = halo_args(op, op.d_weight, d_in, d_zero, 128, halo_strip_geom(op, false, st.bm));
   return y3_by_dtype(op.dtype, [&](auto tag) {
-    return HaloWsMi::pick(mi, [&](auto m) {
-      return HaloWsNsb::pick(nsb, [&](auto ns) {
-        return y3_launch<conv_halo_ws_kernel<decltype(tag), ns.value, m.value>>(grid, dim3(768), lds, s, a);
+    return HaloWsMi::pick(st.bm / 64, [&](auto m) {
+      return HaloWsNsb::pick(st.ns, [&](auto ns) {
+        return y3_launch<conv_halo_ws_kernel<decltype(tag), ns.value, m.value>>(st.dims, s, a);
       });
     });
   });
@@ -1349,11 +1364,14 @@ static int launch_conv_halo(const y3_op *ops, const y3_step &st, const void *d_i
 int y3_choose_conv_halo(const y3_op &op, const y3_options &o, y3_step &st) {
   const int es = y3_elem_size(op.dtype);
   Y3_REQUIRE(y3_conv_halo_ws_fits(op), "conv block %d: shape not supported by the halo kernel", op.block_idx);
-  Y3_REQUIRE((long long)op.batch * op.in_h * op.in_w < (1ll << 31), "conv block %d: too many pixels for the 32-bit tile index", op.block_idx);
   const int mi = halo_tile_fragments(op.batch * op.in_h * op.in_w, op.out_c / 128, op.in_c / (128 / es), y3_device_cus(), o);
+  // the geometry of the tile picked (y3_conv_halo_ws_fits asked about 256 pixels; a 192-pixel tile's halo is smaller)
+  const HaloGeom g = halo_strip_geom(op, false, 64 * mi);
+  Y3_REQUIRE(g.fits && HaloWsMi::has(mi) && HaloWsNsb::has(g.nsb), "wave-specialised halo kernel: row width %d does not fit", op.in_w);
   st.launch = launch_conv_halo;
   st.bm = 64 * mi;
-  st.threads = y3_ceil_div64((long long)op.batch * op.in_h * op.in_w, st.bm) * (op.out_c / 128) * 768;
+  st.ns = g.nsb;
+  st.dims = g.dims;
   st.name = mi == 3 ? Y3_KNAME(op.dtype, "conv_halo_ws_", "_192x128") : Y3_KNAME(op.dtype, "conv_halo_ws_", "_256x128");
   return Y3_OK;
 }

@@ -859,36 +859,28 @@ struct IgemmShape {
   static constexpr int WM = BM == 64 ? 1 : (BN == 32 ? 4 : 2), WN = 4 / WM;
 };
 
+// the instance of each version for a tile (and stage count), K-tiling mode picked here; launched as the step `st` records
 template <typename T, int TILE, int NS>
-int launch_cfg3(IgemmArgs a, int kmode, hipStream_t s) {
+int launch_cfg3(const IgemmArgs &a, int kmode, const y3_step &st, hipStream_t s) {
   typedef IgemmShape<TILE> S;
-  a.m_tiles = y3_ceil_div(a.M, S::BM);
-  a.n_tiles = y3_ceil_div(a.Cout, S::BN);
-  const dim3 grid(a.m_tiles * a.n_tiles), block(128 * S::WM * S::WN);
   return IgemmKmodes::pick(kmode, [&](auto k) {
-    return y3_launch<conv_igemm3_kernel<T, S::BM, S::BN, S::WM, S::WN, k.value, NS>>(grid, block, 0, s, a);
+    return y3_launch<conv_igemm3_kernel<T, S::BM, S::BN, S::WM, S::WN, k.value, NS>>(st.dims, s, a);
   });
 }
 
 template <typename T, int TILE>
-int launch_cfg2(IgemmArgs a, int kmode, hipStream_t s) {
+int launch_cfg2(const IgemmArgs &a, int kmode, const y3_step &st, hipStream_t s) {
   typedef IgemmShape<TILE> S;
-  a.m_tiles = y3_ceil_div(a.M, S::BM);
-  a.n_tiles = y3_ceil_div(a.Cout, S::BN);
-  const dim3 grid(a.m_tiles * a.n_tiles), block(64 * S::WM * S::WN);
   return IgemmKmodes::pick(kmode, [&](auto k) {
-    return y3_launch<conv_igemm2_kernel<T, S::BM, S::BN, S::WM, S::WN, k.value>>(grid, block, 0, s, a);
+    return y3_launch<conv_igemm2_kernel<T, S::BM, S::BN, S::WM, S::WN, k.value>>(st.dims, s, a);
   });
 }
 
 template <typename T, int TILE>
-int launch_cfg(IgemmArgs a, bool generic, hipStream_t s) {
+int launch_cfg(const IgemmArgs &a, bool generic, const y3_step &st, hipStream_t s) {
   typedef IgemmShape<TILE> S;
-  a.m_tiles = y3_ceil_div(a.M, S::BM);
-  a.n_tiles = y3_ceil_div(a.Cout, S::BN);
-  const dim3 grid(a.m_tiles * a.n_tiles), block(256);
-  if (generic) return y3_launch<conv_igemm_kernel<T, S::BM, S::BN, S::WM, S::WN, true>>(grid, block, 0, s, a);
-  return y3_launch<conv_igemm_kernel<T, S::BM, S::BN, S::WM, S::WN, false>>(grid, block, 0, s, a);
+  if (generic) return y3_launch<conv_igemm_kernel<T, S::BM, S::BN, S::WM, S::WN, true>>(st.dims, s, a);
+  return y3_launch<conv_igemm_kernel<T, S::BM, S::BN, S::WM, S::WN, false>>(st.dims, s, a);
 }
 
 }  // namespace
@@ -916,65 +908,80 @@ static int igemm_ktiles(const y3_op &op, int &kmode) {
   return y3_ceil_div(op.ksize * op.ksize * op.in_c, bke);
 }
 
-static int launch_conv_igemm(const y3_op *ops, const y3_step &st, const void *d_in, const void *d_zero, hipStream_t s) {
-  const y3_op &op = ops[0];
-  const int bke = 128 / y3_elem_size(op.dtype);
+// Geometry of an implicit GEMM of `version` with bm x bn tiles: one workgroup of 256 threads per tile, 512 on the wave-specialised
+// kernel (version 3); no dynamic LDS.  Version 1 tiles every K that is not whole 128-byte chunks per tap as one flat run.
+struct IgemmGeom { int kmode, n_ktiles, m_tiles, n_tiles; y3_dims dims; };
+static IgemmGeom igemm_geom(const y3_op &op, int version, int bm, int bn) {
+  IgemmGeom g;
+  g.n_ktiles = igemm_ktiles(op, g.kmode);
+  if (version == 1 && g.kmode != 0) g.n_ktiles = y3_ceil_div(op.ksize * op.ksize * op.in_c, 128 / y3_elem_size(op.dtype));
+  g.m_tiles = (int)y3_ceil_div64((long long)op.batch * op.out_h * op.out_w, bm);
+  g.n_tiles = y3_ceil_div(op.out_c, bn);
+  g.dims.grid = (long long)g.m_tiles * g.n_tiles;
+  g.dims.block = version == 3 ? 512 : 256;
+  return g;
+}
+
+// IgemmArgs of conv `op` with geometry g; `yolo`: the detection-head form (launch_head_decode), whose logits stay in the workgroup
+// (no output, no shortcut operand) and are decoded for the YOLO op `yolo`
+static IgemmArgs igemm_args(const y3_op &op, const void *d_in, const void *d_zero, const IgemmGeom &g, const y3_op *yolo = nullptr) {
   IgemmArgs a;
   a.in = static_cast<const char *>(d_in);
   a.wgt = static_cast<const char *>(op.d_weight);
   a.scale = op.d_scale;
   a.bias = op.d_bias;
-  a.res = static_cast<const char *>(op.d_res);
-  a.out = static_cast<char *>(op.d_out);
+  a.res = yolo ? nullptr : static_cast<const char *>(op.d_res);
+  a.out = yolo ? nullptr : static_cast<char *>(op.d_out);
   a.zero = static_cast<const char *>(d_zero);
   a.H = op.in_h; a.W = op.in_w; a.Cin = op.in_c; a.in_ld = op.in_ld;
-  a.Ho = op.out_h; a.Wo = op.out_w; a.Cout = op.out_c; a.out_ld = op.out_ld; a.res_ld = op.res_ld;
-  a.ks = op.ksize; a.stride = op.stride; a.pad = op.pad;
+  a.Ho = op.out_h; a.Wo = op.out_w; a.Cout = op.out_c; a.out_ld = op.out_ld; a.res_ld = yolo ? 0 : op.res_ld;
+  a.ks = op.ksize; a.stride = op.stride; a.pad = yolo ? 0 : op.pad;
   a.HoWo = op.out_h * op.out_w;
   a.M = op.batch * a.HoWo;
   a.k_ld = op.k_ld;
   a.K = op.ksize * op.ksize * op.in_c;
-  int kmode;
-  a.n_ktiles = igemm_ktiles(op, kmode);
-  a.ktiles_per_tap = kmode == 0 ? op.in_c / bke : 0;
+  a.n_ktiles = g.n_ktiles;
+  a.ktiles_per_tap = g.kmode == 0 ? op.in_c / (128 / y3_elem_size(op.dtype)) : 0;
   a.n_taps = op.ksize * op.ksize;
-  a.m_tiles = a.n_tiles = 0;
+  a.m_tiles = g.m_tiles; a.n_tiles = g.n_tiles;
   // Each XCD gets one contiguous run of tile ids (y3_xcd_remap) and has its own L2.  Channel tiles innermost: the run covers a
   // few pixel tiles x ALL channel tiles, so every XCD fetches the whole weight matrix and 1/8 of the activations; pixel
   // tiles innermost: every XCD fetches all activations and 1/8 of the weights.  Whichever operand is bigger is the one to
   // split (yolov3-tiny's 13^2 layers at batch 8: 18.9 MB of float32 weights against 2.8 MB of input -- 45 MB of traffic per
   // launch for 16 MB algorithmic before this, profiles/r03_traffic.json).  Placement only: results do not change.
-  a.n_major = (double)op.out_c * a.K > (double)op.batch * op.in_h * op.in_w * op.in_c ? 1 : 0;
+  // (The head form has one channel tile.)
+  a.n_major = !yolo && (double)op.out_c * a.K > (double)op.batch * op.in_h * op.in_w * op.in_c ? 1 : 0;
   a.flags = op.flags;
   y3_fast_div((uint32_t)a.HoWo, a.mul_hw, a.sh_hw);
   y3_fast_div((uint32_t)a.Wo, a.mul_w, a.sh_w);
-  const int tile = igemm_tile(st.bm, st.bn);
+  if (yolo) a.dec = y3_decode_args(*yolo);
+  return a;
+}
+
+static int launch_conv_igemm(const y3_op *ops, const y3_step &st, const void *d_in, const void *d_zero, hipStream_t s) {
+  const y3_op &op = ops[0];
+  const IgemmGeom g = igemm_geom(op, st.version, st.bm, st.bn);
+  const IgemmArgs a = igemm_args(op, d_in, d_zero, g);
+  const int tile = igemm_tile(st.bm, st.bn), kmode = g.kmode;
   if (st.version == 1) {
-    const bool generic = kmode != 0;
-    if (generic) a.n_ktiles = y3_ceil_div(a.K, bke);
     return IgemmTiles1::pick(tile, [&](auto t) {
-      return y3_by_dtype(op.dtype, [&](auto tag) { return launch_cfg<decltype(tag), t.value>(a, generic, s); });
+      return y3_by_dtype(op.dtype, [&](auto tag) { return launch_cfg<decltype(tag), t.value>(a, kmode != 0, st, s); });
     });
   }
   if (st.version == 3) {
-    // (a two-stage form existed; it needed more than the 128 VGPRs that two co-resident workgroups leave and measured
-    // slower than every other variant, so 2 now means 3)
-    const int ns = st.ns == 4 ? 4 : 3;
     return IgemmTiles3::pick(tile, [&](auto t) {
       auto go = [&](auto tag) {
-        return IgemmNs::pick(ns, [&](auto n) { return launch_cfg3<decltype(tag), t.value, n.value>(a, kmode, s); });
+        return IgemmNs::pick(st.ns, [&](auto n) { return launch_cfg3<decltype(tag), t.value, n.value>(a, kmode, st, s); });
       };
-      if constexpr (IgemmShape<t.value>::BM == 64) {
-        Y3_REQUIRE(y3_is16(op.dtype), "conv block %d: no 64-pixel float32 tiles", op.block_idx);
+      if constexpr (IgemmShape<t.value>::BM == 64) {   // (16-bit modes only: the chooser's refusal)
         return y3_by_dtype16(op.dtype, go);
       } else {
         return y3_by_dtype(op.dtype, go);
       }
     });
   }
-  Y3_REQUIRE(st.version == 2, "implicit GEMM version %d has no kernel", st.version);
   return IgemmTiles2::pick(tile, [&](auto t) {
-    return y3_by_dtype(op.dtype, [&](auto tag) { return launch_cfg2<decltype(tag), t.value>(a, kmode, s); });
+    return y3_by_dtype(op.dtype, [&](auto tag) { return launch_cfg2<decltype(tag), t.value>(a, kmode, st, s); });
   });
 }
 
@@ -987,15 +994,22 @@ int y3_choose_conv_igemm(const y3_op &op, const y3_options &o, y3_step &st, int 
   int kmode;
   const int n_ktiles = igemm_ktiles(op, kmode), M = op.batch * op.out_h * op.out_w;
   Y3_REQUIRE(n_ktiles * (128 / y3_elem_size(op.dtype)) <= op.k_ld, "conv block %d: k_ld %d too small for %d K-tiles", op.block_idx, op.k_ld, n_ktiles);
-  Y3_REQUIRE((long long)op.batch * op.out_h * op.out_w < (1ll << 31), "conv block %d: too many output pixels for the 32-bit tile index", op.block_idx);
   const int dt = op.dtype;
   const bool bf = y3_is16(dt);                   // a 16-bit storage mode (bf16 / IEEE half): same tiles, same selection
   st.launch = launch_conv_igemm;
-  st.ns = ns;
+  // (a two-stage form existed; it needed more than the 128 VGPRs that two co-resident workgroups leave and measured
+  // slower than every other variant, so 2 now means 3)
+  st.ns = ns == 4 ? 4 : 3;
   st.bm = 128;
-  // grid x block of the launch (launch_cfg / launch_cfg2 / launch_cfg3): 256 threads per tile, 512 on the wave-specialised kernel
+  // the variant is decided: it has an instance, and its launch is recorded
   auto done = [&]() {
-    st.threads = y3_ceil_div64(M, st.bm) * y3_ceil_div(op.out_c, st.bn) * (st.version == 3 ? 512 : 256);
+    const int tile = igemm_tile(st.bm, st.bn);
+    Y3_REQUIRE(st.version >= 1 && st.version <= 3, "implicit GEMM version %d has no kernel", st.version);
+    Y3_REQUIRE(st.bm != 64 || bf, "conv block %d: no 64-pixel float32 tiles", op.block_idx);
+    const bool inst = st.version == 1 ? IgemmTiles1::has(tile)
+                                      : (st.version == 2 ? IgemmTiles2::has(tile) : IgemmTiles3::has(tile) && IgemmNs::has(st.ns));
+    Y3_REQUIRE(inst && IgemmKmodes::has(kmode), "conv block %d: no implicit GEMM %d instance with %d x %d tiles", op.block_idx, st.version, st.bm, st.bn);
+    st.dims = igemm_geom(op, st.version, st.bm, st.bn).dims;
     return Y3_OK;
   };
   // channel-tile width follows Cout so narrow layers do not multiply zero padding ...
@@ -1066,44 +1080,20 @@ bool y3_choose_conv_head_decode(const y3_op &op0, const y3_op &op1, const y3_opt
   if (y3_conv_head_dw_fits(op0, o)) {
     y3_choose_conv_head_decode_dw(op0, o, st);
   } else {
+    // 64 pixels x all 255 channels per workgroup (version 2's kernel, one channel tile): 80 KiB of LDS (two operand stages; the
+    // padded logit tile of 64 x 260 floats is parked in them), so two workgroups share a CU and one's decode runs under the
+    // other's loads (128-pixel tiles, one per CU, measured equal in isolation: profiles/r02n_heads.txt)
     st.launch = launch_head_decode;
     st.name = Y3_KNAME(op0.dtype, "conv_head_decode_", "_64x256");
-    st.threads = y3_ceil_div64((long long)op0.batch * op0.out_h * op0.out_w, 64) * 256;
+    st.dims = igemm_geom(op0, 2, 64, 256).dims;
   }
   return true;
 }
 
-static int launch_head_decode(const y3_op *ops, const y3_step &, const void *, const void *d_zero, hipStream_t s) {
-  const y3_op &op0 = ops[0], &op1 = ops[1];
-  IgemmArgs a;
-  a.in = static_cast<const char *>(op0.d_in);
-  a.wgt = static_cast<const char *>(op0.d_weight);
-  a.scale = op0.d_scale;
-  a.bias = op0.d_bias;
-  a.res = nullptr;
-  a.out = nullptr;
-  a.zero = static_cast<const char *>(d_zero);
-  a.H = op0.in_h; a.W = op0.in_w; a.Cin = op0.in_c; a.in_ld = op0.in_ld;
-  a.Ho = op0.out_h; a.Wo = op0.out_w; a.Cout = op0.out_c; a.out_ld = op0.out_ld; a.res_ld = 0;
-  a.ks = 1; a.stride = 1; a.pad = 0;
-  a.HoWo = op0.out_h * op0.out_w;
-  a.M = op0.batch * a.HoWo;
-  a.k_ld = op0.k_ld;
-  a.K = op0.in_c;
-  a.ktiles_per_tap = op0.in_c / 64;
-  a.n_taps = 1;
-  a.n_ktiles = a.ktiles_per_tap;
-  a.flags = op0.flags;
-  y3_fast_div((uint32_t)a.HoWo, a.mul_hw, a.sh_hw);
-  y3_fast_div((uint32_t)a.Wo, a.mul_w, a.sh_w);
-  a.dec = y3_decode_args(op1);
-  // 64 pixels x all 255 channels per workgroup: 80 KiB of LDS (two operand stages; the padded logit tile of 64 x 260 floats
-  // is parked in them), so two workgroups share a CU and one's decode runs under the other's loads (128-pixel tiles, one
-  // per CU, measured equal in isolation: profiles/r02n_heads.txt)
-  a.n_tiles = 1;
-  a.n_major = 0;
-  a.m_tiles = y3_ceil_div(a.M, 64);
+static int launch_head_decode(const y3_op *ops, const y3_step &st, const void *, const void *d_zero, hipStream_t s) {
+  const y3_op &op0 = ops[0];
+  const IgemmArgs a = igemm_args(op0, op0.d_in, d_zero, igemm_geom(op0, 2, 64, 256), &ops[1]);
   return y3_by_dtype16(op0.dtype, [&](auto tag) {
-    return y3_launch<conv_igemm2_kernel<decltype(tag), 64, 256, 1, 4, 0, true>>(dim3(a.m_tiles), dim3(256), 0, s, a);
+    return y3_launch<conv_igemm2_kernel<decltype(tag), 64, 256, 1, 4, 0, true>>(st.dims, s, a);
   });
 }

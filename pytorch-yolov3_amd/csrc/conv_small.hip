@@ -265,7 +265,7 @@ __global__ __launch_bounds__(256) void conv_direct_kernel(DirectArgs p) {
 
 }  // namespace
 
-static int launch_conv_small(const y3_op *ops, const y3_step &, const void *d_in, const void *, hipStream_t s) {
+static int launch_conv_small(const y3_op *ops, const y3_step &st, const void *d_in, const void *, hipStream_t s) {
   const y3_op &op = ops[0];
   SmallArgs a;
   a.in = d_in;
@@ -280,11 +280,9 @@ static int launch_conv_small(const y3_op *ops, const y3_step &, const void *d_in
   a.flags = op.flags;
   const bool u8 = op.flags & Y3_F_IN_NHWC_U8BGR;
   const int odt = (op.flags & Y3_F_OUT_F32) ? Y3_F32 : op.dtype;   // element type of the output
-  const dim3 grid(y3_ceil_div(a.M, 256)), block(256);
-  const size_t lds = ((size_t)27 * op.cout_pad + 256) * sizeof(float);
   return y3_by_dtype(odt, [&](auto tag) {
-    if (u8) return y3_launch<conv_stem3x3_kernel<decltype(tag), 1>>(grid, block, lds, s, a);
-    return y3_launch<conv_stem3x3_kernel<decltype(tag), 0>>(grid, block, lds, s, a);
+    if (u8) return y3_launch<conv_stem3x3_kernel<decltype(tag), 1>>(st.dims, s, a);
+    return y3_launch<conv_stem3x3_kernel<decltype(tag), 0>>(st.dims, s, a);
   });
 }
 
@@ -297,7 +295,8 @@ int y3_choose_conv_small(const y3_op &op, y3_step &st) {
   Y3_REQUIRE(!(op.flags & Y3_F_RESIDUAL), "conv block %d: stem kernel has no residual input", op.block_idx);
   const int odt = (op.flags & Y3_F_OUT_F32) ? Y3_F32 : op.dtype;
   st.launch = launch_conv_small;
-  st.threads = y3_ceil_div64((long long)op.batch * op.out_h * op.out_w, 256) * 256;
+  // one thread per output pixel; all weights and 256 floats in LDS
+  st.dims = {y3_ceil_div64((long long)op.batch * op.out_h * op.out_w, 256), 256, ((size_t)27 * op.cout_pad + 256) * sizeof(float)};
   st.name = (op.flags & Y3_F_IN_NHWC_U8BGR) ? Y3_KNAME(odt, "conv_stem3x3_u8_", "") : Y3_KNAME(odt, "conv_stem3x3_nchw_", "");
   return Y3_OK;
 }
@@ -308,7 +307,11 @@ bool y3_conv_stem_mfma_supported(const y3_op &op) {
          op.in_c == 3 && op.ksize == 3 && op.stride == 1 && op.pad == 1 && op.out_c <= 32 && op.out_ld % 4 == 0;
 }
 
-static int launch_conv_stem_mfma(const y3_op *ops, const y3_step &, const void *d_in, const void *, hipStream_t s) {
+// tiles (kStemTW x kStemTH output pixels, one workgroup each) of the MFMA stem along x and y
+static int stem_mfma_tiles_x(const y3_op &op) { return y3_ceil_div(op.in_w, kStemTW); }
+static int stem_mfma_tiles_y(const y3_op &op) { return y3_ceil_div(op.in_h, kStemTH); }
+
+static int launch_conv_stem_mfma(const y3_op *ops, const y3_step &st, const void *d_in, const void *, hipStream_t s) {
   const y3_op &op = ops[0];
   return y3_by_dtype16(op.dtype, [&](auto tag) {
     typedef decltype(tag) T;
@@ -318,22 +321,22 @@ static int launch_conv_stem_mfma(const y3_op *ops, const y3_step &, const void *
     a.scale = op.d_scale; a.bias = op.d_bias;
     a.out = static_cast<T *>(op.d_out);
     a.B = op.batch; a.H = op.in_h; a.W = op.in_w; a.Cout = op.out_c; a.out_ld = op.out_ld;
-    a.tiles_x = y3_ceil_div(op.in_w, kStemTW);
-    a.tiles_y = y3_ceil_div(op.in_h, kStemTH);
+    a.tiles_x = stem_mfma_tiles_x(op);
+    a.tiles_y = stem_mfma_tiles_y(op);
     a.flags = op.flags;
-    return y3_launch<conv_stem_mfma_kernel<T>>(dim3(a.tiles_x * a.tiles_y * op.batch), dim3(256), 0, s, a);
+    return y3_launch<conv_stem_mfma_kernel<T>>(st.dims, s, a);
   });
 }
 
 int y3_choose_conv_stem_mfma(const y3_op &op, y3_step &st) {
   Y3_REQUIRE(y3_conv_stem_mfma_supported(op), "conv block %d: not a shape for the MFMA stem", op.block_idx);
   st.launch = launch_conv_stem_mfma;
-  st.threads = (long long)y3_ceil_div(op.in_w, kStemTW) * y3_ceil_div(op.in_h, kStemTH) * op.batch * 256;
+  st.dims = {(long long)stem_mfma_tiles_x(op) * stem_mfma_tiles_y(op) * op.batch, 256, 0};
   st.name = op.dtype == Y3_F16 ? "conv_stem_mfma_u8_f16" : "conv_stem_mfma_u8_bf16";
   return Y3_OK;
 }
 
-static int launch_conv_direct(const y3_op *ops, const y3_step &, const void *d_in, const void *, hipStream_t s) {
+static int launch_conv_direct(const y3_op *ops, const y3_step &st, const void *d_in, const void *, hipStream_t s) {
   const y3_op &op = ops[0];
   DirectArgs a;
   a.in = d_in; a.wgt = op.d_weight; a.scale = op.d_scale; a.bias = op.d_bias; a.res = op.d_res;
@@ -343,16 +346,15 @@ static int launch_conv_direct(const y3_op *ops, const y3_step &, const void *d_i
   a.ks = op.ksize; a.stride = op.stride; a.pad = op.pad; a.k_ld = op.k_ld;
   a.total = (long long)op.batch * op.out_h * op.out_w * op.out_c;
   a.flags = op.flags;
-  const dim3 grid((unsigned)((a.total + 255) / 256)), block(256);
   return y3_by_dtype(op.dtype, [&](auto tag) {
-    return y3_launch<conv_direct_kernel<decltype(tag)>>(grid, block, 0, s, a);
+    return y3_launch<conv_direct_kernel<decltype(tag)>>(st.dims, s, a);
   });
 }
 
 int y3_choose_conv_direct(const y3_op &op, y3_step &st) {
   Y3_REQUIRE(op.k_ld >= op.ksize * op.ksize * op.in_c, "conv block %d: k_ld too small", op.block_idx);
   st.launch = launch_conv_direct;
-  st.threads = y3_ceil_div64((long long)op.batch * op.out_h * op.out_w * op.out_c, 256) * 256;   // one thread per output element
+  st.dims = {y3_ceil_div64((long long)op.batch * op.out_h * op.out_w * op.out_c, 256), 256, 0};   // one thread per output element
   st.name = Y3_KNAME(op.dtype, "conv_direct_", "");
   return Y3_OK;
 }

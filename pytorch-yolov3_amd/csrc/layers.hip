@@ -224,7 +224,7 @@ int y3_choose_layer(const y3_op &op, y3_step &st) {
   Y3_REQUIRE(op.in_c == op.out_c, "block %d: channel count changes in a pool/upsample/add/copy op", op.block_idx);
   // one thread per 16-byte chunk or per element of the output (an op that reads the plan's input: its address is not known yet
   // and is taken as aligned; launch_layer checks what it really launches)
-  st.threads = y3_ceil_div64(layer_threads(op, layer_is_wide(op, (op.flags & Y3_F_PLAN_INPUT) ? nullptr : op.d_in)), 256) * 256;
+  st.dims = {y3_ceil_div64(layer_threads(op, layer_is_wide(op, (op.flags & Y3_F_PLAN_INPUT) ? nullptr : op.d_in)), 256), 256, 0};
   st.launch = launch_layer;
   switch (op.kind) {
     case Y3_OP_MAXPOOL:
@@ -314,7 +314,7 @@ __global__ __launch_bounds__(256) void reorg_kernel(ReorgArgs p) {
       static_cast<const U *>(p.in)[(((long long)b * p.H + yi) * p.W + xi) * p.in_ld + ci];
 }
 
-int launch_reorg(const y3_op *ops, const y3_step &, const void *d_in, const void *, hipStream_t s) {
+int launch_reorg(const y3_op *ops, const y3_step &st, const void *d_in, const void *, hipStream_t s) {
   const y3_op &op = ops[0];
   ReorgArgs a;
   a.in = d_in;
@@ -325,11 +325,7 @@ int launch_reorg(const y3_op *ops, const y3_step &, const void *d_in, const void
   a.oc = op.in_c / (op.stride * op.stride);
   a.form3d = (op.flags & Y3_F_REORG_3D) ? 1 : 0;
   a.total = (long long)op.batch * op.out_h * op.out_w * op.out_c;
-  const dim3 grid((unsigned)((a.total + 255) / 256)), block(256);
-  if (y3_elem_size(op.dtype) == 4) Y3_LAUNCH(reorg_kernel<uint32_t>, grid, block, 0, s, a);
-  else Y3_LAUNCH(reorg_kernel<uint16_t>, grid, block, 0, s, a);
-  Y3_HIP_CHECK(hipGetLastError());
-  return Y3_OK;
+  return y3_elem_size(op.dtype) == 4 ? y3_launch<reorg_kernel<uint32_t>>(st.dims, s, a) : y3_launch<reorg_kernel<uint16_t>>(st.dims, s, a);
 }
 
 }  // namespace
@@ -351,7 +347,7 @@ int y3_choose_reorg(const y3_op &op, y3_step &st) {
   Y3_REQUIRE((long long)op.in_c * op.in_h * op.in_w < (1ll << 31), "reorg block %d: a frame of %d x %d x %d elements is too large",
              op.block_idx, op.in_c, op.in_h, op.in_w);
   st.launch = launch_reorg;
-  st.threads = y3_ceil_div64((long long)op.batch * op.out_h * op.out_w * op.out_c, 256) * 256;   // one thread per output element
+  st.dims = {y3_ceil_div64((long long)op.batch * op.out_h * op.out_w * op.out_c, 256), 256, 0};   // one thread per output element
   st.name = (op.flags & Y3_F_REORG_3D) ? Y3_KNAME(op.dtype, "reorg3d_", "") : Y3_KNAME(op.dtype, "reorg_", "");
   return Y3_OK;
 }
@@ -498,14 +494,15 @@ bool y3_choose_maxpool_spp(const y3_op &a, const y3_op &b, const y3_op &c, y3_st
   }
   if (seen != 7 || spp_lds_bytes(a) > 64 * 1024) return false;
   // one workgroup of 256 threads per frame and 32-byte channel group; past the launch limit: three single pools
-  st.threads = (long long)a.batch * (a.in_c * y3_elem_size(a.dtype) / 32) * 256;
-  if (st.threads > kY3MaxThreads) { st.threads = 0; return false; }
+  const long long grid = (long long)a.batch * (a.in_c * y3_elem_size(a.dtype) / 32);
+  if (grid * 256 > kY3MaxThreads) return false;
+  st.dims = {grid, 256, spp_lds_bytes(a)};
   st.launch = launch_maxpool_spp;
   st.name = (a.flags & Y3_F_POOL_DARKNET) ? Y3_KNAME(a.dtype, "maxpool_spp_pyramid_dk_", "") : Y3_KNAME(a.dtype, "maxpool_spp_pyramid_", "");
   return true;
 }
 
-static int launch_maxpool_spp(const y3_op *ops, const y3_step &, const void *, const void *, hipStream_t s) {
+static int launch_maxpool_spp(const y3_op *ops, const y3_step &st, const void *, const void *, hipStream_t s) {
   const y3_op &a = ops[0];
   const y3_op *o[3] = {&ops[0], &ops[1], &ops[2]};
   SppArgs p;
@@ -517,13 +514,9 @@ static int launch_maxpool_spp(const y3_op *ops, const y3_step &, const void *, c
     else if (q->ksize == 9) { p.out9 = static_cast<char *>(q->d_out); p.ld9 = q->out_ld; }
     else { p.out13 = static_cast<char *>(q->d_out); p.ld13 = q->out_ld; }
   }
-  const size_t lds = spp_lds_bytes(a);
-  const dim3 grid((unsigned)(a.batch * p.cgroups)), block(256);
   return y3_by_dtype(a.dtype, [&](auto tag) {
-    if (a.flags & Y3_F_POOL_DARKNET) Y3_LAUNCH((maxpool_spp_kernel<decltype(tag), true>), grid, block, lds, s, p);
-    else Y3_LAUNCH((maxpool_spp_kernel<decltype(tag), false>), grid, block, lds, s, p);
-    Y3_HIP_CHECK(hipGetLastError());
-    return Y3_OK;
+    if (a.flags & Y3_F_POOL_DARKNET) return y3_launch<maxpool_spp_kernel<decltype(tag), true>>(st.dims, s, p);
+    return y3_launch<maxpool_spp_kernel<decltype(tag), false>>(st.dims, s, p);
   });
 }
 

@@ -159,6 +159,8 @@ __global__ __launch_bounds__(LANES == 1 ? 256 : 384) void yolo_decode_kernel(Yol
 }  // namespace
 
 
+using YoloLanes = y3_ints<4, 1>;   // lanes per box
+
 static int launch_yolo(const y3_op *ops, const y3_step &st, const void *d_in, const void *, hipStream_t s) {
   const y3_op &op = ops[0];
   YoloArgs a;
@@ -174,11 +176,8 @@ static int launch_yolo(const y3_op *ops, const y3_step &st, const void *d_in, co
   a.mode = y3_decode_mode(op);
   for (int i = 0; i < 8; ++i) { a.aw[i] = op.anchor_w[i]; a.ah[i] = op.anchor_h[i]; }
   a.total = (long long)op.batch * op.in_h * op.in_w * op.n_anchor;
-  const long long npix = (long long)op.batch * op.in_h * op.in_w;
-  const size_t lds = (size_t)kPix * (op.in_ld + 1) * sizeof(float);
-  const dim3 grid((unsigned)((npix + kPix - 1) / kPix));
-  return y3_ints<4, 1>::pick(st.lanes, [&](auto lanes) {   // lanes per box
-    return y3_launch<yolo_decode_kernel<lanes.value>>(grid, dim3(lanes.value == 1 ? 256 : 384), lds, s, a);
+  return YoloLanes::pick(st.lanes, [&](auto lanes) {
+    return y3_launch<yolo_decode_kernel<lanes.value>>(st.dims, s, a);
   });
 }
 
@@ -190,6 +189,8 @@ int y3_choose_yolo(const y3_op &op, const y3_options &o, y3_step &st) {
   st.name = "yolo_decode_f32";
   // bf16 networks (throughput mode) take the four-lanes-per-box form; float32 networks keep the sequential class loop
   st.lanes = y3_is16(op.dtype) && o.decode_lanes != 1 ? 4 : 1;
-  st.threads = y3_ceil_div64((long long)op.batch * op.in_h * op.in_w, kPix) * (st.lanes == 1 ? 256 : 384);
+  static_assert(YoloLanes::has(4) && YoloLanes::has(1), "both forms are instances");
+  // kPix pixels per workgroup, their logits (one padded row each) in LDS
+  st.dims = {y3_ceil_div64((long long)op.batch * op.in_h * op.in_w, kPix), st.lanes == 1 ? 256 : 384, (size_t)kPix * (op.in_ld + 1) * sizeof(float)};
   return Y3_OK;
 }

@@ -22,10 +22,11 @@ RUN_AHEAD = ("conv1x1_dw_kernel", "conv_dw48_kernel", "conv_halo_dw_kernel")
 
 # Instances no y3_op can reach under any y3_options: {symbol: the chooser condition that excludes it}.  They stay compiled
 # (removing one moves the device code); a later change may delete them from their y3_ints list.
-_HALO_WS_33 = ("conv_halo.hip:1330-1333 (launch_conv_halo) takes three weight slots only when four do not fit: na > 12 or "
-               "4 * 16 KiB + 2 * na * 4 KiB > 160 KiB, i.e. na >= 13.  At 192-pixel tiles (MI = 3) na = ceil((196 + 2 W) / 32) "
-               "(:1322-1323), and conv_halo.hip:1211-1212 (y3_conv_halo_ws_fits, required by y3_choose_conv_halo :1351) admits "
-               "only ceil((260 + 2 W) / 32) <= 14, i.e. W <= 94, where na <= 12: the loop always stops at four slots")
+_HALO_WS_33 = ("conv_halo.hip:1221-1225 (halo_strip_geom, the one place that sizes the ring) takes three weight slots only when four "
+               "do not fit: na > 12 or 4 * 16 KiB + 2 * na * 4 KiB > 160 KiB, i.e. na >= 13.  At 192-pixel tiles (MI = 3) na = "
+               "ceil((196 + 2 W) / 32) (:1210-1211), and conv_halo.hip:1271 (y3_conv_halo_ws_fits, required by y3_choose_conv_halo "
+               ":1366) asks the same function about 256-pixel tiles and so admits only ceil((260 + 2 W) / 32) <= 14, i.e. W <= 94, "
+               "where the 192-pixel tile has na <= 12: the loop always stops at four slots, which the chooser records (:1369-1373)")
 UNREACHABLE = {
     "_ZN12_GLOBAL__N_119conv_halo_ws_kernelIfLi3ELi3EEEvNS_8HaloArgsE": _HALO_WS_33,
     "_ZN12_GLOBAL__N_119conv_halo_ws_kernelIDF16bLi3ELi3EEEvNS_8HaloArgsE": _HALO_WS_33,
