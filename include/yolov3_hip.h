@@ -240,6 +240,7 @@ int y3_abi_version(void);
 #define Y3_CAP_PREPROCESS_DARKNET 512u /* y3_preprocess_darknet_f32            */
 #define Y3_CAP_REORG 1024u     /* Y3_OP_REORG and Y3_F_REORG_3D              */
 #define Y3_CAP_LAUNCH_LOG 2048u /* y3_debug_launch_log_begin, y3_debug_launch_log_end */
+#define Y3_CAP_PLAN_OP_DIMS 4096u /* y3_plan_op_dims and y3_set_tuning("device_cus", n) */
 uint32_t y3_capabilities(void);
 const char *y3_last_error(void);
 /* number of visible HIP devices whose arch is gfx950 (0 on a CPU-only machine) */
@@ -265,6 +266,10 @@ int y3_plan_run_timed(y3_plan *plan, const void *d_input, void *stream, float *m
 int y3_plan_run_profiled(y3_plan *plan, const void *d_input, void *stream, float *kernel_ms_per_op);
 /* name of the kernel an op dispatches to, e.g. "conv_igemm_bf16_128x128" (static string)     */
 const char *y3_plan_op_kernel(const y3_plan *plan, int op_index);
+/* the launch an op's step recorded when the plan was created: out[0] workgroups, out[1] threads per workgroup, out[2] bytes of
+ * dynamic LDS; three zeros for an op that an earlier step launches (a fused group's second op, the SPP pyramid's second and
+ * third pool).  Tests and tools: the launchers launch exactly these.                                                   */
+int y3_plan_op_dims(const y3_plan *plan, int op_index, int64_t out[3]);
 /* algorithmic FLOPs (2*k*k*Cin*Cout*Hout*Wout*B for convs, else 0) and compulsory bytes      */
 double y3_plan_op_flops(const y3_plan *plan, int op_index);
 double y3_plan_op_bytes(const y3_plan *plan, int op_index);
@@ -287,7 +292,12 @@ int y3_conv_make_fragment_weights(const y3_op *op, void *d_dst, void *stream);
 /* A/B measurements only (tools/conv_bench.py, bench.py --tuning): changes ONE field of the process-wide DEFAULT
  * options by name ("auto_mask", "igemm_version", "igemm_ns", "igemm_bm", "use_graph", "fuse_stem",
  * "fuse_head", "fuse_spp", "decode_lanes", "fuse_block").  Plans created afterwards without explicit options pick it up; existing
- * plans keep the options they were created with.                                                                  */
+ * plans keep the options they were created with.
+ * One key is no option field: "device_cus".  0 [default] asks the device for its compute-unit count, as ever; 1 .. 4096 is the
+ * count every chooser gets instead, for every device, until it is set back to 0 (any other value: Y3_ERR_INVALID).  The count
+ * sizes persistent grids, picks tile shapes and moves ops between kernels, all at plan creation: a plan keeps what it was
+ * created with.  It is how the tests make, on an unpartitioned MI355X, the plans that a DPX / QPX / CPX compute partition
+ * (128 / 64 / 32 CUs) gets; a grid of 32 workgroups computes the same values on either.  Not a speed knob.            */
 int y3_set_tuning(const char *key, int value);
 
 /* Launch log (tests and tools only; host code, the kernels are the same): between the two calls every kernel the CALLING

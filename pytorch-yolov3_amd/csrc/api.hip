@@ -52,8 +52,13 @@ int y3_debug_flags() { return g_y3_debug; }
 int y3_debug_flags() { return 0; }
 #endif
 
+// y3_set_tuning("device_cus", n): 0 asks the device; 1 .. 4096 is the count every chooser gets for every device (the plans of a
+// compute partition of 128, 64 or 32 CUs, made and run on an unpartitioned device).  Read here and nowhere else.
+static std::atomic<int> g_y3_device_cus{0};
 // CU count of the current device (256 on an MI355X; 256 as well when no device is visible: dry runs on a CPU box)
 int y3_device_cus() {
+  const int forced = g_y3_device_cus.load(std::memory_order_relaxed);
+  if (forced > 0) return forced;
   static std::atomic<int> cus[32];                 // (zero-initialised; concurrent first calls store the same value)
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 32) { (void)hipGetLastError(); return 256; }
@@ -304,7 +309,7 @@ int y3_abi_version(void) { return Y3_ABI_VERSION; }
 uint32_t y3_capabilities(void) {
   return Y3_CAP_MISH | Y3_CAP_SCALE_X_Y | Y3_CAP_LOGISTIC | Y3_CAP_NEW_COORDS | Y3_CAP_LETTERBOX | Y3_CAP_POOL_DARKNET |
          Y3_CAP_NMS_DARKNET | Y3_CAP_SCORES_DARKNET | Y3_CAP_MULTI_LABEL | Y3_CAP_PREPROCESS_DARKNET | Y3_CAP_REORG |
-         Y3_CAP_LAUNCH_LOG;
+         Y3_CAP_LAUNCH_LOG | Y3_CAP_PLAN_OP_DIMS;
 }
 
 int y3_debug_launch_log_begin(void) {
@@ -553,6 +558,16 @@ const char *y3_plan_op_kernel(const y3_plan *plan, int op_index) {
   return plan->steps[op_index].name;
 }
 
+int y3_plan_op_dims(const y3_plan *plan, int op_index, int64_t out[3]) {
+  Y3_REQUIRE(plan && out && op_index >= 0 && (size_t)op_index < plan->ops.size(), "y3_plan_op_dims: bad arguments");
+  const y3_step &st = plan->steps[op_index];
+  const bool launched = st.fuse != y3_fuse::into_prev;
+  out[0] = launched ? (int64_t)st.dims.grid : 0;
+  out[1] = launched ? (int64_t)st.dims.block : 0;
+  out[2] = launched ? (int64_t)st.dims.lds : 0;
+  return Y3_OK;
+}
+
 double y3_plan_op_flops(const y3_plan *plan, int op_index) {
   if (!plan || op_index < 0 || (size_t)op_index >= plan->ops.size()) return 0.0;
   auto conv_flops = [](const y3_op &o) {
@@ -620,6 +635,11 @@ int y3_set_tuning(const char *key, int value) {
       {"fuse_block", &g_y3_defaults.fuse_block}};
   for (auto &f : fields)
     if (!strcmp(key, f.name)) { *f.field = value; return Y3_OK; }
+  if (!strcmp(key, "device_cus")) {
+    Y3_REQUIRE(value >= 0 && value <= 4096, "y3_set_tuning: device_cus %d (0 asks the device; 1 .. 4096 is the count to plan for)", value);
+    g_y3_device_cus.store(value, std::memory_order_relaxed);
+    return Y3_OK;
+  }
 #ifdef Y3_HAS_DEBUG_KEY
   if (!strcmp(key, "debug")) { g_y3_debug = value; return Y3_OK; }
 #endif

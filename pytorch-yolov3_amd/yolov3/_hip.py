@@ -39,6 +39,7 @@ F_MISH, F_LOGISTIC, F_NEW_COORDS, F_POOL_DARKNET, F_SCORES_DARKNET, F_REORG_3D =
 CAP_MISH, CAP_SCALE_X_Y, CAP_LOGISTIC, CAP_NEW_COORDS, CAP_LETTERBOX, CAP_POOL_DARKNET = 1, 2, 4, 8, 16, 32
 CAP_NMS_DARKNET, CAP_SCORES_DARKNET, CAP_MULTI_LABEL, CAP_PREPROCESS_DARKNET, CAP_REORG = 64, 128, 256, 512, 1024
 CAP_LAUNCH_LOG = 2048
+CAP_PLAN_OP_DIMS = 4096
 # Darknet's suppression measures (include/yolov3_hip.h: Y3_NMS_*), by the cfg's spelling of `nms_kind`
 NMS_IOU, NMS_GREEDY, NMS_DIOU = 0, 1, 2
 NMS_KINDS = {"iou": NMS_IOU, "greedynms": NMS_GREEDY, "diounms": NMS_DIOU}
@@ -126,6 +127,7 @@ PROTOTYPES = {
     "y3_plan_run_profiled": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                             ctypes.POINTER(ctypes.c_float)]),
     "y3_plan_op_kernel": (ctypes.c_char_p, [ctypes.c_void_p, ctypes.c_int]),
+    "y3_plan_op_dims": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int64)]),
     "y3_plan_op_flops": (ctypes.c_double, [ctypes.c_void_p, ctypes.c_int]),
     "y3_plan_op_bytes": (ctypes.c_double, [ctypes.c_void_p, ctypes.c_int]),
     "y3_conv_path": (ctypes.c_int, [ctypes.POINTER(Y3Op)]),
@@ -188,7 +190,7 @@ PROTOTYPES = {
 _OPTIONAL = ("y3_capabilities", "y3_detect_letterbox", "y3_letterbox_geometry", "y3_letterbox_u8",
              "y3_detect_darknet_workspace_bytes", "y3_detect_darknet", "y3_nms_darknet_workspace_bytes", "y3_nms_darknet",
              "y3_expand_labels_workspace_bytes", "y3_expand_labels", "y3_preprocess_darknet_f32",
-             "y3_debug_launch_log_begin", "y3_debug_launch_log_end")
+             "y3_debug_launch_log_begin", "y3_debug_launch_log_end", "y3_plan_op_dims")
 
 
 class HipLibraryError(RuntimeError):
@@ -310,6 +312,35 @@ class launch_log:
         if exc[0] is None:
             check(rc)
         return False
+
+
+class device_cus:
+    """``with device_cus(n):`` every plan created inside the block is made for a device of ``n`` compute units
+    (``y3_set_tuning("device_cus", n)``: the plans a DPX / QPX / CPX compute partition of 128 / 64 / 32 CUs gets), whatever the
+    device reports; the key is back at 0 -- ask the device -- when the block ends, an exception included.  A plan keeps what it
+    was created with; ``Darknet`` caches plans by shape, so a network built outside the block is not re-planned inside it.
+    Tests and tools only."""
+
+    def __init__(self, n):
+        self.n = int(n)
+
+    def __enter__(self):
+        if not capabilities() & CAP_PLAN_OP_DIMS:
+            raise HipLibraryError("the loaded libyolov3_hip.so has no device_cus key (rebuild: make -C pytorch-yolov3_amd/csrc)")
+        check(lib().y3_set_tuning(b"device_cus", self.n))
+        return self
+
+    def __exit__(self, *exc):
+        lib().y3_set_tuning(b"device_cus", 0)
+        return False
+
+
+def plan_op_dims(handle, op_index):
+    """(workgroups, threads per workgroup, dynamic LDS bytes) that op ``op_index`` of plan ``handle`` launches, as recorded at plan
+    creation; (0, 0, 0) for an op that an earlier step launches."""
+    out = (ctypes.c_int64 * 3)()
+    check(lib().y3_plan_op_dims(handle, op_index, out))
+    return int(out[0]), int(out[1]), int(out[2])
 
 
 def options(**overrides):

@@ -215,6 +215,15 @@ def _opts():
         default={},
         stem_phased=dict(fuse_stem=2),
         fuse_block=dict(fuse_block=2),
+        # the sets under which a chooser rule that reads the CU count decides (tests/cu_count_util.py ONE_OP_ROWS): the fused block only
+        # where its rectangles fill 70 % of the chip, the direct-weights strip kernel only where its cost model says it pays, the
+        # small-grid kernel with the wave count and the grid limits its chooser picks, the default set without that kernel (the small-grid rule of
+        # the 3x3 layers), the deep-1x1 rule alone
+        fuse_block1=dict(fuse_block=1),
+        halo_dw_pays=dict(auto_mask=halo | H.AM_HALO_DW),
+        dw48_auto=dict(auto_mask=H.AM_SMALL_DW | H.AM_SMALL_DW_WIDE),
+        no_small_dw=dict(auto_mask=H.AM_DEFAULT & ~(H.AM_SMALL_DW | H.AM_SMALL_DW_WIDE)),
+        deep_1x1=dict(auto_mask=H.AM_IGEMM3_1X1_DEEP),
         head_tiled=dict(fuse_head=2),
         head48=dict(fuse_head=3),
         head96=dict(fuse_head=4),
@@ -328,6 +337,9 @@ def cases():
         _conv("halo_dw_full", "conv_halo_dw_%s_192x256", "halo_dw", B16, 2, 24, 16, 128, 256, 3, 1, res=True),
         _conv("halo_dw_ragged", "conv_halo_dw_%s_192x256", "halo_dw", B16, 3, 19, 13, 256, 512, 3, 1),
         _conv("halo_dw_ragged_res", "conv_halo_dw_%s_192x256", "halo_dw", B16, 2, 38, 26, 128, 256, 3, 1, res=True),
+        # 13 tiles of 192 pixels x 2 channel tiles: one round on 32 CUs, where 10 tiles of 256 x 4 of the wave-specialised kernel are
+        # two -- the shape at which y3_conv_halo_dw_pays decides by the CU count (tests/cu_count_util.py: option set halo_dw_pays)
+        _conv("halo_dw_ragged_29x27", "conv_halo_dw_%s_192x256", "halo_dw", B16, 3, 29, 27, 256, 512, 3, 1),
         # instances: five halo passes per chunk (rows of 31 .. 62 px) and six (63 .. 94); the rows above have four
         _conv("halo_dw_na5_w38", "conv_halo_dw_%s_192x256", "halo_dw", B16, 1, 19, 38, 128, 256, 3, 1, res=True),
         _conv("halo_dw_na6_w76", "conv_halo_dw_%s_192x256", "halo_dw", B16, 1, 13, 76, 128, 256, 3, 1),
@@ -336,11 +348,18 @@ def cases():
         _conv("patch_full", "conv_patch_wsp_%s_8x32x128", "patch", ALL, 1, 16, 160, 64, 128, 3, 1, res=True, out_unit=8),
         _conv("patch_ragged", "conv_patch_wsp_%s_8x32x128", "patch", ALL, 2, 13, 139, 64, 128, 3, 1, out_unit=8),
         _conv("patch_ragged_res", "conv_patch_wsp_%s_8x32x128", "patch", ALL, 1, 21, 150, 64, 256, 3, 1, res=True, out_unit=8),
+        # 6 x 4 tiles x 2 frames x 2 channel tiles = 96 tiles: on 20 CUs a workgroup owns 5 or 4 of them, in two frames and both channel tiles
+        _conv("patch_strided_tiles", "conv_patch_wsp_%s_8x32x128", "patch", ALL, 2, 29, 161, 64, 256, 3, 1, res=True, out_unit=8),
         # ---- 1x1 kernels (conv_1x1.hip): weights-resident persistent (128-pixel tiles), direct-weights (48 / 96 pixels)
         _conv("wres_128_full", "conv1x1_wres_%s_128x128", "wres", B16, 2, 16, 16, 256, 128, 1, 1),
         _conv("wres_128_ragged", "conv1x1_wres_%s_128x128", "wres", B16, 3, 19, 13, 256, 128, 1, 1),
         _conv("wres_64_full", "conv1x1_wres_%s_128x64", "wres", B16, 2, 16, 16, 128, 64, 1, 1),
         _conv("wres_64_ragged", "conv1x1_wres_%s_128x64", "wres", B16, 3, 21, 17, 128, 64, 1, 1),
+        # persistent grids whose workgroups own SEVERAL tiles each, and unequal numbers of them, on a device of 20 CUs
+        # (tests/cu_count_util.py; on 256 CUs the rows above and these give every workgroup one tile): 40 pixel tiles x 3 channel
+        # tiles on 18 workgroups, six per channel tile -- 20 is no multiple of 3 -- which stream 7 or 6 pixel tiles each
+        _conv("wres_128_strided_tiles", "conv1x1_wres_%s_128x128", "wres", B16, 3, 39, 43, 256, 384, 1, 1),
+        _conv("wres_64_strided_tiles", "conv1x1_wres_%s_128x64", "wres", B16, 3, 39, 43, 128, 192, 1, 1),
         # (the direct-weights kernel takes grids of one round only: 96-pixel tiles from 192 tiles on, 48-pixel tiles for 64 ..
         # 191 -- conv_1x1.hip dw1x1_bm -- hence the batches)
         _conv("dw1x1_96_full", "conv1x1_dw_%s_96x256", "dw1x1", B16, 16, 36, 32, 512, 256, 1, 1),
@@ -408,12 +427,20 @@ def cases():
         # instance: the phase-by-phase form of the fused stem pair (fuse_stem = 2), one name with the pipelined form
         dict(id="stem_s2_phased_full", group="stem_pair", family="conv_stem_s2_fused_u8_%s", opt="stem_phased", dtypes=B16, B=2, h=64, w=64),
         dict(id="stem_s2_phased_ragged", group="stem_pair", family="conv_stem_s2_fused_u8_%s", opt="stem_phased", dtypes=B16, B=3, h=45, w=37),
+        # 3 x 5 tiles of 16 x 8 (pipelined) / 3 x 3 of 16 x 16 (phased, and the residual block) x 5 frames = 75 / 45 tiles: on 20 CUs a
+        # workgroup owns 4 or 3 / 3 or 2 of them; on one CU one workgroup owns them all (tests/cu_count_util.py)
+        dict(id="stem_s2_strided_tiles", group="stem_pair", family="conv_stem_s2_fused_u8_%s", opt="default", dtypes=B16, B=5, h=74, w=70),
+        dict(id="stem_s2_phased_strided_tiles", group="stem_pair", family="conv_stem_s2_fused_u8_%s", opt="stem_phased", dtypes=B16, B=5, h=74, w=70),
+        dict(id="resblock_strided_tiles", group="resblock", family="conv_resblock_fused_%s_64_32_64", opt="default", dtypes=B16, B=5, h=45, w=37),
         # the shortcut operand of the fused residual block IS the group's input (always: the chooser requires it)
         dict(id="resblock_full", group="resblock", family="conv_resblock_fused_%s_64_32_64", opt="default", dtypes=B16, B=2, h=32, w=32),
         dict(id="resblock_ragged", group="resblock", family="conv_resblock_fused_%s_64_32_64", opt="default", dtypes=B16, B=3, h=29, w=21),
         dict(id="block_full_res", group="block", family="conv_block_fused_%s_x128", opt="fuse_block", dtypes=B16, B=2, h=32, w=32, cin=256, cout=256, res=True),
         dict(id="block_ragged_res", group="block", family="conv_block_fused_%s_x128", opt="fuse_block", dtypes=B16, B=3, h=19, w=13, cin=256, cout=256, res=True),
         dict(id="block_ragged_nores", group="block", family="conv_block_fused_%s_x128", opt="fuse_block", dtypes=B16, B=2, h=21, w=17, cin=192, cout=128, res=False),
+        # a 19 x 19 map is ONE rectangle of 361 of the 384 pixels a workgroup takes: on one CU three frames fill 94 % of three rounds,
+        # which passes the 70 % rule of fuse_block = 1 (tests/cu_count_util.py); on 256 CUs they fill 1 % of one
+        dict(id="block_19x19_res", group="block", family="conv_block_fused_%s_x128", opt="fuse_block", dtypes=B16, B=3, h=19, w=19, cin=256, cout=256, res=True),
         dict(id="head_tiled_full", group="head", family="conv_head_decode_%s_64x256", opt="head_tiled", dtypes=B16, B=2, h=16, w=16, cin=256),
         dict(id="head_tiled_ragged", group="head", family="conv_head_decode_%s_64x256", opt="head_tiled", dtypes=B16, B=3, h=13, w=11, cin=192),
         dict(id="head48_full", group="head", family="conv_head_decode_dw_%s_48x256", opt="head48", dtypes=B16, B=2, h=12, w=12, cin=256),
@@ -1126,16 +1153,75 @@ def nan_violations(t, n_frames, fmt, chunk=CHUNK):
     return None
 
 
-def launch_threads(case, dtype, B):
-    """grid x block of the launch of ``case`` at batch ``B``, restated from the launchers of csrc/*.hip (None: a persistent grid of
-    about one workgroup per CU, or the fused block, which its 2^32-byte rule bounds first).  A launch holds fewer than 2^32
-    threads: MAX_THREADS (csrc/api.hip check_launch)."""
+def block_tile(H, W):
+    """(tile width, tile height) of the fused bottleneck block on an H x W map, restated from csrc/conv_block.hip choose_tile: widths
+    8 .. 24, the tallest rectangle of at most 384 pixels whose one-pixel border fits 448 halo rows, no taller than its number of tile
+    rows needs; of those the one with the fewest tiles, the narrowest first.  The chooser ranks by ROUNDS of workgroups over the CU
+    count before it ranks by tiles; rounds never fall as tiles rise, so the count cannot change the pick (it enters the 70 % rule of
+    fuse_block = 1 only): tests/test_cu_count_host.py holds the library to that."""
+    cd = lambda a, b: -(-a // b)
+    best = None
+    for tw in range(8, 25):
+        th = 384 // tw
+        while th > 0 and (tw + 2) * (th + 2) > 448:
+            th -= 1
+        th = min(th, H)
+        if tw > W or th < 4:
+            continue
+        rows = cd(H, th)
+        th = cd(H, rows)
+        tiles = cd(W, tw) * rows
+        if best is None or tiles < best[0]:
+            best = (tiles, tw, th)
+    return None if best is None else best[1:]
+
+
+def persistent_grid(case, op, B, n_cu):
+    """workgroups of the four families with a persistent grid on a device of ``n_cu`` CUs, and of the fused block (one workgroup a
+    rectangle), restated from the op's fields (csrc/conv_1x1.hip wres_geom, csrc/conv_halo.hip patch_geom, csrc/conv_fused.hip
+    fused_geom, csrc/conv_block.hip block_geom); None for another family"""
+    cd = lambda a, b: -(-a // b)
+    fam = case["family"].split("_%s")[0]
+    if fam == "conv1x1_wres":
+        # a whole number of workgroups per channel tile, about one per CU, at least one per channel tile, at most one per tile
+        bn = int(case["family"].rsplit("x", 1)[1])
+        n_tiles, m_tiles = op.out_c // bn, cd(B * op.in_h * op.in_w, 128)
+        per_tile = max(1, n_cu // n_tiles)
+        return n_tiles * min(per_tile, m_tiles)
+    if fam == "conv_patch_wsp":
+        return min(n_cu, cd(op.in_w, 32) * cd(op.in_h, 8) * B * (op.out_c // 128))
+    if fam == "conv_stem_s2_fused_u8":
+        # the OUTPUT map of the pair's stride-2 conv in tiles of 16 x 8 (the pipelined kernel) or 16 x 16 (phase by phase)
+        ho, wo = (op.in_h + 2 - 3) // 2 + 1, (op.in_w + 2 - 3) // 2 + 1
+        return min(n_cu, cd(wo, 16) * cd(ho, 16 if case["opt"] == "stem_phased" else 8) * B)
+    if fam == "conv_resblock_fused":
+        return min(n_cu, cd(op.in_w, 16) * cd(op.in_h, 16) * B)
+    if fam == "conv_block_fused":
+        tw, th = block_tile(op.in_h, op.in_w)
+        return cd(op.in_w, tw) * cd(op.in_h, th) * B      # (one workgroup a rectangle: no persistent grid, the count picks nothing)
+    return None
+
+
+PERSISTENT_BLOCK = {"conv1x1_wres": 512, "conv_patch_wsp": 768, "conv_stem_s2_fused_u8": 1024, "conv_resblock_fused": 512,
+                    "conv_block_fused": 512}
+
+
+def launch_threads(case, dtype, B, n_cu=None):
+    """grid x block of the launch of ``case`` at batch ``B``, restated from the launchers of csrc/*.hip.  Five families give None
+    without ``n_cu`` -- four persistent grids of about one workgroup per CU, and the fused block, which its 2^32-byte rule bounds first
+    --; with it, their launch on a device of that many CUs (persistent_grid).  A launch holds fewer than 2^32 threads: MAX_THREADS
+    (csrc/api.hip check_launch)."""
     H = _H()
     ops, _, _, _ = build(dict(case, B=3), dtype, "strided", H.options(**_opts()[case["opt"]]))
     op = ops[0]
     cd = lambda a, b: -(-a // b)
     P, Po, es = B * op.in_h * op.in_w, B * op.out_h * op.out_w, ES[dtype]
     fam, cout = case["family"], op.out_c
+    if n_cu is not None and fam.split("_%s")[0] in PERSISTENT_BLOCK:
+        block = PERSISTENT_BLOCK[fam.split("_%s")[0]]
+        if fam.startswith("conv_stem_s2") and case["opt"] == "stem_phased":
+            block = 512
+        return persistent_grid(case, op, B, n_cu) * block
     if fam.startswith("conv_igemm"):                    # conv_igemm.hip launch_cfg / 2 / 3: 256 threads a tile, version 3 512
         bm, bn = (int(x) for x in fam.rsplit("_", 1)[1].split("x"))
         return cd(Po, bm) * cd(cout, bn) * (512 if fam.startswith("conv_igemm3") else 256)
