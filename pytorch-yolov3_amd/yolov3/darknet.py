@@ -561,7 +561,9 @@ class Darknet(object):
     def _get_plan(self, batch, height, width, input_mode, slot=0, options=None):
         # `slot` selects an independent arena + output buffers (one per in-flight batch when the caller
         # pipelines batches over several HIP streams); `options` (a dict, see __init__) override the network's
-        # plan options for this plan only (yolov3/pipeline.py asks for the throughput tile choice)
+        # plan options for this plan only (yolov3/pipeline.py asks for the throughput tile choice).  Any hashable `slot` names a
+        # plan: whole numbers belong to forward_frames' callers (0: inference(), on the caller's stream), pipeline.plan_slot(k)
+        # to the pipelines, which run theirs on streams of their own
         okey = tuple(sorted(options.items())) if options else None
         key = (batch, height, width, input_mode, self.dtype, str(self.device), slot, okey)
         cp = self._plans.get(key)

@@ -31,6 +31,14 @@ from .inference import Detector, raise_label_overflow
 # streams (a second Pipeline with four streams of its own cost the first one 15 % -- and yolov3-tiny, whose kernels are short,
 # 20 %: profiles/r04m_pipeline_depth.txt).  Pipelines that are active at the same time then share streams: still correct
 # (everything is ordered by streams and events), just not concurrent with each other.
+#
+# The invariant that makes it correct: plan slot k of a network (its arena and its bbox / prob / cls buffers, ``plan_slot``
+# below) runs on compute stream k of the network's device and on no other stream, whichever Pipeline launches it.  Two Pipelines
+# of one network and one batch shape -- ``stream.detect_in_frames`` builds a second one while the cached one is busy -- ask
+# ``Darknet._get_plan`` for the same slots and so share those plans; the pool hands both the same stream objects in the same
+# order, and the one stream orders their forwards and detection tails.  A pool that made fresh streams per Pipeline, or dealt
+# them in another order, would put two unordered streams on one arena (tests/test_gpu_frame_loop.py:
+# test_two_generators_interleaved_on_one_network asserts the stream identity).
 _STREAMS = {}
 
 
@@ -43,6 +51,15 @@ def _device_streams(dev, n_compute, want_side):
     if want_side and pool["side"] is None:
         pool["side"] = torch.cuda.Stream(device=dev)
     return pool["compute"][:n_compute], pool["copy"], pool["side"] if want_side else None
+
+
+def plan_slot(k):
+    """The ``slot`` under which a Pipeline asks ``Darknet._get_plan`` / ``forward_frames`` for the plan of its stream k: a
+    namespace of its own.  ``inference()`` and ``forward_frames()`` run slot 0 (and callers of ``forward_frames(slot=...)``
+    whole numbers) on the CALLER's current stream; a pipeline plan under one of those keys would share its arena and output
+    buffers with a stream nothing orders it against (with ``in_flight=1`` and no options it used to be ``inference()``'s own
+    plan).  The plan options are part of the key as well, but are not what keeps the two apart."""
+    return ("pipeline", int(k))
 
 
 class Pipeline(object):
@@ -106,8 +123,9 @@ class Pipeline(object):
             distributed = world > 1 or (torch.distributed.is_available() and torch.distributed.is_initialized())
             # one side stream for all gathers of this rank: every HIP stream needs a hardware queue of its own to overlap
             self.streams, self.copy_stream, side = _device_streams(dev, self.in_flight, distributed)
-            plans = [net._get_plan(self.batch, self.height, self.width, "u8", slot=k, options=self.options)
-                     for k in range(self.in_flight)]
+            self._slots = [plan_slot(k) for k in range(self.in_flight)]
+            self.plans = plans = [net._get_plan(self.batch, self.height, self.width, "u8", slot=slot, options=self.options)
+                                  for slot in self._slots]
             self.rows = plans[0].rows_total
             self.max_open = 2 * self.in_flight
             # multi-label networks: the detection tail works on `label_capacity` candidates per frame, made from the head
@@ -231,7 +249,7 @@ class Pipeline(object):
                 fr = self.dev_frames[j]
             if tuple(fr.shape) != (self.batch, self.height, self.width, 3):
                 raise ValueError("device frames must be ({}, {}, {}, 3) uint8".format(self.batch, self.height, self.width))
-            out = self.net.forward_frames(fr, fresh=False, slot=k, options=self.options)
+            out = self.net.forward_frames(fr, fresh=False, slot=self._slots[k], options=self.options)
             if j is not None:
                 self.free_ev[j].record(cur)
             det = self.dets[d]

@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from . import _hip
-from .preprocess import letterbox_frames_device, prepare_frames_device
+from .preprocess import letterbox_frames_device, prepare_frames_device, reference_dsize
 
 IMAGE_EXTENSIONS = (".jpg", ".jpeg", ".png", ".bmp", ".ppm", ".webp", ".tif", ".tiff")
 
@@ -64,19 +64,44 @@ def _batches(frames, batch_size):
         yield batch
 
 
+def _frames_on_device(frames, height, width, dev, stream, resize, letterbox, letterbox_fill):
+    """The frames of one batch as a uint8 (B, h, w, 3) device tensor, prepared on ``stream``: uploaded (host frames) or copied
+    (device frames) one by one and resized, or letterboxed with one launch.  Returns (batch, original shapes)."""
+    with torch.cuda.device(dev):
+        if any(isinstance(f, torch.Tensor) and f.is_cuda for f in frames):
+            stream.wait_stream(torch.cuda.current_stream())   # whatever the caller's stream still writes into its frames
+        with torch.cuda.stream(stream):
+            if letterbox:
+                return letterbox_frames_device(frames, height, width, dev, letterbox_fill)
+            return prepare_frames_device(frames, height, width, dev, resize)
+
+
 def detect_in_frames(net, frames, batch_size=16, prob_thresh=0.05, nms_iou_thresh=0.3, resize=True,
                      in_flight=3, kmax=512, letterbox=False, letterbox_fill=128, nms_kind=None, beta_nms=0.6,
                      label_capacity=None, preprocess=None):
     """Generator over ``[bbox_tlbr, class_prob, class_idx]`` for every frame of the iterable
-    ``frames`` (HxWx3 uint8 BGR arrays; sizes may differ when ``resize``), in order.
+    ``frames`` (HxWx3 uint8 BGR frames; sizes may differ when ``resize``), in order.  A frame is a numpy array, a torch
+    tensor in host memory or a torch tensor on the network's device.
 
     The frames run through :class:`yolov3.pipeline.Pipeline` -- the loop ``bench.py`` times -- in batches of
     ``batch_size`` with ``in_flight`` batches on their own HIP streams: a batch's detections are taken only when its
     slot is needed again (or at the end), so decoding / uploading batch k+1 overlaps the kernels of batch k.
-    Net-sized frames are stacked straight into one of the pipeline's pinned host buffers and uploaded from there;
-    other sizes are uploaded one by one and resized on the GPU.  ``frames`` may also yield whole (B, H, W, 3) batches
-    of net-sized frames: a pinned torch tensor is then uploaded from where it lies (no host copy at all), which is how
-    a decoder that fills ``Pipeline.host_frames`` reaches the benchmark's rate.
+    Net-sized host frames are stacked straight into one of the pipeline's pinned host buffers and uploaded from there;
+    other sizes are uploaded one by one and resized on the GPU, and a batch with a device frame in it is put together on the
+    GPU whatever its sizes.  ``frames`` may also yield whole (B, H, W, 3) batches of net-sized frames (numpy, host tensor or
+    device tensor; the last one may be short): a pinned torch tensor is then uploaded from where it lies (no host copy at
+    all), which is how a decoder that fills ``Pipeline.host_frames`` reaches the benchmark's rate, and a device tensor is
+    read where it lies.
+
+    ``resize=False`` takes net-sized frames only.  ``inference(resize=False)`` runs a frame of another size through a plan of
+    that size; this loop keeps its pipelines at the network's size, so the first frame of any other size is refused with a
+    ValueError that names both sizes, before anything of it is uploaded.
+
+    Results equal per-frame ``inference()`` with the same arguments.  That includes its choice of input size: like the
+    reference it hands ``cv2.resize`` the pair (height, width) where OpenCV reads (width, height), so a network that is not
+    square sees the frames it resizes (not the net-sized ones) transposed, width x height (``preprocess.reference_dsize``).
+    Batches of such frames run on a second pipeline of that size; ``letterbox=True`` has no such quirk.  ``inference()`` may be
+    called on the same network while a generator is open: pipelines compile plans of their own.
 
     ``letterbox=True`` letterboxes the frames that are not net-sized (one ``y3_letterbox_u8`` launch per batch, fill
     byte ``letterbox_fill``) instead of stretching them, and corrects their boxes back; net-sized frames take the pinned
@@ -127,62 +152,83 @@ def detect_in_frames(net, frames, batch_size=16, prob_thresh=0.05, nms_iou_thres
         net.cuda()
     dev = net._torch_device()
     height, width = net.net_info["height"], net.net_info["width"]
-    state = {"pipe": None, "keep": {}, "filled": 0}
+    # by the (rows, columns) the batches enter the network with: the network's own size and, where the network is not square,
+    # the transposed size its stretched frames come out with (preprocess.reference_dsize), each with a pipeline of its own
+    state = {"pipes": {}, "keep": {}, "filled": {}}
 
-    def pipeline(batch):
+    def pipeline(batch, size):
         # Pipelines are kept on the network (streams, pinned and device buffers, detector workspaces: ~50 ms to set up, half a
         # second of video at the rate they run at) and handed to one generator at a time
-        if state["pipe"] is None:
+        if size not in state["pipes"]:
             cache = net.__dict__.setdefault("_pipelines", {})
-            key = (batch, height, width, in_flight, kmax, str(net.device), net.dtype, label_capacity)
+            key = (batch, size[0], size[1], in_flight, kmax, str(net.device), net.dtype, label_capacity)
             pipe = cache.get(key)
             if pipe is None or pipe.busy:
-                pipe = Pipeline(net, batch, height, width, in_flight=in_flight, kmax=kmax, label_capacity=label_capacity)
+                pipe = Pipeline(net, batch, size[0], size[1], in_flight=in_flight, kmax=kmax, label_capacity=label_capacity)
                 if key not in cache or not cache[key].busy:
                     cache[key] = pipe
             pipe.busy = True
             pipe.prob_thresh, pipe.nms_iou_thresh = float(np.float32(prob_thresh)), float(nms_iou_thresh)
             pipe.nms_kind, pipe.beta_nms = nms_kind, beta_nms
-            state["pipe"] = pipe
-        return state["pipe"]
+            state["pipes"][size] = pipe
+            state["filled"][size] = 0
+        return state["pipes"][size]
+
+    def on_device(f):
+        return isinstance(f, torch.Tensor) and f.is_cuda
 
     def submit(batch):
-        """batch: list of frames, or one (B, H, W, 3) array / tensor.  Returns the ticket."""
+        """batch: list of frames, or one (B, H, W, 3) array / tensor.  Returns (pipeline, ticket)."""
         whole = not isinstance(batch, list)
         n = int(batch.shape[0]) if whole else len(batch)
-        pipe = pipeline(n)
+        if whole and tuple(batch.shape[1:]) != (height, width, 3):
+            raise ValueError("whole batches must be net-sized: (B, {}, {}, 3)".format(height, width))
+        net_sized = whole or all(tuple(f.shape[:2]) == (height, width) for f in batch)
+        size = (height, width) if net_sized or letterbox else tuple(reference_dsize(height, width))
+        pipe = pipeline(n, size)
         if n > pipe.batch:
             raise ValueError("a batch of {} frames after the pipeline was sized for {}".format(n, pipe.batch))
         if whole:
-            if tuple(batch.shape[1:]) != (height, width, 3):
-                raise ValueError("whole batches must be net-sized: (B, {}, {}, 3)".format(height, width))
             if n == pipe.batch:
-                return pipe.submit(batch, n_frames=n)
-            batch = list(batch)                               # a short last batch: through the staging path below
-        if all(tuple(f.shape[:2]) == (height, width) for f in batch):
-            j = state["filled"] % pipe.nbuf
-            state["filled"] += 1
+                if on_device(batch):
+                    # read where it lies, on the batch's stream: after what the caller's stream still writes into it, and kept
+                    # until the ticket's buffers are reused (its memory must not go to another tensor before the forward ran)
+                    stream, slot = pipe.next_slot()
+                    with torch.cuda.device(dev):
+                        stream.wait_stream(torch.cuda.current_stream())
+                    state["keep"][size, slot] = batch
+                return pipe, pipe.submit(batch, n_frames=n)
+            batch = list(batch)                               # a short last batch: through the staging paths below
+        if net_sized and not any(on_device(f) for f in batch):
+            j = state["filled"][size] % pipe.nbuf             # (this call's count of pinned batches, not the ticket: batches
+            state["filled"][size] += 1                        # that take the device path below use no pinned buffer)
             pipe.upload_done(j)                               # the upload that last read this pinned buffer is over
             host = pipe.host_frames(j).numpy()
             for i, f in enumerate(batch):
                 host[i] = f.numpy() if isinstance(f, torch.Tensor) else f
-            return pipe.submit(pipe.host_frames(j), n_frames=n)
+            return pipe, pipe.submit(pipe.host_frames(j), n_frames=n)
         # frames of other sizes: uploaded one by one and resized (or letterboxed, the whole batch in one launch) on the GPU,
-        # on the stream the pipeline will run the batch on
+        # on the stream the pipeline will run the batch on; device frames, net-sized or not, are copied there the same way
         stream, slot = pipe.next_slot()
         pad = batch + [batch[-1]] * (pipe.batch - n)
-        with torch.cuda.device(dev), torch.cuda.stream(stream):
-            if letterbox:
-                dev_frames, shapes = letterbox_frames_device(pad, height, width, dev, letterbox_fill)
-            else:
-                dev_frames, shapes = prepare_frames_device(pad, height, width, dev, resize)
-        state["keep"][slot] = dev_frames                      # alive until the ticket's buffers are reused
+        dev_frames, shapes = _frames_on_device(pad, height, width, dev, stream, resize, letterbox, letterbox_fill)
+        state["keep"][size, slot] = dev_frames                # alive until the ticket's buffers are reused
         orig_hw = np.array([[s[0], s[1]] for s in shapes], dtype=np.int32)
-        return pipe.submit(dev_frames, orig_hw=orig_hw, n_frames=n, letterbox=letterbox)
+        return pipe, pipe.submit(dev_frames, orig_hw=orig_hw, n_frames=n, letterbox=letterbox)
+
+    def checked(item):
+        if not resize:
+            got = tuple(item.shape[-3:-1])
+            if got != (height, width):
+                raise ValueError("resize=False: a {} x {} frame, but the network's input is {} x {} and the frame loop runs at "
+                                 "that size only; inference(resize=False) runs a frame at its own size".format(
+                                     got[0], got[1], height, width))
+        return item
 
     def batches():
         group = []
         for item in frames:
+            checked(item)
             if getattr(item, "ndim", 3) == 4:
                 if group:
                     yield group
@@ -199,17 +245,20 @@ def detect_in_frames(net, frames, batch_size=16, prob_thresh=0.05, nms_iou_thres
     open_tickets = []
     try:
         for batch in batches():
-            if state["pipe"] is not None and len(open_tickets) == state["pipe"].max_open:   # the buffers this ticket will take
-                for result in state["pipe"].results(open_tickets.pop(0)):
+            # (the buffers the new ticket will take; every pipeline of this call has the same max_open, and with no more than
+            # that open in all none of them has more)
+            if open_tickets and len(open_tickets) == open_tickets[0][0].max_open:
+                pipe, ticket = open_tickets.pop(0)
+                for result in pipe.results(ticket):
                     yield result
             open_tickets.append(submit(batch))
-        for ticket in open_tickets:
-            for result in state["pipe"].results(ticket):
+        for pipe, ticket in open_tickets:
+            for result in pipe.results(ticket):
                 yield result
     finally:
-        if state["pipe"] is not None:
-            state["pipe"].synchronize()                       # (a generator abandoned half way leaves nothing in flight)
-            state["pipe"].busy = False
+        for pipe in state["pipes"].values():
+            pipe.synchronize()                                # (a generator abandoned half way leaves nothing in flight)
+            pipe.busy = False
 
 
 def detect_in_images(net, path, batch_size=16, prob_thresh=0.05, nms_iou_thresh=0.3, letterbox=False, letterbox_fill=128,

@@ -94,6 +94,268 @@ def test_video_and_camera_need_opencv_and_say_so(tmp_path):
         stream.detect_in_cam(None)
 
 
+# ------------------------------------------------------------------- the frame loop's own bookkeeping, on a recording pipeline
+# detect_in_frames with yolov3.pipeline.Pipeline replaced by a stub that records what it is asked to do and whose ``results``
+# return the ids of the frames it was given (a frame's id is its byte [0, 0, 0]), so the generator's grouping, draining, buffer
+# rotation and clean-up run without a GPU.  The same cases on the real pipeline: tests/test_gpu_frame_loop.py.
+class _FakeNet(object):
+    def __init__(self, height=4, width=6):
+        self.net_info = {"height": height, "width": width}
+        self.device, self.dtype = "cuda", "float32"
+
+    def _torch_device(self):
+        return None
+
+
+def _frame(i, h=4, w=6):
+    f = np.zeros((h, w, 3), dtype=np.uint8)
+    f[0, 0, 0] = i
+    return f
+
+
+@pytest.fixture
+def loop(monkeypatch):
+    """Patches the frame loop onto the recording stub.  ``loop.made``: the stubs built, in order; ``loop.staged``: weak
+    references to the device batches the (patched) device path returned."""
+    import types
+    import weakref
+    import torch
+    from yolov3 import _hip, pipeline
+
+    rec = types.SimpleNamespace(made=[], staged=[])
+
+    class StubPipeline(object):
+        def __init__(self, net, batch, height=None, width=None, in_flight=3, kmax=512, label_capacity=None):
+            self.batch, self.height, self.width, self.in_flight = batch, height, width, in_flight
+            self.max_open = self.nbuf = 2 * in_flight
+            self.busy = False
+            self._n = 0
+            self.log = []             # ("submit", ticket, ids, path, pinned buffer) / ("results", ticket) / ("synchronize",)
+            self._host = {}
+            self._given = {}
+            rec.made.append(self)
+
+        def host_frames(self, j):
+            assert 0 <= j < self.nbuf
+            if j not in self._host:
+                self._host[j] = torch.zeros((self.batch, self.height, self.width, 3), dtype=torch.uint8)
+            return self._host[j]
+
+        def upload_done(self, j, wait=True):
+            self.log.append(("upload_done", j))
+            return True
+
+        def next_slot(self):
+            return None, self._n % self.max_open
+
+        def submit(self, frames, orig_hw=None, n_frames=None, letterbox=False):
+            assert self.busy, "a pipeline is used by the generator that marked it busy"
+            assert tuple(frames.shape) == (self.batch, self.height, self.width, 3)
+            buf = [j for j, h in self._host.items() if h is frames]
+            path = "pinned" if buf else ("device" if orig_hw is not None else "whole")
+            ids = [int(f[0, 0, 0]) for f in frames[:n_frames]]
+            self._given[self._n] = ids
+            self.log.append(("submit", self._n, ids, path, buf[0] if buf else None))
+            self._n += 1
+            return self._n - 1
+
+        def results(self, ticket):
+            assert self._n - self.max_open <= ticket < self._n, "ticket {} is not open".format(ticket)
+            self.log.append(("results", ticket))
+            return list(self._given[ticket])
+
+        def synchronize(self):
+            self.log.append(("synchronize",))
+
+        def events(self, *kinds):
+            return [e for e in self.log if e[0] in kinds]
+
+    def frames_on_device(frames, height, width, dev, stream, resize, letterbox, letterbox_fill):
+        same = letterbox or all(tuple(f.shape[:2]) == (height, width) for f in frames)
+        h, w = (height, width) if same else (width, height)          # preprocess.reference_dsize
+        out = torch.zeros((len(frames), h, w, 3), dtype=torch.uint8)
+        for i, f in enumerate(frames):
+            out[i, 0, 0, 0] = int(f[0, 0, 0])
+        rec.staged.append(weakref.ref(out))
+        return out, [tuple(f.shape) for f in frames]
+
+    monkeypatch.setattr(pipeline, "Pipeline", StubPipeline)
+    monkeypatch.setattr(_hip, "require_gpu", lambda: None)
+    monkeypatch.setattr(stream, "_frames_on_device", frames_on_device)
+    return rec
+
+
+def test_frame_loop_groups_frames_and_flushes_before_a_whole_batch(loop):
+    """Single frames are grouped into batches of ``batch_size``; a pending group is flushed (short) before a whole
+    (B, H, W, 3) item, which is submitted as it is when it fills the pipeline and staged when it is a short last batch."""
+    net = _FakeNet()
+    items = [_frame(0), _frame(1), _frame(2), np.stack([_frame(3), _frame(4)]), _frame(5), _frame(6),
+             np.stack([_frame(7)])]
+    assert list(stream.detect_in_frames(net, iter(items), batch_size=2, in_flight=3)) == list(range(8))
+    pipe, = loop.made
+    assert (pipe.batch, pipe.height, pipe.width, pipe.in_flight) == (2, 4, 6, 3)
+    assert [e[1:] for e in pipe.events("submit")] == [(0, [0, 1], "pinned", 0), (1, [2], "pinned", 1), (2, [3, 4], "whole", None),
+                                                      (3, [5, 6], "pinned", 2), (4, [7], "pinned", 3)]
+    assert loop.staged == []
+
+
+def test_frame_loop_refuses_a_batch_larger_than_its_pipeline(loop):
+    net = _FakeNet()
+    items = [_frame(0), _frame(1), np.stack([_frame(2), _frame(3), _frame(4)])]
+    gen = stream.detect_in_frames(net, items, batch_size=2, in_flight=1)
+    with pytest.raises(ValueError, match="a batch of 3 frames after the pipeline was sized for 2"):
+        list(gen)
+    pipe, = loop.made
+    assert [e[2] for e in pipe.events("submit")] == [[0, 1]]
+    assert not pipe.busy and len(pipe.events("synchronize")) == 1
+
+
+def test_frame_loop_drains_the_oldest_ticket_first_and_all_at_the_end(loop):
+    """With ``max_open`` tickets open the oldest one's results are taken before the next submit (which reuses its buffers);
+    what is open at the end of the iterable is drained in order."""
+    net = _FakeNet()
+    assert list(stream.detect_in_frames(net, [_frame(i) for i in range(5)], batch_size=1, in_flight=1)) == list(range(5))
+    pipe, = loop.made
+    assert pipe.max_open == 2
+    assert [e[:2] for e in pipe.events("submit", "results", "synchronize")] == [
+        ("submit", 0), ("submit", 1), ("results", 0), ("submit", 2), ("results", 1), ("submit", 3), ("results", 2), ("submit", 4),
+        ("results", 3), ("results", 4), ("synchronize",)]
+    assert not pipe.busy
+
+
+def _abandon(how, net):
+    """One generator over 8 one-frame batches at ``in_flight=1``, left in the way ``how`` names."""
+    import gc
+
+    def source():
+        for i in range(8):
+            if how == "iterable raises" and i == 2:
+                raise KeyError("decoder")
+            yield _frame(i)
+
+    gen = stream.detect_in_frames(net, source(), batch_size=1, in_flight=1)
+    if how == "exhausted":
+        assert list(gen) == list(range(8))
+    elif how == "iterable raises":
+        with pytest.raises(KeyError):
+            list(gen)
+    else:
+        assert next(gen) == 0                                  # tickets 0 and 1 were submitted; 1 is still open
+        if how == "close":
+            gen.close()
+        elif how == "throw":
+            with pytest.raises(ZeroDivisionError):
+                gen.throw(ZeroDivisionError("consumer"))
+        elif how == "dropped":
+            del gen
+            gc.collect()
+
+
+@pytest.mark.parametrize("how", ["exhausted", "close", "iterable raises", "throw", "dropped"])
+def test_frame_loop_leaves_its_pipeline_idle_on_every_exit_path(loop, how):
+    """However the generator ends, it synchronises its pipeline once and clears ``busy``; the next call gets the same
+    pipeline from the cache."""
+    net = _FakeNet()
+    _abandon(how, net)
+    pipe, = loop.made
+    assert not pipe.busy and len(pipe.events("synchronize")) == 1 and pipe.log[-1] == ("synchronize",)
+    assert list(net._pipelines.values()) == [pipe]
+    before = pipe._n
+    assert list(stream.detect_in_frames(net, [_frame(9), _frame(10)], batch_size=1, in_flight=1)) == [9, 10]
+    assert loop.made == [pipe] and pipe._n == before + 2 and not pipe.busy and len(pipe.events("synchronize")) == 2
+
+
+def test_a_busy_cached_pipeline_is_not_handed_out_twice(loop):
+    net = _FakeNet()
+    a = stream.detect_in_frames(net, [_frame(i) for i in range(4)], batch_size=1, in_flight=1)
+    b = stream.detect_in_frames(net, [_frame(i) for i in range(10, 14)], batch_size=1, in_flight=1)
+    assert next(a) == 0 and next(b) == 10
+    first, second = loop.made
+    assert first is not second and first.busy and second.busy
+    assert list(net._pipelines.values()) == [first]             # the cache keeps the pipeline it had
+    assert [next(a), next(b), next(a), next(b)] == [1, 11, 2, 12]
+    assert list(a) == [3] and list(b) == [13]
+    assert [e[2] for e in first.events("submit")] == [[0], [1], [2], [3]]
+    assert [e[2] for e in second.events("submit")] == [[10], [11], [12], [13]]
+    assert not first.busy and not second.busy and list(net._pipelines.values()) == [first]
+    assert list(stream.detect_in_frames(net, [_frame(20)], batch_size=1, in_flight=1)) == [20]
+    assert loop.made == [first, second] and first._n == 5
+    # another cache key (batch size, in_flight) is another pipeline
+    assert list(stream.detect_in_frames(net, [_frame(21)], batch_size=1, in_flight=2)) == [21]
+    assert len(loop.made) == 3 and len(net._pipelines) == 2
+
+
+def test_pinned_buffers_rotate_by_the_calls_own_count_not_by_ticket(loop):
+    """Batches alternate between the pinned path and the device path.  The pinned batches take the pinned buffers 0, 1, 2, ...
+    in turn, so that the one refilled is always the one whose upload is oldest and all ``nbuf`` are in use -- indexed by ticket
+    they would take every other buffer here and wait for an upload two batches back instead of four.  The count starts again
+    with every call; the tickets go on."""
+    net = _FakeNet()
+
+    def mixed(first):
+        return [_frame(first + i) if i % 2 == 0 else _frame(first + i, 5, 7) for i in range(10)]
+
+    for call, first in enumerate((0, 100)):
+        assert list(stream.detect_in_frames(net, mixed(first), batch_size=1, in_flight=1, letterbox=True)) == list(range(first, first + 10))
+        pipe, = loop.made
+        submits = pipe.events("submit")[10 * call:]
+        assert [e[1] for e in submits] == list(range(10 * call, 10 * call + 10))
+        assert [e[3] for e in submits] == ["pinned", "device"] * 5
+        assert [e[4] for e in submits if e[3] == "pinned"] == [0, 1, 0, 1, 0]       # nbuf = 2
+        waits = [e[1] for e in pipe.events("upload_done")][5 * call:]
+        assert waits == [0, 1, 0, 1, 0]                          # asked before each refill, for that buffer
+
+
+def test_device_frames_stay_alive_while_their_ticket_is_open(loop):
+    """The batch the device path made is referenced by nothing on the host once it is submitted, except by the generator:
+    until the ticket's slot comes round again its memory must not go back to the allocator under the forward that reads it."""
+    import gc
+    net = _FakeNet()
+    gen = stream.detect_in_frames(net, [_frame(i, 5, 7) for i in range(6)], batch_size=1, in_flight=1, letterbox=True)
+    assert next(gen) == 0                                       # tickets 0 and 1 submitted
+    gc.collect()
+    assert len(loop.staged) == 2 and all(ref() is not None for ref in loop.staged)
+    assert next(gen) == 1                                       # ticket 2 took the slot of ticket 0
+    gc.collect()
+    assert len(loop.staged) == 3 and loop.staged[0]() is None and loop.staged[1]() is not None and loop.staged[2]() is not None
+    assert list(gen) == [2, 3, 4, 5]
+
+
+def test_stretched_frames_of_a_network_that_is_not_square_get_a_pipeline_of_their_size(loop):
+    """``inference()`` runs the frames it stretches at ``preprocess.reference_dsize`` -- width x height, the reference's
+    ``cv2.resize`` quirk -- and net-sized ones at height x width: the loop keeps one pipeline per size and the order of the
+    results; letterboxed frames are net-sized."""
+    net = _FakeNet(4, 6)
+    items = [_frame(0), _frame(1, 5, 7), _frame(2, 9, 3), _frame(3)]
+    assert list(stream.detect_in_frames(net, items, batch_size=1, in_flight=1)) == [0, 1, 2, 3]
+    own, turned = loop.made
+    assert (own.height, own.width) == (4, 6) and (turned.height, turned.width) == (6, 4)
+    assert [e[2:4] for e in own.events("submit")] == [([0], "pinned"), ([3], "pinned")]
+    assert [e[2:4] for e in turned.events("submit")] == [([1], "device"), ([2], "device")]
+    assert all(not p.busy and len(p.events("synchronize")) == 1 for p in loop.made) and len(net._pipelines) == 2
+    assert list(stream.detect_in_frames(net, items, batch_size=1, in_flight=1, letterbox=True)) == [0, 1, 2, 3]
+    assert len(loop.made) == 2 and len(own.events("submit")) == 6
+
+
+def test_resize_false_refuses_the_first_frame_of_another_size(loop):
+    """``resize=False``: the loop runs at the network's size only.  The first frame (or whole batch) of another size is a
+    ValueError that names both sizes and where such frames do run; nothing of that frame's batch reaches the pipeline."""
+    net = _FakeNet()
+    with pytest.raises(ValueError, match=r"5 x 7.*4 x 6.*inference\(resize=False\)"):
+        list(stream.detect_in_frames(net, [_frame(0, 5, 7)], batch_size=2, resize=False))
+    assert loop.made == [] and loop.staged == []
+    frames = [_frame(0), _frame(1), _frame(2), _frame(3, 5, 7), _frame(4)]
+    gen = stream.detect_in_frames(net, frames, batch_size=2, in_flight=1, resize=False)
+    with pytest.raises(ValueError, match=r"5 x 7.*4 x 6.*inference\(resize=False\)"):
+        list(gen)
+    pipe, = loop.made
+    assert [e[2] for e in pipe.events("submit")] == [[0, 1]] and loop.staged == []      # frame 2 waited for its group
+    assert not pipe.busy and len(pipe.events("synchronize")) == 1
+    with pytest.raises(ValueError, match=r"5 x 7.*4 x 6.*inference\(resize=False\)"):
+        list(stream.detect_in_frames(net, [np.stack([_frame(0, 5, 7)] * 2)], batch_size=2, in_flight=1, resize=False))
+    assert list(stream.detect_in_frames(net, [_frame(5), _frame(6)], batch_size=2, in_flight=1, resize=False)) == [5, 6]
+
+
 # ---------------------------------------------------------------------------------------------- GPU
 IMAGES = ["000000000785.jpg", "000000017627.jpg", "000000024919.jpg", "000000035279.jpg", "000000037777.jpg"]
 
