@@ -21,13 +21,11 @@ import torch
 from . import _hip
 from .cfgparse import parse_config
 from .plan import build_plan, check_blocks, check_pool_mode
+from .plan_ops import STORAGE, fill_ops, head_views, multi_label_options, padded_weight_dims
+from .plan_ops import _round_up, fill_maxpool_op, yolo_decode_flags  # noqa: F401  (lived here; callers import them from here)
 from .weights import conv_layout, read_darknet_weights
 
 BN_EPS = np.float32(1e-5)
-
-
-def _round_up(v, m):
-    return (v + m - 1) // m * m
 
 
 def f32_to_bf16_bits(a):
@@ -46,9 +44,9 @@ def f32_to_f16_bits(a):
 
 # storage modes: name -> (C ABI element type, bytes per element, torch view dtype, host rounding to bit patterns)
 DTYPES = {
-    "float32": (_hip.Y3_F32, 4, torch.float32, None),
-    "bf16": (_hip.Y3_BF16, 2, torch.bfloat16, f32_to_bf16_bits),
-    "fp16": (_hip.Y3_F16, 2, torch.float16, f32_to_f16_bits),
+    "float32": STORAGE["float32"] + (torch.float32, None),
+    "bf16": STORAGE["bf16"] + (torch.bfloat16, f32_to_bf16_bits),
+    "fp16": STORAGE["fp16"] + (torch.float16, f32_to_f16_bits),
 }
 DTYPE_ALIASES = {"float32": "float32", "fp32": "float32", "f32": "float32", "bf16": "bf16", "bfloat16": "bf16",
                  "fp16": "fp16", "f16": "fp16", "float16": "fp16", "half": "fp16"}
@@ -64,32 +62,6 @@ class BlockInfo(object):
 
     def __repr__(self):
         return "BlockInfo({}, {})".format(self.index, self.type)
-
-
-def fill_maxpool_op(op, od):
-    """Kind, size, stride and pooling rule of a plan's maxpool op dict into the C ABI's ``y3_op``; returns the library
-    capabilities the op relies on.  Darknet's rule (``od["pool"] == "darknet"``) travels as Y3_F_POOL_DARKNET with the
-    cfg's ``padding`` in ``pad``; the default sets neither."""
-    op.kind = _hip.OP_MAXPOOL
-    op.ksize, op.stride = od["ksize"], od["stride"]
-    if od.get("pool") == "darknet":
-        op.flags |= _hip.F_POOL_DARKNET
-        op.pad = od["pad"]
-        return _hip.CAP_POOL_DARKNET
-    return 0
-
-
-def yolo_decode_flags(od, scores):
-    """(y3_op.flags bits, library capabilities) of a plan's yolo op dict under the class scoring ``scores``.  A new_coords
-    head scores the Darknet way already, so it is the same op in both modes; any other head carries Y3_F_SCORES_DARKNET
-    under "darknet".  A [region] head (YOLOv2, softmax=1) is the default decode in both modes as well."""
-    if od.get("new_coords"):
-        return _hip.F_NEW_COORDS, _hip.CAP_NEW_COORDS
-    if od.get("region"):
-        return 0, 0          # a [region] head with softmax=1: Darknet's rule for it IS the soft-max, in both modes
-    if scores == "darknet":
-        return _hip.F_SCORES_DARKNET, _hip.CAP_SCORES_DARKNET
-    return 0, 0
 
 
 class _CompiledPlan(object):
@@ -113,6 +85,35 @@ class _CompiledPlan(object):
             self.destroy()
         except Exception:
             pass
+
+
+class _PlanMemory(object):
+    """What ``plan_ops.fill_ops`` asks for addresses, backed by tensors: the compiled plan ``cp`` owns its arena and output
+    buffers and keeps the network's shared device weights alive."""
+
+    def __init__(self, net, cp, dev):
+        self.net, self.cp, self.dev = net, cp, dev
+
+    def arena(self, nbytes):
+        self.cp.arena = torch.empty(nbytes, dtype=torch.uint8, device=self.dev)
+        return self.cp.arena.data_ptr()
+
+    def conv(self, slot, path):
+        wts = self.net._device_weights(slot, path, self.net.dtype, self.dev)
+        self.cp.keep.append(wts)
+        return wts["weight"].data_ptr(), wts["scale"].data_ptr(), wts["bias"].data_ptr()
+
+    def fragment(self, slot, op, nbytes):
+        frag = self.net._fragment_weights(slot, self.dev, op, nbytes)
+        self.cp.keep.append(frag)
+        return frag.data_ptr()
+
+    def outputs(self, batch, rows_total):
+        cp = self.cp
+        cp.bbox = torch.empty((batch, rows_total, 4), dtype=torch.float32, device=self.dev)
+        cp.prob = torch.empty((batch, rows_total), dtype=torch.float32, device=self.dev)
+        cp.cls = torch.empty((batch, rows_total), dtype=torch.int64, device=self.dev)
+        return cp.bbox.data_ptr(), cp.prob.data_ptr(), cp.cls.data_ptr()
 
 
 class Darknet(object):
@@ -340,24 +341,19 @@ class Darknet(object):
         cout, cin, k = c["cout"], c["cin"], c["k"]
         w = self._params[slot]["weight"].astype(np.float32)
         scale, bias = self._fold_bn(slot)
+        cout_pad, k_ld = padded_weight_dims(path, cout, cin, k, es)
         if path == _hip.PATH_STEM_MFMA:
             # 16-bit [32][32]: row = output channel, k = ky*9 + kx*3 + c_mem with c_mem the BYTE order of the
             # uint8 BGR frame (c_mem = 2 - c_rgb), zero padded (csrc/conv_small.hip: conv_stem_mfma_kernel)
-            cout_pad = 32
-            k_ld = 32
-            host = np.zeros((32, 32), dtype=np.float32)
+            host = np.zeros((cout_pad, k_ld), dtype=np.float32)
             wk = w[:, ::-1, :, :].transpose(0, 2, 3, 1).reshape(cout, 27)      # (co, ky, kx, c_mem)
             host[:cout, :27] = wk
             dw = torch.from_numpy(to_bits(host).view(np.int16)).to(dev)
         elif path == _hip.PATH_STEM:
-            cout_pad = _round_up(cout, 8)
-            k_ld = cout_pad
             host = np.zeros((k * k * cin, cout_pad), dtype=np.float32)
             host[:, :cout] = w.transpose(2, 3, 1, 0).reshape(k * k * cin, cout)
             dw = torch.from_numpy(host).to(dev)
         else:
-            cout_pad = _round_up(cout, 128)
-            k_ld = _round_up(k * k * cin, 128 // es)
             host = np.zeros((cout_pad, k_ld), dtype=np.float32)
             host[:cout, :k * k * cin] = w.transpose(0, 2, 3, 1).reshape(cout, k * k * cin)
             if to_bits is not None:
@@ -405,21 +401,15 @@ class Darknet(object):
         if self._params is None:
             raise RuntimeError("call load_weights() / set_params() before forward()")
         dev = self._torch_device()
-        lib = _hip.lib()
-        options = options if options is not None else self.options
-        if self._multi_label:
-            # the head convs' float32 outputs must reach memory: the fused head kernels keep them in LDS (fuse_head)
-            options = dict(options or {}, fuse_head=0)
+        options = multi_label_options(options if options is not None else self.options, self._multi_label)
         opt = _hip.options(**options) if options else None
         self._made_fragments = False
-        c_dtype, es = DTYPES[self.dtype][0], DTYPES[self.dtype][1]
-        bf16 = es == 2                       # a 16-bit storage mode (bf16 or fp16)
-        desc = build_plan(self.blocks, self.net_info, batch, height, width, es, reuse=not self.keep_all, fuse=self.fuse,
-                          pool=self.pool, keep_heads=self._multi_label)
+        desc = build_plan(self.blocks, self.net_info, batch, height, width, DTYPES[self.dtype][1], reuse=not self.keep_all,
+                          fuse=self.fuse, pool=self.pool, keep_heads=self._multi_label)
         cp = _CompiledPlan()
         cp.batch = batch
         cp.rows_total = desc["rows_total"]
-        cp.arena = torch.empty(desc["arena_bytes"], dtype=torch.uint8, device=dev)
+        cp.desc = desc
         # The zero page (source of padding taps and tile tails in the conv kernels) must outlive every plan that holds its
         # address: one per device index, and every plan keeps a reference.  (Until round 4 the test below compared
         # ``cuda:0`` with ``cuda``, so EVERY compile made a new page and dropped the old one under the plans compiled before:
@@ -428,133 +418,17 @@ class Darknet(object):
         if self._zero is None or (self._zero.device.index or 0) != (dev.index if dev.index is not None else torch.cuda.current_device()):
             self._zero = torch.zeros(4096, dtype=torch.uint8, device=dev)
         cp.keep.append(self._zero)
-        base = cp.arena.data_ptr()
-
-        def addr(t, elem):
-            if t is None:
-                return None
-            if t.buf == "input":
-                return None
-            return base + desc["offsets"][t.buf] + t.off * elem
-
-        ops = (_hip.Y3Op * len(desc["ops"]))()
-        needs = 0                            # library capabilities (y3_capabilities) the plan relies on
-        for n, od in enumerate(desc["ops"]):
-            op = ops[n]
-            kind = od["kind"]
-            op.dtype = c_dtype
-            op.batch = batch
-            op.block_idx = od["block"]
-            tin = od["inp"]
-            op.in_h, op.in_w, op.in_c, op.in_ld = tin.h, tin.w, tin.c, tin.ld
-            in_es = 4 if tin.f32 else es
-            if tin.buf == "input":
-                op.flags |= _hip.F_PLAN_INPUT
-                op.flags |= _hip.F_IN_NHWC_U8BGR if input_mode == "u8" else _hip.F_IN_NCHW_F32
-            else:
-                op.d_in = addr(tin, in_es)
-            tout = od.get("out")
-            if tout is not None:
-                op.out_h, op.out_w, op.out_c, op.out_ld = tout.h, tout.w, tout.c, tout.ld
-                op.d_out = addr(tout, 4 if tout.f32 else es)
-                if tout.f32 and bf16:
-                    op.flags |= _hip.F_OUT_F32
-            res = od.get("res")
-            if res is not None:
-                op.d_res = addr(res, es)
-                op.res_ld = res.ld
-            if kind == "conv":
-                op.kind = _hip.OP_CONV
-                op.ksize, op.stride, op.pad = od["ksize"], od["stride"], od["pad"]
-                if od["leaky"]:
-                    op.flags |= _hip.F_LEAKY
-                if od.get("mish"):
-                    op.flags |= _hip.F_MISH
-                    needs |= _hip.CAP_MISH
-                if od.get("logistic"):
-                    op.flags |= _hip.F_LOGISTIC
-                    needs |= _hip.CAP_LOGISTIC
-                if od.get("fuse_next"):
-                    op.flags |= _hip.F_FUSE_NEXT
-                if res is not None:
-                    op.flags |= _hip.F_RESIDUAL
-                c = self._convs[od["slot"]]
-                # provisional padded sizes so that y3_conv_path can judge the shape
-                op.cout_pad = _round_up(c["cout"], 128)
-                op.k_ld = _round_up(c["k"] * c["k"] * c["cin"], 128 // es)
-                path = lib.y3_conv_path(ctypes.byref(op))     # (does not depend on the plan options)
-                wts = self._device_weights(od["slot"], path, self.dtype, dev)
-                op.cout_pad, op.k_ld = wts["cout_pad"], wts["k_ld"]
-                op.d_weight = wts["weight"].data_ptr()
-                op.d_scale = wts["scale"].data_ptr()
-                op.d_bias = wts["bias"].data_ptr()
-                cp.keep.append(wts)
-                nfrag = lib.y3_conv_fragment_weight_bytes(ctypes.byref(op), ctypes.byref(opt) if opt is not None else None)
-                if nfrag:
-                    frag = self._fragment_weights(od["slot"], dev, op, nfrag)
-                    op.d_weight_frag = frag.data_ptr()
-                    cp.keep.append(frag)
-            elif kind == "maxpool":
-                needs |= fill_maxpool_op(op, od)
-            elif kind == "upsample":
-                op.kind = _hip.OP_UPSAMPLE
-                op.ksize, op.stride = 1, od["stride"]
-            elif kind == "add":
-                op.kind = _hip.OP_ADD
-                op.ksize = op.stride = 1
-            elif kind == "copy":
-                op.kind = _hip.OP_COPY
-                op.ksize = op.stride = 1
-            elif kind == "reorg":
-                op.kind = _hip.OP_REORG
-                op.ksize, op.stride = 1, od["stride"]
-                if od.get("form3d"):
-                    op.flags |= _hip.F_REORG_3D
-                needs |= _hip.CAP_REORG
-            elif kind == "yolo":
-                op.kind = _hip.OP_YOLO
-                op.n_anchor = len(od["anchors"])
-                op.n_attr = od["n_attr"]
-                for a, (aw, ah) in enumerate(od["anchors"]):
-                    op.anchor_w[a] = float(aw)
-                    op.anchor_h[a] = float(ah)
-                op.row_offset, op.rows_total = od["row_offset"], od["rows_total"]
-                op.net_w, op.net_h = float(self.net_info["width"]), float(self.net_info["height"])
-                if "scale_x_y" in od:
-                    op.scale_x_y = od["scale_x_y"]
-                    needs |= _hip.CAP_SCALE_X_Y
-                flags, caps = yolo_decode_flags(od, self._scores)
-                op.flags |= flags
-                needs |= caps
-            else:
-                raise AssertionError(kind)
-        if self._multi_label:
-            needs |= _hip.CAP_MULTI_LABEL
+        cp.ops, needs, _ = fill_ops(desc, self.net_info, self._convs, self.dtype, batch, input_mode, self._scores, opt,
+                                    _PlanMemory(self, cp, dev))
+        cp.n_ops = len(cp.ops)
         _hip.require_capabilities(needs, self.config_fpath)
         if self._multi_label:
-            yolo = [ops[n] for n in range(len(desc["ops"])) if ops[n].kind == _hip.OP_YOLO]
-            cp.heads = (_hip.Y3HeadView * len(yolo))()
-            for view, op in zip(cp.heads, yolo):
-                view.d_head, view.h, view.w, view.ld = op.d_in, op.in_h, op.in_w, op.in_ld
-                view.n_anchor, view.n_attr, view.row_offset = op.n_anchor, op.n_attr, op.row_offset
-                view.new_coords = int(bool(op.flags & _hip.F_NEW_COORDS))
-        cp.ops = ops
-        cp.n_ops = len(desc["ops"])
-        cp.desc = desc
-        # persistent output buffers: every head's decode kernel writes its row range in place
-        m = cp.rows_total
-        cp.bbox = torch.empty((batch, m, 4), dtype=torch.float32, device=dev)
-        cp.prob = torch.empty((batch, m), dtype=torch.float32, device=dev)
-        cp.cls = torch.empty((batch, m), dtype=torch.int64, device=dev)
-        for n in range(cp.n_ops):
-            if ops[n].kind == _hip.OP_YOLO:
-                ops[n].d_bbox, ops[n].d_prob, ops[n].d_cls = (
-                    cp.bbox.data_ptr(), cp.prob.data_ptr(), cp.cls.data_ptr())
+            cp.heads = head_views(cp.ops)
         handle = ctypes.c_void_p()
         if self._made_fragments:          # plans run on other streams than the one the copies were made on
             torch.cuda.current_stream().synchronize()
-        _hip.check(lib.y3_plan_create_ex(ops, cp.n_ops, self._zero.data_ptr(),
-                                         ctypes.byref(opt) if opt is not None else None, ctypes.byref(handle)))
+        _hip.check(_hip.lib().y3_plan_create_ex(cp.ops, cp.n_ops, self._zero.data_ptr(),
+                                                ctypes.byref(opt) if opt is not None else None, ctypes.byref(handle)))
         cp.handle = handle
         return cp
 

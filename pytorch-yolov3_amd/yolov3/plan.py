@@ -265,7 +265,7 @@ def build_plan(blocks, net_info, batch, height, width, elem_size, reuse=True, fu
     """Resolve the graph.  ``blocks`` must already carry absolute route indices.
 
     Returns dict(ops=[...], buffers={id: nbytes}, offsets={id: arena offset}, arena_bytes,
-    rows_total, shapes).  Each op is a dict; tensors are :class:`Tensor`.
+    rows_total, shapes, keep_heads).  Each op is a dict; tensors are :class:`Tensor`.
     ``fuse`` (default: same as ``reuse``): mark conv pairs the executor may run as one kernel; with
     ``reuse=False, fuse=True`` (per-block parity tests) the intermediate tensor of a fused pair keeps
     its arena slot but is never written.
@@ -534,4 +534,4 @@ def build_plan(blocks, net_info, batch, height, width, elem_size, reuse=True, fu
 
     return dict(ops=ops, buffers=nbytes, offsets=offsets, arena_bytes=max(top, ALIGN),
                 rows_total=rows_total, shapes=shapes, n_convs=conv_slot, live=(first, last),
-                tensor_of=tensor_of)
+                tensor_of=tensor_of, keep_heads=bool(keep_heads))

@@ -10,7 +10,6 @@ COUNTS: 32, 64 and 128 are the partitions, 256 the whole chip.  1 and 20 are str
 of a persistent grid and every ``n_cu / 4`` threshold is zero; 20 is no multiple of 8, so csrc/common.h y3_xcd_remap takes its
 ``r != 0`` branch, and none of 3, so csrc/conv_1x1.hip wres_geom takes its ``n_cu % n_tiles`` branch."""
 import ctypes
-import os
 
 from yolov3 import _hip
 
@@ -40,28 +39,12 @@ PERSISTENT_ROWS = ("wres_128_strided_tiles", "wres_64_strided_tiles", "patch_str
                    "stem_s2_phased_strided_tiles", "resblock_strided_tiles")
 
 
-def mish_blocks(model):
-    from yolov3.cfgparse import parse_config
-    blocks, _ = parse_config(os.path.join(kc.MODEL_DIR, model + ".cfg"))
-    return {i for i, b in enumerate(blocks) if b["type"] == "convolutional" and b.get("activation") == "mish"}
-
-
 def plan_steps(model, dim, dtype, batch, overrides, width=None, input_mode="u8"):
     """[{"kernel", "dims": (grid, block, lds), "op": a copy of the y3_op} per op] of the plan made on fake addresses under the CU
-    count in force (kernel_choice_util.build_ops; the mish convs of the YOLOv4 cfgs flagged as Darknet._compile_on_device flags them)"""
+    count in force (kernel_choice_util.build_ops: the ops ``Darknet`` compiles)"""
     lib = _hip.lib()
     opt = _hip.options(**overrides)
     ops, _, fake = kc.build_ops(model, dim, dtype, batch, input_mode, opt, width)
-    mish = mish_blocks(model)
-    for n in range(len(ops)):
-        if ops[n].kind == _hip.OP_CONV and ops[n].block_idx in mish:
-            ops[n].flags |= _hip.F_MISH
-    # (the fragment-weight query of build_ops ran before the flag: ask again, so that no plan here makes a private copy)
-    for n in range(len(ops)):
-        if ops[n].kind == _hip.OP_CONV and not ops[n].d_weight_frag:
-            nfrag = int(lib.y3_conv_fragment_weight_bytes(ctypes.byref(ops[n]), ctypes.byref(opt)))
-            if nfrag:
-                ops[n].d_weight_frag = fake(nfrag)
     handle = ctypes.c_void_p()
     _hip.check(lib.y3_plan_create_ex(ops, len(ops), fake(4096), ctypes.byref(opt), ctypes.byref(handle)))
     try:

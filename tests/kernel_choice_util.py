@@ -1,18 +1,18 @@
 """Kernel choice of every plan step, without a GPU (tools/make_kernel_choice.py writes tests/golden/kernel_choice.json,
 tests/test_kernel_choice.py checks it).
 
-The ops are those ``Darknet._compile_on_device`` builds -- same plan description, flags, padded weight sizes -- with fake,
-aligned device addresses in place of the arena, the parameters and the output buffers.  Every conv whose kernel reads
-fragment-order weights gets a (fake) ``d_weight_frag``, so ``y3_plan_create_ex`` neither allocates nor launches anything: it
-only decides.  Never hand these ops to a library that can see a GPU (the test skips when torch sees one)."""
+The ops are those ``Darknet`` compiles: ``build_ops`` takes the description of a ``Darknet`` on the CPU through ``build_plan`` and
+``plan_ops.fill_ops``, the product's own translation, and hands it fake, aligned device addresses in place of the arena, the
+parameters and the output buffers.  Every conv whose kernel reads fragment-order weights gets a (fake) ``d_weight_frag``, so
+``y3_plan_create_ex`` neither allocates nor launches anything: it only decides.  Never hand these ops to a library that can see a GPU (the test skips when torch sees one)."""
 import ctypes
+import functools
 import os
 
 from yolov3 import _hip
-from yolov3.darknet import DTYPES, _round_up
-from yolov3.cfgparse import parse_config
+from yolov3.darknet import DTYPES, Darknet
 from yolov3.plan import build_plan
-from yolov3.weights import conv_layout
+from yolov3.plan_ops import fill_ops, padded_weight_dims
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 MODEL_DIR = os.path.join(ROOT, "pytorch-yolov3_amd", "models")
@@ -66,111 +66,50 @@ def configs():
 
 
 class _Fake:
-    """distinct, 4 KiB-aligned fake device addresses"""
+    """distinct, 4 KiB-aligned fake device addresses: called for one, and the ``mem`` of ``plan_ops.fill_ops``"""
 
-    def __init__(self):
+    def __init__(self, convs=(), es=4):
         self.next = 1 << 44
+        self.convs, self.es = convs, es
 
     def __call__(self, nbytes):
         a = self.next
-        self.next += _round_up(max(int(nbytes), 1), 4096) + 4096
+        self.next += (max(int(nbytes), 1) + 4095) // 4096 * 4096 + 4096
         return a
 
+    def arena(self, nbytes):
+        self.base = self(nbytes)
+        return self.base
 
-def build_ops(model, dim, dtype, batch, input_mode, opt, width=None):
-    """the ops of one plan (a ctypes array) as Darknet._compile_on_device builds them, and the fragment-weight bytes of each
-    conv (None for other ops) asked under ``opt``.  The input is ``dim`` x ``dim``, or ``dim`` high and ``width`` wide."""
-    lib = _hip.lib()
-    blocks, net_info = parse_config(os.path.join(MODEL_DIR, model + ".cfg"))
-    for i, blk in enumerate(blocks):            # absolute route indices (Darknet.__init__)
-        if blk["type"] == "route":
-            blk["layers"] = [j if j >= 0 else i + j for j in blk["layers"]]
-    _, convs = conv_layout(blocks, net_info)
-    c_dtype, es = DTYPES[dtype][0], DTYPES[dtype][1]
-    desc = build_plan(blocks, net_info, batch, dim, width or dim, es, reuse=True, fuse=True)
-    fake = _Fake()
-    base = fake(desc["arena_bytes"])
+    def conv(self, slot, path):
+        c = self.convs[slot]
+        cout_pad, k_ld = padded_weight_dims(path, c["cout"], c["cin"], c["k"], self.es)
+        return self(cout_pad * k_ld * self.es), self(cout_pad * 4), self(cout_pad * 4)
 
-    def addr(t, elem):
-        if t is None or t.buf == "input":
-            return None
-        return base + desc["offsets"][t.buf] + t.off * elem
+    def fragment(self, slot, op, nbytes):
+        return self(nbytes)
 
-    ops = (_hip.Y3Op * len(desc["ops"]))()
-    frag = []
-    for n, od in enumerate(desc["ops"]):
-        op = ops[n]
-        kind = od["kind"]
-        op.dtype = c_dtype
-        op.batch = batch
-        op.block_idx = od["block"]
-        tin = od["inp"]
-        op.in_h, op.in_w, op.in_c, op.in_ld = tin.h, tin.w, tin.c, tin.ld
-        if tin.buf == "input":
-            op.flags |= _hip.F_PLAN_INPUT
-            op.flags |= _hip.F_IN_NHWC_U8BGR if input_mode == "u8" else _hip.F_IN_NCHW_F32
-        else:
-            op.d_in = addr(tin, 4 if tin.f32 else es)
-        tout = od.get("out")
-        if tout is not None:
-            op.out_h, op.out_w, op.out_c, op.out_ld = tout.h, tout.w, tout.c, tout.ld
-            op.d_out = addr(tout, 4 if tout.f32 else es)
-            if tout.f32 and es == 2:
-                op.flags |= _hip.F_OUT_F32
-        res = od.get("res")
-        if res is not None:
-            op.d_res = addr(res, es)
-            op.res_ld = res.ld
-        nfrag = None
-        if kind == "conv":
-            op.kind = _hip.OP_CONV
-            op.ksize, op.stride, op.pad = od["ksize"], od["stride"], od["pad"]
-            if od["leaky"]:
-                op.flags |= _hip.F_LEAKY
-            if od.get("fuse_next"):
-                op.flags |= _hip.F_FUSE_NEXT
-            if res is not None:
-                op.flags |= _hip.F_RESIDUAL
-            c = convs[od["slot"]]
-            op.cout_pad = _round_up(c["cout"], 128)
-            op.k_ld = _round_up(c["k"] * c["k"] * c["cin"], 128 // es)
-            path = lib.y3_conv_path(ctypes.byref(op))
-            if path == _hip.PATH_STEM_MFMA:                      # (Darknet._device_weights)
-                op.cout_pad, op.k_ld = 32, 32
-            elif path == _hip.PATH_STEM:
-                op.cout_pad = op.k_ld = _round_up(c["cout"], 8)
-            op.d_weight = fake(op.cout_pad * op.k_ld * es)
-            op.d_scale = fake(op.cout_pad * 4)
-            op.d_bias = fake(op.cout_pad * 4)
-            nfrag = int(lib.y3_conv_fragment_weight_bytes(ctypes.byref(op), ctypes.byref(opt)))
-            if nfrag:
-                op.d_weight_frag = fake(nfrag)
-        elif kind == "maxpool":
-            op.kind = _hip.OP_MAXPOOL
-            op.ksize, op.stride = od["ksize"], od["stride"]
-        elif kind == "upsample":
-            op.kind = _hip.OP_UPSAMPLE
-            op.ksize, op.stride = 1, od["stride"]
-        elif kind in ("add", "copy"):
-            op.kind = _hip.OP_ADD if kind == "add" else _hip.OP_COPY
-            op.ksize = op.stride = 1
-        elif kind == "yolo":
-            op.kind = _hip.OP_YOLO
-            op.n_anchor = len(od["anchors"])
-            op.n_attr = od["n_attr"]
-            for a, (aw, ah) in enumerate(od["anchors"]):
-                op.anchor_w[a] = float(aw)
-                op.anchor_h[a] = float(ah)
-            op.row_offset, op.rows_total = od["row_offset"], od["rows_total"]
-            op.net_w, op.net_h = float(net_info["width"]), float(net_info["height"])
-        else:
-            raise AssertionError(kind)
-        frag.append(nfrag)
-    m = desc["rows_total"]
-    bbox, prob, cls = fake(batch * m * 16), fake(batch * m * 4), fake(batch * m * 8)
-    for n in range(len(ops)):
-        if ops[n].kind == _hip.OP_YOLO:
-            ops[n].d_bbox, ops[n].d_prob, ops[n].d_cls = bbox, prob, cls
+    def outputs(self, batch, rows_total):
+        return self(batch * rows_total * 16), self(batch * rows_total * 4), self(batch * rows_total * 8)
+
+
+@functools.lru_cache(maxsize=None)
+def network(model, dtype, pool="reference", scores="reference", multi_label=False):
+    """the description of a shipped cfg, a ``Darknet`` on the CPU: parsed once, read only"""
+    return Darknet(os.path.join(MODEL_DIR, model + ".cfg"), dtype=dtype, pool=pool, scores=scores, multi_label=multi_label)
+
+
+def build_ops(model, dim, dtype, batch, input_mode, opt, width=None, pool="reference", scores="reference", multi_label=False):
+    """the ops of one plan (a ctypes array) as ``Darknet`` compiles them -- its description, ``build_plan`` and
+    ``plan_ops.fill_ops`` -- on fake addresses, the fragment-weight bytes of each conv (None for other ops) asked under ``opt``,
+    and the allocator.  The input is ``dim`` x ``dim``, or ``dim`` high and ``width`` wide.  A ``multi_label`` network
+    compiles with ``fuse_head=0`` (``plan_ops.multi_label_options``): the caller's ``opt`` must say so."""
+    net = network(model, dtype, pool, scores, multi_label)
+    es = DTYPES[net.dtype][1]
+    desc = build_plan(net.blocks, net.net_info, batch, dim, width or dim, es, reuse=not net.keep_all, fuse=net.fuse,
+                      pool=net.pool, keep_heads=net.multi_label)
+    fake = _Fake(net._convs, es)
+    ops, _, frag = fill_ops(desc, net.net_info, net._convs, net.dtype, batch, input_mode, net.scores, opt, fake)
     return ops, frag, fake
 
 

@@ -18,7 +18,7 @@ Two modes:
 
 What the device code does regardless of the ``Tensor`` is stated once each: the decode loads 4-byte elements
 (``yolo_decode_kernel``), whatever its input's ``f32`` says, and a shortcut operand is addressed with the plan's element size
-(``Darknet._compile``: ``d_res``).
+(``plan_ops.fill_ops``: ``d_res``).
 
 ``reference_blocks`` is the other side: a forward of the same cfg by block index, which knows nothing of the planner and calls
 the same arithmetic functions on the same values, so the comparison is bit for bit.

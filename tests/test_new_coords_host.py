@@ -125,15 +125,12 @@ def _csp_ops(dtype, batch, opt):
     import kernel_choice_util as kc
     ops, _, fake = kc.build_ops("yolov4-csp", 512, dtype, batch, "u8", opt)
     blocks, _ = _blocks()
-    for n in range(len(ops)):
-        blk = blocks[ops[n].block_idx]
-        if ops[n].kind == _hip.OP_CONV and blk["activation"] == "mish":
-            ops[n].flags |= _hip.F_MISH
-        elif ops[n].kind == _hip.OP_CONV and blk["activation"] == "logistic":
-            ops[n].flags |= _hip.F_LOGISTIC
-        elif ops[n].kind == _hip.OP_YOLO:
-            ops[n].flags |= _hip.F_NEW_COORDS
-            ops[n].scale_x_y = 2.0
+    convs = {i: b["activation"] for i, b in enumerate(blocks) if b["type"] == "convolutional"}
+    assert {op.block_idx for op in ops if op.flags & _hip.F_MISH} == {i for i, act in convs.items() if act == "mish"}
+    assert {op.block_idx for op in ops if op.flags & _hip.F_LOGISTIC} == {i for i, act in convs.items() if act == "logistic"}
+    yolos = [op for op in ops if op.kind == _hip.OP_YOLO]
+    assert [op.block_idx for op in yolos] == [h + 1 for h in HEADS]
+    assert all(op.flags & _hip.F_NEW_COORDS and op.scale_x_y == float(blocks[op.block_idx]["scale_x_y"]) for op in yolos)
     return ops, fake
 
 

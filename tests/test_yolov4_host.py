@@ -176,9 +176,10 @@ def test_no_fused_kernel_takes_a_mish_op(model, dim, dtype, batch):
     ops, _, fake = kc.build_ops(model, dim, dtype, batch, "u8", opt)
     blocks, _ = _blocks(model)
     mish_blocks = {i for i, b in enumerate(blocks) if b["type"] == "convolutional" and b["activation"] == "mish"}
-    for n in range(len(ops)):
-        if ops[n].kind == _hip.OP_CONV and ops[n].block_idx in mish_blocks:
-            ops[n].flags |= _hip.F_MISH
+    assert {op.block_idx for op in ops if op.flags & _hip.F_MISH} == mish_blocks
+    assert not any(op.flags & _hip.F_LOGISTIC for op in ops)
+    assert [op.scale_x_y for op in ops if op.kind == _hip.OP_YOLO] == [
+        ctypes.c_float(float(b["scale_x_y"])).value for b in blocks if b["type"] == "yolo"]
     handle = ctypes.c_void_p()
     _hip.check(lib.y3_plan_create_ex(ops, len(ops), fake(4096), ctypes.byref(opt), ctypes.byref(handle)))
     try:
