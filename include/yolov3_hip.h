@@ -241,6 +241,7 @@ int y3_abi_version(void);
 #define Y3_CAP_REORG 1024u     /* Y3_OP_REORG and Y3_F_REORG_3D              */
 #define Y3_CAP_LAUNCH_LOG 2048u /* y3_debug_launch_log_begin, y3_debug_launch_log_end */
 #define Y3_CAP_PLAN_OP_DIMS 4096u /* y3_plan_op_dims and y3_set_tuning("device_cus", n) */
+#define Y3_CAP_TILES 8192u     /* y3_tiles_u8, y3_detect_tiled and its workspace query */
 uint32_t y3_capabilities(void);
 const char *y3_last_error(void);
 /* number of visible HIP devices whose arch is gfx950 (0 on a CPU-only machine) */
@@ -342,6 +343,31 @@ int y3_detect_letterbox(const float *d_bbox, const float *d_prob, const int64_t 
                         const int32_t *d_orig_hw, float prob_thresh, double iou_thresh, void *d_workspace,
                         size_t workspace_bytes, int32_t *d_det_count, int64_t *d_det_tlbr, float *d_det_prob,
                         int64_t *d_det_cls, int32_t *d_det_row, int net_h, int net_w, void *stream);
+
+/* the same for frames that were run as TILES: windows of the frame cut out at full resolution (y3_tiles_u8 below), each one
+ * network input of its own.  Not in the reference.  d_bbox (batch * tiles, rows, 4), d_prob and d_cls (batch * tiles, rows) are
+ * the forward outputs of frame b's tiles, contiguous: tiles b * tiles .. b * tiles + tiles - 1.  A frame's candidates are all rows
+ * of all its tiles; row r of tile t is the combined row t * rows + r, which is what d_det_row reports.  d_geom is a DEVICE array
+ * of batch * tiles y3_tile_geom, one per tile in the same order; with g the entry of its tile, a candidate (x, y, w, h) becomes
+ *   cx = (int64)(x * g.sx) + g.ox,  cy = (int64)(y * g.sy) + g.oy,  bw = (int64)(w * g.sx),  bh = (int64)(h * g.sy)
+ * (float32 products truncated toward zero; the offset is added after the truncation), corners = centre -/+ (size >> 1), and
+ * from there on everything is y3_detect's on the union: >= prob_thresh, per-class suppression on the integer corners with +1
+ * areas and strict >, order (class asc, score desc, combined row desc).  A window cut 1:1 at (y0, x0) of the frame carries
+ * {net_w, net_h, x0, y0}; the whole frame stretched to the network carries {src_w, src_h, 0, 0}.  With tiles = 1 and
+ * {orig_w, orig_h, 0, 0} the outputs equal y3_detect's bit for bit.  Outputs have capacity tiles * rows per frame:
+ * d_det_count (batch); d_det_tlbr (batch, tiles * rows, 4); d_det_prob, d_det_cls, d_det_row (batch, tiles * rows).
+ * tiles * rows must fit an int32.  The same kernel as y3_detect, one launch.  Darknet's suppression kinds, the letterbox
+ * correction and multi-label virtual rows have no tiled form.  An object cut by a tile border yields partial boxes that the
+ * suppression does not merge: overlapping windows (and a stretched overview for large objects) are the caller's guard.   */
+typedef struct {
+  float sx, sy;      /* pixels per unit of the tile's relative x / y */
+  int32_t ox, oy;    /* the tile's origin in the frame, pixels        */
+} y3_tile_geom;
+size_t y3_detect_tiled_workspace_bytes(int batch, int tiles, int rows);
+int y3_detect_tiled(const float *d_bbox, const float *d_prob, const int64_t *d_cls, int batch, int tiles, int rows,
+                    const y3_tile_geom *d_geom, float prob_thresh, double iou_thresh, void *d_workspace, size_t workspace_bytes,
+                    int32_t *d_det_count, int64_t *d_det_tlbr, float *d_det_prob, int64_t *d_det_cls, int32_t *d_det_row,
+                    void *stream);
 
 /* Darknet's suppression rule (src/box.c: box_iou, box_diou, box_diounms; do_nms_sort, diounms_sort) instead of the
  * reference's.  Not in the reference.  ONLY the decision which candidates survive changes: thresholding, candidate order
@@ -467,6 +493,17 @@ typedef struct {
  * be reused as soon as the call returns.  Frames of different sizes share one call.                              */
 int y3_letterbox_u8(const y3_letterbox_frame *frames, int batch, uint8_t *d_dst, int net_h, int net_w, int fill,
                     void *stream);
+
+/* Tiles: net-sized windows of larger frames, cut out 1:1 on the device.  Not in the reference.  d_dst (n_tiles, net_h, net_w, 3)
+ * uint8: pixel (y, x) of tile i is pixel (y0 + y, x0 + x) of its frame d_src (src_h, src_w, 3) where that lies inside the frame,
+ * else the byte `fill` (0..255).  0 <= y0 < src_h and 0 <= x0 < src_w.  Tiles of different frames may share a call.  `tiles` is
+ * a HOST array: the descriptors travel as kernel arguments (32 per launch, several launches on `stream` for more), so the array
+ * may be reused as soon as the call returns.  The kernel of y3_letterbox_u8, which copies where a frame has no tap tables.  */
+typedef struct {
+  const uint8_t *d_src;
+  int32_t src_h, src_w, y0, x0;
+} y3_tile;
+int y3_tiles_u8(const y3_tile *tiles, int n_tiles, uint8_t *d_dst, int net_h, int net_w, int fill, void *stream);
 
 /* Darknet's own preprocessing (load_image -> letterbox_image / resize_image): uint8 BGR frames of any size -> the float32
  * network input, bit for bit what `darknet detector test` / `map` feed the network.  Not in the reference, which resizes the

@@ -27,6 +27,8 @@
 #include "common.h"
 #include "letterbox.h"
 
+#include <limits.h>
+
 namespace {
 
 constexpr int kThreads = 1024;
@@ -74,6 +76,10 @@ struct DetectArgs {
   const float *in_xywh;         // caller-boxes mode: [n][4] centre / size
   float *c_fbox;                // workspace, per frame: [rows][4] float32 (x, y, w, h) of every candidate
   float dk_thresh, dk_beta;
+  // tiled frames (y3_detect_tiled): a frame's `rows` are those of rows / tile_rows tiles, tile_rows each, and row r is scaled
+  // and moved by geom[b * (rows / tile_rows) + r / tile_rows] instead of scaled by orig_hw[b]; null = not tiled
+  const y3_tile_geom *geom;
+  int tile_rows;
 };
 
 constexpr int kDkOff = 0, kDkIou = 1, kDkGreedy = 2, kDkDiou = 3;   // kDkIou .. = Y3_NMS_IOU .. + 1
@@ -324,7 +330,9 @@ __global__ __launch_bounds__(kThreads) void detect_kernel(DetectArgs p) {
     float *w_prob = p.c_prob + (long long)b * R;
     int *w_cls = p.c_cls + (long long)b * R;
     int *w_row = p.c_row + (long long)b * R;
-    const float oh = (float)p.orig_hw[b * 2 + 0], ow = (float)p.orig_hw[b * 2 + 1];
+    const bool tiled = p.geom != nullptr;   // uniform: the whole launch is tiled or not
+    const float oh = tiled ? 0.f : (float)p.orig_hw[b * 2 + 0], ow = tiled ? 0.f : (float)p.orig_hw[b * 2 + 1];
+    const y3_tile_geom *geom = tiled ? p.geom + (long long)b * (p.rows / p.tile_rows) : nullptr;
     // letterbox correction (Darknet's correct_yolo_boxes with letter=1; include/yolov3_hip.h, y3_detect_letterbox):
     // x' = (x - deltaw / 2 / net_w) / ratiow in float64 rounded to float32, w' = w * (1 / ratiow) in float32
     const bool lb = p.lb_net_h > 0;
@@ -386,9 +394,16 @@ __global__ __launch_bounds__(kThreads) void detect_kernel(DetectArgs p) {
             bb[3] = bb[3] * inv_rh;
           }
           if constexpr (DK != kDkOff) *reinterpret_cast<f32x4 *>(p.c_fbox + ((long long)b * R + slot) * 4) = bb;
+          // a tile's own scale, and its place in the frame: added to the centre AFTER the truncation
+          float sx = ow, sy = oh;
+          long long ox = 0, oy = 0;
+          if (tiled) {
+            const y3_tile_geom g = geom[r / p.tile_rows];
+            sx = g.sx; sy = g.sy; ox = g.ox; oy = g.oy;
+          }
           // float32 products, then truncation toward zero (inference.py:351-353)
-          const long long cx = (long long)(bb[0] * ow), cy = (long long)(bb[1] * oh);
-          const long long bw = (long long)(bb[2] * ow), bh = (long long)(bb[3] * oh);
+          const long long cx = (long long)(bb[0] * sx) + ox, cy = (long long)(bb[1] * sy) + oy;
+          const long long bw = (long long)(bb[2] * sx), bh = (long long)(bb[3] * sy);
           const long long hw = bw >> 1, hh = bh >> 1;  // floor division by 2 (inference.py:281-282)
           long long *o = w_box + (long long)slot * 4;
           o[0] = cx - hw; o[1] = cy - hh; o[2] = cx + hw; o[3] = cy + hh;
@@ -810,6 +825,32 @@ extern "C" int y3_detect(const float *d_bbox, const float *d_prob, const int64_t
   if (int rc = forward_args("y3_detect", d_bbox, d_prob, d_cls, batch, rows, d_orig_hw, prob_thresh, iou_thresh, d_workspace,
                             d_det_count, d_det_tlbr, d_det_prob, d_det_cls, d_det_row, a)) return rc;
   if (int rc = map_workspace("y3_detect", d_workspace, workspace_bytes, batch, rows, false, a)) return rc;
+  return launch<false>(a, batch, kDkOff, stream);
+}
+
+extern "C" size_t y3_detect_tiled_workspace_bytes(int batch, int tiles, int rows) {
+  if (batch <= 0 || tiles <= 0 || rows <= 0 || (long long)tiles * rows > INT_MAX) return 0;
+  return ws_layout(batch, tiles * rows).total;
+}
+
+extern "C" int y3_detect_tiled(const float *d_bbox, const float *d_prob, const int64_t *d_cls, int batch, int tiles, int rows,
+                               const y3_tile_geom *d_geom, float prob_thresh, double iou_thresh, void *d_workspace,
+                               size_t workspace_bytes, int32_t *d_det_count, int64_t *d_det_tlbr, float *d_det_prob,
+                               int64_t *d_det_cls, int32_t *d_det_row, void *stream) {
+  Y3_REQUIRE(tiles > 0, "y3_detect_tiled: tiles must be positive");
+  Y3_REQUIRE(rows <= 0 || (long long)tiles * rows <= INT_MAX, "y3_detect_tiled: %d tiles of %d rows are too many for one frame",
+             tiles, rows);
+  Y3_REQUIRE(batch <= 0 || (long long)batch * tiles <= INT_MAX, "y3_detect_tiled: %d frames of %d tiles are too many", batch,
+             tiles);
+  DetectArgs a = {};
+  // (d_geom stands where the frame sizes stand in y3_detect: the null check is shared)
+  if (int rc = forward_args("y3_detect_tiled", d_bbox, d_prob, d_cls, batch, rows, reinterpret_cast<const int32_t *>(d_geom),
+                            prob_thresh, iou_thresh, d_workspace, d_det_count, d_det_tlbr, d_det_prob, d_det_cls, d_det_row, a))
+    return rc;
+  if (int rc = map_workspace("y3_detect_tiled", d_workspace, workspace_bytes, batch, tiles * rows, false, a)) return rc;
+  a.orig_hw = nullptr;
+  a.geom = d_geom;
+  a.tile_rows = rows;
   return launch<false>(a, batch, kDkOff, stream);
 }
 

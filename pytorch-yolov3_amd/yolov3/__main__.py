@@ -36,6 +36,8 @@ _MODEL_OPTIONS = [
     (("--nms-kind",), dict(choices=["iou", "greedynms", "diounms"], default=None, help="suppress by Darknet's rule on the float32 boxes instead of the reference's on integer pixel corners: iou (a cfg without nms_kind), greedynms (yolov4.cfg) or diounms (yolov4-csp.cfg); -i is its threshold (Darknet's own defaults are -p 0.25 -i 0.45)")),
     (("--darknet-scores",), dict(action="store_true", help="score every class of a box by Darknet's independent logistic, sigmoid(obj) * sigmoid(class), instead of the reference's soft-max over the classes; use it with weights trained by Darknet for yolov3, yolov3-tiny, yolov3-spp, yolov4 and yolov4-tiny (yolov4-csp scores that way already)")),
     (("--multi-label",), dict(action="store_true", help="report every class of a box that scores above -p, as Darknet does, not the best class only (a box may then appear once per class); implies --darknet-scores")),
+    (("--tile-overlap",), dict(type=float, default=None, metavar="<fraction>", help="tiled inference for images larger than the network (-I only): cut every image into network-sized tiles at full resolution whose neighbours share at least this fraction (0 .. 0.9) of the network size, run them all and suppress over their union; objects too small to survive the resize are found, objects cut by a tile border may come out as partial boxes")),
+    (("--no-tile-overview",), dict(action="store_true", help="with --tile-overlap: leave out the extra tile that holds the whole image resized to the network (it finds objects larger than a tile)")),
     (("--beta-nms",), dict(type=float, default=0.6, metavar="<beta>", help="exponent of the distance penalty of --nms-kind diounms (default 0.6, the cfgs' beta_nms)")),
 ]
 _OUTPUT_OPTIONS = [
@@ -89,8 +91,25 @@ def _write_frames(frames, fps, path):
         Image.fromarray(frame[:, :, ::-1]).save(os.path.join(path, "frame_%06d.png" % i))
 
 
+def check_tiling(args):
+    """``--tile-overlap`` and what it does not combine with: SystemExit before anything is loaded.  args: the parsed options."""
+    if args["tile_overlap"] is None:
+        if args["no_tile_overview"]:
+            raise SystemExit("yolov3: --no-tile-overview means nothing without --tile-overlap")
+        return
+    if not args["image"]:
+        raise SystemExit("yolov3: --tile-overlap refused with video or camera input -- tiled inference runs on images (-I) only")
+    from .tiles import check_options
+    try:
+        check_options(args["tile_overlap"], letterbox=args["letterbox"], preprocess="darknet" if args["darknet_resize"] else None,
+                      nms_kind=args["nms_kind"], multi_label=args["multi_label"])
+    except ValueError as exc:
+        raise SystemExit("yolov3: --tile-overlap refused: %s" % exc)
+
+
 def main(argv=None):
     args = vars(build_parser().parse_args(argv))
+    check_tiling(args)
     for key in ("class_names", "config", "weights", "image", "video", "output", "json"):
         args[key] = _abspath(args[key])
     device = args["device"]
@@ -124,10 +143,16 @@ def main(argv=None):
     if args["image"]:
         directory, names = stream.list_image_files(args["image"])
         images = [stream.load_image_bgr(os.path.join(directory, n)) for n in names]
-        results = list(stream.detect_in_frames(net, images, batch_size=args["batch_size"],
-                                               prob_thresh=args["prob_thresh"], nms_iou_thresh=args["iou_thresh"],
-                                               letterbox=args["letterbox"], nms_kind=args["nms_kind"],
-                                               beta_nms=args["beta_nms"], preprocess=preprocess))
+        if args["tile_overlap"] is not None:
+            results = [tuple(yolov3.inference(net, image, device=device, prob_thresh=args["prob_thresh"],
+                                              nms_iou_thresh=args["iou_thresh"], tile_overlap=args["tile_overlap"],
+                                              tile_overview=not args["no_tile_overview"], tile_batch=args["batch_size"])[0])
+                       for image in images]
+        else:
+            results = list(stream.detect_in_frames(net, images, batch_size=args["batch_size"],
+                                                   prob_thresh=args["prob_thresh"], nms_iou_thresh=args["iou_thresh"],
+                                                   letterbox=args["letterbox"], nms_kind=args["nms_kind"],
+                                                   beta_nms=args["beta_nms"], preprocess=preprocess))
         if frames is not None:
             for image, (bbox_tlbr, class_prob, class_idx) in zip(images, results):
                 stream.draw_boxes(image, bbox_tlbr, class_idx=class_idx, class_names=class_names)

@@ -40,6 +40,7 @@ CAP_MISH, CAP_SCALE_X_Y, CAP_LOGISTIC, CAP_NEW_COORDS, CAP_LETTERBOX, CAP_POOL_D
 CAP_NMS_DARKNET, CAP_SCORES_DARKNET, CAP_MULTI_LABEL, CAP_PREPROCESS_DARKNET, CAP_REORG = 64, 128, 256, 512, 1024
 CAP_LAUNCH_LOG = 2048
 CAP_PLAN_OP_DIMS = 4096
+CAP_TILES = 8192
 # Darknet's suppression measures (include/yolov3_hip.h: Y3_NMS_*), by the cfg's spelling of `nms_kind`
 NMS_IOU, NMS_GREEDY, NMS_DIOU = 0, 1, 2
 NMS_KINDS = {"iou": NMS_IOU, "greedynms": NMS_GREEDY, "diounms": NMS_DIOU}
@@ -71,6 +72,17 @@ class Y3LetterboxFrame(ctypes.Structure):
     """Mirror of ``y3_letterbox_frame`` (include/yolov3_hip.h): one frame of a ``y3_letterbox_u8`` batch."""
     _fields_ = [("d_src", ctypes.c_void_p), ("src_h", ctypes.c_int32), ("src_w", ctypes.c_int32),
                 ("d_ytab", ctypes.c_void_p), ("d_xtab", ctypes.c_void_p)]
+
+
+class Y3Tile(ctypes.Structure):
+    """Mirror of ``y3_tile`` (include/yolov3_hip.h): one net-sized window of a frame, for ``y3_tiles_u8``."""
+    _fields_ = [("d_src", ctypes.c_void_p), ("src_h", ctypes.c_int32), ("src_w", ctypes.c_int32),
+                ("y0", ctypes.c_int32), ("x0", ctypes.c_int32)]
+
+
+class Y3TileGeom(ctypes.Structure):
+    """Mirror of ``y3_tile_geom`` (include/yolov3_hip.h): scale and origin of one tile's boxes, for ``y3_detect_tiled``."""
+    _fields_ = [("sx", ctypes.c_float), ("sy", ctypes.c_float), ("ox", ctypes.c_int32), ("oy", ctypes.c_int32)]
 
 
 class Y3DarknetFrame(ctypes.Structure):
@@ -146,6 +158,11 @@ PROTOTYPES = {
                                            ctypes.c_void_p, ctypes.c_float, ctypes.c_double, ctypes.c_void_p,
                                            ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    "y3_detect_tiled_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "y3_detect_tiled": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                       ctypes.c_void_p, ctypes.c_float, ctypes.c_double, ctypes.c_void_p, ctypes.c_size_t,
+                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                       ctypes.c_void_p]),
     "y3_detect_darknet_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
     "y3_detect_darknet": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
                                          ctypes.c_void_p, ctypes.c_float, ctypes.c_double, ctypes.c_void_p,
@@ -177,6 +194,8 @@ PROTOTYPES = {
                                              ctypes.POINTER(ctypes.c_int32)]),
     "y3_letterbox_u8": (ctypes.c_int, [ctypes.POINTER(Y3LetterboxFrame), ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
                                        ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    "y3_tiles_u8": (ctypes.c_int, [ctypes.POINTER(Y3Tile), ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                   ctypes.c_int, ctypes.c_void_p]),
     "y3_preprocess_darknet_f32": (ctypes.c_int, [ctypes.POINTER(Y3DarknetFrame), ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
                                                  ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
     "y3_copy_bytes": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p]),
@@ -190,7 +209,8 @@ PROTOTYPES = {
 _OPTIONAL = ("y3_capabilities", "y3_detect_letterbox", "y3_letterbox_geometry", "y3_letterbox_u8",
              "y3_detect_darknet_workspace_bytes", "y3_detect_darknet", "y3_nms_darknet_workspace_bytes", "y3_nms_darknet",
              "y3_expand_labels_workspace_bytes", "y3_expand_labels", "y3_preprocess_darknet_f32",
-             "y3_debug_launch_log_begin", "y3_debug_launch_log_end", "y3_plan_op_dims")
+             "y3_debug_launch_log_begin", "y3_debug_launch_log_end", "y3_plan_op_dims",
+             "y3_tiles_u8", "y3_detect_tiled_workspace_bytes", "y3_detect_tiled")
 
 
 class HipLibraryError(RuntimeError):
@@ -236,7 +256,8 @@ def require_capabilities(needs, what):
     linear, ignore scale_x_y, run a logistic head as linear, decode new_coords heads the YOLOv3 way, stretch frames
     that were to be letterboxed, pool the reference's way where Darknet's rule was asked for, suppress by the
     reference's rule where Darknet's was asked for, score boxes by the reference's soft-max where Darknet's logistic scores
-    were asked for, lack the multi-label expansion, lack Darknet's float preprocessing, or reject a [reorg] op as of unknown kind."""
+    were asked for, lack the multi-label expansion, lack Darknet's float preprocessing, reject a [reorg] op as of unknown kind,
+    or lack the tile cutter and the tiled detection tail."""
     missing = needs & ~capabilities()
     if missing:
         names = [n for n, b in (("mish", CAP_MISH), ("scale_x_y", CAP_SCALE_X_Y), ("logistic", CAP_LOGISTIC),
@@ -244,7 +265,8 @@ def require_capabilities(needs, what):
                                 ("Darknet max-pooling", CAP_POOL_DARKNET), ("Darknet NMS", CAP_NMS_DARKNET),
                                 ("Darknet class scores", CAP_SCORES_DARKNET),
                                 ("multi-label detections", CAP_MULTI_LABEL),
-                                ("Darknet preprocessing", CAP_PREPROCESS_DARKNET), ("reorg", CAP_REORG)) if missing & b]
+                                ("Darknet preprocessing", CAP_PREPROCESS_DARKNET), ("reorg", CAP_REORG),
+                                ("tiled inference", CAP_TILES)) if missing & b]
         raise HipLibraryError("{}: the loaded libyolov3_hip.so cannot compute {} (rebuild: make -C pytorch-yolov3_amd/csrc)"
                               .format(what, ", ".join(names)))
 

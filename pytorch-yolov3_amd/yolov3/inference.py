@@ -24,7 +24,10 @@
   per class and a box's second class takes part in that class's suppression;
 * ``preprocess="darknet"`` (opt-in, not in the reference) prepares the frames the way Darknet itself does: ``byte / 255`` first,
   then Darknet's float32 ``resize_image`` (or ``letterbox_image`` on a canvas of 0.5 with ``letterbox=True``) in one launch per
-  batch (``y3_preprocess_darknet_f32``), and the network runs from that float input instead of the fused uint8 stem.
+  batch (``y3_preprocess_darknet_f32``), and the network runs from that float input instead of the fused uint8 stem;
+* ``tile_overlap=f`` (opt-in, not in the reference) looks at a frame larger than the network through net-sized windows at full
+  resolution (``yolov3/tiles.py``): the windows are cut on the device (``y3_tiles_u8``), run through the network in chunks, and
+  all their rows are one frame's candidates, each mapped back by its window's origin, before one suppression (``y3_detect_tiled``).
 
 There is no CPU fallback: without the HIP library / a GPU these functions raise.
 """
@@ -33,8 +36,8 @@ import ctypes
 import numpy as np
 import torch
 
-from . import _hip
-from .preprocess import darknet_frames_device, letterbox_frames_device, prepare_frames_device
+from . import _hip, tiles as _tiles
+from .preprocess import _fill_byte, darknet_frames_device, letterbox_frames_device, prepare_frames_device, resize_on_device
 
 
 def _device(device=None):
@@ -274,6 +277,31 @@ class Detector(object):
         else:
             _hip.check(lib.y3_detect(*args, _hip.stream_ptr()))
 
+    def run_tiled(self, out, geom, tiles, prob_thresh, iou_thresh):
+        """The detection tail over frames that were run as tiles (``y3_detect_tiled``).  out: forward outputs of
+        ``batch * tiles`` tiles, frame by frame (device tensors).  geom: ``y3_tile_geom`` of every tile in that order -- a uint8
+        device tensor of 16 bytes per tile, or a list of (sx, sy, ox, oy).  This Detector's ``rows`` is the capacity of a frame,
+        ``tiles`` times the rows of a tile, and the rows ``fetch`` reports are combined rows, tile * rows of a tile + row.  The
+        reference's suppression only: no letterbox correction, no Darknet kinds, no multi-label rows."""
+        _hip.require_capabilities(_hip.CAP_TILES, "Detector.run_tiled")
+        bbox, prob, cls = out["bbox_xywh"], out["class_prob"], out["class_idx"]
+        tiles = int(tiles)
+        if tiles < 1 or self.rows % tiles or tuple(prob.shape) != (self.batch * tiles, self.rows // tiles):
+            raise ValueError("Detector of batch {} and {} rows given {} tiles a frame and outputs of shape {}".format(
+                self.batch, self.rows, tiles, tuple(prob.shape)))
+        if not (bbox.is_contiguous() and prob.is_contiguous() and cls.is_contiguous()):
+            raise ValueError("Detector.run_tiled: the outputs must be contiguous")
+        if not isinstance(geom, torch.Tensor):
+            geom = tile_geom_tensor(geom, self.device)
+        if geom.dtype != torch.uint8 or geom.numel() != 16 * self.batch * tiles or not geom.is_contiguous():
+            raise ValueError("Detector.run_tiled: expected {} tile geometries of 16 bytes".format(self.batch * tiles))
+        self._tail, self._label_run = self, None
+        self._geom = geom                                   # alive until the next run
+        _hip.check(_hip.lib().y3_detect_tiled(
+            bbox.data_ptr(), prob.data_ptr(), cls.data_ptr(), self.batch, tiles, self.rows // tiles, geom.data_ptr(),
+            ctypes.c_float(prob_thresh), ctypes.c_double(iou_thresh), self.ws.data_ptr(), self.ws_bytes, self.count.data_ptr(),
+            self.tlbr.data_ptr(), self.prob.data_ptr(), self.cls.data_ptr(), self.row.data_ptr(), _hip.stream_ptr()))
+
     def _run_labels(self, out, orig_hw, prob_thresh, iou_thresh, letterbox, nms_kind, beta_nms, labels, label_capacity):
         _hip.require_capabilities(_hip.CAP_MULTI_LABEL, "Detector.run(labels=...)")
         bbox = out["bbox_xywh"]
@@ -366,6 +394,99 @@ def raise_label_overflow(counts, cap):
                                "pass a larger label_capacity= (or a higher prob_thresh)".format(frame, count, cap))
 
 
+def tile_geom_tensor(geom, device):
+    """[(sx, sy, ox, oy), ...] -> the ``y3_tile_geom`` array as a uint8 device tensor (16 bytes per tile)."""
+    arr = np.array([tuple(g) for g in geom], dtype=np.dtype([("sx", "<f4"), ("sy", "<f4"), ("ox", "<i4"), ("oy", "<i4")]))
+    return torch.from_numpy(arr.view(np.uint8).copy()).to(device)
+
+
+def cut_tiles_device(frame, net_h, net_w, grid, fill=128, out=None):
+    """The windows of ``grid`` ((y0, x0) origins) of one uint8 (H, W, 3) device frame as a (len(grid), net_h, net_w, 3) uint8
+    tensor (``out``, or a new one): ``y3_tiles_u8`` on the current stream, bit-identical to ``tiles.cut_tiles_u8``."""
+    _hip.require_capabilities(_hip.CAP_TILES, "cut_tiles_device")
+    if frame.dim() != 3 or frame.shape[2] != 3 or frame.dtype != torch.uint8 or not frame.is_contiguous():
+        raise ValueError("cut_tiles_device: the frame is not a contiguous uint8 (H, W, 3) tensor: {} {}".format(
+            tuple(frame.shape), frame.dtype))
+    sh, sw = int(frame.shape[0]), int(frame.shape[1])
+    if out is None:
+        out = torch.empty((len(grid), net_h, net_w, 3), dtype=torch.uint8, device=frame.device)
+    descs = (_hip.Y3Tile * len(grid))(*[_hip.Y3Tile(frame.data_ptr(), sh, sw, int(y0), int(x0)) for y0, x0 in grid])
+    with torch.cuda.device(frame.device):
+        _hip.check(_hip.lib().y3_tiles_u8(descs, len(grid), out.data_ptr(), net_h, net_w, _fill_byte(fill), _hip.stream_ptr()))
+    return out
+
+
+def frame_tiles_device(image, net_h, net_w, device, overlap, overview=True, fill=128, out=None):
+    """One frame -> (its tiles as a (T, net_h, net_w, 3) uint8 device tensor, their [(sx, sy, ox, oy), ...]): the windows of
+    ``tiles.tile_grid`` in its order and, with ``overview``, the whole frame resized by ``inference()``'s default resize
+    (``y3_resize_bilinear_u8``) to net_h rows and net_w columns -- a tile like the others, so a rectangular network does not get
+    the transposed input that ``preprocess.reference_dsize`` gives its untiled frames."""
+    src = image if isinstance(image, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(image))
+    src = src.to(device).contiguous()
+    if src.dim() != 3 or src.shape[2] != 3 or src.dtype != torch.uint8:
+        raise ValueError("tiled inference: a frame is not uint8 (H, W, 3): {} {}".format(tuple(src.shape), src.dtype))
+    sh, sw = int(src.shape[0]), int(src.shape[1])
+    grid = _tiles.tile_grid(sh, sw, net_h, net_w, overlap)
+    n = len(grid) + (1 if overview else 0)
+    if out is None:
+        out = torch.empty((n, net_h, net_w, 3), dtype=torch.uint8, device=device)
+    cut_tiles_device(src, net_h, net_w, grid, fill, out=out[:len(grid)])
+    if overview:
+        resize_on_device(src, net_h, net_w, device, out=out[len(grid)])
+    return out, _tiles.tile_geometry(sh, sw, net_h, net_w, grid, overview)
+
+
+def tile_chunks(n_tiles, tile_batch):
+    """[(start, stop), ...]: the chunks in which ``n_tiles`` tiles go through the network, at most ``tile_batch`` each."""
+    return [(i, min(i + tile_batch, n_tiles)) for i in range(0, n_tiles, tile_batch)]
+
+
+class _TileBuffers(object):
+    """Device buffers of tiled inference for one tile count and network size, made once: the tiles and, per row count of a
+    tile, the concatenated forward outputs."""
+
+    def __init__(self, n_tiles, net_h, net_w, device):
+        self.n_tiles, self.device = n_tiles, device
+        self.frames = torch.empty((n_tiles, net_h, net_w, 3), dtype=torch.uint8, device=device)
+        self._outs = {}
+
+    def outputs(self, rows):
+        out = self._outs.get(rows)
+        if out is None:
+            n, dev = self.n_tiles, self.device
+            out = self._outs[rows] = {"bbox_xywh": torch.empty((n, rows, 4), dtype=torch.float32, device=dev),
+                                      "class_prob": torch.empty((n, rows), dtype=torch.float32, device=dev),
+                                      "class_idx": torch.empty((n, rows), dtype=torch.int64, device=dev)}
+        return out
+
+
+_tile_buffers = {}
+
+
+def _inference_tiled(net, images, dev, prob_thresh, iou_thresh, return_rows, overlap, overview, fill, tile_batch):
+    _hip.require_capabilities(_hip.CAP_TILES, "inference(tile_overlap=...)")
+    net_h, net_w = net.net_info["height"], net.net_info["width"]
+    results = []
+    for image in images:
+        n_tiles = len(_tiles.tile_grid(int(image.shape[0]), int(image.shape[1]), net_h, net_w, overlap)) + (1 if overview else 0)
+        key = (n_tiles, net_h, net_w, str(dev))
+        buf = _tile_buffers.get(key)
+        if buf is None:
+            buf = _tile_buffers[key] = _TileBuffers(n_tiles, net_h, net_w, dev)
+        with torch.cuda.device(dev):
+            frames, geom = frame_tiles_device(image, net_h, net_w, dev, overlap, overview, fill, out=buf.frames)
+            for start, stop in tile_chunks(n_tiles, tile_batch):
+                out = net.forward_frames(frames[start:stop], fresh=False)
+                union = buf.outputs(int(out["class_prob"].shape[1]))
+                for k, v in out.items():                     # the plan's buffers are rewritten by the next chunk of this size
+                    union[k][start:stop].copy_(v)
+            rows = int(union["class_prob"].shape[1])
+            det = get_detector(1, n_tiles * rows, dev)
+            det.run_tiled(union, geom, n_tiles, prob_thresh, iou_thresh)
+            results.extend(det.fetch(return_rows=return_rows))
+    return results
+
+
 _detectors = {}
 
 
@@ -380,7 +501,7 @@ def get_detector(batch, rows, device):
 
 def inference(net, images, device="cuda", prob_thresh=0.05, nms_iou_thresh=0.3, resize=True,
               return_rows=False, letterbox=False, letterbox_fill=128, nms_kind=None, beta_nms=0.6, label_capacity=None,
-              preprocess=None):
+              preprocess=None, tile_overlap=None, tile_overview=True, tile_fill=128, tile_batch=16):
     """Run detection on one frame or a list of HxWx3 uint8 BGR frames.
 
     Returns, per frame, ``[bbox_tlbr int64 (K,4), class_prob float32 (K,), class_idx int64 (K,)]``
@@ -404,7 +525,24 @@ def inference(net, images, device="cuda", prob_thresh=0.05, nms_iou_thresh=0.3, 
     ``letterbox_fill`` is ignored) with the same box correction, False its ``resize_image`` to the whole network input, boxes
     scaled as in the default mode.  Frames of different sizes may share the call either way.  It needs ``resize``; any other
     value is a ValueError, as is a frame so long and thin that its target would be one pixel wide.
+
+    ``tile_overlap``: None [default] = every frame is resized to the network, as above; a fraction in [0, 0.9] = tiled
+    inference (``yolov3/tiles.py``).  Every frame, one at a time, is cut into net-sized windows at full resolution whose
+    neighbours share at least that fraction of the network size (a frame that fits the network is one window, padded with
+    the byte ``tile_fill``), plus -- with ``tile_overview`` -- the whole frame resized by the default 8-bit resize to net_h rows
+    and net_w columns, for objects larger than a window.  The tiles run through the network in chunks of at most ``tile_batch``; all their rows are the
+    frame's candidates, in frame pixels, for one suppression.  With ``return_rows`` the row of a detection is
+    ``tile * rows of one tile + row``, tiles in ``tiles.tile_grid``'s order and the overview last.  An object cut by a window's
+    border yields partial boxes that suppression does not merge: choose the overlap larger than the objects looked for.
+    ValueError with ``letterbox=True``, ``preprocess="darknet"``, ``resize=False``, an ``nms_kind``, a ``multi_label``
+    network, or an overlap outside [0, 0.9].
     """
+    if tile_overlap is not None:
+        tile_overlap = _tiles.check_options(tile_overlap, letterbox=letterbox, preprocess=preprocess, resize=resize,
+                                            nms_kind=nms_kind, multi_label=getattr(net, "multi_label", False))
+        tile_fill = _fill_byte(tile_fill)
+        if int(tile_batch) < 1:
+            raise ValueError("tile_batch must be >= 1, got {!r}".format(tile_batch))
     _hip.nms_mode(nms_kind, beta_nms)
     mode = _hip.check_preprocess_mode(preprocess)
     if letterbox and not resize:
@@ -416,6 +554,9 @@ def inference(net, images, device="cuda", prob_thresh=0.05, nms_iou_thresh=0.3, 
     if str(device).startswith("cuda") and not str(net.device).startswith("cuda"):
         net.cuda(device)
     dev = net._torch_device()
+    if tile_overlap is not None:
+        return _inference_tiled(net, list(images), dev, float(np.float32(prob_thresh)), float(nms_iou_thresh), return_rows,
+                                tile_overlap, bool(tile_overview), tile_fill, int(tile_batch))
     net_h, net_w = net.net_info["height"], net.net_info["width"]
     if mode == "darknet":
         _hip.require_capabilities(_hip.CAP_PREPROCESS_DARKNET | (_hip.CAP_LETTERBOX if letterbox else 0),
