@@ -137,8 +137,16 @@ typedef struct y3_op {
   const void *d_weight;
   const float *d_scale;
   const float *d_bias;
-  /* Y3_OP_YOLO: d_in is the float32 head tensor (B,h,w,ld) with channel = anchor*n_attr + attr */
-  int32_t n_anchor, n_attr;
+  /* Y3_OP_YOLO: d_in is the float32 head tensor (B,h,w,ld) with channel = anchor*n_attr + attr.
+   * Y3_OP_CONV: `groups` shares n_anchor's four bytes (only YOLO ops read n_anchor).  0 and 1 both mean an ordinary conv.
+   * With groups > 1 the op still has in_c input and out_c output channels in all; output channel co belongs to group
+   * g = co / (out_c / groups) and reads input channels [g * in_c / groups, (g + 1) * in_c / groups).  Weight layouts: see
+   * y3_conv_path (answers 4 and 5).  y3_capabilities() reports Y3_CAP_GROUPED_CONV                                        */
+  union {
+    int32_t n_anchor;
+    int32_t groups;
+  };
+  int32_t n_attr;
   float anchor_w[8], anchor_h[8]; /* pixels, already selected by `mask` (darknet.py:44) */
   int32_t row_offset, rows_total; /* this head's first row / total rows M of the concatenated output */
   float net_w, net_h;             /* cfg [net] width/height (darknet.py:395-399)          */
@@ -242,6 +250,7 @@ int y3_abi_version(void);
 #define Y3_CAP_LAUNCH_LOG 2048u /* y3_debug_launch_log_begin, y3_debug_launch_log_end */
 #define Y3_CAP_PLAN_OP_DIMS 4096u /* y3_plan_op_dims and y3_set_tuning("device_cus", n) */
 #define Y3_CAP_TILES 8192u     /* y3_tiles_u8, y3_detect_tiled and its workspace query */
+#define Y3_CAP_GROUPED_CONV 16384u /* y3_op.groups on conv ops, y3_conv_path answers 4 and 5, y3_set_tuning("grouped_generic", v) */
 uint32_t y3_capabilities(void);
 const char *y3_last_error(void);
 /* number of visible HIP devices whose arch is gfx950 (0 on a CPU-only machine) */
@@ -271,7 +280,8 @@ const char *y3_plan_op_kernel(const y3_plan *plan, int op_index);
  * dynamic LDS; three zeros for an op that an earlier step launches (a fused group's second op, the SPP pyramid's second and
  * third pool).  Tests and tools: the launchers launch exactly these.                                                   */
 int y3_plan_op_dims(const y3_plan *plan, int op_index, int64_t out[3]);
-/* algorithmic FLOPs (2*k*k*Cin*Cout*Hout*Wout*B for convs, else 0) and compulsory bytes      */
+/* algorithmic FLOPs (2*k*k*Cin*Cout*Hout*Wout*B for convs, divided by `groups` for a grouped one, else 0) and compulsory
+ * bytes (a grouped conv's weights count k*k*(Cin/groups)*Cout elements)                                              */
 double y3_plan_op_flops(const y3_plan *plan, int op_index);
 double y3_plan_op_bytes(const y3_plan *plan, int op_index);
 
@@ -279,7 +289,23 @@ double y3_plan_op_bytes(const y3_plan *plan, int op_index);
  * the op dtype), 1 = 3-channel stem (weights float32 [27][cout_pad]), 2 = direct fallback (same
  * layout as 0), 3 = MFMA stem for uint8 BGR frames -> bf16 (weights bf16 [32][32], k = ky*9 + kx*3 +
  * byte-channel, zero padded; scale/bias 32 floats); -1 if `op` is not a conv.  The host lays weights
- * out accordingly.                                                                              */
+ * out accordingly.
+ * A conv with groups > 1 is asked about before anything else and gets one of two answers of its own:
+ *   4 = grouped (csrc/conv_grouped.hip: conv_grouped_*): weights [cout_pad][k_ld] in the op dtype, row = output channel,
+ *       k = (ky*ksize + kx) * (in_c / groups) + c with c the channel inside the group: layout 0 with the group's channel
+ *       count.  k_ld >= ksize*ksize*(in_c / groups), cout_pad >= out_c; scale / bias have cout_pad entries.
+ *   5 = depthwise (conv_dwise_*): groups == in_c == out_c with in_c, in_ld, out_ld (and res_ld) multiples of 8 and d_in, d_out,
+ *       d_res, d_weight, d_scale, d_bias (those that are set) 16-byte aligned; a depthwise op off that grain is answered 4.  Weights
+ *       [ksize*ksize][k_ld] in the op dtype, tap-major with the channel innermost; k_ld = cout_pad = c_pad =
+ *       round_up(out_c, 8) (a larger multiple of 8 as k_ld is accepted); scale / bias have c_pad entries.
+ * Both kernels take float32, bf16 and fp16, any ksize / stride / pad that give the op's output size, every activation
+ * and Y3_F_RESIDUAL.  They sum a value in float32 from 0 in the order ky outermost, kx next, channel of the group
+ * innermost, every product rounded before it is added (no fused multiply-add); taps outside the image add nothing.  So a
+ * depthwise op gives the same bits on either -- for finite weights: the depthwise kernel adds the zero products of the columns
+ * outside the image where the grouped kernel skips the tap, and 0 * inf is NaN (a damaged weights file).  Under y3_set_tuning("grouped_generic", 1) the answer is 4 for every grouped
+ * op.  Plan creation refuses, with Y3_ERR_INVALID and the block's number: groups < 0; in_c or out_c no multiple of groups;
+ * groups > 1 with Y3_F_IN_NCHW_F32, Y3_F_IN_NHWC_U8BGR, Y3_F_PLAN_INPUT or Y3_F_OUT_F32 (a grouped stem or head conv);
+ * k_ld / cout_pad below the layout's.  No fused group takes a grouped op.                                              */
 int y3_conv_path(const y3_op *op);
 
 /* Fragment-order weights of the direct-weights strip kernel (csrc/conv_halo.hip: 1-KiB blocks of 16 output channels x 32
@@ -298,7 +324,11 @@ int y3_conv_make_fragment_weights(const y3_op *op, void *d_dst, void *stream);
  * count every chooser gets instead, for every device, until it is set back to 0 (any other value: Y3_ERR_INVALID).  The count
  * sizes persistent grids, picks tile shapes and moves ops between kernels, all at plan creation: a plan keeps what it was
  * created with.  It is how the tests make, on an unpartitioned MI355X, the plans that a DPX / QPX / CPX compute partition
- * (128 / 64 / 32 CUs) gets; a grid of 32 workgroups computes the same values on either.  Not a speed knob.            */
+ * (128 / 64 / 32 CUs) gets; a grid of 32 workgroups computes the same values on either.  Not a speed knob.
+ * Another is "grouped_generic".  0 [default]: a depthwise conv on the 8-channel grain runs conv_dwise_*.  1: every grouped
+ * conv runs conv_grouped_* and y3_conv_path answers 4 for it (other values: Y3_ERR_INVALID).  Process-wide like "device_cus",
+ * because y3_conv_path has no options argument; the host must lay the weights out under the value the plan is created
+ * under.  Same bits either way: tests and A/B runs.                                                                   */
 int y3_set_tuning(const char *key, int value);
 
 /* Launch log (tests and tools only; host code, the kernels are the same): between the two calls every kernel the CALLING

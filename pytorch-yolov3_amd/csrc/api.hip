@@ -55,6 +55,10 @@ int y3_debug_flags() { return 0; }
 // y3_set_tuning("device_cus", n): 0 asks the device; 1 .. 4096 is the count every chooser gets for every device (the plans of a
 // compute partition of 128, 64 or 32 CUs, made and run on an unpartitioned device).  Read here and nowhere else.
 static std::atomic<int> g_y3_device_cus{0};
+// y3_set_tuning("grouped_generic", v): 1 sends every grouped conv to conv_grouped_* (y3_conv_path answers 4); process-wide,
+// because y3_conv_path has no options to read it from.  Read by conv_path and nowhere else.
+static std::atomic<int> g_y3_grouped_generic{0};
+int y3_grouped_generic() { return g_y3_grouped_generic.load(std::memory_order_relaxed); }
 // CU count of the current device (256 on an MI355X; 256 as well when no device is visible: dry runs on a CPU box)
 int y3_device_cus() {
   const int forced = g_y3_device_cus.load(std::memory_order_relaxed);
@@ -93,8 +97,10 @@ struct y3_plan {
 
 namespace {
 
-// 0 = MFMA implicit GEMM, 1 = 3-channel stem kernel (VALU), 2 = direct fallback, 3 = MFMA stem (uint8 -> bf16)
+// 0 = MFMA implicit GEMM, 1 = 3-channel stem kernel (VALU), 2 = direct fallback, 3 = MFMA stem (uint8 -> bf16),
+// 4 = grouped, 5 = depthwise (a grouped op is asked about first: no other family's chooser ever sees one)
 int conv_path(const y3_op &op) {
+  if (op.groups > 1) return !y3_grouped_generic() && y3_conv_dwise_fits(op) ? 5 : 4;
   const bool net_input = op.flags & (Y3_F_IN_NCHW_F32 | Y3_F_IN_NHWC_U8BGR);
   if (y3_conv_stem_mfma_supported(op)) return 3;
   if (net_input && op.in_c == 3 && op.ksize == 3 && !(op.flags & Y3_F_RESIDUAL)) return 1;
@@ -114,6 +120,8 @@ int choose_conv(const y3_op &op, const y3_options &o, y3_step &st) {
     case 1: return y3_choose_conv_small(op, st);
     case 2: return y3_choose_conv_direct(op, st);
     case 3: return y3_choose_conv_stem_mfma(op, st);
+    case 4: return y3_choose_conv_grouped(op, st);
+    case 5: return y3_choose_conv_dwise(op, st);
     default: break;
   }
   const unsigned am = (unsigned)o.auto_mask;
@@ -177,6 +185,30 @@ int check_flags(const y3_op &op) {
              "op for block %d: Y3_F_SCORES_DARKNET on an op of kind %d (YOLO ops only)", op.block_idx, op.kind);
   Y3_REQUIRE(!(op.flags & Y3_F_REORG_3D) || op.kind == Y3_OP_REORG,
              "op for block %d: Y3_F_REORG_3D on an op of kind %d (reorg ops only)", op.block_idx, op.kind);
+  return Y3_OK;
+}
+
+// y3_op.groups of a conv op (it shares its bytes with n_anchor, which only YOLO ops read): checked for every op of a plan
+// before any chooser sees it
+int check_groups(const y3_op &op) {
+  if (op.kind != Y3_OP_CONV) return Y3_OK;
+  const int g = op.groups;
+  Y3_REQUIRE(g >= 0, "conv block %d: groups=%d", op.block_idx, g);
+  if (g <= 1) return Y3_OK;
+  Y3_REQUIRE(op.in_c % g == 0 && op.out_c % g == 0, "conv block %d: groups=%d does not divide %d input and %d output channels",
+             op.block_idx, g, op.in_c, op.out_c);
+  Y3_REQUIRE(!(op.flags & (Y3_F_IN_NCHW_F32 | Y3_F_IN_NHWC_U8BGR | Y3_F_PLAN_INPUT)),
+             "conv block %d: a grouped conv (groups=%d) cannot read the network input", op.block_idx, g);
+  Y3_REQUIRE(!(op.flags & Y3_F_OUT_F32), "conv block %d: a grouped conv (groups=%d) cannot store float32 from 16-bit storage (a detection-head conv)",
+             op.block_idx, g);
+  if (conv_path(op) == 5)
+    Y3_REQUIRE(op.k_ld >= (op.out_c + 7) / 8 * 8 && op.cout_pad >= (op.out_c + 7) / 8 * 8,
+               "conv block %d: depthwise weights [%d][c_pad] need k_ld and cout_pad >= %d (k_ld %d, cout_pad %d)", op.block_idx,
+               op.ksize * op.ksize, (op.out_c + 7) / 8 * 8, op.k_ld, op.cout_pad);
+  else
+    Y3_REQUIRE((long long)op.k_ld >= (long long)op.ksize * op.ksize * (op.in_c / g) && op.cout_pad >= op.out_c,
+               "conv block %d: grouped weights need k_ld >= %lld and cout_pad >= %d (k_ld %d, cout_pad %d)", op.block_idx,
+               (long long)op.ksize * op.ksize * (op.in_c / g), op.out_c, op.k_ld, op.cout_pad);
   return Y3_OK;
 }
 
@@ -309,7 +341,7 @@ int y3_abi_version(void) { return Y3_ABI_VERSION; }
 uint32_t y3_capabilities(void) {
   return Y3_CAP_MISH | Y3_CAP_SCALE_X_Y | Y3_CAP_LOGISTIC | Y3_CAP_NEW_COORDS | Y3_CAP_LETTERBOX | Y3_CAP_POOL_DARKNET |
          Y3_CAP_NMS_DARKNET | Y3_CAP_SCORES_DARKNET | Y3_CAP_MULTI_LABEL | Y3_CAP_PREPROCESS_DARKNET | Y3_CAP_REORG |
-         Y3_CAP_LAUNCH_LOG | Y3_CAP_PLAN_OP_DIMS | Y3_CAP_TILES;
+         Y3_CAP_LAUNCH_LOG | Y3_CAP_PLAN_OP_DIMS | Y3_CAP_TILES | Y3_CAP_GROUPED_CONV;
 }
 
 int y3_debug_launch_log_begin(void) {
@@ -360,7 +392,7 @@ size_t y3_conv_fragment_weight_bytes(const y3_op *op, const y3_options *options)
   y3_step st;
   // (a detection-head conv is chosen for together with the YOLO op behind it, at plan creation: asked about by its shape here)
   if (o.fuse_head && y3_conv_head_dw_fits(*op, o)) return y3_conv_halo_dw_weight_bytes(*op);
-  if (check_flags(*op) != Y3_OK || check_size(*op) != Y3_OK) return 0;
+  if (check_flags(*op) != Y3_OK || check_groups(*op) != Y3_OK || check_size(*op) != Y3_OK) return 0;
   return choose_op(*op, o, st) == Y3_OK && st.frag ? y3_conv_halo_dw_weight_bytes(*op) : 0;
 }
 
@@ -396,6 +428,7 @@ int y3_plan_create_ex(const y3_op *ops, int n_ops, const void *d_zero, const y3_
   for (int i = 0; i < n_ops; ++i) {
     y3_step &st = p->steps[i];
     int rc = check_flags(q[i]);
+    if (rc == Y3_OK) rc = check_groups(q[i]);
     if (rc == Y3_OK) rc = check_size(q[i]);
     if (rc != Y3_OK) {
       y3_plan_destroy(p);
@@ -571,7 +604,8 @@ int y3_plan_op_dims(const y3_plan *plan, int op_index, int64_t out[3]) {
 double y3_plan_op_flops(const y3_plan *plan, int op_index) {
   if (!plan || op_index < 0 || (size_t)op_index >= plan->ops.size()) return 0.0;
   auto conv_flops = [](const y3_op &o) {
-    return o.kind != Y3_OP_CONV ? 0.0 : 2.0 * o.ksize * o.ksize * o.in_c * (double)o.out_c * o.out_h * o.out_w * o.batch;
+    return o.kind != Y3_OP_CONV ? 0.0 : 2.0 * o.ksize * o.ksize * o.in_c * (double)o.out_c * o.out_h * o.out_w * o.batch /
+                                            (o.groups > 1 ? o.groups : 1);
   };
   const y3_op *q = &plan->ops[op_index];
   switch (plan->steps[op_index].fuse) {
@@ -614,7 +648,8 @@ double y3_plan_op_bytes(const y3_plan *plan, int op_index) {
       if (o.flags & Y3_F_IN_NCHW_F32) in_es = 4;
       if (o.flags & Y3_F_IN_NHWC_U8BGR) in_es = 1;
       const double out_es = (o.flags & Y3_F_OUT_F32) ? 4 : es;
-      double b = in_px * o.in_c * in_es + out_px * o.out_c * out_es + (double)o.ksize * o.ksize * o.in_c * o.out_c * es;
+      double b = in_px * o.in_c * in_es + out_px * o.out_c * out_es +
+                 (double)o.ksize * o.ksize * o.in_c * o.out_c * es / (o.groups > 1 ? o.groups : 1);
       if (o.flags & Y3_F_RESIDUAL) b += out_px * o.out_c * es;
       return b;
     }
@@ -640,6 +675,11 @@ int y3_set_tuning(const char *key, int value) {
     g_y3_device_cus.store(value, std::memory_order_relaxed);
     return Y3_OK;
   }
+  if (!strcmp(key, "grouped_generic")) {
+    Y3_REQUIRE(value == 0 || value == 1, "y3_set_tuning: grouped_generic %d (0: conv_dwise where it fits; 1: conv_grouped for every grouped op)", value);
+    g_y3_grouped_generic.store(value, std::memory_order_relaxed);
+    return Y3_OK;
+  }
 #ifdef Y3_HAS_DEBUG_KEY
   if (!strcmp(key, "debug")) { g_y3_debug = value; return Y3_OK; }
 #endif
@@ -656,6 +696,7 @@ int y3_op_run(const y3_op *op, const void *d_input, const void *d_zero, void *st
   int rc = check_pointers(*op, in);
   y3_step st;
   if (rc == Y3_OK) rc = check_flags(*op);
+  if (rc == Y3_OK) rc = check_groups(*op);
   if (rc == Y3_OK) rc = check_size(*op);
   if (rc == Y3_OK) rc = choose_op(*op, g_y3_defaults, st);
   if (rc == Y3_OK) rc = check_launch(*op, st);

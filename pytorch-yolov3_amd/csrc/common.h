@@ -339,6 +339,16 @@ __device__ __forceinline__ void y3_bn_act8(float (&v)[8], const f32x4 &lo, const
   if (act >= Y3_ACT_MISH) y3_act_tail8(v, act);
 }
 
+// y3_bn_act8 for ONE value, operation by operation (acc * scale + bias, max(t, slope * t), then the mish / logistic tail): a
+// kernel's one-element form gives the bits of the eight-wide epilogue (conv_grouped.hip).  Kept next to it: change both.
+__device__ __forceinline__ float y3_bn_act1(float acc, float sc, float bi, int act) {
+  const float slope = act == Y3_ACT_LEAKY ? Y3_LEAKY_SLOPE : 1.0f;
+  const float t = acc * sc + bi;
+  float v = y3_vmax(t, t * slope);
+  if (act >= Y3_ACT_MISH) v = y3_act_tail(v, act);
+  return v;
+}
+
 // Diagnostic build only (-DY3_STAMPS, `make stamps`): per-workgroup phase timing with s_memtime.
 // Lane 0 of wave 0 adds the cycle count of each phase into g_y3_stamps[phase]; slot 7 counts
 // workgroups.  Never compiled into the shipped library.
@@ -505,3 +515,13 @@ bool y3_conv_patch_fits(const y3_op &op);
 int y3_choose_conv_patch(const y3_op &op, y3_step &st);
 // true when the MFMA implicit-GEMM kernel can take this conv
 bool y3_conv_igemm_supported(const y3_op &op);
+// Grouped convs (y3_op.groups > 1; conv_grouped.hip).  conv_path (api.hip) asks about them before anything else, so no other
+// single-op chooser ever sees one; every fused chooser declines a group that holds one.
+static inline bool y3_is_grouped(const y3_op &op) { return op.kind == Y3_OP_CONV && op.groups > 1; }
+// y3_set_tuning("grouped_generic", v) (api.hip): 1 sends every grouped op to conv_grouped_*
+int y3_grouped_generic();
+// depthwise kernel: whether the op is on its grain (then y3_conv_path answers 5 unless grouped_generic), and its chooser
+bool y3_conv_dwise_fits(const y3_op &op);
+int y3_choose_conv_dwise(const y3_op &op, y3_step &st);
+// every other grouped op (y3_conv_path answers 4)
+int y3_choose_conv_grouped(const y3_op &op, y3_step &st);

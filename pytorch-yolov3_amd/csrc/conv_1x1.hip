@@ -417,6 +417,7 @@ int dw_head_bm(const y3_op &op, const y3_options &o) {
   const int mode = o.fuse_head;
   if (mode == 0 || mode == 2) return 0;
   if (op.kind != Y3_OP_CONV || !y3_is16(op.dtype) || op.ksize != 1 || op.stride != 1 || op.pad != 0 || !(op.flags & Y3_F_OUT_F32)) return 0;
+  if (y3_is_grouped(op)) return 0;
   if (op.flags & (Y3_F_LEAKY | Y3_F_MISH | Y3_F_RESIDUAL | Y3_F_IN_NCHW_F32 | Y3_F_IN_NHWC_U8BGR | Y3_F_PLAN_INPUT)) return 0;   // (logistic: new_coords heads)
   if (op.out_c > 256 || op.cout_pad < 256 || op.cout_pad % 32 != 0 || op.in_ld % 8 != 0 || op.k_ld % 32 != 0 || op.k_ld < op.in_c) return 0;
   // (asked about a conv's shape before plan creation's size check as well: y3_conv_fragment_weight_bytes)

@@ -470,6 +470,7 @@ bool y3_choose_conv_block_fused(const y3_op &op0, const y3_op &op1, const y3_opt
   if ((op0.flags & (bad | Y3_F_RESIDUAL)) || (op1.flags & bad)) return false;
   // the kernel knows LeakyReLU and linear only (its leaky1 / leaky3 map every other op to linear): no mish, no logistic
   if ((op0.flags | op1.flags) & (Y3_F_MISH | Y3_F_LOGISTIC)) return false;
+  if (y3_is_grouped(op0) || y3_is_grouped(op1)) return false;
   if (op1.d_in != op0.d_out || op1.in_ld != op0.out_ld) return false;
   // z must not overlap x: a workgroup writes its rectangle of z while its neighbours still read those pixels of x as their
   // one-pixel border (phase A), and nothing orders workgroups of different rounds / streams.  The arena planner frees x after

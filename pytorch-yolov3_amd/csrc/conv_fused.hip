@@ -947,6 +947,7 @@ bool y3_choose_conv_fused_stem_s2(const y3_op &op0, const y3_op &op1, const y3_o
   if (!y3_conv_stem_mfma_supported(op0) || op0.out_c != 32 || (op0.flags & Y3_F_RESIDUAL)) return false;
   if (!(op0.flags & Y3_F_LEAKY) || !(op1.flags & Y3_F_LEAKY)) return false;   // the kernel hard-wires LeakyReLU(0.1)
   if ((op0.flags | op1.flags) & (Y3_F_MISH | Y3_F_LOGISTIC)) return false;
+  if (y3_is_grouped(op0) || y3_is_grouped(op1)) return false;
   if (op1.kind != Y3_OP_CONV || op1.dtype != op0.dtype || op1.ksize != 3 || op1.stride != 2 || op1.pad != 1) return false;
   if (op1.in_c != 32 || op1.out_c != 64 || op1.out_ld % 8 != 0 || op1.out_ld < 64) return false;
   if (op1.flags & (Y3_F_RESIDUAL | Y3_F_OUT_F32 | Y3_F_IN_NCHW_F32 | Y3_F_IN_NHWC_U8BGR | Y3_F_PLAN_INPUT)) return false;
@@ -995,6 +996,7 @@ bool y3_choose_conv_fused_resblock(const y3_op &op0, const y3_op &op1, const y3_
   if ((op0.flags & (bad | Y3_F_RESIDUAL)) || (op1.flags & bad)) return false;
   if (!(op0.flags & Y3_F_LEAKY) || !(op1.flags & Y3_F_LEAKY) || !(op1.flags & Y3_F_RESIDUAL)) return false;   // LeakyReLU only
   if ((op0.flags | op1.flags) & (Y3_F_MISH | Y3_F_LOGISTIC)) return false;
+  if (y3_is_grouped(op0) || y3_is_grouped(op1)) return false;
   if (op1.d_in != op0.d_out || op1.d_res != op0.d_in || op1.res_ld != op0.in_ld) return false;
   if (op0.in_h != op1.in_h || op0.in_w != op1.in_w || op0.batch != op1.batch) return false;
   if (op0.out_h != op0.in_h || op0.out_w != op0.in_w || op1.out_h != op1.in_h || op1.out_w != op1.in_w) return false;

@@ -1067,7 +1067,7 @@ static int launch_head_decode(const y3_op *ops, const y3_step &, const void *, c
 
 bool y3_choose_conv_head_decode(const y3_op &op0, const y3_op &op1, const y3_options &o, y3_step &st) {
   if (!o.fuse_head) return false;
-  if (op0.kind != Y3_OP_CONV || op1.kind != Y3_OP_YOLO || !y3_is16(op0.dtype)) return false;
+  if (op0.kind != Y3_OP_CONV || op1.kind != Y3_OP_YOLO || !y3_is16(op0.dtype) || y3_is_grouped(op0)) return false;
   if (op0.ksize != 1 || op0.stride != 1 || !(op0.flags & Y3_F_OUT_F32)) return false;
   if (op0.flags & (Y3_F_LEAKY | Y3_F_MISH | Y3_F_RESIDUAL | Y3_F_IN_NCHW_F32 | Y3_F_IN_NHWC_U8BGR | Y3_F_PLAN_INPUT)) return false;
   // (a logistic head conv -- new_coords networks -- is fine: the kernel applies the op's activation to its logits, linear or logistic)

@@ -41,14 +41,34 @@ CAP_NMS_DARKNET, CAP_SCORES_DARKNET, CAP_MULTI_LABEL, CAP_PREPROCESS_DARKNET, CA
 CAP_LAUNCH_LOG = 2048
 CAP_PLAN_OP_DIMS = 4096
 CAP_TILES = 8192
+CAP_GROUPED_CONV = 16384
 # Darknet's suppression measures (include/yolov3_hip.h: Y3_NMS_*), by the cfg's spelling of `nms_kind`
 NMS_IOU, NMS_GREEDY, NMS_DIOU = 0, 1, 2
 NMS_KINDS = {"iou": NMS_IOU, "greedynms": NMS_GREEDY, "diounms": NMS_DIOU}
-PATH_IGEMM, PATH_STEM, PATH_DIRECT, PATH_STEM_MFMA = 0, 1, 2, 3
+PATH_IGEMM, PATH_STEM, PATH_DIRECT, PATH_STEM_MFMA, PATH_GROUPED, PATH_DWISE = 0, 1, 2, 3, 4, 5
+
+
+class _Y3OpGroups(ctypes.Union):
+    """``groups`` of a conv op shares the four bytes of ``n_anchor``, which only YOLO ops read."""
+    _fields_ = [("n_anchor", ctypes.c_int32), ("groups", ctypes.c_int32)]
+
+    # four bytes with two names: compared by value, like the plain int32 field it replaces (code that walks Y3Op._fields_)
+    def __eq__(self, other):
+        return isinstance(other, _Y3OpGroups) and self.n_anchor == other.n_anchor
+
+    def __ne__(self, other):
+        return not self == other
+
+    def __hash__(self):
+        return hash(self.n_anchor)
+
+    def __repr__(self):
+        return "n_anchor/groups={}".format(self.n_anchor)
 
 
 class Y3Op(ctypes.Structure):
     """Mirror of ``struct y3_op`` (include/yolov3_hip.h)."""
+    _anonymous_ = ("_groups",)
     _fields_ = [
         ("kind", ctypes.c_int32), ("dtype", ctypes.c_int32), ("flags", ctypes.c_uint32),
         ("batch", ctypes.c_int32),
@@ -58,7 +78,7 @@ class Y3Op(ctypes.Structure):
         ("res_ld", ctypes.c_int32), ("k_ld", ctypes.c_int32), ("cout_pad", ctypes.c_int32),
         ("d_in", ctypes.c_void_p), ("d_out", ctypes.c_void_p), ("d_res", ctypes.c_void_p),
         ("d_weight", ctypes.c_void_p), ("d_scale", ctypes.c_void_p), ("d_bias", ctypes.c_void_p),
-        ("n_anchor", ctypes.c_int32), ("n_attr", ctypes.c_int32),
+        ("_groups", _Y3OpGroups), ("n_attr", ctypes.c_int32),
         ("anchor_w", ctypes.c_float * 8), ("anchor_h", ctypes.c_float * 8),
         ("row_offset", ctypes.c_int32), ("rows_total", ctypes.c_int32),
         ("net_w", ctypes.c_float), ("net_h", ctypes.c_float),
@@ -257,7 +277,7 @@ def require_capabilities(needs, what):
     that were to be letterboxed, pool the reference's way where Darknet's rule was asked for, suppress by the
     reference's rule where Darknet's was asked for, score boxes by the reference's soft-max where Darknet's logistic scores
     were asked for, lack the multi-label expansion, lack Darknet's float preprocessing, reject a [reorg] op as of unknown kind,
-    or lack the tile cutter and the tiled detection tail."""
+    lack the tile cutter and the tiled detection tail, or run a grouped conv as a dense one."""
     missing = needs & ~capabilities()
     if missing:
         names = [n for n, b in (("mish", CAP_MISH), ("scale_x_y", CAP_SCALE_X_Y), ("logistic", CAP_LOGISTIC),
@@ -266,7 +286,7 @@ def require_capabilities(needs, what):
                                 ("Darknet class scores", CAP_SCORES_DARKNET),
                                 ("multi-label detections", CAP_MULTI_LABEL),
                                 ("Darknet preprocessing", CAP_PREPROCESS_DARKNET), ("reorg", CAP_REORG),
-                                ("tiled inference", CAP_TILES)) if missing & b]
+                                ("tiled inference", CAP_TILES), ("grouped convolution", CAP_GROUPED_CONV)) if missing & b]
         raise HipLibraryError("{}: the loaded libyolov3_hip.so cannot compute {} (rebuild: make -C pytorch-yolov3_amd/csrc)"
                               .format(what, ", ".join(names)))
 
@@ -354,6 +374,31 @@ class device_cus:
 
     def __exit__(self, *exc):
         lib().y3_set_tuning(b"device_cus", 0)
+        return False
+
+
+class grouped_generic:
+    """``with grouped_generic():`` every grouped conv laid out and planned inside the block runs ``conv_grouped_*``
+    (``y3_set_tuning("grouped_generic", 1)``: ``y3_conv_path`` answers 4 for it), the depthwise ones included; the key is back at
+    what it was before when the block ends.  Weights are laid out by the path the library answers, so a network must compile its plans inside
+    the block it is to run under.  Same bits either way: tests and A/B runs only."""
+
+    current = 0          # the key's value as this class last set it (the library has no getter; nothing else in the package sets it)
+
+    def __init__(self, on=True):
+        self.on = int(bool(on))
+
+    def __enter__(self):
+        if not capabilities() & CAP_GROUPED_CONV:
+            raise HipLibraryError("the loaded libyolov3_hip.so has no grouped convolution (rebuild: make -C pytorch-yolov3_amd/csrc)")
+        self.before = grouped_generic.current
+        check(lib().y3_set_tuning(b"grouped_generic", self.on))
+        grouped_generic.current = self.on
+        return self
+
+    def __exit__(self, *exc):
+        lib().y3_set_tuning(b"grouped_generic", self.before)      # (what it was: a nested block leaves the outer one's value)
+        grouped_generic.current = self.before
         return False
 
 

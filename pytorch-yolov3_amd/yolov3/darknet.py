@@ -20,7 +20,7 @@ import torch
 
 from . import _hip
 from .cfgparse import parse_config
-from .plan import build_plan, check_blocks, check_pool_mode
+from .plan import build_plan, check_blocks, check_grouped_conv, check_pool_mode
 from .plan_ops import STORAGE, fill_ops, head_views, multi_label_options, padded_weight_dims
 from .plan_ops import _round_up, fill_maxpool_op, yolo_decode_flags  # noqa: F401  (lived here; callers import them from here)
 from .weights import conv_layout, read_darknet_weights
@@ -50,6 +50,23 @@ DTYPES = {
 }
 DTYPE_ALIASES = {"float32": "float32", "fp32": "float32", "f32": "float32", "bf16": "bf16", "bfloat16": "bf16",
                  "fp16": "fp16", "f16": "fp16", "float16": "fp16", "half": "fp16"}
+
+
+def grouped_weight_layout(path, w, groups, cout_pad, k_ld):
+    """Host array (float32, zero padded) of a grouped conv's kernel ``w`` (Cout, Cin / groups, k, k) in the layout of kernel
+    family ``path`` (include/yolov3_hip.h: y3_conv_path).  PATH_GROUPED: [cout_pad][k_ld], row = output channel, column
+    (ky * k + kx) * (Cin / groups) + c: the implicit-GEMM layout with the group's channel count.  PATH_DWISE (one channel per
+    group): [k * k][k_ld], row = tap ky * k + kx, column = channel."""
+    cout, cg, k = w.shape[0], w.shape[1], w.shape[2]
+    if path == _hip.PATH_DWISE:
+        if cg != 1 or groups != cout:
+            raise ValueError("depthwise layout asked for a kernel of shape {} with groups={}".format(w.shape, groups))
+        host = np.zeros((k * k, k_ld), dtype=np.float32)
+        host[:, :cout] = w.reshape(cout, k * k).T
+        return host
+    host = np.zeros((cout_pad, k_ld), dtype=np.float32)
+    host[:cout, :k * k * cg] = w.transpose(0, 2, 3, 1).reshape(cout, k * k * cg)
+    return host
 
 
 class BlockInfo(object):
@@ -189,6 +206,8 @@ class Darknet(object):
                 self.blocks_to_cache.add(i + blk["from"])
         check_blocks(self.blocks)       # what the kernels cannot compute is refused here, not run with other semantics
         self._out_channels, self._convs = conv_layout(self.blocks, self.net_info)
+        for c in self._convs:           # groups= against the channel counts the layout has just worked out
+            check_grouped_conv(self.blocks, c["block_idx"], c["cin"])
         if self.blocks and self.blocks[0]["type"] != "convolutional":
             raise ValueError("the first block must be [convolutional] (it reads the network input)")
         self.modules_ = [BlockInfo(i, b) for i, b in enumerate(self.blocks)]
@@ -338,11 +357,14 @@ class Darknet(object):
         if key in self._dev_weights:
             return self._dev_weights[key]
         c = self._convs[slot]
-        cout, cin, k = c["cout"], c["cin"], c["k"]
+        cout, cin, k, groups = c["cout"], c["cin"], c["k"], c.get("groups", 1)
         w = self._params[slot]["weight"].astype(np.float32)
         scale, bias = self._fold_bn(slot)
-        cout_pad, k_ld = padded_weight_dims(path, cout, cin, k, es)
-        if path == _hip.PATH_STEM_MFMA:
+        cout_pad, k_ld = padded_weight_dims(path, cout, cin, k, es, groups)
+        if path in (_hip.PATH_GROUPED, _hip.PATH_DWISE):
+            host = grouped_weight_layout(path, w, groups, cout_pad, k_ld)
+            dw = torch.from_numpy(to_bits(host).view(np.int16) if to_bits is not None else host).to(dev)
+        elif path == _hip.PATH_STEM_MFMA:
             # 16-bit [32][32]: row = output channel, k = ky*9 + kx*3 + c_mem with c_mem the BYTE order of the
             # uint8 BGR frame (c_mem = 2 - c_rgb), zero padded (csrc/conv_small.hip: conv_stem_mfma_kernel)
             host = np.zeros((cout_pad, k_ld), dtype=np.float32)

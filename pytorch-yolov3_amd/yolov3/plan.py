@@ -121,6 +121,28 @@ def check_region(blocks, i):
                          "filters={})".format(i, num * (5 + classes), i - 1, head.get("type"), head.get("filters")))
 
 
+def check_grouped_conv(blocks, i, cin):
+    """Refuse, naming block and numbers, a ``groups=`` on conv block ``i`` (``cin`` input channels) that the grouped kernels do
+    not compute.  Called where the channel count is known: by ``infer_shapes`` for every plan and by ``Darknet`` on the
+    descriptors of ``weights.conv_layout``."""
+    blk = blocks[i]
+    groups = int(blk.get("groups", 1))
+    if groups == 1:
+        return
+    if groups < 1:
+        raise ValueError("conv block {}: grouped convolution with groups={} (at least 1)".format(i, groups))
+    if i == 0:
+        raise ValueError("conv block {}: grouped convolution (groups={}) is not supported on the conv that reads the network "
+                         "input".format(i, groups))
+    filters = int(blk["filters"])
+    if cin % groups or filters % groups:
+        raise ValueError("conv block {}: grouped convolution: groups={} does not divide {} input channels and filters={}".format(
+            i, groups, cin, filters))
+    if i + 1 < len(blocks) and blocks[i + 1]["type"] in HEAD_KINDS:
+        raise ValueError("conv block {}: grouped convolution (groups={}) is not supported directly in front of {} block {} (a "
+                         "detection-head conv)".format(i, groups, blocks[i + 1]["type"], i + 1))
+
+
 def check_blocks(blocks):
     """Refuse, naming the block, what the kernels cannot compute: any of it would otherwise run with different semantics
     and return wrong boxes without an error."""
@@ -131,8 +153,6 @@ def check_blocks(blocks):
             if act not in ACTIVATIONS:
                 raise ValueError("conv block {}: activation {!r} is not supported (only {})".format(
                     i, act, ", ".join(ACTIVATIONS)))
-            if int(blk.get("groups", 1)) != 1:
-                raise ValueError("conv block {}: grouped convolution (groups={}) is not supported".format(i, blk["groups"]))
             if int(blk.get("dilation", 1)) != 1:
                 raise ValueError("conv block {}: dilated convolution (dilation={}) is not supported".format(
                     i, blk["dilation"]))
@@ -221,6 +241,7 @@ def infer_shapes(blocks, net_info, height, width, pool="reference"):
     for i, blk in enumerate(blocks):
         kind = blk["type"]
         if kind == "convolutional":
+            check_grouped_conv(blocks, i, c)       # (groups= against the input channel count, known here)
             k, s = blk["size"], blk["stride"]
             pad = (k - 1) // 2 if "pad" in blk else 0
             h = (h + 2 * pad - k) // s + 1
@@ -251,8 +272,8 @@ def infer_shapes(blocks, net_info, height, width, pool="reference"):
             if kind == "reorg" and c % (s * s):
                 raise ValueError("reorg block {}: {} channels are not a multiple of stride*stride = {}".format(i, c, s * s))
             c, h, w = c * s * s, h // s, w // s
-        elif kind in HEAD_KINDS:
-            pass
+        elif kind in HEAD_KINDS or kind == "dropout":
+            pass                                   # ([dropout]: Darknet skips it at inference; its keys are read and ignored)
         else:
             raise ValueError("unsupported block type {!r} (block {})".format(kind, i))
         if h <= 0 or w <= 0:
@@ -290,6 +311,9 @@ def build_plan(blocks, net_info, batch, height, width, elem_size, reuse=True, fu
         elif kind == "route":
             for j in blk["layers"]:
                 readers[j].append((i, "route"))
+        elif kind == "dropout":
+            if i > 0:
+                readers[i - 1].append((i, "route"))   # an alias of its input, as a single-layer route of -1 is
         elif kind == "shortcut":
             readers[i - 1].append((i, "sc_prev"))
             readers[i + blk["from"]].append((i, "sc_from"))
@@ -306,9 +330,10 @@ def build_plan(blocks, net_info, batch, height, width, elem_size, reuse=True, fu
 
     # ---- concat placement ------------------------------------------------------------------
     def resolve(j):
-        """follow single-source routes down to the block that really produces the data"""
-        while kinds[j] == "route" and len(blocks[j]["layers"]) == 1 and route_groups(blocks[j])[0] == 1:
-            j = blocks[j]["layers"][0]
+        """follow single-source routes (and [dropout] blocks) down to the block that really produces the data"""
+        while j > 0 and (kinds[j] == "dropout" or
+                         (kinds[j] == "route" and len(blocks[j]["layers"]) == 1 and route_groups(blocks[j])[0] == 1)):
+            j = j - 1 if kinds[j] == "dropout" else blocks[j]["layers"][0]
         return j
 
     buffers = {}            # id -> dict(bytes, first, last)
@@ -389,6 +414,8 @@ def build_plan(blocks, net_info, batch, height, width, elem_size, reuse=True, fu
                             # keep-every-tensor debugging mode.  Whether a fused kernel exists is the executor's call.
                             fuse_next=bool(fuse and i not in conv_fused and i + 1 < n and
                                            kinds[i + 1] == "convolutional" and readers[i] == [(i + 1, "in")]))
+            if int(blk.get("groups", 1)) > 1:
+                op["groups"] = int(blk["groups"])      # (ordinary convs carry no key: their op dicts are what they were)
             if blk["activation"] == "mish":
                 op["mish"] = True
             elif blk["activation"] == "logistic":
@@ -415,6 +442,8 @@ def build_plan(blocks, net_info, batch, height, width, elem_size, reuse=True, fu
                 op["form3d"] = True                # the space-to-depth form (default: Darknet's original flat form)
             ops.append(op)
             tensor_of[i] = out
+        elif kind == "dropout":
+            tensor_of[i] = prev_tensor(i)          # no op, no buffer
         elif kind == "shortcut":
             if i in fused_into:
                 pass                               # produced by the conv's epilogue

@@ -16,10 +16,15 @@ def _round_up(v, m):
     return (v + m - 1) // m * m
 
 
-def padded_weight_dims(path, cout, cin, k, es):
+def padded_weight_dims(path, cout, cin, k, es, groups=1):
     """``(cout_pad, k_ld)`` of a conv's device weights in the layout of kernel family ``path`` (``y3_conv_path``), elements of
     ``es`` bytes: the 32 x 32 block of the MFMA stem, the stem's [K][cout rounded to 8], or rows of K rounded to 128 bytes
-    under cout rounded to 128."""
+    under cout rounded to 128.  A grouped conv (``cin`` input channels in all, ``groups`` of them): rows of the group's
+    K = k * k * cin / groups rounded to 8 elements under cout rounded to 8; a depthwise one k * k rows of cout rounded to 8."""
+    if path == _hip.PATH_DWISE:
+        return _round_up(cout, 8), _round_up(cout, 8)
+    if path == _hip.PATH_GROUPED:
+        return _round_up(cout, 8), _round_up(k * k * (cin // groups), 8)
     if path == _hip.PATH_STEM_MFMA:
         return 32, 32
     if path == _hip.PATH_STEM:
@@ -123,10 +128,14 @@ def fill_ops(desc, net_info, convs, dtype, batch, input_mode, scores, opt, mem):
             if res is not None:
                 op.flags |= _hip.F_RESIDUAL
             c = convs[od["slot"]]
+            groups = int(od.get("groups", 1))
+            if groups > 1:
+                op.groups = groups
+                needs |= _hip.CAP_GROUPED_CONV
             # provisional padded sizes so that y3_conv_path can judge the shape
             op.cout_pad, op.k_ld = padded_weight_dims(_hip.PATH_IGEMM, c["cout"], c["cin"], c["k"], es)
             path = lib.y3_conv_path(ctypes.byref(op))     # (does not depend on the plan options)
-            op.cout_pad, op.k_ld = padded_weight_dims(path, c["cout"], c["cin"], c["k"], es)
+            op.cout_pad, op.k_ld = padded_weight_dims(path, c["cout"], c["cin"], c["k"], es, groups)
             op.d_weight, op.d_scale, op.d_bias = mem.conv(od["slot"], path)
             nfrag = int(lib.y3_conv_fragment_weight_bytes(ctypes.byref(op), p_opt))
             if nfrag:

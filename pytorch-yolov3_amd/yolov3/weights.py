@@ -6,7 +6,8 @@ files of Darknet's version 0.1, whose ``seen`` counter is 32 bits), then float32
 values; per ``[convolutional]`` block in cfg order either
 ``beta, gamma, running_mean, running_var`` (each Cout values, when the block
 has a truthy ``batch_normalize``) or ``conv bias`` (Cout), followed by the conv
-kernel in (Cout, Cin, kh, kw) order.
+kernel in (Cout, Cin, kh, kw) order -- (Cout, Cin / groups, kh, kw) for a block with
+``groups=``, Darknet's ``filters * (c / groups) * size * size`` values.
 
 Real YOLOv3 checkpoints cannot be fetched here (no network), so tests and the
 benchmark use *procedural* weights: every value is a pure function of
@@ -26,7 +27,8 @@ def conv_layout(blocks, net_info):
     """Per-block channel bookkeeping (reference darknet.py:229-313).
 
     Returns a list (one entry per block) of output channel counts, and a list
-    of conv descriptors ``dict(block_idx, cin, cout, k, bn)`` in cfg order.
+    of conv descriptors ``dict(block_idx, cin, cout, k, groups, bn)`` in cfg order.  ``cin`` is the block's input
+    channel count whatever ``groups`` says; a filter of a grouped conv spans ``cin // groups`` of them.
     """
     out_ch = []
     convs = []
@@ -37,7 +39,7 @@ def conv_layout(blocks, net_info):
         if kind == "convolutional":
             cur = blk["filters"]
             convs.append(dict(
-                block_idx=i, cin=prev, cout=cur, k=blk["size"],
+                block_idx=i, cin=prev, cout=cur, k=blk["size"], groups=int(blk.get("groups", 1)),
                 # builder keys on presence (darknet.py:237), loader on
                 # presence AND truthiness (darknet.py:428)
                 bn_module="batch_normalize" in blk,
@@ -66,14 +68,14 @@ def stream_length(blocks, net_info):
     n = 0
     for c in convs:
         n += (4 if c["bn"] else 1) * c["cout"]
-        n += c["cout"] * c["cin"] * c["k"] * c["k"]
+        n += c["cout"] * (c["cin"] // c["groups"]) * c["k"] * c["k"]      # Darknet: filters * (c / groups) * size * size
     return n
 
 
 def read_darknet_weights(path, blocks, net_info):
     """Read a ``.weights`` file -> (header int32[5], or int32[4] for a version 0.1 file, list of per-conv dicts).
 
-    Each dict has ``weight`` (Cout,Cin,k,k) and either ``bn_beta, bn_gamma,
+    Each dict has ``weight`` (Cout,Cin/groups,k,k) and either ``bn_beta, bn_gamma,
     bn_mean, bn_var`` or ``bias``.  A short file raises ``RuntimeError`` (the
     reference fails in ``view_as``); trailing bytes are ignored like the
     reference does.
@@ -102,7 +104,7 @@ def read_darknet_weights(path, blocks, net_info):
 
     params = []
     for c in convs:
-        co, ci, k, bi = c["cout"], c["cin"], c["k"], c["block_idx"]
+        co, ci, k, bi = c["cout"], c["cin"] // c["groups"], c["k"], c["block_idx"]
         entry = dict(block_idx=bi)
         if c["bn"]:
             entry["bn_beta"] = take(co, "bn beta", bi).copy()
@@ -205,7 +207,7 @@ def synth_params(blocks, net_info, seed=0, obj_bias=-3.0, calib=None,
     for li, c in enumerate(convs):
         if upto_conv is not None and li >= upto_conv:
             break
-        co, ci, k, bi = c["cout"], c["cin"], c["k"], c["block_idx"]
+        co, ci, k, bi = c["cout"], c["cin"] // c["groups"], c["k"], c["block_idx"]      # (a filter spans its group's channels)
         fan_in = ci * k * k
         entry = dict(block_idx=bi)
         base = li * 8

@@ -1,0 +1,487 @@
+"""Grouped and depthwise convs without a GPU: what the cfg reader accepts and refuses, Darknet's stream order for ``groups=``, the
+two device weight layouts, [dropout] as an alias, the ``groups`` field of ``y3_op`` and what the library's chooser and plan
+creation say about it.  tests/grouped_restate.py is held to ``torch.nn.functional.conv2d(..., groups=G)`` here, and the one-op
+cases of tests/test_gpu_grouped.py are shown to fit their gates on the CPU first: the restatement accumulating in float32 against
+the same restatement accumulating in float64, on the inputs the GPU test uses."""
+import ctypes
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import yolov3
+from yolov3 import _hip
+from yolov3 import weights as W
+from yolov3.cfgparse import parse_config
+from yolov3.plan import build_plan
+from yolov3.plan_ops import fill_ops, padded_weight_dims
+
+import grouped_cases as GC
+import grouped_restate as GR
+import kernel_choice_util as kc
+from golden_util import GOLDEN, MODELS
+
+CFG = os.path.join(GOLDEN, "cfg", "grouped.cfg")
+# block -> (groups, runs on the depthwise kernel) of grouped.cfg
+GROUPED_BLOCKS = {2: (48, True), 7: (64, True), 9: (24, True), 11: (20, False), 14: (4, False), 18: (3, False), 20: (2, False),
+                  22: (16, True), 24: (32, True), 26: (80, True)}
+no_gpu = pytest.mark.skipif(torch.cuda.is_available(), reason="fake device addresses must never reach a library that can launch")
+
+HEAD = """[net]
+width=32
+height=32
+channels=3
+
+[convolutional]
+batch_normalize=1
+filters=12
+size=3
+stride=1
+pad=1
+activation=leaky
+"""
+TAIL = """
+[convolutional]
+filters=18
+size=1
+stride=1
+pad=1
+activation=linear
+
+[yolo]
+mask=0,1,2
+anchors=6,8, 12,10, 20,24
+classes=1
+num=3
+"""
+
+
+def _conv(filters, groups=None, extra=""):
+    g = "groups=%s\n" % groups if groups is not None else ""
+    return "\n[convolutional]\nbatch_normalize=1\nfilters=%d\n%ssize=3\nstride=1\npad=1\nactivation=leaky\n%s" % (filters, g, extra)
+
+
+def _write(tmp_path, text):
+    p = tmp_path / "net.cfg"
+    p.write_text(text)
+    return str(p)
+
+
+# ---------------------------------------------------------------------------------------------- the restatement
+
+@pytest.mark.parametrize("cin,cout,groups,k,s,pad,act,bn", [
+    (12, 12, 12, 3, 1, 1, "leaky", True), (12, 12, 12, 5, 2, 2, "mish", True), (8, 16, 4, 3, 1, 1, "linear", True),
+    (24, 48, 3, 3, 2, 0, "leaky", True), (40, 48, 2, 1, 1, 0, "logistic", False), (20, 20, 1, 3, 1, 1, "leaky", False)])
+def test_restatement_is_conv2d_with_groups(cin, cout, groups, k, s, pad, act, bn):
+    gen = torch.Generator().manual_seed(cin * 131 + cout * 7 + groups)
+    x = torch.rand((2, cin, 9, 11), generator=gen) - 0.5
+    p = {"weight": (torch.rand((cout, cin // groups, k, k), generator=gen) - 0.5).numpy()}
+    if bn:
+        p.update(bn_gamma=(torch.rand(cout, generator=gen) + 0.5).numpy(), bn_beta=(torch.rand(cout, generator=gen) - 0.5).numpy(),
+                 bn_mean=(torch.rand(cout, generator=gen) - 0.5).numpy(), bn_var=(torch.rand(cout, generator=gen) + 0.5).numpy())
+    else:
+        p["bias"] = (torch.rand(cout, generator=gen) - 0.5).numpy()
+    got = GR.grouped_conv_block(x, p, s, pad, act, groups, accumulate="f64")
+    want = GR.conv2d_f64(x, p, s, pad, act, groups)
+    assert got.shape == want.shape and got.shape[1] == cout
+    # the oracle rounds its float64 conv to float32 before batch norm and activation run in float32
+    torch.testing.assert_close(got.double(), want, rtol=2e-6, atol=2e-6)
+    if groups > 1:      # ... and the groups matter: the dense conv of the first group's filters alone is another tensor
+        assert not torch.allclose(got[:, :cout // groups].double(), want[:, cout // groups:2 * cout // groups])
+
+
+@pytest.mark.parametrize("cid", sorted(GC.CASES))
+def test_gates_fit_the_one_op_cases_on_the_cpu(cid):
+    """float32 accumulation against float64 accumulation in the restatement, on the GPU test's inputs, under the GPU test's
+    gates: a kernel that sums in float32 in any order can pass them"""
+    import test_gpu_bf16 as G
+    case = GC.CASES[cid]
+    for dtype in GC.DTYPES:
+        data = GC.make(case, dtype)
+        f32, f64 = GC.reference(case, dtype, data, "f32"), GC.reference(case, dtype, data, "f64")
+        assert f32.shape == (3, case["cout"]) + GC.out_hw(case) and bool(torch.isfinite(f64).all())
+        if dtype == "float32":
+            np.testing.assert_allclose(f32.numpy(), f64.numpy(), err_msg=cid, **G.F32_BLOCK_TOL)
+        else:
+            rnd = G.MODES[dtype]["rnd"]
+            G._close_bf16(rnd(f32), rnd(f64), "%s %s" % (cid, dtype), None, dtype)
+
+
+# ---------------------------------------------------------------------------------------------- the cfg reader
+
+@pytest.mark.parametrize("body,msg", [
+    (_conv(16, 5), r"conv block 1: grouped convolution: groups=5 does not divide 12 input channels and filters=16"),
+    (_conv(16, 3), r"conv block 1: grouped convolution: groups=3 does not divide 12 input channels and filters=16"),
+    (_conv(12, 0), r"conv block 1: grouped convolution with groups=0"),
+    (_conv(12, -2), r"conv block 1: grouped convolution with groups=-2"),
+    (_conv(12, 12, "dilation=2\n"), r"dilated convolution"),
+])
+def test_refuses_by_message(tmp_path, body, msg):
+    cfg = _write(tmp_path, HEAD + body + TAIL)
+    with pytest.raises(ValueError, match=msg):
+        yolov3.Darknet(cfg)
+    blocks, net_info = parse_config(cfg)
+    with pytest.raises(ValueError, match=msg):
+        build_plan(blocks, net_info, 1, 32, 32, 4)
+
+
+def test_refuses_a_grouped_stem_and_a_grouped_head_conv(tmp_path):
+    stem = HEAD.replace("filters=12\n", "filters=12\ngroups=3\n") + TAIL
+    with pytest.raises(ValueError, match=r"conv block 0: grouped convolution \(groups=3\) is not supported on the conv that reads the network input"):
+        yolov3.Darknet(_write(tmp_path, stem))
+    head = HEAD + _conv(18) + TAIL.replace("filters=18\n", "filters=18\ngroups=3\n")
+    with pytest.raises(ValueError, match=r"conv block 2: grouped convolution \(groups=3\) is not supported directly in front of yolo block 3"):
+        yolov3.Darknet(_write(tmp_path, head))
+
+
+def test_accepts_groups_that_divide_both_counts(tmp_path):
+    for groups, filters in ((1, 16), (2, 16), (4, 16), (12, 12), (12, 24)):
+        net = yolov3.Darknet(_write(tmp_path, HEAD + _conv(filters, groups) + TAIL))
+        assert net._convs[1]["groups"] == groups and net._convs[1]["cin"] == 12
+
+
+def test_mini_cfg_groups_on_the_first_conv_stays_refused(tmp_path):
+    text = open(MODELS["mini"]).read()
+    head = "[convolutional]\n"
+    i = text.index(head) + len(head)
+    cfg = _write(tmp_path, text[:i] + "groups=2\n" + text[i:])
+    with pytest.raises(ValueError, match=r"grouped convolution \(groups=2\) is not supported"):
+        yolov3.Darknet(cfg)
+    blocks, net_info = parse_config(cfg)
+    with pytest.raises(ValueError, match=r"grouped convolution \(groups=2\) is not supported"):
+        build_plan(blocks, net_info, 1, 64, 64, 4)
+
+
+def test_dropout_was_an_unsupported_block_and_is_an_alias_now():
+    net = yolov3.Darknet(CFG)
+    assert net.blocks[5]["type"] == "dropout"
+    for reuse in (True, False):
+        d = build_plan(net.blocks, net.net_info, 2, 64, 96, 2, reuse=reuse)
+        assert all(op["block"] != 5 for op in d["ops"]) and "t5" not in d["buffers"]
+        assert d["tensor_of"][5] is d["tensor_of"][4] and d["shapes"][5] == d["shapes"][4] == (16, 64, 96)
+        conv6 = next(op for op in d["ops"] if op["block"] == 6)
+        assert conv6["inp"] is d["tensor_of"][4]
+        # the shortcut in front of it is still fused into conv 3, which a second reader of conv 3 would forbid
+        conv3 = next(op for op in d["ops"] if op["block"] == 3)
+        assert conv3["res"] is d["tensor_of"][0] and conv3["out"] is d["tensor_of"][4]
+
+
+def test_plan_of_grouped_cfg():
+    net = yolov3.Darknet(CFG)
+    d = build_plan(net.blocks, net.net_info, 2, 64, 96, 2)
+    convs = {op["block"]: op for op in d["ops"] if op["kind"] == "conv"}
+    assert {b: op.get("groups") for b, op in convs.items() if "groups" in op} == {b: g for b, (g, _) in GROUPED_BLOCKS.items()}
+    # operands that are channel slices of concat buffers: conv 22 reads one slice of route 23's buffer and writes the other;
+    # conv 24 writes into route 25's; conv 26's fused shortcut operand is route 25 itself
+    t = convs[22]
+    assert (t["inp"].buf, t["inp"].off, t["inp"].ld, t["inp"].c) == ("cat23", 0, 32, 16)
+    assert (t["out"].buf, t["out"].off, t["out"].ld, t["out"].c) == ("cat23", 16, 32, 16)
+    assert (convs[24]["out"].buf, convs[24]["out"].off, convs[24]["out"].ld) == ("cat25", 0, 80)
+    assert (convs[18]["out"].buf, convs[18]["out"].off, convs[18]["out"].ld) == ("cat25", 32, 80)
+    assert convs[26]["res"] is d["tensor_of"][25] and d["tensor_of"][27] is convs[26]["out"]
+    assert not any(op["kind"] in ("add", "copy") for op in d["ops"])
+
+
+# ---------------------------------------------------------------------------------------------- the weight stream
+
+def test_stream_length_and_round_trip(tmp_path):
+    blocks, net_info = parse_config(CFG)
+    _, convs = W.conv_layout(blocks, net_info)
+    want = 0
+    for c in convs:
+        blk = blocks[c["block_idx"]]
+        g = int(blk.get("groups", 1))
+        assert c["groups"] == g and c["cin"] % g == 0
+        want += (4 if blk.get("batch_normalize") else 1) * blk["filters"] + blk["filters"] * (c["cin"] // g) * blk["size"] ** 2
+    assert W.stream_length(blocks, net_info) == want == 25374
+    params = W.synth_params(blocks, net_info, seed=3)
+    for c, p in zip(convs, params):
+        assert p["weight"].shape == (c["cout"], c["cin"] // c["groups"], c["k"], c["k"])
+    path = str(tmp_path / "grouped.weights")
+    W.write_darknet_weights(path, params)
+    assert os.path.getsize(path) == 20 + 4 * want
+    _, back = W.read_darknet_weights(path, blocks, net_info)
+    assert len(back) == len(params)
+    for a, b in zip(params, back):
+        assert sorted(a) == sorted(b)
+        for key in a:
+            assert np.array_equal(np.asarray(a[key]), np.asarray(b[key])), key
+
+
+def test_stream_order_is_cout_cin_over_groups_k_k(tmp_path):
+    """a hand-made stream: bias first (no batch norm), then filters * (c / groups) * size * size values, filter-major"""
+    cfg = _write(tmp_path, HEAD + "\n[convolutional]\nfilters=4\ngroups=2\nsize=3\nstride=1\npad=1\nactivation=linear\n" + _conv(18) + TAIL)
+    blocks, net_info = parse_config(cfg)
+    n0 = 4 * 12 + 12 * 3 * 9
+    n1 = 4 + 4 * 6 * 9
+    total = W.stream_length(blocks, net_info)
+    assert total == n0 + n1 + (4 * 18 + 18 * 4 * 9) + (18 + 18 * 18)
+    stream = np.arange(total, dtype=np.float32)
+    path = str(tmp_path / "hand.weights")
+    with open(path, "wb") as fh:
+        np.array([0, 2, 0, 0, 0], dtype=np.int32).tofile(fh)
+        stream.tofile(fh)
+    _, params = W.read_darknet_weights(path, blocks, net_info)
+    p = params[1]
+    assert np.array_equal(p["bias"], n0 + np.arange(4, dtype=np.float32))
+    assert p["weight"].shape == (4, 6, 3, 3)
+    for co in range(4):
+        for c in range(6):
+            for ky in range(3):
+                for kx in range(3):
+                    assert p["weight"][co, c, ky, kx] == n0 + 4 + ((co * 6 + c) * 3 + ky) * 3 + kx
+
+
+def test_ungrouped_synth_params_are_unchanged():
+    """groups == 1 leaves every hashed value where it was: the shipped cfgs' goldens do not move"""
+    blocks, net_info = parse_config(MODELS["mini"])
+    _, convs = W.conv_layout(blocks, net_info)
+    assert all(c["groups"] == 1 for c in convs)
+    p = W.synth_params(blocks, net_info, seed=0)[1]
+    c = convs[1]
+    fan = c["cin"] * c["k"] ** 2
+    a = np.sqrt(3.0 * 2.0 / (1.01 * fan))
+    want = (-a + 2 * a * W.hash_uniform(0, 8, c["cout"] * fan)).astype(np.float32).reshape(c["cout"], c["cin"], c["k"], c["k"])
+    assert np.array_equal(p["weight"], want)
+
+
+# ---------------------------------------------------------------------------------------------- device layouts
+
+def test_device_layouts_element_by_element():
+    net = yolov3.Darknet(CFG, dtype="float32")
+    net.set_params(W.synth_params(net.blocks, net.net_info, seed=1))
+    slot_of = {c["block_idx"]: s for s, c in enumerate(net._convs)}
+    for block, path in ((2, _hip.PATH_DWISE), (9, _hip.PATH_DWISE), (14, _hip.PATH_GROUPED), (18, _hip.PATH_GROUPED),
+                        (20, _hip.PATH_GROUPED), (11, _hip.PATH_GROUPED), (2, _hip.PATH_GROUPED)):
+        slot = slot_of[block]
+        c = net._convs[slot]
+        w = net._params[slot]["weight"]
+        cout, cg, k = c["cout"], c["cin"] // c["groups"], c["k"]
+        entry = net._device_weights(slot, path, "float32", "cpu")
+        host = entry["weight"].numpy()
+        scale, bias = net._fold_bn(slot)
+        assert (entry["cout_pad"], entry["k_ld"]) == padded_weight_dims(path, cout, c["cin"], k, 4, c["groups"])
+        assert entry["cout_pad"] == (cout + 7) // 8 * 8 and entry["scale"].numel() == entry["bias"].numel() == entry["cout_pad"]
+        assert np.array_equal(entry["scale"].numpy()[:cout], scale) and np.array_equal(entry["bias"].numpy()[:cout], bias)
+        seen = np.zeros(host.shape, dtype=bool)
+        if path == _hip.PATH_DWISE:
+            assert host.shape == (k * k, (cout + 7) // 8 * 8) and cg == 1
+            for ky in range(k):
+                for kx in range(k):
+                    for co in range(cout):
+                        assert host[ky * k + kx, co] == w[co, 0, ky, kx]
+                        seen[ky * k + kx, co] = True
+        else:
+            assert host.shape == (entry["cout_pad"], entry["k_ld"]) and entry["k_ld"] >= k * k * cg and entry["k_ld"] % 8 == 0
+            for co in range(cout):
+                for ky in range(k):
+                    for kx in range(k):
+                        for ci in range(cg):
+                            assert host[co, (ky * k + kx) * cg + ci] == w[co, ci, ky, kx]
+                            seen[co, (ky * k + kx) * cg + ci] = True
+        assert not host[~seen].any()                                  # the padding is zero
+        want, cp, k_ld = GC.device_weights(None, path, w)            # the GPU test's own layout code agrees
+        assert (cp, k_ld) == (entry["cout_pad"], entry["k_ld"]) and np.array_equal(want, host)
+    bits = net._device_weights(slot_of[2], _hip.PATH_DWISE, "bf16", "cpu")["weight"]
+    assert bits.dtype == torch.int16 and bits.shape == (9, 48)
+    assert torch.equal(bits.view(torch.bfloat16).float(), torch.from_numpy(net._params[slot_of[2]]["weight"].reshape(48, 9).T.copy()).bfloat16().float())
+
+
+# ---------------------------------------------------------------------------------------------- the C ABI
+
+def test_y3_op_keeps_its_size_and_offsets():
+    assert ctypes.sizeof(_hip.Y3Op) == 248
+    assert _hip.Y3Op.groups.offset == _hip.Y3Op.n_anchor.offset == 120 and _hip.Y3Op.n_attr.offset == 124
+    op = _hip.Y3Op()
+    op.groups = 7
+    assert op.n_anchor == 7
+    assert _hip.capabilities() & _hip.CAP_GROUPED_CONV == 16384
+
+
+def test_conv_path_sends_misaligned_depthwise_ops_to_the_grouped_kernel():
+    """the depthwise kernel loads and stores 16 bytes at a time: an op on 8-channel strides whose input, output or shortcut
+    operand does not start on a 16-byte boundary is answered 4, not 5 (and so runs instead of being refused)"""
+    lib = _hip.lib()
+    fake = kc._Fake()
+    ops = _one_op(fake, cin=24, cout=24, groups=24)
+    assert lib.y3_conv_path(ctypes.byref(ops[0])) == _hip.PATH_DWISE
+    for field in ("d_in", "d_out"):
+        ops = _one_op(fake, cin=24, cout=24, groups=24)
+        setattr(ops[0], field, getattr(ops[0], field) + 8)
+        assert lib.y3_conv_path(ctypes.byref(ops[0])) == _hip.PATH_GROUPED, field
+    ops = _one_op(fake, cin=24, cout=24, groups=24, flags=_hip.F_LEAKY | _hip.F_RESIDUAL, res_ld=24, d_res=fake(1 << 16) + 8)
+    assert lib.y3_conv_path(ctypes.byref(ops[0])) == _hip.PATH_GROUPED
+    ops = _one_op(fake, cin=24, cout=24, groups=24, flags=_hip.F_LEAKY | _hip.F_RESIDUAL, res_ld=24, d_res=fake(1 << 16))
+    assert lib.y3_conv_path(ctypes.byref(ops[0])) == _hip.PATH_DWISE
+
+
+def _fill(dtype, batch=2):
+    net = yolov3.Darknet(CFG, dtype=dtype)
+    es = kc.DTYPES[net.dtype][1]
+    desc = build_plan(net.blocks, net.net_info, batch, 64, 96, es, reuse=True, fuse=True)
+    fake = kc._Fake(net._convs, es)
+    ops, needs, frag = fill_ops(desc, net.net_info, net._convs, net.dtype, batch, "u8", net.scores, None, fake)
+    return net, ops, needs, frag, fake
+
+
+@pytest.mark.parametrize("dtype", ["float32", "bf16", "fp16"])
+def test_fill_ops_sets_groups_paths_and_the_capability(dtype):
+    lib = _hip.lib()
+    net, ops, needs, frag, _ = _fill(dtype)
+    assert needs == _hip.CAP_GROUPED_CONV | _hip.CAP_MISH
+    es = kc.DTYPES[net.dtype][1]
+    for op in ops:
+        if op.kind != _hip.OP_CONV:
+            continue
+        groups, dwise = GROUPED_BLOCKS.get(op.block_idx, (0, False))
+        assert op.groups == groups, op.block_idx
+        path = lib.y3_conv_path(ctypes.byref(op))
+        if groups:
+            assert path == (_hip.PATH_DWISE if dwise else _hip.PATH_GROUPED), op.block_idx
+            assert lib.y3_conv_fragment_weight_bytes(ctypes.byref(op), None) == 0
+            c = next(c for c in net._convs if c["block_idx"] == op.block_idx)
+            assert (op.cout_pad, op.k_ld) == padded_weight_dims(path, c["cout"], c["cin"], c["k"], es, groups)
+            _hip.check(lib.y3_set_tuning(b"grouped_generic", 1))
+            try:
+                assert lib.y3_conv_path(ctypes.byref(op)) == _hip.PATH_GROUPED
+            finally:
+                _hip.check(lib.y3_set_tuning(b"grouped_generic", 0))
+            assert lib.y3_conv_path(ctypes.byref(op)) == path
+        else:
+            assert path in (_hip.PATH_IGEMM, _hip.PATH_STEM, _hip.PATH_DIRECT, _hip.PATH_STEM_MFMA)
+    assert lib.y3_set_tuning(b"grouped_generic", 2) != 0 and b"grouped_generic" in lib.y3_last_error()
+    # a stale library is refused by name
+    real = _hip.capabilities
+    _hip.capabilities = lambda: real() & ~_hip.CAP_GROUPED_CONV
+    try:
+        with pytest.raises(_hip.HipLibraryError, match="grouped convolution"):
+            _hip.require_capabilities(needs, CFG)
+    finally:
+        _hip.capabilities = real
+
+
+@no_gpu
+@pytest.mark.parametrize("dtype", ["float32", "bf16", "fp16"])
+def test_plan_of_grouped_cfg_names_the_kernels(dtype):
+    """plan creation on fake addresses: which op runs which kernel, its FLOPs divided by groups, its weight bytes the group's"""
+    lib = _hip.lib()
+    net, ops, _, _, fake = _fill(dtype)
+    tag = {"float32": "f32", "bf16": "bf16", "fp16": "f16"}[dtype]
+    es = kc.DTYPES[net.dtype][1]
+    want = {2: "conv_dwise_%s_k3s1", 7: "conv_dwise_%s_k3s2", 9: "conv_dwise_%s_kn", 11: "conv_grouped_%s_oc1", 14: "conv_grouped_%s_oc8",
+            18: "conv_grouped_%s_oc8", 20: "conv_grouped_%s_oc8", 22: "conv_dwise_%s_k3s1", 24: "conv_dwise_%s_k3s1", 26: "conv_dwise_%s_k3s1"}
+    for generic in (0, 1):
+        _hip.check(lib.y3_set_tuning(b"grouped_generic", generic))
+        try:
+            if generic:
+                net, ops, _, _, fake = _fill(dtype)        # (the weight layout follows the path)
+            handle = ctypes.c_void_p()
+            _hip.check(lib.y3_plan_create(ops, len(ops), fake(4096), ctypes.byref(handle)))
+        finally:
+            _hip.check(lib.y3_set_tuning(b"grouped_generic", 0))
+        try:
+            for i, op in enumerate(ops):
+                name = lib.y3_plan_op_kernel(handle, i).decode()
+                if op.block_idx in want:
+                    first = want[op.block_idx] % tag
+                    if generic and "dwise" in first:
+                        first = "conv_grouped_%s_oc1" % tag
+                    assert name == first, (op.block_idx, name)
+                    dense = 2.0 * op.ksize ** 2 * op.in_c * op.out_c * op.out_h * op.out_w * op.batch
+                    assert lib.y3_plan_op_flops(handle, i) == dense / op.groups
+                    px_in, px_out = op.batch * op.in_h * op.in_w, op.batch * op.out_h * op.out_w
+                    nbytes = (px_in * op.in_c + px_out * op.out_c * (2 if op.flags & _hip.F_RESIDUAL else 1) +
+                              op.ksize ** 2 * (op.in_c // op.groups) * op.out_c) * es
+                    assert lib.y3_plan_op_bytes(handle, i) == nbytes
+                    assert _hip.plan_op_dims(handle, i)[1] % 64 == 0
+                else:
+                    assert "dwise" not in name and "grouped" not in name, (op.block_idx, name)
+        finally:
+            lib.y3_plan_destroy(handle)
+
+
+def _one_op(fake, cin=16, cout=16, groups=16, k=3, flags=_hip.F_LEAKY, **over):
+    ops = (_hip.Y3Op * 1)()
+    op = ops[0]
+    op.kind, op.dtype, op.flags, op.batch, op.block_idx = _hip.OP_CONV, _hip.Y3_BF16, flags, 1, 7
+    op.in_h = op.in_w = op.out_h = op.out_w = 8
+    op.in_c, op.in_ld, op.out_c, op.out_ld = cin, cin, cout, cout
+    op.ksize, op.stride, op.pad = k, 1, (k - 1) // 2
+    op.groups = groups
+    op.cout_pad, op.k_ld = 128, 1024
+    op.d_in, op.d_out, op.d_weight, op.d_scale, op.d_bias = (fake(1 << 16) for _ in range(5))
+    for key, val in over.items():
+        setattr(op, key, val)
+    return ops
+
+
+@no_gpu
+def test_plan_creation_refuses_the_bad_ops():
+    lib = _hip.lib()
+    fake = kc._Fake()
+
+    def create(ops):
+        handle = ctypes.c_void_p()
+        rc = lib.y3_plan_create(ops, 1, fake(4096), ctypes.byref(handle))
+        if rc == 0:
+            lib.y3_plan_destroy(handle)
+        return rc, lib.y3_last_error().decode()
+
+    assert create(_one_op(fake))[0] == 0
+    assert create(_one_op(fake, cin=24, cout=48, groups=3))[0] == 0
+    for ops, words in (
+            (_one_op(fake, groups=-1), "conv block 7: groups=-1"),
+            (_one_op(fake, cin=16, cout=16, groups=3), "conv block 7: groups=3 does not divide 16 input and 16 output channels"),
+            (_one_op(fake, cin=16, cout=20, groups=8), "conv block 7: groups=8 does not divide 16 input and 20 output channels"),
+            (_one_op(fake, flags=_hip.F_PLAN_INPUT | _hip.F_IN_NCHW_F32), "conv block 7: a grouped conv (groups=16) cannot read the network input"),
+            (_one_op(fake, flags=_hip.F_PLAN_INPUT | _hip.F_IN_NHWC_U8BGR), "cannot read the network input"),
+            (_one_op(fake, flags=_hip.F_PLAN_INPUT), "cannot read the network input"),
+            (_one_op(fake, flags=_hip.F_OUT_F32), "conv block 7: a grouped conv (groups=16) cannot store float32"),
+            (_one_op(fake, k_ld=8), "conv block 7: depthwise weights"),
+            (_one_op(fake, cin=32, cout=32, groups=4, k_ld=64), "conv block 7: grouped weights need k_ld >= 72"),
+            (_one_op(fake, cin=32, cout=32, groups=4, cout_pad=24), "conv block 7: grouped weights need")):
+        rc, err = create(ops)
+        assert rc == -1 and words in err, (words, rc, err)
+    # zero-initialised callers: groups 0 and 1 are the ordinary conv they always were
+    for g in (0, 1):
+        ops = _one_op(fake, cin=128, cout=128, groups=g, k_ld=9 * 128)
+        assert lib.y3_conv_path(ctypes.byref(ops[0])) == _hip.PATH_IGEMM
+        opt = _hip.options(auto_mask=_hip.AM_IGEMM_ONLY)     # (no kernel that would make a fragment-order weight copy here)
+        handle = ctypes.c_void_p()
+        _hip.check(lib.y3_plan_create_ex(ops, 1, fake(4096), ctypes.byref(opt), ctypes.byref(handle)))
+        assert lib.y3_plan_op_kernel(handle, 0).decode().startswith("conv_igemm")
+        lib.y3_plan_destroy(handle)
+
+
+# ---------------------------------------------------------------------------------------------- the grouped library's device code
+
+def test_grouped_library_code_objects_and_census():
+    """tests/test_code_object.py's checks on libyolov3_hip_grouped.so, the dependency of libyolov3_hip.so that holds conv_dwise and
+    conv_grouped: gfx950 code only, no kernel spills to scratch, budgets inside a CU, blocks of whole waves; and the census: every
+    compiled instance is launched by a footprint case of tests/test_gpu_grouped.py (tests/golden/kernel_instances_grouped.json,
+    recorded on an MI355X by tools/make_grouped_kernel_instances.py), one key per instance and dtype, and no recorded symbol is
+    missing from the library.  The main library holds none of these kernels, so its own census is what it was."""
+    import json
+
+    import test_code_object as T
+    if not os.path.exists(GC.GROUPED_LIB):
+        pytest.fail("libyolov3_hip_grouped.so is not built (python -c 'import __graft_entry__ as g; g.build()')")
+    kernels = GC.library_kernels()
+    names = sorted(k[".name"] for k in kernels)
+    assert len(names) == 15 and sum("conv_dwise_kernel" in n for n in names) == 9 and sum("conv_grouped_kernel" in n for n in names) == 6
+    for k in kernels:
+        assert k[".private_segment_fixed_size"] == 0, (k[".name"], "uses scratch memory (register spills)")
+        assert k[".vgpr_count"] + k.get(".agpr_count", 0) <= 512 and k[".group_segment_fixed_size"] == 0, k[".name"]
+        assert k[".wavefront_size"] == 64 and k[".max_flat_workgroup_size"] % 64 == 0, k[".name"]
+    with open(GC.CENSUS_FIXTURE) as fh:
+        fixture = json.load(fh)
+    uncovered, stale = GC.census_report(fixture, names)
+    assert not uncovered and not stale, (uncovered, stale)
+    assert sorted(fixture["footprint"]) == sorted("grouped_%s-%s" % (i, d) for i in (
+        "dwise_k3s1", "dwise_k3s2", "dwise_kn", "grouped_oc1", "grouped_oc8") for d in GC.DTYPES)
+    assert all(len(v) == 1 for v in fixture["footprint"].values())
+    assert len({v[0] for v in fixture["footprint"].values()}) == 15        # one key per (kernel instance, dtype)
+    with open(T.LIB, "rb") as fh:
+        main = {k[".name"] for _, elf in T._code_objects(fh.read()) for k in T._kernels(elf)}
+    assert not main & set(names)
