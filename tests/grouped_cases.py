@@ -52,7 +52,7 @@ DWISE = (
 
 # grouped kernel: the group shapes of tests/golden/cfg/grouped.cfg (4 groups of 8 -> 8, 3 groups of 8 -> 16, a 1x1 with 2 groups
 # of 20 -> 24: eight output channels per thread, with 16-byte and with scalar loads), 4 channels per group and a depthwise conv
-# on 20 channels (one output element per thread)
+# on 20 channels (one output element per thread); TINY_MAPS below adds maps of one pixel and of one pixel across
 GROUPED = [
     _gr("gr_4x8", 32, 32, 4, 13, 10), _gr("gr_4x8_s2_res", 32, 32, 4, 13, 10, s=2, res=True),
     _gr("gr_4x8_wide_res", 32, 32, 4, 7, 7, wide=True, res=True, act="mish"),
@@ -62,9 +62,19 @@ GROUPED = [
     _dw("gr_dw_c20", 20, 13, 10), _dw("gr_dw_c20_k5_res", 20, 7, 7, k=5, pad=2, res=True, act="linear"),
     # depthwise on 8-channel strides but at a channel offset of 4: addresses off the 16-byte grain, so not the depthwise kernel's
     _dw("gr_dw_c24_off4", 24, 7, 7, wide=True, off=4, res=True), _gr("gr_4x8_off4", 32, 32, 4, 7, 7, wide=True, off=4, res=True)]
+# ... and both forms on maps of one pixel and of one pixel across (stride 2 makes 1 x 3 and 3 x 1 of the latter: every tap row or
+# column but one lies outside), and 5x5 on one pixel, where 24 of the 25 taps lie outside
+TINY_MAPS = ((1, 1), (1, 5), (5, 1))
+GROUPED += (
+    [_gr("gr_%s_%dx%d_s%d" % (tag, h, w, s), c, c, 4, h, w, s=s)
+     for tag, c in (("4x8", 32), ("4x4", 16)) for h, w in TINY_MAPS for s in (1, 2) if not (s == 2 and (h, w) == (1, 1))] +
+    [_gr("gr_4x8_k5_1x1", 32, 32, 4, 1, 1, k=5, pad=2), _gr("gr_4x4_k5_1x1", 16, 16, 4, 1, 1, k=5, pad=2)])
 
 CASES = {c["id"]: c for c in DWISE + GROUPED}
 assert len(CASES) == len(DWISE) + len(GROUPED)
+# mish and logistic run __expf and v_rcp_f32: these cases stay on the toleranced gates alone; every other case is also held bit
+# for bit to tests/grouped_ordered.py
+NOT_ORDERED = ("dw_mish", "dw_logistic", "dw_res_mish", "gr_4x8_wide_res", "gr_4x4_wide_res")
 
 
 def out_hw(case):

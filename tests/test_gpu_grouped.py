@@ -4,6 +4,8 @@ tests/golden/cfg/grouped.cfg, and on strided slices of poisoned buffers.
 * One-op cases (tests/grouped_cases.py), float32 / bf16 / fp16, each against the restatement (tests/grouped_restate.py: the
   oracle's conv_block per group) computed from the same input: float32 under ``F32_BLOCK_TOL``, the 16-bit modes under
   ``_close_bf16`` at one storage ulp (tests/test_gpu_bf16.py).  tests/test_grouped_host.py shows on the CPU that the gates fit.
+  Every linear and leaky case must also be, bit for bit, the float32 restatement in the kernels' stated sum order
+  (tests/grouped_ordered.py); mish and logistic cases (``GC.NOT_ORDERED``) stay on the gates above.
 * Every depthwise case again under ``grouped_generic``: ``conv_grouped_*`` gives the bits ``conv_dwise_*`` gave.
 * grouped.cfg block by block, teacher-forced, as tests/test_gpu_odd_cfg.py walks odd.cfg; which kernel ran which block; the arena
   against ``keep_all=True``; two runs of one plan.
@@ -25,6 +27,7 @@ from yolov3.synthdata import synth_frames
 
 import footprint_util as fu
 import grouped_cases as GC
+import grouped_ordered as GO
 import grouped_restate as GR
 import test_gpu_footprint as TF
 from golden_util import GOLDEN
@@ -116,6 +119,29 @@ def _run_one_op(case, dtype, generic=False):
     return got.permute(0, 3, 1, 2).contiguous(), name
 
 
+_ordered_cache = {}
+
+
+def _ordered_gate(case, dtype, got, what):
+    """linear and leaky ops: the stored bits are those of tests/grouped_ordered.py, the float32 restatement in the kernels' stated
+    sum order.  True where the demand was made; mish and logistic cases (GC.NOT_ORDERED) are left out."""
+    exact = case.get("act", "leaky") in GO.EXACT_ACTS
+    assert exact == (case["id"] not in GC.NOT_ORDERED), case["id"]
+    if not exact:
+        return False
+    key = (case["id"], dtype)
+    if key not in _ordered_cache:
+        _ordered_cache[key] = torch.from_numpy(GO.of_case(case, dtype, _reference(case, dtype)[0]))
+    want = _ordered_cache[key]
+    if not torch.equal(got, want):
+        bad = (got.view(torch.int32) != want.view(torch.int32)).nonzero()
+        b, c, y, x = (int(v) for v in bad[0])
+        pytest.fail("%s: %d of %d stored values are not the ordered restatement's; first at frame %d channel %d pixel (%d, %d): got %r (%08x), want %r (%08x)" % (
+            what, len(bad), got.numel(), b, c, y, x, float(got[b, c, y, x]), int(got.view(torch.int32)[b, c, y, x]) & 0xffffffff,
+            float(want[b, c, y, x]), int(want.view(torch.int32)[b, c, y, x]) & 0xffffffff))
+    return True
+
+
 def _gate(got, want_unrounded, dtype, what):
     if dtype == "float32":
         np.testing.assert_allclose(got.numpy(), want_unrounded.numpy(), err_msg=what, **F32_BLOCK_TOL)
@@ -129,9 +155,11 @@ def test_depthwise_kernel_one_op(cid, dtype):
     case = GC.CASES[cid]
     got, name = _run_one_op(case, dtype)
     _gate(got, _reference(case, dtype)[1], dtype, "%s %s (%s)" % (cid, dtype, name))
+    _ordered_gate(case, dtype, got, "%s %s (%s)" % (cid, dtype, name))
     # the same op on the grouped kernel: the same sum order, the same epilogue, the same bits
     again, other = _run_one_op(case, dtype, generic=True)
     assert other.startswith("conv_grouped_")
+    _ordered_gate(case, dtype, again, "%s %s (%s)" % (cid, dtype, other))
     assert torch.equal(got, again), "%s %s: %s and %s differ in %d values" % (cid, dtype, name, other, int((got != again).sum()))
 
 
@@ -141,6 +169,13 @@ def test_grouped_kernel_one_op(cid, dtype):
     case = GC.CASES[cid]
     got, name = _run_one_op(case, dtype)
     _gate(got, _reference(case, dtype)[1], dtype, "%s %s (%s)" % (cid, dtype, name))
+    _ordered_gate(case, dtype, got, "%s %s (%s)" % (cid, dtype, name))
+
+
+def test_ordered_gate_covers_every_linear_and_leaky_case():
+    """exactly the mish and logistic cases stay on the toleranced gates alone"""
+    left_out = sorted(c["id"] for c in GC.DWISE + GC.GROUPED if c.get("act", "leaky") not in GO.EXACT_ACTS)
+    assert left_out == sorted(GC.NOT_ORDERED) == ["dw_logistic", "dw_mish", "dw_res_mish", "gr_4x4_wide_res", "gr_4x8_wide_res"]
 
 
 # ---------------------------------------------------------------------------------------------- grouped.cfg through Darknet

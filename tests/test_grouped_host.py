@@ -2,7 +2,10 @@
 two device weight layouts, [dropout] as an alias, the ``groups`` field of ``y3_op`` and what the library's chooser and plan
 creation say about it.  tests/grouped_restate.py is held to ``torch.nn.functional.conv2d(..., groups=G)`` here, and the one-op
 cases of tests/test_gpu_grouped.py are shown to fit their gates on the CPU first: the restatement accumulating in float32 against
-the same restatement accumulating in float64, on the inputs the GPU test uses."""
+the same restatement accumulating in float64, on the inputs the GPU test uses.  The ordered float32 restatement the GPU test demands
+bit for bit (tests/grouped_ordered.py) is held to the same gates and shown to see the order.  Last, the kernel-level suites'
+tables (tests/grouped_suites.py): the lock against the library's census, the rows past 4 GiB and their refusals at the pixel and
+launch limits, and the epilogue forms, all on fake addresses."""
 import ctypes
 import os
 
@@ -106,6 +109,52 @@ def test_gates_fit_the_one_op_cases_on_the_cpu(cid):
         else:
             rnd = G.MODES[dtype]["rnd"]
             G._close_bf16(rnd(f32), rnd(f64), "%s %s" % (cid, dtype), None, dtype)
+
+
+@pytest.mark.parametrize("cid", sorted(GC.CASES))
+def test_ordered_restatement_is_the_same_operation(cid):
+    """tests/grouped_ordered.py (float32, the kernels' sum order, every operation rounded) against ``GC.reference`` under the GPU
+    test's own gates: the values the GPU test demands bit for bit are values of the operation the toleranced gates describe"""
+    import grouped_ordered as GO
+    import test_gpu_bf16 as G
+    case = GC.CASES[cid]
+    for dtype in GC.DTYPES:
+        data = GC.make(case, dtype)
+        got = torch.from_numpy(GO.of_case(case, dtype, data))
+        want = GC.reference(case, dtype, data)
+        assert got.shape == want.shape and got.dtype == torch.float32 and bool(torch.isfinite(got).all())
+        if dtype == "float32":
+            np.testing.assert_allclose(got.numpy(), want.numpy(), err_msg=cid, **G.F32_BLOCK_TOL)
+        else:
+            assert torch.equal(got, G.MODES[dtype]["rnd"](got)), (cid, dtype, "not storage values")
+            G._close_bf16(got, G.MODES[dtype]["rnd"](want), "%s %s" % (cid, dtype), None, dtype)
+
+
+def test_ordered_restatement_sees_the_order():
+    """the same sums with taps and channels visited in descending order differ from the stated order in stored bits: an equality
+    with the ordered restatement is a statement about the order.  In float32 every case shows it, and fp16 shows it on the grouped
+    shapes.  A product of two bf16 values has 16 significant bits and is exact in float32, and so are these sums of up to 72 such
+    products nearly everywhere; what inexactness is left disappears in the rounding to 8 bits.  In bf16 the equality therefore
+    holds the products, the epilogue and the one rounding, and the float32 runs hold the order (the kernels are one template)."""
+    import grouped_ordered as GO
+    seen = {d: 0 for d in GC.DTYPES}
+    for cid in ("dw_c24", "dw_linear", "gr_4x8", "gr_4x4", "gr_dw_c20_k5_res"):
+        case = GC.CASES[cid]
+        assert case.get("act", "leaky") in GO.EXACT_ACTS
+        for dtype in GC.DTYPES:
+            data = GC.make(case, dtype)
+            stated, reverse = GO.of_case(case, dtype, data), GO.of_case(case, dtype, data, reverse=True)
+            differ = int((stated.view(np.uint32) != reverse.view(np.uint32)).sum())
+            print("%s %s: %d of %d stored values differ between the two orders" % (cid, dtype, differ, stated.size))
+            seen[dtype] += differ > 0
+            assert differ > 0 or dtype != "float32", (cid, dtype)
+    assert seen["float32"] == 5 and seen["fp16"] >= 1, seen
+
+
+def test_ordered_gate_leaves_out_mish_and_logistic_only():
+    import grouped_ordered as GO
+    left_out = sorted(c["id"] for c in GC.DWISE + GC.GROUPED if c.get("act", "leaky") not in GO.EXACT_ACTS)
+    assert left_out == sorted(GC.NOT_ORDERED) == ["dw_logistic", "dw_mish", "dw_res_mish", "gr_4x4_wide_res", "gr_4x8_wide_res"]
 
 
 # ---------------------------------------------------------------------------------------------- the cfg reader
@@ -485,3 +534,149 @@ def test_grouped_library_code_objects_and_census():
     with open(T.LIB, "rb") as fh:
         main = {k[".name"] for _, elf in T._code_objects(fh.read()) for k in T._kernels(elf)}
     assert not main & set(names)
+
+
+# ---------------------------------------------------------------------------------------------- the kernel-level suites
+# tests/grouped_suites.py: the epilogue forms of tests/test_gpu_grouped_epilogue.py and the rows past 4 GiB of
+# tests/test_gpu_grouped_big.py, on fake addresses
+
+def test_every_compiled_instance_has_an_epilogue_form_and_a_big_row():
+    """no skip list: every (instance, dtype) of the grouped library's census has an epilogue form and, fp16 aside (it shares
+    bf16's address code), a row past 4 GiB; an instance compiled later fails here until both suites hold it"""
+    import json
+
+    import epilogue_cases as E
+    import grouped_suites as GS
+    with open(GC.CENSUS_FIXTURE) as fh:
+        keys = sorted(json.load(fh)["footprint"])
+    assert len(keys) == 15
+    pinned = {GS.census_key(f["instance"], d) for f in GS.EPILOGUE_FORMS.values() for d in E.DTYPES}
+    big = {GS.census_key(i, d) for i in GS.BIG_ROWS for d in GS.BIG_DTYPES}
+    assert set(keys) - pinned == set(), "instances without an epilogue form: %s" % sorted(set(keys) - pinned)
+    need_big = {k for k in keys if not k.endswith("-fp16")}
+    assert need_big - big == set(), "instances without a row past 4 GiB: %s" % sorted(need_big - big)
+    assert pinned - set(keys) == set() and big - set(keys) == set()          # ... and neither table names an instance that is gone
+    # each form and each row is a shape of the instance it is listed under
+    for form in GS.EPILOGUE_FORMS:
+        GS.epilogue_case(form)
+    for instance, case in GS.BIG_ROWS.items():
+        assert GS.instance_of(case) == instance and case.get("res") and case.get("act", "leaky") == "leaky"
+    assert [f["instance"] for f in GS.EPILOGUE_FORMS.values()].count("grouped_oc8") == 2      # 16-byte stores, and element by element
+
+
+@no_gpu
+@pytest.mark.parametrize("instance", ["dwise_k3s1", "dwise_k3s2", "dwise_kn", "grouped_oc8", "grouped_oc1"])
+def test_big_rows_span_4_gib_on_odd_maps_and_keep_their_instance(instance):
+    import footprint_util as fu
+    import grouped_suites as GS
+    case = GS.BIG_ROWS[instance]
+    ho, wo = GC.out_hw(case)
+    assert (ho % 2 == 1 and wo % 2 == 1) if case["s"] == 2 else (case["h"] % 2 == 1 and case["w"] % 2 == 1)
+    assert case["k"] == (5 if instance == "dwise_kn" else 3)
+    for dtype in GS.BIG_DTYPES:
+        B = GS.big_batch(case, dtype)
+        ops, lay = GS.build(case, dtype, B, "strided", lead=[fu.pad_operand()])
+        op = ops[0]
+        name, dims, err = GS.create(ops, lay)
+        assert name == GS.kernel_name(instance, dtype), (instance, dtype, name, err)
+        assert lay.operands[0].name == "pad" and lay.operands[0].body_bytes >= (1 << 32)
+        assert max(B * op.in_h * op.in_w, B * op.out_h * op.out_w) <= fu.MAX_PIXELS
+        spans = GS.span_operands(lay)
+        assert [o.name for o in spans] == ["input", "output", "residual"]
+        assert len({op.in_ld, op.out_ld, op.res_ld}) == 3 and all(o.slices[0][0] > 0 for o in spans)
+        for o in spans:
+            frame = o.body_bytes // B
+            assert frame * B == o.body_bytes == o.pixels * o.ld * o.es
+            assert o.body_bytes > fu.SPAN + frame, (instance, dtype, o.name, o.body_bytes)
+            assert frame & (frame - 1) != 0, (instance, o.name, frame)
+        # ... and the batch is no larger than that takes
+        assert any(o.body_bytes - 2 * (o.body_bytes // B) <= fu.SPAN + o.body_bytes // B for o in spans)
+        # the launch, restated: batch x out_h x ceil(out_w / 4) x out_c / 8 lanes, or pixels x out_c / bn, in blocks of 256
+        assert dims[1] == 256 and dims[0] * dims[1] == GS.launch_threads(case, B) <= fu.MAX_THREADS, (dims, GS.launch_threads(case, B))
+        assert lay.total < 32 << 30
+
+
+def _largest_batch(case):
+    """(the largest batch plan creation takes, "pixels" or "threads": what refuses the next one), from the restated launch"""
+    import footprint_util as fu
+    import grouped_suites as GS
+    ok = fu.MAX_PIXELS // GS.frame_pixels(case)
+    if GS.launch_threads(case, ok) <= fu.MAX_THREADS:
+        return ok, "pixels"
+    lo, hi = 1, ok
+    while lo < hi:
+        mid = (lo + hi + 1) // 2
+        lo, hi = (mid, hi) if GS.launch_threads(case, mid) <= fu.MAX_THREADS else (lo, mid - 1)
+    return lo, "threads"
+
+
+# the same instances with so few channels that a launch holds at most two threads per pixel: there the pixel limit comes first
+NARROW_ROWS = {"dwise_k3s1": dict(cin=8, cout=8, groups=8), "dwise_k3s2": dict(cin=8, cout=8, groups=8),
+               "dwise_kn": dict(cin=8, cout=8, groups=8), "grouped_oc8": dict(cin=16, cout=16, groups=2),
+               "grouped_oc1": dict(cin=2, cout=2, groups=2)}
+# (the stride-2 row has 81 input pixels and 5 x 2 x 15 lanes a frame, so its input pixels come first; at 240 channels its launch does)
+WIDE_ROWS = {"dwise_k3s2": dict(cin=240, cout=240, groups=240)}
+
+
+@no_gpu
+@pytest.mark.parametrize("instance", ["dwise_k3s1", "dwise_k3s2", "dwise_kn", "grouped_oc8", "grouped_oc1"])
+def test_big_rows_are_refused_at_the_pixel_and_the_launch_limit(instance):
+    """plan creation takes each row at its true limit and refuses it one frame later: by check_size's message where 2^31 pixels
+    less one tile come first, by check_launch's message naming the kernel where 2^32 - 256 threads do.  The rows themselves meet
+    the launch limit first (120 / 8 chunks, 8 or 16 threads a pixel; not the stride-2 row); their narrow forms meet the pixel limit."""
+    import footprint_util as fu
+    import grouped_suites as GS
+    seen = set()
+    row = GS.BIG_ROWS[instance]
+    for case in [row, dict(row, **NARROW_ROWS[instance])] + ([dict(row, **WIDE_ROWS[instance])] if instance in WIDE_ROWS else []):
+        assert GS.instance_of(case) == instance
+        ok, why = _largest_batch(case)
+        seen.add(why)
+        for dtype in GS.BIG_DTYPES:
+            want = GS.kernel_name(instance, dtype)
+            ops, lay = GS.build(case, dtype, ok, "strided")
+            name, dims, err = GS.create(ops, lay)
+            assert name == want, (instance, dtype, ok, name, err)
+            assert dims[0] * dims[1] == GS.launch_threads(case, ok) <= fu.MAX_THREADS
+            ops, lay = GS.build(case, dtype, ok + 1, "strided")
+            name, dims, err = GS.create(ops, lay)
+            assert name is None and "block 1" in err, (instance, dtype, ok + 1, name)
+            if why == "pixels":
+                assert ok == fu.MAX_PIXELS // GS.frame_pixels(case) and (ok + 1) * GS.frame_pixels(case) > fu.MAX_PIXELS
+                assert "pixels" in err and "limit is %d" % fu.MAX_PIXELS in err, err
+            else:
+                assert (ok + 1) * GS.frame_pixels(case) <= fu.MAX_PIXELS
+                assert "threads" in err and "limit is %d" % fu.MAX_THREADS in err and want in err, err
+                assert "launch of %d threads" % GS.launch_threads(case, ok + 1) in err, err
+    assert seen == {"pixels", "threads"}, (instance, seen)
+
+
+@no_gpu
+@pytest.mark.parametrize("form", ["dwise_k3s1", "dwise_k3s2", "dwise_kn", "grouped_oc8_vec", "grouped_oc8_elem", "grouped_oc1"])
+def test_epilogue_forms_name_their_kernels(form):
+    """the one-op plans of tests/test_gpu_grouped_epilogue.py on fake addresses laid out as the GPU test lays them out"""
+    import grouped_suites as GS
+    assert sorted(GS.EPILOGUE_FORMS) == sorted(["dwise_k3s1", "dwise_k3s2", "dwise_kn", "grouped_oc8_vec", "grouped_oc8_elem", "grouped_oc1"])
+    case = GS.epilogue_case(form)
+    fake = kc._Fake()
+    for dtype in GC.DTYPES:
+        es = 4 if dtype == "float32" else 2
+        (in_off, in_ld), (out_off, out_ld) = GC.strides(case, case["cin"], dtype), GC.strides(case, case["cout"], dtype)
+        res_off, res_ld = (out_off + 8, out_ld + 16) if case.get("wide") else (out_off, out_ld)
+        code = {"float32": _hip.Y3_F32, "bf16": _hip.Y3_BF16, "fp16": _hip.Y3_F16}[dtype]
+        ops = _one_op(fake, cin=case["cin"], cout=case["cout"], groups=case["groups"], k=case["k"], dtype=code,
+                      flags=_hip.F_LEAKY | _hip.F_RESIDUAL, batch=case["B"], in_h=case["h"], in_w=case["w"], in_ld=in_ld, out_ld=out_ld,
+                      res_ld=res_ld, stride=case["s"], pad=case["pad"], out_h=GC.out_hw(case)[0], out_w=GC.out_hw(case)[1])
+        op = ops[0]
+        op.d_in, op.d_out, op.d_res = fake(1 << 16) + in_off * es, fake(1 << 16) + out_off * es, fake(1 << 16) + res_off * es
+        path = _hip.lib().y3_conv_path(ctypes.byref(op))
+        _, op.cout_pad, op.k_ld = GC.device_weights(case, path, np.zeros((case["cout"], case["cin"] // case["groups"], case["k"], case["k"]), dtype=np.float32))
+        handle = ctypes.c_void_p()
+        _hip.check(_hip.lib().y3_plan_create(ops, 1, fake(4096), ctypes.byref(handle)))
+        name = _hip.lib().y3_plan_op_kernel(handle, 0).decode()
+        _hip.lib().y3_plan_destroy(handle)
+        assert name == GS.kernel_name(case["instance"], dtype), (form, dtype, name)
+        if case.get("off"):
+            assert op.d_in % 16 == op.d_out % 16 == op.d_res % 16 == 8       # vec_in == vec_out == 0 in launch_conv_grouped
+        else:
+            assert op.d_in % 16 == op.d_out % 16 == op.d_res % 16 == 0
