@@ -65,18 +65,122 @@ __device__ __forceinline__ void decode_idx(long long idx, int cgroups, int Wo, i
   b = (int)(pix / Ho);
 }
 
+// ---- max-pool arithmetic: integer keys -----------------------------------------------------------------------------------
+// Every max-pool here (element-wise, 16-byte wide, the SPP pyramid; both padding rules; three element types) takes its
+// maximum on unsigned integer keys, not on floats.  The rule ("The layer kernels on every storage pattern"): IEEE
+// 754-2019 `maximum` of the taps that count, +0 above -0, the winner's bits returned unchanged, a NaN tap left out, -inf when
+// nothing is left.  With U the unsigned integer of the element's size, SIGN its top bit, INF the pattern of +inf, R = ~SIGN - INF
+// (all mantissa bits) and arithmetic modulo 2^bits:
+//   u = p ^ (p negative ? all ones : SIGN)    sign-magnitude -> unsigned order: -NaN < -inf < ... < -0 < +0 < ... < +inf < +NaN,
+//                                             -inf at R, +inf at ~R;
+//   v = u + R                                 rotates the positive NaNs (u > ~R) round to [0, R), below everything; the negative
+//                                             NaNs follow at [R, 2R), -inf lands on 2R, the order of the rest is kept;
+//   key = max(v, 2R)                          every NaN becomes -inf, the identity of max: exactly "left out", and -inf if all are
+//                                             (CLAMP = false leaves this to a running maximum that starts at 2R: the single pools).
+// Unsigned max on keys is then the rule, in any order and any grouping: a cascade and a scan give the same bits.  Back:
+// u = key - R, p = u ^ (u has its top bit ? SIGN : all ones).  Five packed integer instructions per tap (v_pk_ashrrev_i16, v_or,
+// v_xor, v_pk_add_u16, v_pk_max_u16) and one per maximum.  No float instruction touches the data, so neither the denormal mode nor
+// the quieting of a signalling NaN (v_max_f32 answers one with a quiet NaN, and a bf16 widened by a shift can be one) has a say.
+typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
+typedef short s16x8 __attribute__((ext_vector_type(8)));
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+
+template <typename T>
+struct PoolBits;
+template <>
+struct PoolBits<float> {
+  typedef uint32_t U;
+  typedef int32_t S;
+  typedef u32x4 V;
+  typedef i32x4 SV;
+  static constexpr U SIGN = 0x80000000u, R = 0x007FFFFFu;
+};
+template <>
+struct PoolBits<bf16_t> {
+  typedef uint16_t U;
+  typedef int16_t S;
+  typedef u16x8 V;
+  typedef s16x8 SV;
+  static constexpr U SIGN = 0x8000, R = 0x007F;
+};
+template <>
+struct PoolBits<f16_t> {
+  typedef uint16_t U;
+  typedef int16_t S;
+  typedef u16x8 V;
+  typedef s16x8 SV;
+  static constexpr U SIGN = 0x8000, R = 0x03FF;
+};
+// the key of -inf: what a tap left out counts as, and what an empty maximum is
+template <typename T>
+__device__ __forceinline__ constexpr typename PoolBits<T>::U pool_least() {
+  return (typename PoolBits<T>::U)(2 * PoolBits<T>::R);
+}
+// the key of +0 (a padded tap of the reference's rule): u = SIGN, v = SIGN + R
+template <typename T>
+__device__ __forceinline__ constexpr typename PoolBits<T>::U pool_zero() {
+  return (typename PoolBits<T>::U)(PoolBits<T>::SIGN + PoolBits<T>::R);
+}
+
+// one element (U) ...
+__device__ __forceinline__ uint16_t pool_max(uint16_t a, uint16_t b) { return a > b ? a : b; }
+__device__ __forceinline__ uint32_t pool_max(uint32_t a, uint32_t b) { return a > b ? a : b; }
+template <typename T, bool CLAMP = true>
+__device__ __forceinline__ typename PoolBits<T>::U pool_key(typename PoolBits<T>::U p) {
+  typedef PoolBits<T> P;
+  typedef typename P::U U;
+  const U x = (U)((U)((typename P::S)p >> (8 * sizeof(U) - 1)) | P::SIGN);
+  const U v = (U)((U)(p ^ x) + P::R);
+  return CLAMP ? pool_max(v, pool_least<T>()) : v;
+}
+template <typename T>
+__device__ __forceinline__ typename PoolBits<T>::U pool_unkey(typename PoolBits<T>::U k) {
+  typedef PoolBits<T> P;
+  typedef typename P::U U;
+  const U u = (U)(k - P::R);
+  return (U)(u ^ (U)((U)~(U)((typename P::S)u >> (8 * sizeof(U) - 1)) | P::SIGN));
+}
+// ... and the 16 bytes of one load (V: 8 x uint16 or 4 x uint32)
+__device__ __forceinline__ u16x8 pool_max(const u16x8 &a, const u16x8 &b) { return __builtin_elementwise_max(a, b); }
+__device__ __forceinline__ u32x4 pool_max(const u32x4 &a, const u32x4 &b) { return __builtin_elementwise_max(a, b); }
+template <typename T, bool CLAMP = true>
+__device__ __forceinline__ typename PoolBits<T>::V pool_key(typename PoolBits<T>::V p) {
+  typedef PoolBits<T> P;
+  typedef typename P::V V;
+  typedef typename P::U U;
+  const V x = __builtin_bit_cast(V, __builtin_bit_cast(typename P::SV, p) >> (typename P::S)(8 * sizeof(U) - 1)) | P::SIGN;
+  const V v = (p ^ x) + P::R;
+  return CLAMP ? pool_max(v, (V)(pool_least<T>())) : v;
+}
+template <typename T>
+__device__ __forceinline__ typename PoolBits<T>::V pool_unkey(typename PoolBits<T>::V k) {
+  typedef PoolBits<T> P;
+  typedef typename P::V V;
+  typedef typename P::U U;
+  const V u = k - P::R;
+  return u ^ (~__builtin_bit_cast(V, __builtin_bit_cast(typename P::SV, u) >> (typename P::S)(8 * sizeof(U) - 1)) | P::SIGN);
+}
+
+// what one thread of a single pool holds: one element or one 16-byte chunk, as patterns
+template <typename T, int VEC>
+struct PoolChunk {
+  typedef typename std::conditional<VEC == 1, typename PoolBits<T>::U, typename PoolBits<T>::V>::type X;
+  static __device__ __forceinline__ X splat(typename PoolBits<T>::U v) {
+    if constexpr (VEC == 1) return v; else return (X)(v);
+  }
+};
+
 // Reference MaxPool2d.forward (darknet.py:21-29): stride 1 & k > 1 -> window [y, y+k) x [x, x+k)
 // with out-of-range taps contributing 0.0 (zero padding right/bottom); otherwise floor-mode
 // pooling without padding (all taps in range).
 template <typename T, int VEC>
 __global__ __launch_bounds__(256) void maxpool_kernel(LayerArgs p) {
+  typedef typename PoolChunk<T, VEC>::X X;
   const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
   if (idx >= p.total) return;
   int b, oy, ox, cg;
   decode_idx(idx, p.C / VEC, p.Wo, p.Ho, b, oy, ox, cg);
-  float best[VEC];
-#pragma unroll
-  for (int j = 0; j < VEC; ++j) best[j] = -INFINITY;
+  X best = PoolChunk<T, VEC>::splat(pool_least<T>());
   bool padded = false;
   for (int ky = 0; ky < p.k; ++ky) {
     const int iy = oy * p.stride + ky;
@@ -86,25 +190,21 @@ __global__ __launch_bounds__(256) void maxpool_kernel(LayerArgs p) {
         padded = true;
         continue;
       }
-      float v[VEC];
-      load_vec<T, VEC>(static_cast<const T *>(p.in) + (((long long)b * p.H + iy) * p.W + ix) * p.in_ld + cg * VEC, v);
-#pragma unroll
-      for (int j = 0; j < VEC; ++j) best[j] = fmaxf(best[j], v[j]);
+      const X v = *reinterpret_cast<const X *>(static_cast<const T *>(p.in) + (((long long)b * p.H + iy) * p.W + ix) * p.in_ld + cg * VEC);
+      best = pool_max(best, pool_key<T, false>(v));
     }
   }
-  if (padded && p.zero_pad) {
-#pragma unroll
-    for (int j = 0; j < VEC; ++j) best[j] = fmaxf(best[j], 0.f);
-  }
-  store_vec<T, VEC>(static_cast<T *>(p.out) + (((long long)b * p.Ho + oy) * p.Wo + ox) * p.out_ld + cg * VEC, best);
+  if (padded && p.zero_pad) best = pool_max(best, PoolChunk<T, VEC>::splat(pool_zero<T>()));   // a padded tap is a +0 tap
+  *reinterpret_cast<X *>(static_cast<T *>(p.out) + (((long long)b * p.Ho + oy) * p.Wo + ox) * p.out_ld + cg * VEC) = pool_unkey<T>(best);
 }
 
 // Darknet's rule (Y3_F_POOL_DARKNET; include/yolov3_hip.h): the window of output (oy, ox) starts at
 // (oy * stride - pad_lo, ox * stride - pad_lo) with pad_lo = padding / 2, and only its taps inside [0, H) x [0, W)
 // count: the tap ranges are clipped up front, nothing stands in for the taps left out.  y3_choose_layer has checked that
-// no window is empty, so `best` never stays at its -inf start on NaN-free input (fmaxf ignores a NaN tap).
+// no window is empty, so `best` stays at its -inf start only where every tap is NaN or -inf.
 template <typename T, int VEC>
 __global__ __launch_bounds__(256) void maxpool_dk_kernel(LayerArgs p) {
+  typedef typename PoolChunk<T, VEC>::X X;
   const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
   if (idx >= p.total) return;
   int b, oy, ox, cg;
@@ -112,19 +212,13 @@ __global__ __launch_bounds__(256) void maxpool_dk_kernel(LayerArgs p) {
   const int y0 = oy * p.stride - p.pad_lo, x0 = ox * p.stride - p.pad_lo;
   const int ky0 = y0 < 0 ? -y0 : 0, ky1 = min(p.k, p.H - y0);
   const int kx0 = x0 < 0 ? -x0 : 0, kx1 = min(p.k, p.W - x0);
-  float best[VEC];
-#pragma unroll
-  for (int j = 0; j < VEC; ++j) best[j] = -INFINITY;
+  X best = PoolChunk<T, VEC>::splat(pool_least<T>());
   for (int ky = ky0; ky < ky1; ++ky) {
     const T *row = static_cast<const T *>(p.in) + (((long long)b * p.H + y0 + ky) * p.W + x0) * p.in_ld + cg * VEC;
-    for (int kx = kx0; kx < kx1; ++kx) {
-      float v[VEC];
-      load_vec<T, VEC>(row + (long long)kx * p.in_ld, v);
-#pragma unroll
-      for (int j = 0; j < VEC; ++j) best[j] = fmaxf(best[j], v[j]);
-    }
+    for (int kx = kx0; kx < kx1; ++kx)
+      best = pool_max(best, pool_key<T, false>(*reinterpret_cast<const X *>(row + (long long)kx * p.in_ld)));
   }
-  store_vec<T, VEC>(static_cast<T *>(p.out) + (((long long)b * p.Ho + oy) * p.Wo + ox) * p.out_ld + cg * VEC, best);
+  *reinterpret_cast<X *>(static_cast<T *>(p.out) + (((long long)b * p.Ho + oy) * p.Wo + ox) * p.out_ld + cg * VEC) = pool_unkey<T>(best);
 }
 
 // nn.Upsample(scale_factor, mode="nearest") (darknet.py:302-305)
@@ -358,8 +452,8 @@ int y3_choose_reorg(const y3_op &op, y3_step &st) {
 // [y, y+k) x [x, x+k), out-of-range taps contribute 0.0 (ZeroPad2d right/bottom, then an unpadded pool).
 //
 // One workgroup = one frame x one 32-byte channel group (16 bf16 / 8 float32 channels).  The (H+12) x (W+12)
-// zero-padded image of that group is staged in LDS once (16-byte vectors, two per position), then the pyramid is
-// a cascade, exact because max is associative and the windows nest:
+// zero-padded image of that group is staged in LDS once (16-byte vectors, two per position; as integer keys, NaN taps as
+// -inf: "max-pool arithmetic" above), then the pyramid is a cascade, exact because max is associative and the windows nest:
 //   R5[y][x]  = max(A[y][x .. x+4])                               (row pass)
 //   P5[y][x]  = max(R5[y .. y+4][x])                              on (H+8) x (W+8)
 //   P9[y][x]  = max(P5[y][x], P5[y+4][x], P5[y][x+4], P5[y+4][x+4])   on (H+4) x (W+4)   ([y,y+9) = [y,y+5) u [y+4,y+9))
@@ -385,19 +479,19 @@ struct SppArgs {
   int H, W, in_ld, ld5, ld9, ld13, cgroups;
 };
 
+// the tile holds keys (pool_key above): staged once, combined with integer max, turned back into patterns at the stores
 template <typename T>
 __device__ __forceinline__ u32x4 vmax16(const u32x4 &a, const u32x4 &b) {
-  if constexpr (sizeof(T) == 4) {
-    const f32x4 x = __builtin_bit_cast(f32x4, a), y = __builtin_bit_cast(f32x4, b);
-    return __builtin_bit_cast(u32x4, f32x4{fmaxf(x[0], y[0]), fmaxf(x[1], y[1]), fmaxf(x[2], y[2]), fmaxf(x[3], y[3])});
-  } else {
-    typedef typename H16<T>::v8 V8;
-    const V8 x = __builtin_bit_cast(V8, a), y = __builtin_bit_cast(V8, b);
-    V8 r;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) r[j] = (float)x[j] >= (float)y[j] ? x[j] : y[j];
-    return __builtin_bit_cast(u32x4, r);
-  }
+  typedef typename PoolBits<T>::V V;
+  return __builtin_bit_cast(u32x4, pool_max(__builtin_bit_cast(V, a), __builtin_bit_cast(V, b)));
+}
+template <typename T>
+__device__ __forceinline__ u32x4 spp_key(const u32x4 &raw) {
+  return __builtin_bit_cast(u32x4, pool_key<T>(__builtin_bit_cast(typename PoolBits<T>::V, raw)));
+}
+template <typename T>
+__device__ __forceinline__ u32x4 spp_unkey(const u32x4 &k) {
+  return __builtin_bit_cast(u32x4, pool_unkey<T>(__builtin_bit_cast(typename PoolBits<T>::V, k)));
 }
 
 template <typename T, bool DK>
@@ -411,14 +505,15 @@ __global__ __launch_bounds__(256) void maxpool_spp_kernel(SppArgs p) {
   const long long frame = (long long)b * p.H * p.W;
   // image origin in the tile; tile origin of the 5 x 5 / 9 x 9 results (the 13 x 13 ones start at 0 either way)
   constexpr int O = DK ? 6 : 0, S5 = DK ? 4 : 0, S9 = DK ? 2 : 0;
-  // border value: 0.0, or -inf of the element type (float32 0xFF800000, bf16 0xFF80, fp16 0xFC00)
-  constexpr uint32_t FILL = !DK ? 0u : (ES == 4 ? 0xFF800000u : (std::is_same<T, bf16_t>::value ? 0xFF80FF80u : 0xFC00FC00u));
+  // border value, as a key: +0, or -inf of the element type
+  constexpr uint32_t EDGE = DK ? pool_least<T>() : pool_zero<T>();
+  constexpr uint32_t FILL = ES == 4 ? EDGE : (EDGE << 16 | EDGE);
   const u32x4 border = u32x4{FILL, FILL, FILL, FILL};
   // 1. stage the padded image
   for (int idx = tid; idx < PH * PW * V; idx += 256) {
     const int pos = idx >> 1, v = idx & 1, ty = pos / PW, tx = pos - ty * PW, y = ty - O, x = tx - O;
     A[idx] = ((unsigned)y < (unsigned)p.H && (unsigned)x < (unsigned)p.W)
-                 ? *reinterpret_cast<const u32x4 *>(p.in + ((frame + y * p.W + x) * p.in_ld) * ES + cg * 32 + v * 16)
+                 ? spp_key<T>(*reinterpret_cast<const u32x4 *>(p.in + ((frame + y * p.W + x) * p.in_ld) * ES + cg * 32 + v * 16))
                  : border;
   }
   __syncthreads();
@@ -443,7 +538,7 @@ __global__ __launch_bounds__(256) void maxpool_spp_kernel(SppArgs p) {
     m = vmax16<T>(m, r[4 * PW * V]);
     A[(y * PW + x) * V + v] = m;
     if ((unsigned)(y - S5) < (unsigned)p.H && (unsigned)(x - S5) < (unsigned)p.W)
-      *reinterpret_cast<u32x4 *>(p.out5 + ((frame + (y - S5) * p.W + (x - S5)) * p.ld5) * ES + cg * 32 + v * 16) = m;
+      *reinterpret_cast<u32x4 *>(p.out5 + ((frame + (y - S5) * p.W + (x - S5)) * p.ld5) * ES + cg * 32 + v * 16) = spp_unkey<T>(m);
   }
   __syncthreads();
   // 4. P9 on (H+4) x (W+4) from four taps of P5, kept in Bf; the 9 x 9 pool's output from (S9, S9) on
@@ -454,7 +549,7 @@ __global__ __launch_bounds__(256) void maxpool_spp_kernel(SppArgs p) {
     const u32x4 m = vmax16<T>(vmax16<T>(a[0], a[4 * V]), vmax16<T>(a[4 * PW * V], a[(4 * PW + 4) * V]));
     Bf[(y * PW + x) * V + v] = m;
     if ((unsigned)(y - S9) < (unsigned)p.H && (unsigned)(x - S9) < (unsigned)p.W)
-      *reinterpret_cast<u32x4 *>(p.out9 + ((frame + (y - S9) * p.W + (x - S9)) * p.ld9) * ES + cg * 32 + v * 16) = m;
+      *reinterpret_cast<u32x4 *>(p.out9 + ((frame + (y - S9) * p.W + (x - S9)) * p.ld9) * ES + cg * 32 + v * 16) = spp_unkey<T>(m);
   }
   __syncthreads();
   // 5. P13 on H x W from four taps of P9
@@ -462,7 +557,7 @@ __global__ __launch_bounds__(256) void maxpool_spp_kernel(SppArgs p) {
     const int pos = idx >> 1, v = idx & 1, y = pos / p.W, x = pos - y * p.W;
     const u32x4 *a = Bf + (y * PW + x) * V + v;
     const u32x4 m = vmax16<T>(vmax16<T>(a[0], a[4 * V]), vmax16<T>(a[4 * PW * V], a[(4 * PW + 4) * V]));
-    *reinterpret_cast<u32x4 *>(p.out13 + ((frame + y * p.W + x) * p.ld13) * ES + cg * 32 + v * 16) = m;
+    *reinterpret_cast<u32x4 *>(p.out13 + ((frame + y * p.W + x) * p.ld13) * ES + cg * 32 + v * 16) = spp_unkey<T>(m);
   }
 }
 

@@ -186,6 +186,9 @@ def test_spp_pyramid_centred(dtype, hw, order):
         assert torch.equal(want, torch.nn.functional.max_pool2d(x, k, 1, k // 2))
         assert torch.equal(one[k], want), (dtype, hw, k, "pyramid")
         assert torch.equal(three[k], want), (dtype, hw, k, "three pools")
+        # the same on the bits (the storage values widened to float32 keep theirs): -0.0 == +0.0 as floats
+        assert torch.equal(one[k].view(torch.int32), want.view(torch.int32)), (dtype, hw, k, "pyramid, bits")
+        assert torch.equal(one[k].view(torch.int32), three[k].view(torch.int32)), (dtype, hw, k, "pyramid against three pools, bits")
     assert (rest == SENTINEL).all() and (rest3 == SENTINEL).all()          # nothing outside the three slices is written
 
 

@@ -1406,6 +1406,8 @@ def test_spp_pyramid_kernel_is_bit_identical_to_three_pools(dtype, dim, batch):
     assert sum(r["kernel"].startswith("maxpool_") for r in three.plan_report()) == 3
     for k in a:
         assert torch.equal(a[k], b[k]), k
+        if a[k].dtype == torch.float32:               # bits, not values: -0.0 == +0.0 as floats
+            assert torch.equal(a[k].view(torch.int32), b[k].view(torch.int32)), k
 
 
 def test_bf16_agreement_report_yolov3():
