@@ -60,10 +60,19 @@ def _conv_specs(case):
     return []
 
 
-def _make_data(case, dtype, lay, paths):
+def _make_data(case, dtype, lay, paths, plant=None):
     """{operand name: [storage tensor per slice]} for the input-side operands of ``lay`` and, for the oracle, the float32
-    values: {"x": NCHW input, "res": NCHW, "convs": [params dict per conv]}.  Seeded per case: every run holds the same."""
+    values: {"x": NCHW input, "res": NCHW, "convs": [params dict per conv]}.  Seeded per case: every run holds the same.
+
+    ``plant`` (tests/exact_sums.py ``plant``; conv groups only): its values instead of the seeded random ones -- input,
+    shortcut, and per conv the weights and the folded scale and bias as they are.  Every value must survive the storage
+    type unchanged.  The oracle parameters of such a run hold scale and bias, no batch norm."""
     from yolov3 import _hip as H
+
+    def planted(a, dt):
+        t = torch.from_numpy(np.ascontiguousarray(a)).to(torch.float32)
+        assert torch.equal(t.to(dt).float(), t), "a planted value is no %s" % dt
+        return t.to(dt)
     gen = torch.Generator().manual_seed(sum(map(ord, case["id"])) * 7 + 1)
     tdt = fu.TORCH_DT[dtype]
     B, h, w = case["B"], case["h"], case["w"]
@@ -73,7 +82,22 @@ def _make_data(case, dtype, lay, paths):
             continue
         if o.name in ("input", "input/output", "residual"):
             c = o.slices[0][1]
-            if o.fmt == "u8":
+            if o.fmt == "u8" and plant is not None:
+                import exact_sums as XS
+                t = torch.from_numpy(XS.frames_of(plant))
+                ref["frames"] = t.numpy()
+                data[o.name] = [t.reshape(1, -1)]
+            elif plant is not None:
+                key = "res" if o.name == "residual" else "x"
+                if key == "x" and case["group"] == "conv" and case["inp"] == "nchw":
+                    t = planted(plant["x"].transpose(0, 3, 1, 2), tdt).float()
+                    ref["x"] = t
+                    data[o.name] = [t.reshape(1, -1)]
+                else:
+                    t = planted(plant[key].reshape(o.pixels, c), tdt if o.fmt != "float32" else torch.float32)
+                    ref[key] = t.float().reshape(B, -1, c)
+                    data[o.name] = [t]
+            elif o.fmt == "u8":
                 t = torch.randint(0, 256, (B, h, w, case.get("cin", 3)), generator=gen, dtype=torch.uint8)
                 ref["frames"] = t.numpy()
                 data[o.name] = [t.reshape(1, -1)]
@@ -89,9 +113,13 @@ def _make_data(case, dtype, lay, paths):
                 data[o.name] = [t]
         elif o.name == "zero page" or o.name == "fragment weights":
             data[o.name] = [torch.zeros(o.slices[0][1], dtype=tdt)]
-    for (prefix, cin, cout, k, s, leaky), path in zip(_conv_specs(case), paths):
+    for n, ((prefix, cin, cout, k, s, leaky), path) in enumerate(zip(_conv_specs(case), paths)):
         kk = k * k * cin
-        wt = ((torch.rand((cout, cin, k, k), generator=gen) - 0.5) * (6.0 / kk) ** 0.5).to(tdt).float()
+        if plant is not None:
+            wt = planted(plant["convs"][n]["w"], tdt).float()
+            assert tuple(wt.shape) == (cout, cin, k, k)
+        else:
+            wt = ((torch.rand((cout, cin, k, k), generator=gen) - 0.5) * (6.0 / kk) ** 0.5).to(tdt).float()
         ow = lay[prefix + "weight"]
         if path == H.PATH_STEM_MFMA:
             host = torch.zeros((32, 32))
@@ -113,7 +141,10 @@ def _make_data(case, dtype, lay, paths):
         gamma = torch.rand(cout, generator=gen) + 0.5
         beta = torch.rand(cout, generator=gen) - 0.5
         sc, bi = torch.zeros(cp), torch.zeros(cp)
-        if case["group"] == "head" or not leaky and case.get("out_f32"):
+        if plant is not None:
+            sc[:cout], bi[:cout] = torch.from_numpy(plant["convs"][n]["scale"]), torch.from_numpy(plant["convs"][n]["bias"])
+            p = {"weight": wt.numpy(), "scale": plant["convs"][n]["scale"], "bias": plant["convs"][n]["bias"]}
+        elif case["group"] == "head" or not leaky and case.get("out_f32"):
             sc[:cout], bi[:cout] = 1.0, beta                      # a head conv: bias, no batch norm
             p = {"weight": wt.numpy(), "bias": beta.numpy()}
         else:
@@ -168,8 +199,9 @@ FRAGMENT_KEY = "y3_conv_make_fragment_weights"
 
 # ------------------------------------------------------------------------------------------------ one run
 
-def _run(case, dtype, mode, u8_guard=0, opt_name=None):
-    """(output tensors, footprint message or None, kernel names, float32 reference values)"""
+def _run(case, dtype, mode, u8_guard=0, opt_name=None, plant=None):
+    """(output tensors, footprint message or None, kernel names, float32 reference values, layout).  ``plant``: planted operands
+    for ``_make_data``; such a run also returns the scratch operands as it finds them (the float32 logits of an unfused head)"""
     from yolov3 import _hip as H
     lib = H.lib()
     dev = torch.device("cuda:0")
@@ -183,7 +215,7 @@ def _run(case, dtype, mode, u8_guard=0, opt_name=None):
     ops, lay, frag, path = fu.build(case, dtype, mode, opt, base)
     assert lay.total == lay0.total
     paths = [path, H.PATH_IGEMM]
-    data, ref = _make_data(case, dtype, lay, paths)
+    data, ref = _make_data(case, dtype, lay, paths, plant)
     fu.fill(alloc, lay, data, poisoned=mode != "dense", u8_guard=u8_guard)
     torch.cuda.synchronize()
     # fragment-order weight copies: made by the library into their operand, which is all that call may write
@@ -210,7 +242,7 @@ def _run(case, dtype, mode, u8_guard=0, opt_name=None):
     msg = fu.footprint_violations(before, alloc, lay)
     outs = {}
     for o in lay.operands:
-        if o.side in ("out", "inout"):
+        if o.side in ("out", "inout") or (plant is not None and o.side == "scratch"):
             for k in range(len(o.slices)):
                 outs["%s/%d" % (o.name, k)] = fu.read_slice(alloc, o, k, torch.uint8).cpu()
     return outs, msg, names, ref, lay
