@@ -223,6 +223,12 @@ typedef struct y3_plan y3_plan;
  *                    and batch give enough workgroups to fill the chip (yolov3@608: the 76^2 blocks from batch 12 on); 2:
  *                    wherever the kernel supports the pair (tests).  Same bits either way; measured level with the two
  *                    launches (profiles/r04_block_fused_AB.txt), which is why it is not the default.
+ *                    3: the same pairs under the rule of 1 on the DIRECT-WEIGHTS form of the kernel (csrc/conv_block_dw.hip,
+ *                    libyolov3_hip_block.so), which reads the fragment-order copies of both convs' weights: it takes a pair only
+ *                    when both ops carry y3_op.d_weight_frag (y3_conv_fragment_weight_bytes answers by shape for such ops); a
+ *                    pair without them runs as two launches -- no private copies for fused steps.  Same bits; 8 % faster
+ *                    than the two launches at yolov3@608 batch 16 (profiles/block_dw_AB.txt): what yolov3.Pipeline asks for
+ *                    when batches overlap.  4: the same kernel wherever it supports the pair (tests only).
  */
 typedef struct y3_options {
   int32_t auto_mask, unused0, igemm_version, igemm_ns, igemm_bm;

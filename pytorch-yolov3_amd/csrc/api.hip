@@ -393,6 +393,8 @@ size_t y3_conv_fragment_weight_bytes(const y3_op *op, const y3_options *options)
   // (a detection-head conv is chosen for together with the YOLO op behind it, at plan creation: asked about by its shape here)
   if (o.fuse_head && y3_conv_head_dw_fits(*op, o)) return y3_conv_halo_dw_weight_bytes(*op);
   if (check_flags(*op) != Y3_OK || check_groups(*op) != Y3_OK || check_size(*op) != Y3_OK) return 0;
+  // (so is a member of a 1x1 -> 3x3 pair that fuse_block = 3 / 4 runs on the direct-weights block kernel)
+  if (y3_conv_block_dw_member(*op, o)) return y3_conv_halo_dw_weight_bytes(*op);
   return choose_op(*op, o, st) == Y3_OK && st.frag ? y3_conv_halo_dw_weight_bytes(*op) : 0;
 }
 

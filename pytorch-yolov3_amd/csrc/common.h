@@ -486,6 +486,11 @@ bool y3_choose_maxpool_spp(const y3_op &a, const y3_op &b, const y3_op &c, y3_st
 bool y3_choose_conv_fused_stem_s2(const y3_op &op0, const y3_op &op1, const y3_options &o, y3_step &st);
 bool y3_choose_conv_fused_resblock(const y3_op &op0, const y3_op &op1, const y3_options &o, y3_step &st);
 bool y3_choose_conv_block_fused(const y3_op &op0, const y3_op &op1, const y3_options &o, y3_step &st);
+// its direct-weights form (conv_block_dw.hip, libyolov3_hip_block.so; y3_options.fuse_block = 3 / 4): whether a pair the chooser
+// above accepts carries what it needs, the step on tw x th rectangles, and whether an op can be a member of such a pair
+bool y3_conv_block_dw_fits(const y3_op &op0, const y3_op &op1);
+void y3_choose_conv_block_dw(const y3_op &op0, int tw, int th, y3_step &st);
+bool y3_conv_block_dw_member(const y3_op &op, const y3_options &o);
 // detection head: 1x1 conv + YOLO decode in one launch (conv_igemm.hip: the tiled form and the choice between the two; conv_1x1.hip:
 // the direct-weights form, which reads the fragment-order copy of the head conv's weights)
 bool y3_choose_conv_head_decode(const y3_op &op0, const y3_op &op1, const y3_options &o, y3_step &st);

@@ -11,6 +11,10 @@
 // all 160 KiB of LDS means (a) the chip reads x, computes, and writes z in lock step, so the 16 us of HBM time of a pair
 // overlap with nothing, and (b) the weight ring has three slots, i.e. one K-step of lead, for tiles that all 256
 // workgroups want in the same K-step.
+// LATER: cause (b) is removed in conv_block_dw.hip (fuse_block = 3 / 4): this kernel's geometry with both convs' weight fragments
+// taken straight from the fragment-order copies into registers -- no ring, no barrier inside a 128-channel pass.  61.6 us per pair
+// against 66.8 us for the two launches and 68.5 us for this kernel on one box, +2.7 % end to end (profiles/block_dw_AB.txt).
+// This kernel stays as it is: the A/B baseline and the record.
 //
 // A workgroup owns a TW x TH rectangle of output pixels (<= 384 = 24 MFMA fragments of 16) of one frame and ALL output
 // channels.  At 76 x 76 the rectangle is 19 x 19: sixteen per frame, so a batch of 16 is exactly one workgroup per CU
@@ -459,7 +463,9 @@ int launch_block_fused(const y3_op *ops, const y3_step &st, const void *, const 
 }  // namespace
 
 // op0: 1x1 conv Cin -> 128 whose output only op1 reads; op1: 3x3 stride-1 conv 128 -> Cout, optionally with the shortcut
-// operand == op0's input.  fuse_block: 0 never [default], 1 where the rectangles fill the chip, 2 wherever supported.
+// operand == op0's input.  fuse_block: 0 never [default], 1 where the rectangles fill the chip, 2 wherever supported; 3 / 4: the
+// same two rules for the direct-weights form of the kernel (conv_block_dw.hip), which takes the pairs whose convs both carry
+// y3_op.d_weight_frag -- a pair without them runs as two launches.
 bool y3_choose_conv_block_fused(const y3_op &op0, const y3_op &op1, const y3_options &o, y3_step &st) {
   const int mode = o.fuse_block;
   if (!mode) return false;
@@ -493,13 +499,34 @@ bool y3_choose_conv_block_fused(const y3_op &op0, const y3_op &op1, const y3_opt
   if ((long long)op1.cout_pad * op1.k_ld * 2 >= (1ll << 31) || (long long)op0.cout_pad * op0.k_ld * 2 >= (1ll << 31)) return false;
   int tw, th;
   double eff;
-  if (!choose_tile(op0.in_h, op0.in_w, op0.batch, y3_device_cus(), tw, th, eff) || (mode < 2 && eff < 0.7)) return false;
+  if (!choose_tile(op0.in_h, op0.in_w, op0.batch, y3_device_cus(), tw, th, eff) || ((mode == 1 || mode == 3) && eff < 0.7)) return false;
+  if (mode >= 3) {
+    // the direct-weights form (conv_block_dw.hip): the same pairs, where both convs carry a fragment-order copy of their weights
+    if (!y3_conv_block_dw_fits(op0, op1)) return false;
+    y3_choose_conv_block_dw(op0, tw, th, st);
+    return true;
+  }
   st.tw = tw;
   st.th = th;
   st.launch = launch_block_fused;
   st.dims = {block_geom(op0, tw, th).grid, kNT, kBlockLds};
   st.name = Y3_KNAME(op0.dtype, "conv_block_fused_", "_x128");
   return true;
+}
+
+// Whether `op`, by its shape alone, can be a member of a pair that fuse_block = 3 / 4 runs on the direct-weights kernel: its caller
+// then makes the fragment-order copy of its weights (y3_conv_fragment_weight_bytes).  A copy made for a pair that ends up unfused
+// is harmless.
+bool y3_conv_block_dw_member(const y3_op &op, const y3_options &o) {
+  if (o.fuse_block < 3 || op.kind != Y3_OP_CONV || !y3_is16(op.dtype) || y3_is_grouped(op) || op.stride != 1) return false;
+  if (op.k_ld % 32 != 0 || op.cout_pad % 32 != 0) return false;
+  if (op.flags & (Y3_F_OUT_F32 | Y3_F_IN_NCHW_F32 | Y3_F_IN_NHWC_U8BGR | Y3_F_PLAN_INPUT | Y3_F_MISH | Y3_F_LOGISTIC)) return false;
+  const bool first = op.ksize == 1 && op.in_c % 64 == 0 && op.in_c >= 192 && op.out_c == 128 && !(op.flags & Y3_F_RESIDUAL);
+  const bool second = op.ksize == 3 && op.pad == 1 && op.in_c == 128 && op.out_c % 128 == 0;
+  if (!first && !second) return false;
+  int tw, th;
+  double eff;
+  return choose_tile(op.in_h, op.in_w, op.batch, y3_device_cus(), tw, th, eff) && (o.fuse_block != 3 || eff >= 0.7);
 }
 
 Y3_STAMP_READER(y3_debug_stamps_block)

@@ -113,10 +113,14 @@ class Pipeline(object):
                               in_flight, in_flight + 2, "has" if sure else "was probably initialised with", nq), RuntimeWarning)
         self.copy_blocks = int(copy_blocks)
         # several batches in flight: CU time counts, not one launch's tail -> the strip kernel's 256-pixel tiles
-        # (include/yolov3_hip.h: Y3_AM_HALO_TILE256; profiles/HISTORY.md 3.1c).  Explicit ``options`` win.
+        # (include/yolov3_hip.h: Y3_AM_HALO_TILE256; profiles/HISTORY.md 3.1c), and the 1x1 -> 3x3 bottleneck pairs as one
+        # direct-weights kernel where their rectangles fill the chip (fuse_block = 3: yolov3@608, the 76^2 pairs from batch 12
+        # on; profiles/block_dw_AB.txt) unless the network's options or y3_set_tuning say otherwise.  Explicit ``options`` win.
         if options is None and self.in_flight > 1:
             base = dict(net.options or {})
             base["auto_mask"] = int(base.get("auto_mask", _hip.options().auto_mask)) | _hip.AM_HALO_TILE256
+            if "fuse_block" not in base and _hip.options().fuse_block == 0:
+                base["fuse_block"] = 3
             options = base
         self.options = dict(options) if options else None
         with torch.cuda.device(dev):
