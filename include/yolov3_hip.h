@@ -70,6 +70,29 @@ extern "C" {
                                  out[k][j][i] = in[k % C][j*s + g / s][i*s + g % s].
                              A move of storage elements: bit-exact in every dtype.  in_c = C, out_c = C*s*s, out_h = H/s,
                              out_w = W/s.  y3_capabilities() reports Y3_CAP_REORG                                        */
+/* The attention blocks of Darknet (csrc/attention.hip, libyolov3_hip_attn.so; y3_capabilities() reports Y3_CAP_ATTENTION).  All three
+ * read and write NHWC tensors of the op's dtype with their pixel strides, take no flag at all (none of y3_op.flags: the op never
+ * reads the plan's input and never stores float32 from 16-bit storage), and have a 16-byte form (8 elements of 16-bit storage,
+ * 4 of float32 per thread) and an element form, taken where in_c, a pixel stride or a base address is off the 16-byte grain;
+ * both forms give the same bits.  d_in, in_h, in_w, in_c, in_ld describe `prev`, the output of the block in front; d_res and
+ * res_ld describe `src`, the block the cfg's `from` names (as in Y3_OP_ADD); out_* the output.  in_c == out_c.             */
+#define Y3_OP_AVGPOOL 8   /* [avgpool]: global average pool, (C, H, W) -> (C, 1, 1); out_h = out_w = 1.  With P = in_h * in_w:
+                               out[b][c] = round_to_storage(S / float32(P))
+                             with the correctly rounded float32 division and S the float32 sum of prev[b][.][.][c] in ONE order,
+                             a function of P only (not of batch, channel count, strides, the form that runs, the grid or
+                             y3_set_tuning("device_cus", n)); pixels p = y * W + x:
+                               32 partial sums s[0..31] start at +0.0f; s[r] adds pixels r, r + 32, r + 64, ... in increasing order;
+                               then s[r] += s[r + 16] for r < 16, s[r] += s[r + 8] for r < 8, and so on with 4, 2, 1;  S = s[0].
+                             (numpy float32: s = zeros(32); for p in range(P): s[p % 32] += x[p]; then for h in 16, 8, 4, 2, 1:
+                             s[:h] += s[h:2*h].)  No atomics.  A sum of integer-valued inputs below 2^24 is exact in any order.  */
+#define Y3_OP_SCALE_CHANNELS 9 /* [scale_channels]: out[b][y][x][c] = round_to_storage(float32(src[b][y][x][c]) * float32(prev[b][c])):
+                             prev is (C, 1, 1) (in_h = in_w = 1), out has src's shape.  The float32 product of two bf16 values,
+                             and of two fp16 values, is exact, so in both 16-bit modes the result is the exact product rounded
+                             once (nearest even); in float32 it is the IEEE product.  Zeros keep their sign, 0 * inf and NaN
+                             operands give NaN.  float32 denormal products are KEPT (not flushed), as add_kernel's denormal sums
+                             are: the kernels are compiled with IEEE denormal handling for float32, hipcc's default on gfx950.  */
+#define Y3_OP_SAM 10      /* [sam]: out = round_to_storage(float32(src) * float32(prev)) element by element, prev of src's shape
+                             (in_h == out_h, in_w == out_w); the arithmetic of Y3_OP_SCALE_CHANNELS                         */
 
 /* y3_op.flags */
 #define Y3_F_LEAKY 1u          /* LeakyReLU(0.1) after scale/bias                        */
@@ -257,6 +280,7 @@ int y3_abi_version(void);
 #define Y3_CAP_PLAN_OP_DIMS 4096u /* y3_plan_op_dims and y3_set_tuning("device_cus", n) */
 #define Y3_CAP_TILES 8192u     /* y3_tiles_u8, y3_detect_tiled and its workspace query */
 #define Y3_CAP_GROUPED_CONV 16384u /* y3_op.groups on conv ops, y3_conv_path answers 4 and 5, y3_set_tuning("grouped_generic", v) */
+#define Y3_CAP_ATTENTION 32768u /* Y3_OP_AVGPOOL, Y3_OP_SCALE_CHANNELS and Y3_OP_SAM */
 uint32_t y3_capabilities(void);
 const char *y3_last_error(void);
 /* number of visible HIP devices whose arch is gfx950 (0 on a CPU-only machine) */

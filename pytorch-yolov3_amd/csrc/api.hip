@@ -97,6 +97,8 @@ struct y3_plan {
 
 namespace {
 
+bool y3_is_attention(const y3_op &op) { return op.kind == Y3_OP_AVGPOOL || op.kind == Y3_OP_SCALE_CHANNELS || op.kind == Y3_OP_SAM; }
+
 // 0 = MFMA implicit GEMM, 1 = 3-channel stem kernel (VALU), 2 = direct fallback, 3 = MFMA stem (uint8 -> bf16),
 // 4 = grouped, 5 = depthwise (a grouped op is asked about first: no other family's chooser ever sees one)
 int conv_path(const y3_op &op) {
@@ -185,6 +187,11 @@ int check_flags(const y3_op &op) {
              "op for block %d: Y3_F_SCORES_DARKNET on an op of kind %d (YOLO ops only)", op.block_idx, op.kind);
   Y3_REQUIRE(!(op.flags & Y3_F_REORG_3D) || op.kind == Y3_OP_REORG,
              "op for block %d: Y3_F_REORG_3D on an op of kind %d (reorg ops only)", op.block_idx, op.kind);
+  // the attention ops take no flag: none of the conv-only ones (activations, residual, float32 store, network input, fusion
+  // hint) and none of the pool-only ones
+  if (y3_is_attention(op))
+    Y3_REQUIRE(op.flags == 0, "op for block %d: flags 0x%x on an attention op of kind %d (avgpool, scale_channels and sam ops take none)",
+               op.block_idx, op.flags, op.kind);
   return Y3_OK;
 }
 
@@ -248,6 +255,7 @@ int choose_op(const y3_op &op, const y3_options &o, y3_step &st) {
     case Y3_OP_MAXPOOL: case Y3_OP_UPSAMPLE: case Y3_OP_ADD: case Y3_OP_COPY: return y3_choose_layer(op, st);
     case Y3_OP_REORG: return y3_choose_reorg(op, st);
     case Y3_OP_YOLO: return y3_choose_yolo(op, o, st);
+    case Y3_OP_AVGPOOL: case Y3_OP_SCALE_CHANNELS: case Y3_OP_SAM: return y3_choose_attention(op, st);
     default: break;
   }
   y3_set_error("op for block %d: unknown kind %d", op.block_idx, op.kind);
@@ -275,6 +283,7 @@ int check_pointers(const y3_op &op, const void *in) {
   Y3_REQUIRE(op.d_out != nullptr || op.kind == Y3_OP_YOLO, "op for block %d has no output pointer", op.block_idx);
   Y3_REQUIRE(op.kind != Y3_OP_CONV || (op.d_weight && op.d_scale && op.d_bias), "conv block %d: missing parameters", op.block_idx);
   Y3_REQUIRE(op.kind != Y3_OP_YOLO || (op.d_bbox && op.d_prob && op.d_cls), "yolo block %d: missing output pointers", op.block_idx);
+  Y3_REQUIRE((op.kind != Y3_OP_SCALE_CHANNELS && op.kind != Y3_OP_SAM) || op.d_res, "op for block %d has no source pointer (d_res)", op.block_idx);
   return Y3_OK;
 }
 
@@ -341,7 +350,7 @@ int y3_abi_version(void) { return Y3_ABI_VERSION; }
 uint32_t y3_capabilities(void) {
   return Y3_CAP_MISH | Y3_CAP_SCALE_X_Y | Y3_CAP_LOGISTIC | Y3_CAP_NEW_COORDS | Y3_CAP_LETTERBOX | Y3_CAP_POOL_DARKNET |
          Y3_CAP_NMS_DARKNET | Y3_CAP_SCORES_DARKNET | Y3_CAP_MULTI_LABEL | Y3_CAP_PREPROCESS_DARKNET | Y3_CAP_REORG |
-         Y3_CAP_LAUNCH_LOG | Y3_CAP_PLAN_OP_DIMS | Y3_CAP_TILES | Y3_CAP_GROUPED_CONV;
+         Y3_CAP_LAUNCH_LOG | Y3_CAP_PLAN_OP_DIMS | Y3_CAP_TILES | Y3_CAP_GROUPED_CONV | Y3_CAP_ATTENTION;
 }
 
 int y3_debug_launch_log_begin(void) {
@@ -655,7 +664,8 @@ double y3_plan_op_bytes(const y3_plan *plan, int op_index) {
       if (o.flags & Y3_F_RESIDUAL) b += out_px * o.out_c * es;
       return b;
     }
-    case Y3_OP_ADD: return 3.0 * out_px * o.out_c * es;
+    case Y3_OP_ADD: case Y3_OP_SAM: return 3.0 * out_px * o.out_c * es;
+    case Y3_OP_SCALE_CHANNELS: return (2.0 * out_px + in_px) * o.out_c * es;   // src in, out, and the (C, 1, 1) scales
     case Y3_OP_YOLO: return in_px * o.n_anchor * (o.n_attr * 4.0 + 28.0);
     default: return (in_px * o.in_c + out_px * o.out_c) * es;
   }

@@ -530,3 +530,5 @@ bool y3_conv_dwise_fits(const y3_op &op);
 int y3_choose_conv_dwise(const y3_op &op, y3_step &st);
 // every other grouped op (y3_conv_path answers 4)
 int y3_choose_conv_grouped(const y3_op &op, y3_step &st);
+// [avgpool], [scale_channels] and [sam] (attention.hip, libyolov3_hip_attn.so)
+int y3_choose_attention(const y3_op &op, y3_step &st);

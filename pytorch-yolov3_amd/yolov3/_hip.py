@@ -33,6 +33,7 @@ LIB_PATH = os.environ.get("Y3_HIP_LIB") or os.path.join(_HERE, "..", "lib", "lib
 
 Y3_F32, Y3_BF16, Y3_F16, Y3_F64 = 0, 1, 2, 3
 OP_CONV, OP_MAXPOOL, OP_UPSAMPLE, OP_ADD, OP_COPY, OP_YOLO, OP_REORG = 1, 2, 3, 4, 5, 6, 7
+OP_AVGPOOL, OP_SCALE_CHANNELS, OP_SAM = 8, 9, 10
 F_LEAKY, F_RESIDUAL, F_OUT_F32, F_IN_NCHW_F32, F_IN_NHWC_U8BGR, F_PLAN_INPUT, F_FUSE_NEXT = 1, 2, 4, 8, 16, 32, 64
 F_MISH, F_LOGISTIC, F_NEW_COORDS, F_POOL_DARKNET, F_SCORES_DARKNET, F_REORG_3D = 128, 256, 512, 1024, 2048, 4096
 # y3_capabilities() bits: what the loaded library computes beyond ABI 6 as first released
@@ -42,6 +43,7 @@ CAP_LAUNCH_LOG = 2048
 CAP_PLAN_OP_DIMS = 4096
 CAP_TILES = 8192
 CAP_GROUPED_CONV = 16384
+CAP_ATTENTION = 32768
 # Darknet's suppression measures (include/yolov3_hip.h: Y3_NMS_*), by the cfg's spelling of `nms_kind`
 NMS_IOU, NMS_GREEDY, NMS_DIOU = 0, 1, 2
 NMS_KINDS = {"iou": NMS_IOU, "greedynms": NMS_GREEDY, "diounms": NMS_DIOU}
@@ -277,7 +279,8 @@ def require_capabilities(needs, what):
     that were to be letterboxed, pool the reference's way where Darknet's rule was asked for, suppress by the
     reference's rule where Darknet's was asked for, score boxes by the reference's soft-max where Darknet's logistic scores
     were asked for, lack the multi-label expansion, lack Darknet's float preprocessing, reject a [reorg] op as of unknown kind,
-    lack the tile cutter and the tiled detection tail, or run a grouped conv as a dense one."""
+    lack the tile cutter and the tiled detection tail, run a grouped conv as a dense one, or reject an [avgpool], [scale_channels]
+    or [sam] op as of unknown kind."""
     missing = needs & ~capabilities()
     if missing:
         names = [n for n, b in (("mish", CAP_MISH), ("scale_x_y", CAP_SCALE_X_Y), ("logistic", CAP_LOGISTIC),
@@ -286,7 +289,8 @@ def require_capabilities(needs, what):
                                 ("Darknet class scores", CAP_SCORES_DARKNET),
                                 ("multi-label detections", CAP_MULTI_LABEL),
                                 ("Darknet preprocessing", CAP_PREPROCESS_DARKNET), ("reorg", CAP_REORG),
-                                ("tiled inference", CAP_TILES), ("grouped convolution", CAP_GROUPED_CONV)) if missing & b]
+                                ("tiled inference", CAP_TILES), ("grouped convolution", CAP_GROUPED_CONV),
+                                ("attention blocks", CAP_ATTENTION)) if missing & b]
         raise HipLibraryError("{}: the loaded libyolov3_hip.so cannot compute {} (rebuild: make -C pytorch-yolov3_amd/csrc)"
                               .format(what, ", ".join(names)))
 

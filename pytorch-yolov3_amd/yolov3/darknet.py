@@ -204,6 +204,9 @@ class Darknet(object):
             elif blk["type"] == "shortcut":
                 self.blocks_to_cache.add(i - 1)
                 self.blocks_to_cache.add(i + blk["from"])
+            elif blk["type"] in ("scale_channels", "sam") and isinstance(blk.get("from"), int):
+                self.blocks_to_cache.add(i - 1)          # (a missing `from` is check_blocks' to refuse, below)
+                self.blocks_to_cache.add(i + blk["from"])
         check_blocks(self.blocks)       # what the kernels cannot compute is refused here, not run with other semantics
         self._out_channels, self._convs = conv_layout(self.blocks, self.net_info)
         for c in self._convs:           # groups= against the channel counts the layout has just worked out

@@ -79,6 +79,10 @@ def route_groups(blk):
 
 REORG_KINDS = ("reorg", "reorg3d")
 HEAD_KINDS = ("yolo", "region")
+# Darknet's attention blocks.  [avgpool]: global average pool, (C, H, W) -> (C, 1, 1).  [scale_channels] from=J: block J's output
+# times the (C, 1, 1) output of the block in front, channel by channel (a squeeze-and-excite unit's last step).  [sam] from=J: block
+# J's output times the output of the block in front, element by element.  `from` is read as a [shortcut]'s is: relative to the block.
+ATTENTION_KINDS = ("avgpool", "scale_channels", "sam")
 MAX_ANCHORS = 8      # y3_op.anchor_w[8]
 
 
@@ -199,6 +203,19 @@ def check_blocks(blocks):
             if blk.get("activation", "linear") != "linear":
                 raise ValueError("shortcut block {}: activation {!r} is not supported (linear only)".format(
                     i, blk["activation"]))
+        elif kind in ATTENTION_KINDS:
+            if i == 0:
+                raise ValueError("{} block 0: only a conv reads the network input (the first block must be "
+                                 "[convolutional])".format(kind))
+            if kind == "avgpool":
+                continue                           # (it takes no parameters)
+            if int(blk.get("scale_wh", 0)) != 0:
+                raise ValueError("{} block {}: scale_wh={} is not supported".format(kind, i, blk["scale_wh"]))
+            if blk.get("activation", "linear") != "linear":
+                raise ValueError("{} block {}: activation {!r} is not supported (linear only)".format(
+                    kind, i, blk["activation"]))
+            if not isinstance(blk.get("from"), int) or not 0 <= i + blk["from"] < i:
+                raise ValueError("{} block {}: from={!r} does not name an earlier block".format(kind, i, blk.get("from")))
 
 
 def check_head_readers(blocks, readers, elem_size):
@@ -272,6 +289,16 @@ def infer_shapes(blocks, net_info, height, width, pool="reference"):
             if kind == "reorg" and c % (s * s):
                 raise ValueError("reorg block {}: {} channels are not a multiple of stride*stride = {}".format(i, c, s * s))
             c, h, w = c * s * s, h // s, w // s
+        elif kind == "avgpool":
+            h, w = 1, 1
+        elif kind in ("scale_channels", "sam"):
+            prev, src = shapes[i - 1], shapes[i + blk["from"]]
+            if kind == "scale_channels" and prev != (src[0], 1, 1):
+                raise ValueError("scale_channels block {} scales {} by {}: the scales must be ({}, 1, 1)".format(
+                    i, src, prev, src[0]))
+            if kind == "sam" and prev != src:
+                raise ValueError("sam block {} multiplies {} by {}".format(i, src, prev))
+            c, h, w = src
         elif kind in HEAD_KINDS or kind == "dropout":
             pass                                   # ([dropout]: Darknet skips it at inference; its keys are read and ignored)
         else:
@@ -305,7 +332,7 @@ def build_plan(blocks, net_info, batch, height, width, elem_size, reuse=True, fu
     readers = [[] for _ in range(n)]      # (consumer block, role)
     for i, blk in enumerate(blocks):
         kind = kinds[i]
-        if kind in ("convolutional", "maxpool", "upsample") + REORG_KINDS + HEAD_KINDS:
+        if kind in ("convolutional", "maxpool", "upsample", "avgpool") + REORG_KINDS + HEAD_KINDS:
             if i > 0:
                 readers[i - 1].append((i, "in"))
         elif kind == "route":
@@ -314,7 +341,9 @@ def build_plan(blocks, net_info, batch, height, width, elem_size, reuse=True, fu
         elif kind == "dropout":
             if i > 0:
                 readers[i - 1].append((i, "route"))   # an alias of its input, as a single-layer route of -1 is
-        elif kind == "shortcut":
+        elif kind in ("shortcut", "scale_channels", "sam"):
+            # (an attention block's two inputs under a shortcut's roles: the head rules below cover them, and a conv is fused
+            # with what follows it only when that is its one reader, so no fusion swallows a tensor an attention block reads)
             readers[i - 1].append((i, "sc_prev"))
             readers[i + blk["from"]].append((i, "sc_from"))
 
@@ -360,7 +389,7 @@ def build_plan(blocks, net_info, batch, height, width, elem_size, reuse=True, fu
                 cj = shapes[j][0]
                 dst = Tensor(buf, off, ld, cj, h, w)
                 ok = (src not in placed and off % CH_ALIGN == 0 and src < i
-                      and kinds[src] in ("convolutional", "maxpool", "upsample", "shortcut") + REORG_KINDS
+                      and kinds[src] in ("convolutional", "maxpool", "upsample", "shortcut") + REORG_KINDS + ATTENTION_KINDS
                       and src not in head_of and kinds[src] != "route")
                 if ok:
                     placed[src] = dst
@@ -440,6 +469,15 @@ def build_plan(blocks, net_info, batch, height, width, elem_size, reuse=True, fu
             op = dict(kind="reorg", block=i, inp=prev_tensor(i), out=out, stride=int(blk.get("stride", 1)))
             if kind == "reorg3d":
                 op["form3d"] = True                # the space-to-depth form (default: Darknet's original flat form)
+            ops.append(op)
+            tensor_of[i] = out
+        elif kind in ATTENTION_KINDS:
+            # handled as an unfused [shortcut] is: an op of its own that reads the block in front (and `from`'s block) and writes
+            # a tensor of its own or its slice of a route's buffer; both inputs stay alive until it has run (liveness below)
+            out = placed[i] if i in placed else own_tensor(i)
+            op = dict(kind=kind, block=i, inp=tensor_of[i - 1], out=out)
+            if kind != "avgpool":
+                op["res"] = tensor_of[i + blk["from"]]
             ops.append(op)
             tensor_of[i] = out
         elif kind == "dropout":

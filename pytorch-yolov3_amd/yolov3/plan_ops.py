@@ -12,6 +12,10 @@ from . import _hip
 STORAGE = {"float32": (_hip.Y3_F32, 4), "bf16": (_hip.Y3_BF16, 2), "fp16": (_hip.Y3_F16, 2)}
 
 
+# plan op kinds of the attention blocks -> C ABI op kinds
+ATTENTION_OPS = {"avgpool": _hip.OP_AVGPOOL, "scale_channels": _hip.OP_SCALE_CHANNELS, "sam": _hip.OP_SAM}
+
+
 def _round_up(v, m):
     return (v + m - 1) // m * m
 
@@ -154,6 +158,11 @@ def fill_ops(desc, net_info, convs, dtype, batch, input_mode, scores, opt, mem):
             if od.get("form3d"):
                 op.flags |= _hip.F_REORG_3D
             needs |= _hip.CAP_REORG
+        elif kind in ATTENTION_OPS:
+            # prev in d_in / in_*, src in d_res / res_ld (filled above), no flags; a stale library would not know the kinds
+            op.kind = ATTENTION_OPS[kind]
+            op.ksize = op.stride = 1
+            needs |= _hip.CAP_ATTENTION
         elif kind == "yolo":
             op.kind = _hip.OP_YOLO
             op.n_anchor = len(od["anchors"])

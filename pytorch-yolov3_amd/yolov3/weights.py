@@ -56,7 +56,9 @@ def conv_layout(blocks, net_info):
                         i, cur, out_ch[i + blk["from"]]))
         elif kind in ("reorg", "reorg3d"):
             cur = cur * int(blk.get("stride", 1)) ** 2
-        # maxpool / upsample / yolo / region keep the channel count
+        elif kind in ("scale_channels", "sam"):
+            cur = out_ch[i + blk["from"]]          # the output has the shape of `from`'s block
+        # maxpool / upsample / avgpool / yolo / region keep the channel count
         out_ch.append(cur)
         prev = cur
     return out_ch, convs
