@@ -281,6 +281,7 @@ int y3_abi_version(void);
 #define Y3_CAP_TILES 8192u     /* y3_tiles_u8, y3_detect_tiled and its workspace query */
 #define Y3_CAP_GROUPED_CONV 16384u /* y3_op.groups on conv ops, y3_conv_path answers 4 and 5, y3_set_tuning("grouped_generic", v) */
 #define Y3_CAP_ATTENTION 32768u /* Y3_OP_AVGPOOL, Y3_OP_SCALE_CHANNELS and Y3_OP_SAM */
+#define Y3_CAP_TILE_MERGE 65536u /* y3_merge_tiled and its workspace query   */
 uint32_t y3_capabilities(void);
 const char *y3_last_error(void);
 /* number of visible HIP devices whose arch is gfx950 (0 on a CPU-only machine) */
@@ -418,7 +419,8 @@ int y3_detect_letterbox(const float *d_bbox, const float *d_prob, const int64_t 
  * d_det_count (batch); d_det_tlbr (batch, tiles * rows, 4); d_det_prob, d_det_cls, d_det_row (batch, tiles * rows).
  * tiles * rows must fit an int32.  The same kernel as y3_detect, one launch.  Darknet's suppression kinds, the letterbox
  * correction and multi-label virtual rows have no tiled form.  An object cut by a tile border yields partial boxes that the
- * suppression does not merge: overlapping windows (and a stretched overview for large objects) are the caller's guard.   */
+ * suppression does not merge, unless y3_merge_tiled (below) runs after it: otherwise overlapping windows (and a stretched
+ * overview for large objects) are the caller's guard.                                                                   */
 typedef struct {
   float sx, sy;      /* pixels per unit of the tile's relative x / y */
   int32_t ox, oy;    /* the tile's origin in the frame, pixels        */
@@ -428,6 +430,41 @@ int y3_detect_tiled(const float *d_bbox, const float *d_prob, const int64_t *d_c
                     const y3_tile_geom *d_geom, float prob_thresh, double iou_thresh, void *d_workspace, size_t workspace_bytes,
                     int32_t *d_det_count, int64_t *d_det_tlbr, float *d_det_prob, int64_t *d_det_cls, int32_t *d_det_row,
                     void *stream);
+
+/* Seam merging, an opt-in second pass over the output of y3_detect_tiled (csrc/tile_merge.hip, libyolov3_hip_tilemerge.so;
+ * y3_capabilities() reports Y3_CAP_TILE_MERGE).  Not in the reference.  y3_detect_tiled itself is unchanged: a caller that does
+ * not call this function gets what it always got.  An object cut by a tile border comes out of y3_detect_tiled as partial boxes:
+ * the IoU of a part with the whole, or of two parts, is small, so the suppression keeps them all.  This pass matches boxes of
+ * DIFFERENT tiles by intersection over the smaller area (IoS), which is near 1 for a part against its whole, and merges the
+ * matches into their union box.  Everything is integers plus one float64 division: there is no tolerance anywhere.
+ *   Input: one frame's `count` detections in the canonical order (class ascending, score descending, combined row descending),
+ *   each with int64 corners (x1, y1, x2, y2), a float32 score, an int64 class and an int32 combined row.  The tile of a
+ *   detection is row / tile_rows; the overview is a tile like any other.
+ *   Measures: w = x2 - x1 + 1, h = y2 - y1 + 1, area = w * h in int64 (the +1 pixel convention of y3_detect).  A box with w <= 0
+ *   or h <= 0 is degenerate: it never matches, is never matched, and passes through unchanged.  For two non-degenerate boxes
+ *   iw = min(ax2, bx2) - max(ax1, bx1) + 1 clamped at 0, ih likewise in y, inter = iw * ih, and
+ *     a matches b  iff  (double)inter / (double)min(area_a, area_b) > thr          (true float64 division, strict comparison)
+ *   Greedy pass, in the canonical order, classes independent: a detection that nothing has absorbed is a keeper.  Keeper i
+ *   absorbs every later detection j that has i's class, is not absorbed yet, comes from a different tile than i, and whose
+ *   ORIGINAL box i's ORIGINAL box matches.  The first keeper in order that matches a detection takes it; an absorbed detection
+ *   absorbs nobody; matching never uses a grown box.
+ *   The different-tile condition: within one tile the network saw both boxes in one view and the IoU suppression has already
+ *   ruled -- a small box inside a larger one of its class in the same window is two objects; across tiles it is a part and a whole.
+ *   Output: the keepers, in the input's order (so still canonical).  A keeper's box is the union of its own box and the original
+ *   boxes of everything it absorbed (min of the x1 / y1, max of the x2 / y2); score, class and row are its own; members = 1 + the
+ *   number of detections it absorbed.  Slots past the new count are not written.
+ * thr = 1.0 never matches, and neither does anything when capacity == tile_rows (one tile): the output is then the input bit for bit,
+ * all members 1.  The five inputs are y3_detect_tiled's outputs for `batch` frames of `capacity` (= tiles * rows) slots each and
+ * are only read; tile_rows = rows, a divisor of capacity; thr is finite, 0 <= thr <= 1.  The outputs have the inputs' shapes, plus
+ * d_out_members (batch, capacity) int32, which may be null; no output (nor the workspace) may overlap an input.  A frame whose count is 0
+ * writes count 0 and nothing else; a count past `capacity` is read as `capacity`.  One launch of one 1024-thread workgroup per frame,
+ * no host synchronisation; boxes may lie anywhere in int64 as long as their areas do (those within +-16000 take a 32-bit test
+ * that decides the same).                                                                                                */
+size_t y3_merge_tiled_workspace_bytes(int batch, int capacity);
+int y3_merge_tiled(const int32_t *d_det_count, const int64_t *d_det_tlbr, const float *d_det_prob, const int64_t *d_det_cls,
+                   const int32_t *d_det_row, int batch, int capacity, int tile_rows, double thr, void *d_workspace,
+                   size_t workspace_bytes, int32_t *d_out_count, int64_t *d_out_tlbr, float *d_out_prob, int64_t *d_out_cls,
+                   int32_t *d_out_row, int32_t *d_out_members, void *stream);
 
 /* Darknet's suppression rule (src/box.c: box_iou, box_diou, box_diounms; do_nms_sort, diounms_sort) instead of the
  * reference's.  Not in the reference.  ONLY the decision which candidates survive changes: thresholding, candidate order

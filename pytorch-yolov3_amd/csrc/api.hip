@@ -350,7 +350,8 @@ int y3_abi_version(void) { return Y3_ABI_VERSION; }
 uint32_t y3_capabilities(void) {
   return Y3_CAP_MISH | Y3_CAP_SCALE_X_Y | Y3_CAP_LOGISTIC | Y3_CAP_NEW_COORDS | Y3_CAP_LETTERBOX | Y3_CAP_POOL_DARKNET |
          Y3_CAP_NMS_DARKNET | Y3_CAP_SCORES_DARKNET | Y3_CAP_MULTI_LABEL | Y3_CAP_PREPROCESS_DARKNET | Y3_CAP_REORG |
-         Y3_CAP_LAUNCH_LOG | Y3_CAP_PLAN_OP_DIMS | Y3_CAP_TILES | Y3_CAP_GROUPED_CONV | Y3_CAP_ATTENTION;
+         Y3_CAP_LAUNCH_LOG | Y3_CAP_PLAN_OP_DIMS | Y3_CAP_TILES | Y3_CAP_GROUPED_CONV | Y3_CAP_ATTENTION |
+         Y3_CAP_TILE_MERGE;
 }
 
 int y3_debug_launch_log_begin(void) {

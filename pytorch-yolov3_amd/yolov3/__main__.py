@@ -36,7 +36,8 @@ _MODEL_OPTIONS = [
     (("--nms-kind",), dict(choices=["iou", "greedynms", "diounms"], default=None, help="suppress by Darknet's rule on the float32 boxes instead of the reference's on integer pixel corners: iou (a cfg without nms_kind), greedynms (yolov4.cfg) or diounms (yolov4-csp.cfg); -i is its threshold (Darknet's own defaults are -p 0.25 -i 0.45)")),
     (("--darknet-scores",), dict(action="store_true", help="score every class of a box by Darknet's independent logistic, sigmoid(obj) * sigmoid(class), instead of the reference's soft-max over the classes; use it with weights trained by Darknet for yolov3, yolov3-tiny, yolov3-spp, yolov4 and yolov4-tiny (yolov4-csp scores that way already)")),
     (("--multi-label",), dict(action="store_true", help="report every class of a box that scores above -p, as Darknet does, not the best class only (a box may then appear once per class); implies --darknet-scores")),
-    (("--tile-overlap",), dict(type=float, default=None, metavar="<fraction>", help="tiled inference for images larger than the network (-I only): cut every image into network-sized tiles at full resolution whose neighbours share at least this fraction (0 .. 0.9) of the network size, run them all and suppress over their union; objects too small to survive the resize are found, objects cut by a tile border may come out as partial boxes")),
+    (("--tile-overlap",), dict(type=float, default=None, metavar="<fraction>", help="tiled inference for images larger than the network (-I only): cut every image into network-sized tiles at full resolution whose neighbours share at least this fraction (0 .. 0.9) of the network size, run them all and suppress over their union; objects too small to survive the resize are found, objects cut by a tile border may come out as partial boxes unless --tile-merge is given")),
+    (("--tile-merge",), dict(type=float, default=None, metavar="<threshold>", help="with --tile-overlap: merge detections of one class from different tiles whose intersection over the smaller box exceeds this threshold (0 .. 1; 0.5 is a reasonable start) into one detection with their union box, so that an object cut by a tile border is reported once")),
     (("--no-tile-overview",), dict(action="store_true", help="with --tile-overlap: leave out the extra tile that holds the whole image resized to the network (it finds objects larger than a tile)")),
     (("--beta-nms",), dict(type=float, default=0.6, metavar="<beta>", help="exponent of the distance penalty of --nms-kind diounms (default 0.6, the cfgs' beta_nms)")),
 ]
@@ -92,10 +93,12 @@ def _write_frames(frames, fps, path):
 
 
 def check_tiling(args):
-    """``--tile-overlap`` and what it does not combine with: SystemExit before anything is loaded.  args: the parsed options."""
+    """``--tile-overlap`` (and ``--tile-merge``, which needs it) and what it does not combine with: SystemExit before anything is loaded.  args: the parsed options."""
     if args["tile_overlap"] is None:
         if args["no_tile_overview"]:
             raise SystemExit("yolov3: --no-tile-overview means nothing without --tile-overlap")
+        if args["tile_merge"] is not None:
+            raise SystemExit("yolov3: --tile-merge means nothing without --tile-overlap")
         return
     if not args["image"]:
         raise SystemExit("yolov3: --tile-overlap refused with video or camera input -- tiled inference runs on images (-I) only")
@@ -105,6 +108,12 @@ def check_tiling(args):
                       nms_kind=args["nms_kind"], multi_label=args["multi_label"])
     except ValueError as exc:
         raise SystemExit("yolov3: --tile-overlap refused: %s" % exc)
+    if args["tile_merge"] is not None:
+        from .tiles import check_merge
+        try:
+            check_merge(args["tile_merge"])
+        except ValueError as exc:
+            raise SystemExit("yolov3: --tile-merge refused: %s" % exc)
 
 
 def main(argv=None):
@@ -146,7 +155,8 @@ def main(argv=None):
         if args["tile_overlap"] is not None:
             results = [tuple(yolov3.inference(net, image, device=device, prob_thresh=args["prob_thresh"],
                                               nms_iou_thresh=args["iou_thresh"], tile_overlap=args["tile_overlap"],
-                                              tile_overview=not args["no_tile_overview"], tile_batch=args["batch_size"])[0])
+                                              tile_overview=not args["no_tile_overview"], tile_batch=args["batch_size"],
+                                              tile_merge=args["tile_merge"])[0])
                        for image in images]
         else:
             results = list(stream.detect_in_frames(net, images, batch_size=args["batch_size"],

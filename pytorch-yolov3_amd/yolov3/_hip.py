@@ -44,6 +44,7 @@ CAP_PLAN_OP_DIMS = 4096
 CAP_TILES = 8192
 CAP_GROUPED_CONV = 16384
 CAP_ATTENTION = 32768
+CAP_TILE_MERGE = 65536
 # Darknet's suppression measures (include/yolov3_hip.h: Y3_NMS_*), by the cfg's spelling of `nms_kind`
 NMS_IOU, NMS_GREEDY, NMS_DIOU = 0, 1, 2
 NMS_KINDS = {"iou": NMS_IOU, "greedynms": NMS_GREEDY, "diounms": NMS_DIOU}
@@ -185,6 +186,11 @@ PROTOTYPES = {
                                        ctypes.c_void_p, ctypes.c_float, ctypes.c_double, ctypes.c_void_p, ctypes.c_size_t,
                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                        ctypes.c_void_p]),
+    "y3_merge_tiled_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
+    "y3_merge_tiled": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                      ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_void_p, ctypes.c_size_t,
+                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                      ctypes.c_void_p, ctypes.c_void_p]),
     "y3_detect_darknet_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
     "y3_detect_darknet": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
                                          ctypes.c_void_p, ctypes.c_float, ctypes.c_double, ctypes.c_void_p,
@@ -232,7 +238,8 @@ _OPTIONAL = ("y3_capabilities", "y3_detect_letterbox", "y3_letterbox_geometry", 
              "y3_detect_darknet_workspace_bytes", "y3_detect_darknet", "y3_nms_darknet_workspace_bytes", "y3_nms_darknet",
              "y3_expand_labels_workspace_bytes", "y3_expand_labels", "y3_preprocess_darknet_f32",
              "y3_debug_launch_log_begin", "y3_debug_launch_log_end", "y3_plan_op_dims",
-             "y3_tiles_u8", "y3_detect_tiled_workspace_bytes", "y3_detect_tiled")
+             "y3_tiles_u8", "y3_detect_tiled_workspace_bytes", "y3_detect_tiled",
+             "y3_merge_tiled_workspace_bytes", "y3_merge_tiled")
 
 
 class HipLibraryError(RuntimeError):
@@ -280,7 +287,7 @@ def require_capabilities(needs, what):
     reference's rule where Darknet's was asked for, score boxes by the reference's soft-max where Darknet's logistic scores
     were asked for, lack the multi-label expansion, lack Darknet's float preprocessing, reject a [reorg] op as of unknown kind,
     lack the tile cutter and the tiled detection tail, run a grouped conv as a dense one, or reject an [avgpool], [scale_channels]
-    or [sam] op as of unknown kind."""
+    or [sam] op as of unknown kind, or lack the seam merge of tiled inference."""
     missing = needs & ~capabilities()
     if missing:
         names = [n for n, b in (("mish", CAP_MISH), ("scale_x_y", CAP_SCALE_X_Y), ("logistic", CAP_LOGISTIC),
@@ -290,7 +297,7 @@ def require_capabilities(needs, what):
                                 ("multi-label detections", CAP_MULTI_LABEL),
                                 ("Darknet preprocessing", CAP_PREPROCESS_DARKNET), ("reorg", CAP_REORG),
                                 ("tiled inference", CAP_TILES), ("grouped convolution", CAP_GROUPED_CONV),
-                                ("attention blocks", CAP_ATTENTION)) if missing & b]
+                                ("attention blocks", CAP_ATTENTION), ("tile seam merging", CAP_TILE_MERGE)) if missing & b]
         raise HipLibraryError("{}: the loaded libyolov3_hip.so cannot compute {} (rebuild: make -C pytorch-yolov3_amd/csrc)"
                               .format(what, ", ".join(names)))
 

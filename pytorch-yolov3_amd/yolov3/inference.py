@@ -27,7 +27,11 @@
   batch (``y3_preprocess_darknet_f32``), and the network runs from that float input instead of the fused uint8 stem;
 * ``tile_overlap=f`` (opt-in, not in the reference) looks at a frame larger than the network through net-sized windows at full
   resolution (``yolov3/tiles.py``): the windows are cut on the device (``y3_tiles_u8``), run through the network in chunks, and
-  all their rows are one frame's candidates, each mapped back by its window's origin, before one suppression (``y3_detect_tiled``).
+  all their rows are one frame's candidates, each mapped back by its window's origin, before one suppression (``y3_detect_tiled``);
+* ``tile_merge=t`` (opt-in, with ``tile_overlap`` only; not in the reference) adds the seam merge after that suppression
+  (``y3_merge_tiled``, one more launch on the same stream): detections of one class from DIFFERENT tiles whose intersection over
+  the smaller area exceeds ``t`` become one detection with their union box, so an object cut by a tile border is reported once.
+  ``tiles.merge_detections`` is the same rule in numpy.
 
 There is no CPU fallback: without the HIP library / a GPU these functions raise.
 """
@@ -229,6 +233,8 @@ class Detector(object):
         self._labels = {}        # capacity -> _LabelBuffers of multi-label runs
         self._tail = self        # the Detector that holds the last run's detections (another one for a capacity != rows)
         self._label_run = None   # multi-label: the _LabelBuffers of the last run, whose true counts fetch() checks
+        self._merge = None       # _MergeBuffers of run_tiled(merge=...), made when first asked for
+        self._merge_run = None   # ... when the last run merged: what fetch() then reports
 
     def run(self, out, orig_hw, prob_thresh, iou_thresh, letterbox=None, nms_kind=None, beta_nms=0.6, labels=None,
             label_capacity=None):
@@ -244,7 +250,7 @@ class Detector(object):
         mode = _hip.nms_mode(nms_kind, beta_nms)
         if labels is not None:
             return self._run_labels(out, orig_hw, prob_thresh, iou_thresh, letterbox, nms_kind, beta_nms, labels, label_capacity)
-        self._tail, self._label_run = self, None
+        self._tail, self._label_run, self._merge_run = self, None, None
         if not isinstance(orig_hw, torch.Tensor):
             orig_hw = torch.from_numpy(np.ascontiguousarray(orig_hw, dtype=np.int32))
         if (orig_hw.device == self.orig_hw.device and orig_hw.dtype == torch.int32 and orig_hw.is_contiguous()
@@ -277,13 +283,21 @@ class Detector(object):
         else:
             _hip.check(lib.y3_detect(*args, _hip.stream_ptr()))
 
-    def run_tiled(self, out, geom, tiles, prob_thresh, iou_thresh):
+    def run_tiled(self, out, geom, tiles, prob_thresh, iou_thresh, merge=None):
         """The detection tail over frames that were run as tiles (``y3_detect_tiled``).  out: forward outputs of
         ``batch * tiles`` tiles, frame by frame (device tensors).  geom: ``y3_tile_geom`` of every tile in that order -- a uint8
         device tensor of 16 bytes per tile, or a list of (sx, sy, ox, oy).  This Detector's ``rows`` is the capacity of a frame,
         ``tiles`` times the rows of a tile, and the rows ``fetch`` reports are combined rows, tile * rows of a tile + row.  The
-        reference's suppression only: no letterbox correction, no Darknet kinds, no multi-label rows."""
+        reference's suppression only: no letterbox correction, no Darknet kinds, no multi-label rows.
+        merge: None, or the seam-merge threshold in [0, 1]: ``y3_merge_tiled`` then runs after the tail, on the same stream, into
+        buffers of its own (made on first use); ``fetch`` reports the merged detections and ``members`` how many detections each
+        one stands for.  The unmerged detections stay in ``count`` / ``tlbr`` / ``prob`` / ``cls`` / ``row``.  The merge buffers
+        (outputs, members and workspace at full capacity, about 68 bytes per slot) stay with this Detector once made: a later
+        ``merge=None`` run allocates nothing and launches nothing more, but does not free them either."""
         _hip.require_capabilities(_hip.CAP_TILES, "Detector.run_tiled")
+        if merge is not None:
+            merge = _tiles.check_merge(merge)
+            _hip.require_capabilities(_hip.CAP_TILE_MERGE, "Detector.run_tiled(merge=...)")
         bbox, prob, cls = out["bbox_xywh"], out["class_prob"], out["class_idx"]
         tiles = int(tiles)
         if tiles < 1 or self.rows % tiles or tuple(prob.shape) != (self.batch * tiles, self.rows // tiles):
@@ -295,12 +309,29 @@ class Detector(object):
             geom = tile_geom_tensor(geom, self.device)
         if geom.dtype != torch.uint8 or geom.numel() != 16 * self.batch * tiles or not geom.is_contiguous():
             raise ValueError("Detector.run_tiled: expected {} tile geometries of 16 bytes".format(self.batch * tiles))
-        self._tail, self._label_run = self, None
+        self._tail, self._label_run, self._merge_run = self, None, None
         self._geom = geom                                   # alive until the next run
         _hip.check(_hip.lib().y3_detect_tiled(
             bbox.data_ptr(), prob.data_ptr(), cls.data_ptr(), self.batch, tiles, self.rows // tiles, geom.data_ptr(),
             ctypes.c_float(prob_thresh), ctypes.c_double(iou_thresh), self.ws.data_ptr(), self.ws_bytes, self.count.data_ptr(),
             self.tlbr.data_ptr(), self.prob.data_ptr(), self.cls.data_ptr(), self.row.data_ptr(), _hip.stream_ptr()))
+        if merge is not None:
+            mb = self._merge
+            if mb is None:
+                mb = self._merge = _MergeBuffers(self.batch, self.rows, self.device)
+            _hip.check(_hip.lib().y3_merge_tiled(
+                self.count.data_ptr(), self.tlbr.data_ptr(), self.prob.data_ptr(), self.cls.data_ptr(), self.row.data_ptr(),
+                self.batch, self.rows, self.rows // tiles, ctypes.c_double(merge), mb.ws.data_ptr(), mb.ws_bytes,
+                mb.count.data_ptr(), mb.tlbr.data_ptr(), mb.prob.data_ptr(), mb.cls.data_ptr(), mb.row.data_ptr(),
+                mb.members.data_ptr(), _hip.stream_ptr()))
+            self._merge_run = mb
+
+    @property
+    def members(self):
+        """After ``run_tiled(merge=...)``: the (batch, rows) int32 device tensor whose first ``count`` entries of a frame say how
+        many detections each merged detection stands for (1 = nothing absorbed); None after any other run."""
+        tail = self._tail
+        return tail._merge_run.members if tail._merge_run is not None else None
 
     def _run_labels(self, out, orig_hw, prob_thresh, iou_thresh, letterbox, nms_kind, beta_nms, labels, label_capacity):
         _hip.require_capabilities(_hip.CAP_MULTI_LABEL, "Detector.run(labels=...)")
@@ -328,7 +359,7 @@ class Detector(object):
         lb.index.copy_(tail.row)
         lb.index.clamp_(0, cap - 1)
         torch.gather(lb.vrow, 1, lb.index, out=tail.row)
-        self._tail, self._label_run = tail, lb
+        self._tail, self._label_run, self._merge_run = tail, lb, None
 
     def check_label_capacity(self, n_frames=None):
         """After a multi-label ``run``: RuntimeError if one of the first ``n_frames`` frames (default: all) had more labels than
@@ -352,12 +383,13 @@ class Detector(object):
         from .dist import unpack_records
         lib = _hip.lib()
         kmax = max(1, min(int(kmax), self.rows))
+        src = self._merge_run if self._merge_run is not None else self     # the merged detections of run_tiled(merge=...)
         while True:
             rec = self._records.get(kmax)
             if rec is None:
                 rec = self._records[kmax] = torch.empty((self.batch, kmax, 8), dtype=torch.int32, device=self.device)
-            _hip.check(lib.y3_pack_records(self.count.data_ptr(), self.tlbr.data_ptr(), self.prob.data_ptr(),
-                                           self.cls.data_ptr(), self.row.data_ptr(), self.batch, self.rows, kmax,
+            _hip.check(lib.y3_pack_records(src.count.data_ptr(), src.tlbr.data_ptr(), src.prob.data_ptr(),
+                                           src.cls.data_ptr(), src.row.data_ptr(), self.batch, self.rows, kmax,
                                            rec.data_ptr(), None, _hip.stream_ptr()))
             host = rec.cpu().numpy()                         # the one synchronising copy
             most = int(host[:, 0, 7].max()) if host.size else 0
@@ -368,6 +400,20 @@ class Detector(object):
         for item in unpack_records(host):
             results.append(item[:4] if return_rows else item[:3])
         return results
+
+
+class _MergeBuffers(object):
+    """Device buffers of ``y3_merge_tiled`` for one (batch, capacity): its outputs, the members and its workspace."""
+
+    def __init__(self, batch, rows, device):
+        self.ws_bytes = _hip.lib().y3_merge_tiled_workspace_bytes(batch, rows)
+        self.ws = torch.empty(self.ws_bytes, dtype=torch.uint8, device=device)
+        self.count = torch.zeros(batch, dtype=torch.int32, device=device)
+        self.tlbr = torch.empty((batch, rows, 4), dtype=torch.int64, device=device)
+        self.prob = torch.empty((batch, rows), dtype=torch.float32, device=device)
+        self.cls = torch.empty((batch, rows), dtype=torch.int64, device=device)
+        self.row = torch.empty((batch, rows), dtype=torch.int32, device=device)
+        self.members = torch.empty((batch, rows), dtype=torch.int32, device=device)
 
 
 class _LabelBuffers(object):
@@ -463,8 +509,10 @@ class _TileBuffers(object):
 _tile_buffers = {}
 
 
-def _inference_tiled(net, images, dev, prob_thresh, iou_thresh, return_rows, overlap, overview, fill, tile_batch):
+def _inference_tiled(net, images, dev, prob_thresh, iou_thresh, return_rows, overlap, overview, fill, tile_batch, merge=None):
     _hip.require_capabilities(_hip.CAP_TILES, "inference(tile_overlap=...)")
+    if merge is not None:
+        _hip.require_capabilities(_hip.CAP_TILE_MERGE, "inference(tile_merge=...)")
     net_h, net_w = net.net_info["height"], net.net_info["width"]
     results = []
     for image in images:
@@ -482,7 +530,7 @@ def _inference_tiled(net, images, dev, prob_thresh, iou_thresh, return_rows, ove
                     union[k][start:stop].copy_(v)
             rows = int(union["class_prob"].shape[1])
             det = get_detector(1, n_tiles * rows, dev)
-            det.run_tiled(union, geom, n_tiles, prob_thresh, iou_thresh)
+            det.run_tiled(union, geom, n_tiles, prob_thresh, iou_thresh, merge=merge)
             results.extend(det.fetch(return_rows=return_rows))
     return results
 
@@ -501,7 +549,7 @@ def get_detector(batch, rows, device):
 
 def inference(net, images, device="cuda", prob_thresh=0.05, nms_iou_thresh=0.3, resize=True,
               return_rows=False, letterbox=False, letterbox_fill=128, nms_kind=None, beta_nms=0.6, label_capacity=None,
-              preprocess=None, tile_overlap=None, tile_overview=True, tile_fill=128, tile_batch=16):
+              preprocess=None, tile_overlap=None, tile_overview=True, tile_fill=128, tile_batch=16, tile_merge=None):
     """Run detection on one frame or a list of HxWx3 uint8 BGR frames.
 
     Returns, per frame, ``[bbox_tlbr int64 (K,4), class_prob float32 (K,), class_idx int64 (K,)]``
@@ -533,10 +581,24 @@ def inference(net, images, device="cuda", prob_thresh=0.05, nms_iou_thresh=0.3, 
     and net_w columns, for objects larger than a window.  The tiles run through the network in chunks of at most ``tile_batch``; all their rows are the
     frame's candidates, in frame pixels, for one suppression.  With ``return_rows`` the row of a detection is
     ``tile * rows of one tile + row``, tiles in ``tiles.tile_grid``'s order and the overview last.  An object cut by a window's
-    border yields partial boxes that suppression does not merge: choose the overlap larger than the objects looked for.
+    border yields partial boxes that suppression does not merge unless ``tile_merge`` is given: otherwise choose the overlap
+    larger than the objects looked for.
     ValueError with ``letterbox=True``, ``preprocess="darknet"``, ``resize=False``, an ``nms_kind``, a ``multi_label``
     network, or an overlap outside [0, 0.9].
+
+    ``tile_merge``: None [default] = nothing more (no further launch, no further buffer); a threshold in [0, 1] = the seam merge
+    after the suppression (``y3_merge_tiled``; include/yolov3_hip.h states the rule, ``tiles.merge_detections`` restates it).
+    In the canonical order, a detection absorbs every later one of its class that comes from a DIFFERENT tile, is not absorbed
+    yet, and whose box it matches: intersection over the smaller of the two areas ``>`` the threshold, on the original integer
+    boxes.  What it absorbed is dropped and its box becomes the union; score, class and -- with ``return_rows`` -- row stay its
+    own, so four arrays per frame as before.  Pairs within one tile are left alone: the network saw both in one view and the IoU
+    suppression has ruled.  0.5 is a reasonable start; 1.0 merges nothing.  Its effect on accuracy has not been measured.
+    ValueError without ``tile_overlap``, or for a value that is no number in [0, 1].
     """
+    if tile_merge is not None:
+        if tile_overlap is None:
+            raise ValueError("tile_merge needs tile_overlap: seam merging is a stage of tiled inference")
+        tile_merge = _tiles.check_merge(tile_merge)
     if tile_overlap is not None:
         tile_overlap = _tiles.check_options(tile_overlap, letterbox=letterbox, preprocess=preprocess, resize=resize,
                                             nms_kind=nms_kind, multi_label=getattr(net, "multi_label", False))
@@ -556,7 +618,7 @@ def inference(net, images, device="cuda", prob_thresh=0.05, nms_iou_thresh=0.3, 
     dev = net._torch_device()
     if tile_overlap is not None:
         return _inference_tiled(net, list(images), dev, float(np.float32(prob_thresh)), float(nms_iou_thresh), return_rows,
-                                tile_overlap, bool(tile_overview), tile_fill, int(tile_batch))
+                                tile_overlap, bool(tile_overview), tile_fill, int(tile_batch), merge=tile_merge)
     net_h, net_w = net.net_info["height"], net.net_info["width"]
     if mode == "darknet":
         _hip.require_capabilities(_hip.CAP_PREPROCESS_DARKNET | (_hip.CAP_LETTERBOX if letterbox else 0),

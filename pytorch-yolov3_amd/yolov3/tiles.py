@@ -6,9 +6,17 @@ into the frame (:func:`tile_geometry`), which options tiling refuses (:func:`che
 cutter (:func:`cut_tiles_u8`).  The device side is ``y3_tiles_u8`` (the letterbox kernel's copy form) and ``y3_detect_tiled``
 (the detection tail over the union of a frame's tiles); ``inference(..., tile_overlap=f)`` puts them together.
 
-An object cut by a tile border yields partial boxes, and IoU suppression does not merge a part with the whole: the overlap
+An object cut by a tile border yields partial boxes, and IoU suppression does not merge a part with the whole, unless
+``tile_merge`` (``--tile-merge``) is given: otherwise the overlap
 between neighbouring windows is what guards against that (an object smaller than the overlap lies whole in one window), along
 with the overview -- the whole frame stretched to the network by the default 8-bit resize -- for objects larger than a window.
+
+Seam merging (``inference(..., tile_overlap=f, tile_merge=t)``, ``y3_merge_tiled`` on the device) is an opt-in second pass over
+a frame's detections: boxes of one class from DIFFERENT tiles whose intersection over the smaller area exceeds ``t`` are merged
+into their union box, greedily in the canonical order, always matching on original boxes.  :func:`check_merge` checks the
+threshold and :func:`merge_detections` states the rule in numpy (include/yolov3_hip.h states it in full).  Within one tile the
+network saw both boxes at once and the IoU suppression has ruled, so same-tile pairs are left alone.  0.5 is a reasonable first
+threshold; its effect on accuracy has not been measured here.
 """
 import numpy as np
 
@@ -23,6 +31,19 @@ def check_overlap(overlap):
         raise ValueError("tile_overlap must be a fraction in [0, {}], got {!r}".format(MAX_OVERLAP, overlap))
     if not 0.0 <= f <= MAX_OVERLAP:                          # (NaN fails both comparisons)
         raise ValueError("tile_overlap must be a fraction in [0, {}], got {!r}".format(MAX_OVERLAP, overlap))
+    return f
+
+
+def check_merge(thr):
+    """The seam-merge threshold as a float; ValueError for anything that is not a number in [0, 1] (NaN included)."""
+    try:
+        if isinstance(thr, (bool, str, bytes)):
+            raise TypeError
+        f = float(thr)
+    except (TypeError, ValueError):
+        raise ValueError("tile_merge must be a number in [0, 1], got {!r}".format(thr))
+    if not 0.0 <= f <= 1.0:                                  # (NaN fails both comparisons)
+        raise ValueError("tile_merge must be a number in [0, 1], got {!r}".format(thr))
     return f
 
 
@@ -86,3 +107,45 @@ def check_options(overlap, letterbox=False, preprocess=None, resize=True, nms_ki
         raise ValueError("tile_overlap cannot be combined with a multi_label network: the tiled detection tail takes no "
                          "multi-label virtual rows")
     return f
+
+
+def merge_detections(tlbr, prob, cls, rows, tile_rows, thr):
+    """What ``y3_merge_tiled`` computes for one frame, in numpy: ``(tlbr, prob, cls, rows, members)`` of the keepers.
+
+    The inputs are a frame's detections in canonical order (class ascending, score descending, row descending): int64 corners
+    (n, 4), scores, classes and combined rows; a detection's tile is ``row // tile_rows``.  Areas and intersections are int64 with
+    the +1 pixel convention, a box with ``w <= 0`` or ``h <= 0`` neither matches nor is matched, and ``a`` matches ``b`` iff
+    ``inter / min(area_a, area_b) > thr`` in float64.  In order, a detection that nothing has absorbed is a keeper and absorbs
+    every later, not yet absorbed detection of its class from another tile that its original box matches; a keeper's box
+    becomes the union of its own and its members' original boxes, everything else it carries stays its own."""
+    thr = check_merge(thr)
+    tile_rows = int(tile_rows)
+    if tile_rows < 1:
+        raise ValueError("merge_detections: tile_rows must be positive, got {}".format(tile_rows))
+    box = np.asarray(tlbr, dtype=np.int64).reshape(-1, 4)
+    prob, cls, rows = np.asarray(prob), np.asarray(cls), np.asarray(rows)
+    n = len(box)
+    w, h = box[:, 2] - box[:, 0] + 1, box[:, 3] - box[:, 1] + 1
+    area = w * h
+    ok = (w > 0) & (h > 0)
+    tile = rows.astype(np.int64) // tile_rows
+    out = box.copy()
+    members = np.ones(n, dtype=np.int32)
+    free = np.ones(n, dtype=bool)          # not absorbed
+    for i in range(n):
+        if not (free[i] and ok[i]):
+            continue
+        later = slice(i + 1, n)
+        iw = np.maximum(np.minimum(box[i, 2], box[later, 2]) - np.maximum(box[i, 0], box[later, 0]) + 1, 0)
+        ih = np.maximum(np.minimum(box[i, 3], box[later, 3]) - np.maximum(box[i, 1], box[later, 1]) + 1, 0)
+        small = np.minimum(area[i], area[later])
+        cand = free[later] & ok[later] & (cls[later] == cls[i]) & (tile[later] != tile[i])
+        ios = np.zeros(n - i - 1, dtype=np.float64)
+        ios[cand] = (iw * ih)[cand].astype(np.float64) / small[cand].astype(np.float64)
+        take = np.flatnonzero(cand & (ios > thr)) + i + 1
+        if len(take):
+            free[take] = False
+            members[i] += len(take)
+            out[i, :2] = np.minimum(out[i, :2], box[take, :2].min(axis=0))
+            out[i, 2:] = np.maximum(out[i, 2:], box[take, 2:].max(axis=0))
+    return out[free], prob[free], cls[free], rows[free], members[free]

@@ -1,7 +1,8 @@
 """Time tiled inference on one large frame -- by default 3840 x 2160 through yolov3 at 608 x 608 in bf16, procedural weights,
 overlap 0.2: 40 tiles and the overview -- piece by piece: the tile cutter (y3_tiles_u8) alone, the tiled detection tail
 (y3_detect_tiled) alone at the candidate count the run produces, the forward of the same tiles in the chunks inference() uses,
-and the whole inference() call from a host frame to host detections.  Per line the median of --passes passes of --iters calls
+and the whole inference() call from a host frame to host detections.  With --merge F also the seam merge (y3_merge_tiled) alone on
+what that tail kept, and the whole call with tile_merge=F next to the call without.  Per line the median of --passes passes of --iters calls
 each (device time between two events for the pieces, wall time for the call).
 
 The detection tail is one workgroup per frame and greedy suppression is quadratic in the candidates of a class, so the
@@ -9,6 +10,7 @@ regime matters: the default objectness bias is bench.py's (-8.5, a few hundred c
 candidates and one call takes seconds.  The candidate count is printed before the tail is timed, and a tail whose first call
 takes more than --tail-limit-ms is reported from that one call."""
 import argparse
+import ctypes
 import os
 import statistics
 import sys
@@ -20,7 +22,8 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "pytorch-yolov3_amd"))
 import yolov3  # noqa: E402
-from yolov3.inference import Detector, cut_tiles_device, frame_tiles_device, tile_chunks, tile_geom_tensor  # noqa: E402
+from yolov3 import _hip  # noqa: E402
+from yolov3.inference import Detector, _MergeBuffers, cut_tiles_device, frame_tiles_device, tile_chunks, tile_geom_tensor  # noqa: E402
 from yolov3 import tiles  # noqa: E402
 from yolov3 import weights as W  # noqa: E402
 from yolov3.synthdata import synth_frames  # noqa: E402
@@ -56,6 +59,7 @@ def main():
     ap.add_argument("--tail-limit-ms", type=float, default=100.0)
     ap.add_argument("--thresh", type=float, default=0.05)
     ap.add_argument("--tile-batch", type=int, default=16)
+    ap.add_argument("--merge", type=float, default=None, metavar="F", help="also time the seam merge at this threshold")
     ap.add_argument("--passes", type=int, default=7)
     ap.add_argument("--iters", type=int, default=10)
     args = ap.parse_args()
@@ -111,17 +115,41 @@ def main():
     line("y3_detect_tiled, %d rows, %d candidates, %d kept" % (n_tiles * rows, n_cand, int(det.count[0].item())), ms,
          args.passes, args.iters)
 
-    def call():
-        return yolov3.inference(net, frame, device="cuda:0", prob_thresh=args.thresh, tile_overlap=args.overlap,
-                                tile_batch=args.tile_batch)
-    call()
-    wall = []
-    for _ in range(args.passes):
-        t0 = time.perf_counter()
-        for _ in range(args.iters):
-            kept = len(call()[0][1])
-        wall.append((time.perf_counter() - t0) / args.iters * 1e3)
-    line("inference(tile_overlap=%g), host frame to host detections (%d)" % (args.overlap, kept), wall, args.passes, args.iters)
+    if args.merge is not None:
+        # the merge launch alone, on the detections the tail has just left in the Detector's buffers
+        merge = tiles.check_merge(args.merge)
+        mb = _MergeBuffers(1, n_tiles * rows, dev)
+
+        def merge_launch():
+            _hip.check(_hip.lib().y3_merge_tiled(
+                det.count.data_ptr(), det.tlbr.data_ptr(), det.prob.data_ptr(), det.cls.data_ptr(), det.row.data_ptr(), 1,
+                n_tiles * rows, rows, ctypes.c_double(merge), mb.ws.data_ptr(), mb.ws_bytes, mb.count.data_ptr(), mb.tlbr.data_ptr(),
+                mb.prob.data_ptr(), mb.cls.data_ptr(), mb.row.data_ptr(), mb.members.data_ptr(), _hip.stream_ptr()))
+        ms_merge = device_ms(merge_launch, args.passes, args.iters)
+        kept_in, kept_out = int(det.count[0].item()), int(mb.count[0].item())
+        per_class = int(torch.bincount(det.cls[0, :kept_in].clamp(min=0)).max().item()) if kept_in else 0
+        line("y3_merge_tiled at %g, %d detections (%d in the largest class) -> %d, largest group %d" % (
+            merge, kept_in, per_class, kept_out, int(mb.members[0, :kept_out].max().item()) if kept_out else 0), ms_merge,
+            args.passes, args.iters)
+        print("the merge launch takes %.2f of the y3_detect_tiled launch in front of it" % (
+            statistics.median(ms_merge) / statistics.median(ms)), flush=True)
+
+    def timed_call(merge):
+        def call():
+            return yolov3.inference(net, frame, device="cuda:0", prob_thresh=args.thresh, tile_overlap=args.overlap,
+                                    tile_batch=args.tile_batch, **({} if merge is None else {"tile_merge": merge}))
+        call()
+        wall = []
+        for _ in range(args.passes):
+            t0 = time.perf_counter()
+            for _ in range(args.iters):
+                kept = len(call()[0][1])
+            wall.append((time.perf_counter() - t0) / args.iters * 1e3)
+        line("inference(tile_overlap=%g%s), host frame to host detections (%d)" % (
+            args.overlap, "" if merge is None else ", tile_merge=%g" % merge, kept), wall, args.passes, args.iters)
+    timed_call(None)
+    if args.merge is not None:
+        timed_call(args.merge)
 
     def plain():
         return yolov3.inference(net, frame, device="cuda:0", prob_thresh=args.thresh)
