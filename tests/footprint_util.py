@@ -220,6 +220,11 @@ def _opts():
         # small-grid kernel with the wave count and the grid limits its chooser picks, the default set without that kernel (the small-grid rule of
         # the 3x3 layers), the deep-1x1 rule alone
         fuse_block1=dict(fuse_block=1),
+        # the direct-weights form of the fused block wherever supported (tests/block_dw_cases.py: a table of its own, the kernel
+        # lives in libyolov3_hip_block.so with a census of its own)
+        fuse_block4=dict(fuse_block=4),
+        # ... and only where its rectangles fill 70 % of the chip, the rule of fuse_block = 1 (tests/test_cu_count_host.py)
+        fuse_block3=dict(fuse_block=3),
         halo_dw_pays=dict(auto_mask=halo | H.AM_HALO_DW),
         dw48_auto=dict(auto_mask=H.AM_SMALL_DW | H.AM_SMALL_DW_WIDE),
         no_small_dw=dict(auto_mask=H.AM_DEFAULT & ~(H.AM_SMALL_DW | H.AM_SMALL_DW_WIDE)),
@@ -831,6 +836,10 @@ def build(case, dtype, mode, opt, base=None, lead=()):
             ptrs.append((1, "d_res", "input", 0))
         ops[1].cout_pad, ops[1].k_ld = _conv_weights("op1 ", dtype, shp[1][0], shp[1][1], shp[1][2], H.PATH_IGEMM, operands)
         ptrs += [(1, "d_weight", "op1 weight", 0), (1, "d_scale", "op1 scale", 0), (1, "d_bias", "op1 bias", 0)]
+        if g == "block" and opt.fuse_block >= 3:
+            # the direct-weights form reads BOTH convs' weights from fragment-order copies (finish() drops a copy the library
+            # does not ask for: y3_conv_fragment_weight_bytes answers for the members of such a pair)
+            frag[0], frag[1] = "op0 fragment weights", "op1 fragment weights"
         return finish(ops, ptrs) + (path0,)
 
     if g == "layer":

@@ -179,14 +179,43 @@ def test_block_rectangle_does_not_depend_on_the_count():
     base = fu.case_by_id("block_ragged_nores")
     for h, w, B in ((4, 8, 1), (19, 13, 3), (21, 17, 2), (19, 19, 3), (38, 38, 2), (37, 53, 1), (76, 76, 1), (45, 24, 5), (33, 25, 4)):
         case = dict(base, h=h, w=w, B=B)
-        grids = set()
-        for count in cu.COUNTS + (2, 3, 5, 7, 11):
-            with _hip.device_cus(count):
-                st = cu.case_steps(case, "bf16")[0]
-            assert st["kernel"] == "conv_block_fused_bf16_x128", (h, w, B, count, st["kernel"])
-            grids.add(st["dims"][0])
-        tw, th = fu.block_tile(h, w)
-        assert grids == {-(-w // tw) * -(-h // th) * B}, (h, w, B, grids, tw, th)
+        # ... and for the direct-weights form of the kernel (fuse_block = 4), which takes its rectangle from the same chooser
+        for opt_name, kernel in ((None, "conv_block_fused_bf16_x128"), ("fuse_block4", "conv_block_dw_bf16_x128")):
+            grids = set()
+            for count in cu.COUNTS + (2, 3, 5, 7, 11):
+                with _hip.device_cus(count):
+                    st = cu.case_steps(case, "bf16", opt_name)[0]
+                assert st["kernel"] == kernel, (h, w, B, count, st["kernel"])
+                grids.add(st["dims"][0])
+            tw, th = fu.block_tile(h, w)
+            assert grids == {-(-w // tw) * -(-h // th) * B}, (h, w, B, grids, tw, th)
+
+
+def test_fuse_block_3_names_the_direct_weights_form_exactly_where_fuse_block_1_fuses():
+    """the 70 % rule reads the count, the launch does not: at every count of the list, on the block rows of the table and on the
+    shipped 76 x 76 pair at batches round the rule's edge, fuse_block = 3 names conv_block_dw_* exactly where fuse_block = 1 names
+    conv_block_fused_* -- with the same grid -- and both leave the same two launches elsewhere"""
+    rows = [(fu.case_by_id(cid), {}) for cid in ("block_full_res", "block_ragged_res", "block_ragged_nores", "block_19x19_res")]
+    rows += [(fu.case_by_id("block_full_res"), dict(h=76, w=76, B=B)) for B in (1, 2, 8, 11, 12, 16)]
+    fused_at = set()
+    for case, over in rows:
+        case = dict(case, **over)
+        for dtype in case["dtypes"]:
+            for count in cu.COUNTS:
+                with _hip.device_cus(count):
+                    one = cu.case_steps(case, dtype, "fuse_block1")
+                    three = cu.case_steps(case, dtype, "fuse_block3")
+                fused = one[0]["kernel"] == "conv_block_fused_%s_x128" % fu.TAG[dtype]
+                assert fused == one[0]["kernel"].startswith("conv_block")
+                what = (case["id"], over, dtype, count, one[0]["kernel"], three[0]["kernel"])
+                if fused:
+                    assert three[0]["kernel"] == "conv_block_dw_%s_x128" % fu.TAG[dtype], what
+                    assert three[0]["dims"][:2] == one[0]["dims"][:2] and cu.sane(three[0]["kernel"], three[0]["dims"]) is None, what
+                    assert [s["kernel"] for s in one[1:]] == [s["kernel"] for s in three[1:]] == ["(fused into the previous op)"]
+                    fused_at.add(count)
+                else:
+                    assert [s["kernel"] for s in three] == [s["kernel"] for s in one] and len(three) == 2, what
+    assert {1, 256} <= fused_at          # the rule falls on both sides at both ends of the list
 
 
 # ------------------------------------------------------------------------------------------------ reach

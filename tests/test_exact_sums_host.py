@@ -86,7 +86,10 @@ def test_plants_meet_the_conditions_and_show_every_fault(cid):
     """(a), (b), (c) on every plant; then each fault, on a sample of the output pixels that holds the whole last column, must
     change at least one expected bit pattern on at least one plant of the case"""
     cname, dtype = cid.rsplit("-", 1)
-    case = fu.case_by_id(cname)
+    _conditions_and_faults(fu.case_by_id(cname), cid, dtype)
+
+
+def _conditions_and_faults(case, cid, dtype):
     seen = dict.fromkeys((f for f in XS.FAULTS if XS.fault_applies(f, case, dtype)), 0)
     assert {"tap_shift", "drop_k"} <= set(seen)
     for kind in XS.plants_of(case):
@@ -101,6 +104,27 @@ def test_plants_meet_the_conditions_and_show_every_fault(cid):
             assert n > 0 or kind != "unit" or f not in ("tap_shift", "drop_k"), "%s: the unit plant does not see %s" % (cid, f)
     for f, n in seen.items():
         assert n > 0, "%s: no plant sees %s" % (cid, f)
+
+
+def _block_dw_ids():
+    import block_dw_cases as BDC
+    return ["%s-%s" % p for p in BDC.case_ids()]
+
+
+@pytest.mark.parametrize("cid", _block_dw_ids())
+def test_block_dw_rows_meet_the_conditions_and_show_every_fault(cid):
+    """the rows of tests/block_dw_cases.py (the direct-weights fused block: a table of its own), all three plants in both types
+    as tests/test_gpu_block_dw_suites.py runs them: the same conditions -- (b): at most 1 % of the unit plant's pre-activations
+    outside the output type's exact-integer range -- and each planted reference fault that applies (the three that a 16-bit
+    activation conv has) changes an expected bit pattern"""
+    import block_dw_cases as BDC
+    import test_gpu_block_dw_suites as G
+    assert cid in G.IDS and BDC.PLANTS == XS.PLANTS
+    cname, dtype = cid.rsplit("-", 1)
+    case = BDC.case_by_id(cname)
+    assert XS.plants_of(case) == XS.PLANTS and XS.shortcut_kind(case) == ("input" if case["res"] else None)
+    assert {f for f in XS.FAULTS if XS.fault_applies(f, case, dtype)} == {"tap_shift", "drop_k", "bf16_per_64"}
+    _conditions_and_faults(case, cid, dtype)
 
 
 SMALL = 3e8          # multiply-adds: the rows below it are held to a literal int64 sum and to the oracle (the rest share the code)

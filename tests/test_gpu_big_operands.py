@@ -49,19 +49,25 @@ def _big_data(case, dtype, lay, paths, dev):
             data[name] = [base[idx].reshape(o.pixels, -1)]
     for o in lay.operands:                                   # (a fragment-order copy only the big grid's kernel reads: made below)
         if o.side == "in" and o.name not in data:
-            assert o.name == "fragment weights", o.name
+            assert o.name.endswith("fragment weights"), o.name
             data[o.name] = [torch.zeros(o.slices[0][1], dtype=fu.TORCH_DT[dtype])]
     return data
 
 
 @pytest.mark.parametrize("cid", ["%s-%s" % p for p in fu.big_case_ids()])
 def test_kernel_addresses_operands_past_4_gib(cid):
+    cname, dtype = cid.rsplit("-", 1)
+    big_operands_run(fu.big_row(cname), dtype)
+
+
+def big_operands_run(row, dtype, log=False):
+    """the whole check for one row of big_cases() -- or a row in its format from another table (tests/block_dw_cases.py big_row).
+    ``log``: the big run is taken with the launch log and its symbols are left in test_gpu_footprint.LAUNCHED"""
     from yolov3 import _hip as H
     H.require_gpu()
     lib = H.lib()
     dev = torch.device("cuda:0")
-    cname, dtype = cid.rsplit("-", 1)
-    row = fu.big_row(cname)
+    cid = "%s-%s" % (row["id"], dtype)
     case = fu.big_case(row, dtype)
     B = case["B"]
     want = fu.family_name(row, dtype)
@@ -103,7 +109,10 @@ def test_kernel_addresses_operands_past_4_gib(cid):
         assert names[0] == want and all(n == "(fused into the previous op)" for n in names[1:]), (names, want)
         before = alloc.clone()
         d_input = lay["input"].ptr(base) if lay.has("input") else None
-        H.check(lib.y3_plan_run(handle, d_input, None))
+        if log:
+            G._logged(lambda: H.check(lib.y3_plan_run(handle, d_input, None)))
+        else:
+            H.check(lib.y3_plan_run(handle, d_input, None))
         torch.cuda.synchronize()
     finally:
         lib.y3_plan_destroy(handle)

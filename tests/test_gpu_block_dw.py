@@ -4,9 +4,10 @@ plan under fuse_block = 0: same operands, same K order, same epilogue arithmetic
 through the library's launch log, that it launched the symbol tests/golden/kernel_instances_block.json records for it
 (tools/make_block_kernel_instances.py writes that file on an MI355X).
 
-One case more goes against a float64 oracle at the one-ulp gate of tests/test_gpu_bf16.py, one runs the integer plant of
-tests/exact_sums.py, on which the sums are exact whatever their order, and one runs beside the memory-saturating copy kernel as
-tests/test_gpu_contention.py runs the other run-ahead families: a mis-counted wait shows there as a changed bit.
+One case more goes against a float64 oracle at the one-ulp gate of tests/test_gpu_bf16.py, and one runs beside the
+memory-saturating copy kernel as tests/test_gpu_contention.py runs the other run-ahead families: a mis-counted wait shows there
+as a changed bit.  The kernel-level suites -- strided slices and footprint, the three integer plants of tests/exact_sums.py, the
+row below 2^32 bytes -- are tests/test_gpu_block_dw_suites.py, on the table of tests/block_dw_cases.py.
 Need an MI355X: -m gpu."""
 import os
 import sys
@@ -117,28 +118,6 @@ def test_block_dw_against_the_float64_oracle_at_one_ulp():
     slack = TB._flip_slack(mid, convs[1]["w"], convs[1]["scale"], 1, 1, "bf16")
     z = F.leaky_relu(F.conv2d(orc.bf16_round(mid).double(), convs[1]["w"].double(), padding=1) * a2 + b2, 0.1) + xn
     TB._close_bf16(got.float().cpu().permute(0, 3, 1, 2), orc.bf16_round(z.float()), "block_dw 38x38 bf16", slack, "bf16")
-
-
-@pytest.mark.parametrize("dtype", ["bf16", "fp16"])
-def test_block_dw_exact_sums_on_the_integer_plant(dtype):
-    """The ``unit`` plant of tests/exact_sums.py (integers: every float32 partial sum is exact in any order) on 21 x 13, Cin 256,
-    shortcut: the output equals the int64 convolution's epilogue bit for bit."""
-    import numpy as np
-
-    import epilogue_cases as EC
-    import exact_sums as ES
-    from yolov3 import _hip
-    _hip.require_gpu()
-    h, w = BU.MAPS["21x13"]
-    case = dict(id="block_dw_21x13_c256_res", group="block", B=BU.FRAMES, h=h, w=w, cin=256, cout=256, res=True)
-    p = ES.plant(case, dtype, "unit")
-    _, want = ES.reference(case, dtype, p)
-    convs = [dict(w=torch.from_numpy(c["w"]).float(), scale=torch.from_numpy(c["scale"]), bias=torch.from_numpy(c["bias"])) for c in p["convs"]]
-    t, ops = BU.make_pair(torch.device("cuda:0"), dtype, torch.from_numpy(p["x"]).float(), convs, True)
-    got, name, _ = _run(ops, t, (BU.FRAMES, h, w, 256), dtype, 4, "block_dw_exact_unit-%s" % dtype)
-    assert name == "conv_block_dw_%s_x128" % BU.TAG[dtype]
-    got = got.float().cpu().numpy().reshape(-1, 256)
-    assert np.array_equal(EC.bits(got), EC.bits(want)), ES.first_difference(got, want, case, dtype, p)
 
 
 CONTENTION = [(True, "bf16"), (False, "bf16"), (True, "fp16")]

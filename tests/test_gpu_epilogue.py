@@ -314,43 +314,69 @@ def test_fused_residual_block_epilogues(tmp_path, dtype, dim, batch):
 
 
 def _block_pair(h, batch, acts, r, dtype):
-    """tools/block_bench.py's 1x1 (256 -> 128) + 3x3 (128 -> 256) + shortcut pair with activations ``acts``, every weight and
-    bias zero, both scales 1, and the input (= shortcut operand) r per channel"""
-    import os
-    import sys
-    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tools"))
-    import block_bench as bb
+    """tests/block_dw_util.py's 1x1 (256 -> 128) + 3x3 (128 -> 256) + shortcut pair (the pair of tools/block_bench.py with the
+    fragment-order copies of both weights, which the direct-weights form of the kernel reads) with activations ``acts``, every
+    weight and bias zero, both scales 1, and the input (= shortcut operand) r per channel"""
+    import block_dw_util as bb
     _hip.require_gpu()
-    t, ops = bb.make_pair(torch.device("cuda:0"), batch, h, 256, 256, True, torch.Generator().manual_seed(h), dtype)
+    x = torch.from_numpy(r).view(1, 1, 1, -1).expand(batch, h, h, 256)
+    convs = [dict(w=torch.zeros((co, ci, k, k)), scale=torch.ones(co), bias=torch.zeros(co)) for ci, co, k in ((256, 128, 1), (128, 256, 3))]
+    t, ops = bb.make_pair(torch.device("cuda:0"), dtype, x, convs, True)
     for n, act in enumerate(acts):
         ops[n].flags = (ops[n].flags & ~_hip.F_LEAKY) | (_hip.F_LEAKY if act == "leaky" else 0)
-        t["w%d" % n].zero_()
-        t["sc%d" % n].fill_(1.0)
-        t["bi%d" % n].zero_()
-    t["x"].copy_(torch.from_numpy(r).to(TORCH_DTYPE[dtype]).cuda().view(1, 1, 1, -1).expand_as(t["x"]))
+    assert torch.equal(t["x"].float().cpu()[0, 0, 0], torch.from_numpy(r)) and not bool(t["wf0"].any()) and not bool(t["wf1"].any())
     return bb, t, ops
 
 
-def _block_run(bb, t, ops, mode, batch, h):
+def _refragment(t, ops):
+    """the fragment-order copies of both weights, remade from the weights as they are now: a plan reads the caller's copy, so
+    weights rewritten between runs (``t["w1"].copy_``) reach a kernel that reads fragments only through this"""
+    import ctypes
+    for n in (0, 1):
+        _hip.check(_hip.lib().y3_conv_make_fragment_weights(ctypes.byref(ops[n]), ctypes.c_void_p(t["wf%d" % n].data_ptr()), None))
+    torch.cuda.synchronize()
+
+
+def _block_run(bb, t, ops, mode, batch, h, census_key=None):
+    """``census_key``: the run is taken with the launch log and held to that entry of the block library's census"""
+    import contextlib
     lib = _hip.lib()
     out = torch.full((batch, h, h, 256), 7.0, dtype=t["x"].dtype, device="cuda:0")
     plan = bb.make_plan(ops, t["zero"], out, fuse_block=mode)
     try:
-        _hip.check(lib.y3_plan_run(plan, None, _hip.stream_ptr()))
+        with (_hip.launch_log() if census_key else contextlib.nullcontext()) as log:
+            _hip.check(lib.y3_plan_run(plan, None, _hip.stream_ptr()))
         torch.cuda.synchronize()
         name = lib.y3_plan_op_kernel(plan, 0).decode()
     finally:
         lib.y3_plan_destroy(plan)
+    if census_key:
+        import test_gpu_block_dw as TD
+        assert len(log.symbols) == 1 and "conv_block_dw_kernel" in log.symbols[0], log.symbols
+        TD._assert_launched(census_key, "footprint", log.symbols)
     return out, name
+
+
+# mode -> the name of the pair's first op: fuse_block = 2 the fused kernel, 4 its direct-weights form (csrc/conv_block_dw.hip,
+# which inlines y3_bn_act8 / y3_add8 / y3_pack8 on its own), 0 the two launches
+BLOCK_MODES = (2, 0, 4)
+
+
+def _block_name_ok(name, mode, dtype):
+    want = {2: "conv_block_fused_%s_x128", 4: "conv_block_dw_%s_x128"}.get(mode)
+    if want is None:
+        return not name.startswith("conv_block")
+    return name == want % TAG[dtype]
 
 
 @pytest.mark.parametrize("acts", [("leaky", "leaky"), ("linear", "leaky"), ("leaky", "linear")])
 @pytest.mark.parametrize("h,batch", [(20, 2), (9, 3)])
 @pytest.mark.parametrize("dtype", FUSED_DTYPES)
 def test_fused_bottleneck_block_epilogues(dtype, h, batch, acts):
+    import block_dw_cases as BDC
     r = _operand(256, h, dtype)
     bb, t, ops = _block_pair(h, batch, acts, r, dtype)
-    fused_name = "conv_block_fused_%s_x128" % TAG[dtype]
+    key = BDC.epilogue_key(dtype)
     # the 1x1's epilogue: the whole list in its 128 channels, shown by an identity centre tap
     t1, idx = E.padded(acts[0])
     tags = [E.cases(acts[0])[i].tag for i in idx]
@@ -359,20 +385,31 @@ def test_fused_bottleneck_block_epilogues(dtype, h, batch, acts):
     w = torch.zeros_like(t["w1"])
     w[torch.arange(256), 4 * 128 + torch.arange(256) % 128] = 1.0
     t["w1"].copy_(w)
-    for mode in (2, 0):
-        out, name = _block_run(bb, t, ops, mode, batch, h)
-        assert (name == fused_name) == (mode == 2) and name.startswith("conv_block_fused") == (mode == 2), name
-        _gate(_nchw(out), *_through(dtype, acts[0], acts[1], t1, 256, r), "%s %s first epilogue" % (name, acts), tags * 2, np.tile(t1, 2))
+    _refragment(t, ops)
+    lo, hi, nan = _through(dtype, acts[0], acts[1], t1, 256, r)
+    # where the identity tap puts a non-zero value on top of the shortcut operand: a stale copy (zero weights) would store r alone
+    shown = ~nan & (lo != r) & (hi != r)
+    assert shown.sum() > 100
+    r_dev = torch.from_numpy(r).cuda()
+    for mode in BLOCK_MODES:
+        out, name = _block_run(bb, t, ops, mode, batch, h, key if mode == 4 else None)
+        assert _block_name_ok(name, mode, dtype), (mode, name)
+        _gate(_nchw(out), lo, hi, nan, "%s %s first epilogue" % (name, acts), tags * 2, np.tile(t1, 2))
+        # ... which says that the fragment-order copy was remade after the weights were rewritten; read it all the same: the zero
+        # weights the copy held before would leave the shortcut operand alone
+        assert bool((out.float() - r_dev)[..., torch.from_numpy(shown).cuda()].ne(0).all()), "%s: a stale fragment-order copy (zero weights)" % name
     # the 3x3's epilogue with the fused shortcut: the whole list, then the searched shortcut cases
     t2, idx = E.padded(acts[1])
     ts, stags = E.shortcut_cases(acts[1], dtype, r[128:], h)
     t2, tags = np.concatenate([t2, ts]), [E.cases(acts[1])[i].tag for i in idx] + stags
     t["bi0"].zero_()
     t["w1"].zero_()
+    _refragment(t, ops)
+    assert not bool(t["wf1"].any())
     t["bi1"][:256].copy_(torch.from_numpy(t2))
-    for mode in (2, 0):
-        out, name = _block_run(bb, t, ops, mode, batch, h)
-        assert (name == fused_name) == (mode == 2) and name.startswith("conv_block_fused") == (mode == 2), name
+    for mode in BLOCK_MODES:
+        out, name = _block_run(bb, t, ops, mode, batch, h, key if mode == 4 else None)
+        assert _block_name_ok(name, mode, dtype), (mode, name)
         _gate(_nchw(out), *E.expect(acts[1], dtype, _plus0(t2), r), "%s %s second epilogue" % (name, acts), tags, t2)
 
 

@@ -111,7 +111,7 @@ def _make_data(case, dtype, lay, paths, plant=None):
                 key = "res" if o.name == "residual" else "x"
                 ref[key] = t.float().reshape(B, -1, c)
                 data[o.name] = [t]
-        elif o.name == "zero page" or o.name == "fragment weights":
+        elif o.name == "zero page" or o.name.endswith("fragment weights"):
             data[o.name] = [torch.zeros(o.slices[0][1], dtype=tdt)]
     for n, ((prefix, cin, cout, k, s, leaky), path) in enumerate(zip(_conv_specs(case), paths)):
         kk = k * k * cin
