@@ -1,22 +1,17 @@
-"""Shared by tests/test_gpu_attention.py, tests/test_attention_host.py and tools/make_attn_kernel_instances.py: one attention
+"""Shared by tests/test_gpu_attention.py and tests/test_attention_host.py: one attention
 op (Y3_OP_AVGPOOL / Y3_OP_SCALE_CHANNELS / Y3_OP_SAM, csrc/attention.hip, libyolov3_hip_attn.so) as a one-op plan on operands
 laid out by tests/footprint_util.py -- every operand a channel slice of a wider, NaN-poisoned, guarded body inside one allocation,
-compared as bytes before and after the run --, the expectations, and the census of the library
-(tests/golden/kernel_instances_attn.json, the format of tests/golden/kernel_instances.json)."""
+compared as bytes before and after the run --, the expectations, and the cases of the library's census (the "attn" row of
+tests/kernel_census.py, tests/golden/kernel_instances_attn.json)."""
 import contextlib
 import ctypes
-import json
-import os
 
 import numpy as np
 
 import attention_ordered as AO
 import epilogue_cases as E
 import footprint_util as FU
-from golden_util import GOLDEN, ROOT
 
-ATTN_LIB = os.path.join(ROOT, "pytorch-yolov3_amd", "lib", "libyolov3_hip_attn.so")
-CENSUS_FIXTURE = os.path.join(GOLDEN, "kernel_instances_attn.json")
 DTYPES = ("float32", "bf16", "fp16")
 KINDS = ("avgpool", "scale_channels", "sam")
 TAG = FU.TAG
@@ -43,27 +38,6 @@ def symbol_matches(symbol, kind, form, dtype):
     if kind != "avgpool":
         args += "Lb%dE" % (kind == "scale_channels")
     return "%d%s%s" % (len(TEMPLATE[kind]), TEMPLATE[kind], args) in symbol
-
-
-def library_kernels():
-    """the amdhsa.kernels metadata entries of every code object of the attention library (tests/test_code_object.py's parser)"""
-    import test_code_object as T
-    with open(ATTN_LIB, "rb") as f:
-        data = f.read()
-    objs = list(T._code_objects(data))
-    assert objs and all("gfx950" in triple for triple, _ in objs), [t for t, _ in objs]
-    return [k for _, elf in objs for k in T._kernels(elf)]
-
-
-def load_census():
-    with open(CENSUS_FIXTURE) as f:
-        return json.load(f)
-
-
-def census_report(fixture, library):
-    """(compiled kernels no recorded case launches, recorded symbols the library does not hold), both sorted"""
-    foot = set().union(*fixture["footprint"].values()) if fixture["footprint"] else set()
-    return sorted(set(library) - foot), sorted(foot - set(library))
 
 
 # ---- expectations (numpy, on float32 arrays of storage-type values) ---------------------------------------------------------

@@ -1,10 +1,10 @@
 """The direct-weights fused block kernel (csrc/conv_block_dw.hip, libyolov3_hip_block.so; y3_options.fuse_block = 3 / 4) in the
 kernel-level suites: a case table of its own in the row format of tests/footprint_util.py ``cases()``, shared by
 tests/test_gpu_block_dw_suites.py (footprint trio, exact sums, the row below 2^32 bytes), tests/test_block_dw_host.py (which holds
-the table on the CPU and every suite to the library's census) and tools/make_block_kernel_instances.py.
+the table on the CPU and every suite to the library's census) and tools/make_kernel_instances.py.
 
-The rows are NOT rows of ``cases()``: the kernel lives in a library of its own with a census of its own
-(tests/golden/kernel_instances_block.json), and the main library's census tool would refuse symbols that library lacks.  They
+The rows are NOT rows of ``cases()``: the kernel lives in a library of its own, the "block" row of tests/kernel_census.py, with a
+fixture of its own (tests/golden/kernel_instances_block.json), and the main library's rules would refuse symbols it lacks.  They
 run under the option set ``fuse_block4`` of footprint_util._opts(), for which footprint_util.build registers fragment-order
 copies of BOTH convs' weights.
 

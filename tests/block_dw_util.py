@@ -1,15 +1,9 @@
-"""Shared by tests/test_gpu_block_dw.py, tests/test_block_dw_host.py and tools/make_block_kernel_instances.py: the cases of the
-direct-weights fused block kernel (csrc/conv_block_dw.hip, libyolov3_hip_block.so; y3_options.fuse_block = 3 / 4), a two-op plan
-on given operands with the fragment-order copies the kernel reads, and the census of the library
-(tests/golden/kernel_instances_block.json, the format of tests/golden/kernel_instances.json)."""
+"""Shared by tests/test_gpu_block_dw.py, tests/test_block_dw_host.py and tools/make_kernel_instances.py: the cases of the
+direct-weights fused block kernel (csrc/conv_block_dw.hip, libyolov3_hip_block.so; y3_options.fuse_block = 3 / 4) and a two-op
+plan on given operands with the fragment-order copies the kernel reads.  The library's census is the "block" row of
+tests/kernel_census.py (tests/golden/kernel_instances_block.json)."""
 import ctypes
-import json
-import os
 
-from golden_util import ROOT
-
-BLOCK_LIB = os.path.join(ROOT, "pytorch-yolov3_amd", "lib", "libyolov3_hip_block.so")
-CENSUS_FIXTURE = os.path.join(ROOT, "tests", "golden", "kernel_instances_block.json")
 TAG = {"bf16": "bf16", "fp16": "f16"}
 FRAMES = 3
 
@@ -28,30 +22,6 @@ CASES = [(m, c, "bf16") for m in MAPS for c in CHANNELS] + [("21x13", "c256_res"
 
 def case_key(m, c, dtype):
     return "block_dw_%s_%s-%s" % (m, c, dtype)
-
-
-def library_kernels():
-    """the amdhsa.kernels metadata entries of every code object of the block library (tests/test_code_object.py's parser)"""
-    import test_code_object as T
-    with open(BLOCK_LIB, "rb") as f:
-        data = f.read()
-    objs = list(T._code_objects(data))
-    assert objs and all("gfx950" in triple for triple, _ in objs), [t for t, _ in objs]
-    return [k for _, elf in objs for k in T._kernels(elf)]
-
-
-def load_census():
-    with open(CENSUS_FIXTURE) as f:
-        return json.load(f)
-
-
-def census_report(fixture, library):
-    """(compiled kernels no recorded case launches, recorded symbols the library does not hold, kernels no contention case
-    launches): all sorted, all empty when the census is whole.  Every kernel of this library is a run-ahead kernel."""
-    foot = set().union(*fixture["footprint"].values()) if fixture["footprint"] else set()
-    cont = set().union(*fixture["contention"].values()) if fixture["contention"] else set()
-    library = set(library)
-    return sorted(library - foot), sorted((foot | cont) - library), sorted(library - cont)
 
 
 def make_pair(dev, dtype, x, convs, res):

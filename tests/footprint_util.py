@@ -221,7 +221,7 @@ def _opts():
         # the 3x3 layers), the deep-1x1 rule alone
         fuse_block1=dict(fuse_block=1),
         # the direct-weights form of the fused block wherever supported (tests/block_dw_cases.py: a table of its own, the kernel
-        # lives in libyolov3_hip_block.so with a census of its own)
+        # lives in libyolov3_hip_block.so, the "block" library of tests/kernel_census.py)
         fuse_block4=dict(fuse_block=4),
         # ... and only where its rectangles fill 70 % of the chip, the rule of fuse_block = 1 (tests/test_cu_count_host.py)
         fuse_block3=dict(fuse_block=3),

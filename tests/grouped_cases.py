@@ -10,13 +10,10 @@ The device layouts are written out here, independently of ``yolov3.darknet.group
   grouped   [cout_pad][k_ld], row = output channel, column (ky * k + kx) * (cin / groups) + c
   depthwise [k * k][k_ld], row = tap, column = channel
 """
-import os
-
 import numpy as np
 import torch
 
 import grouped_restate as GR
-from golden_util import GOLDEN, ROOT
 from oracle import darknet_oracle as orc
 
 TORCH_DT = {"float32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}
@@ -140,30 +137,3 @@ def device_weights(case, path, wt):
             for c in range(cg):
                 host[:cout, (ky * k + kx) * cg + c] = wt[:, c, ky, kx]
     return host, cp, k_ld
-
-
-# ---------------------------------------------------------------------------------------------- the library and its census
-# The grouped kernels are compiled into a shared library of their own, which libyolov3_hip.so names as a dependency; its census
-# of compiled instances (the format of tests/golden/kernel_instances.json) is a fixture of its own.
-GROUPED_LIB = os.path.join(ROOT, "pytorch-yolov3_amd", "lib", "libyolov3_hip_grouped.so")
-CENSUS_FIXTURE = os.path.join(GOLDEN, "kernel_instances_grouped.json")
-
-
-def library_kernels():
-    """the amdhsa.kernels metadata entries of every code object of the grouped library (tests/test_code_object.py's parser)"""
-    import test_code_object as T
-    with open(GROUPED_LIB, "rb") as f:
-        data = f.read()
-    objs = list(T._code_objects(data))
-    assert objs and all("gfx950" in triple for triple, _ in objs), [t for t, _ in objs]
-    return [k for _, elf in objs for k in T._kernels(elf)]
-
-
-def library_symbols():
-    return {k[".name"] for k in library_kernels()}
-
-
-def census_report(fixture, library):
-    """(compiled kernels no footprint case of ``fixture`` launches, recorded symbols the library does not hold), both sorted"""
-    foot = set().union(*fixture["footprint"].values()) if fixture["footprint"] else set()
-    return sorted(set(library) - foot), sorted(foot - set(library))

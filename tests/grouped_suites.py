@@ -1,7 +1,7 @@
 """The grouped and depthwise conv kernels (csrc/conv_grouped.hip) in the kernel-level suites: the tables and builders shared by
 tests/test_gpu_grouped_epilogue.py (epilogue pins), tests/test_gpu_grouped_big.py (operands past 4 GiB) and their host half in
-tests/test_grouped_host.py, which also holds both tables to the library's census (tests/golden/kernel_instances_grouped.json):
-an instance compiled later fails there until it has an epilogue form and a big row.
+tests/test_grouped_host.py, which also holds both tables to the library's census (the "grouped" library of
+tests/kernel_census.py, tests/golden/kernel_instances_grouped.json): an instance compiled later fails there until it has an epilogue form and a big row.
 
 No GPU is needed to import this module; ``build`` lays an op out on fake addresses unless it is given the allocation's.
 """

@@ -22,6 +22,8 @@ import attention_interp as AI
 import attention_ordered as AO
 import attention_restate as AR
 import attention_util as AU
+import code_object
+import kernel_census as census
 import kernel_choice_util as kc
 import plan_interp as PI
 from golden_util import GOLDEN, ROOT
@@ -240,7 +242,7 @@ def test_header_constants_and_capability(monkeypatch):
 
 
 def test_main_library_names_the_attention_library_as_a_dependency():
-    with open(os.path.join(os.path.dirname(AU.ATTN_LIB), "libyolov3_hip.so"), "rb") as f:
+    with open(code_object.LIB, "rb") as f:
         data = f.read()
     assert b"libyolov3_hip_attn.so" in data and b"$ORIGIN" in data
     assert b"avgpool_kernel" not in data and b"attn_mul_kernel" not in data          # its device code is not in the main library
@@ -457,42 +459,27 @@ def test_a_stale_library_is_refused_for_this_cfg(monkeypatch):
 
 # ---------------------------------------------------------------------------------------------- the library's device code
 
-@pytest.fixture(scope="module")
-def kernels():
-    if not os.path.exists(AU.ATTN_LIB):
-        pytest.fail("libyolov3_hip_attn.so is not built (python -c 'import __graft_entry__ as g; g.build()')")
-    return AU.library_kernels()          # (asserts: device code for gfx950 only)
-
-
-def test_attention_library_code_objects(kernels):
-    """gfx950 only, wave64, no scratch, LDS at most 160 KiB (the avgpool tree: 32 x 8 x VEC floats, static); 18 instances"""
+def test_attention_library_code_objects():
+    """18 instances in workgroups of 256; the avgpool tree's static LDS (32 x 8 x VEC floats), none in the products; no scratch,
+    no spills, register and LDS budgets and wave64 are tests/test_code_object.py's, for every library, as is that the main
+    library holds none of these kernels"""
+    kernels = census.kernels("attn")          # (asserts: built, device code for gfx950 only)
     names = sorted(k[".name"] for k in kernels)
     assert len(names) == 18 and sum("avgpool_kernel" in n for n in names) == 6 and sum("attn_mul_kernel" in n for n in names) == 12
     for k in kernels:
         name = k[".name"]
-        assert k[".private_segment_fixed_size"] == 0, (name, "uses scratch memory (register spills)")
-        assert k.get(".vgpr_spill_count", 0) == 0 and k.get(".sgpr_spill_count", 0) == 0, name
-        assert k[".vgpr_count"] + k.get(".agpr_count", 0) <= 512, name
-        assert k[".group_segment_fixed_size"] <= 160 * 1024, name
-        assert k[".wavefront_size"] == 64 and k[".max_flat_workgroup_size"] == 256, name
+        assert k[".max_flat_workgroup_size"] == 256, name
         if "avgpool_kernel" in name:
             assert k[".group_segment_fixed_size"] in (32 * 8 * 4 * v for v in (1, 4, 8)), name
         else:
             assert k[".group_segment_fixed_size"] == 0, name
-    import test_code_object as T
-    with open(T.LIB, "rb") as fh:
-        main = {k[".name"] for _, elf in T._code_objects(fh.read()) for k in T._kernels(elf)}
-    assert not main & set(names)
 
 
-def test_attention_library_census(kernels):
-    """every compiled kernel is launched by a recorded case of tests/test_gpu_attention.py (tests/golden/kernel_instances_attn.json,
-    recorded on an MI355X by tools/make_attn_kernel_instances.py), one key per instance, and no recorded symbol is missing from the
-    library"""
-    fixture = AU.load_census()
-    library = {k[".name"] for k in kernels}
-    uncovered, stale = AU.census_report(fixture, library)
-    assert not uncovered and not stale, (uncovered, stale)
+def test_attention_library_census():
+    """one key per compiled instance, each recording the one symbol of its kind, form and type (tests/golden/kernel_instances_attn.json,
+    recorded on an MI355X by tools/make_kernel_instances.py --library attn; that every compiled kernel is launched by a recorded
+    case of tests/test_gpu_attention.py and no recorded symbol is missing from the library are tests/test_code_object.py's rules)"""
+    fixture = census.load("attn")
     assert set(fixture) == {"footprint"} and sorted(fixture["footprint"]) == sorted(AU.CENSUS_KEYS)
     for key, syms in fixture["footprint"].items():
         kind, form, dtype = AU.census_case(key)[:3]

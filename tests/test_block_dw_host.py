@@ -1,6 +1,7 @@
 """CPU-side checks of the direct-weights fused block kernel (csrc/conv_block_dw.hip; y3_options.fuse_block = 3 / 4): the
-shared library it lives in -- gfx950 code only, no scratch, register and LDS budgets, its census
-(tests/golden/kernel_instances_block.json) -- and where plans name it, through the fake-address route of
+shared library it lives in -- its two instances, their register budget, the keys of its census
+(tests/golden/kernel_instances_block.json; the checks every library gets are tests/test_code_object.py's) -- and where plans
+name it, through the fake-address route of
 tests/kernel_choice_util.py.  That every configuration of tests/golden/kernel_choice.json still reproduces, and that the main
 library's census is what it was, is tests/test_kernel_choice.py's and tests/test_code_object.py's to say: they run unchanged."""
 import ctypes
@@ -14,39 +15,34 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import block_dw_cases as BDC  # noqa: E402
 import block_dw_util as BU  # noqa: E402
+import code_object  # noqa: E402
 import footprint_util as fu  # noqa: E402
+import kernel_census as census  # noqa: E402
 
 NAME = {"bf16": "conv_block_dw_bf16_x128", "fp16": "conv_block_dw_f16_x128"}
 
 
 @pytest.fixture(scope="module")
 def kernels():
-    if not os.path.exists(BU.BLOCK_LIB):
-        pytest.fail("libyolov3_hip_block.so is not built (python -c 'import __graft_entry__ as g; g.build()')")
-    return BU.library_kernels()          # (asserts: device code for gfx950 only)
+    return census.kernels("block")          # (asserts: built, device code for gfx950 only)
 
 
 def test_block_library_budgets(kernels):
-    """no scratch, at most 512 VGPR + AGPR, at most 160 KiB of LDS (static; the launch's dynamic size is a plan's to say, below)"""
+    """two instances, at most 256 VGPRs each and workgroups of 512 (the launch's dynamic LDS size is a plan's to say, below); no
+    scratch, no spills, VGPR + AGPR, static LDS and wave64 are tests/test_code_object.py's, for every library"""
     assert len(kernels) == 2, [k[".name"] for k in kernels]
     for k in kernels:
         name = k[".name"]
         assert "conv_block_dw_kernel" in name, name
-        assert k[".private_segment_fixed_size"] == 0, (name, "uses scratch memory (register spills)")
-        assert k.get(".vgpr_spill_count", 0) == 0 and k.get(".sgpr_spill_count", 0) == 0, name
-        assert k[".vgpr_count"] + k.get(".agpr_count", 0) <= 512, name
         assert k[".vgpr_count"] <= 256, name
-        assert k[".group_segment_fixed_size"] <= 160 * 1024, name
-        assert k[".wavefront_size"] == 64 and k[".max_flat_workgroup_size"] == 512, name
+        assert k[".max_flat_workgroup_size"] == 512, name
 
 
-def test_block_library_census(kernels):
-    """the library's symbols equal the fixture's: every compiled kernel launched by a recorded case and by a contention case, no
-    recorded symbol the library lacks; every case of tests/test_gpu_block_dw.py has its entry"""
-    fixture = BU.load_census()
-    library = {k[".name"] for k in kernels}
-    uncovered, stale, quiet_only = BU.census_report(fixture, library)
-    assert not uncovered and not stale and not quiet_only, (uncovered, stale, quiet_only)
+def test_block_library_census():
+    """every case of tests/test_gpu_block_dw.py and of the kernel-level suites has its entry, of one symbol of its storage type
+    (the rules -- every compiled kernel launched by a recorded case and by a contention case, no recorded symbol the library
+    lacks -- are tests/test_code_object.py's, for every library)"""
+    fixture = census.load("block")
     assert set(fixture) == {"footprint", "contention"}
     for table in fixture.values():
         for key, syms in table.items():
@@ -85,7 +81,7 @@ def test_every_compiled_instance_is_held_by_every_suite(kernels):
     """no skip list: an instance compiled later -- another storage type, another x-buffer count -- fails here until a row of the
     footprint trio, an epilogue pin and each exact-sum plant launch it (tests/test_grouped_host.py
     test_every_compiled_instance_has_an_epilogue_form_and_a_big_row is the model)"""
-    fixture = BU.load_census()
+    fixture = census.load("block")
     library = {k[".name"] for k in kernels}
     assert instances_without(fixture, library) == []
     # the check sees a missing suite: without the epilogue keys both instances lack it, and an unknown symbol lacks all five
@@ -97,7 +93,7 @@ def test_every_compiled_instance_is_held_by_every_suite(kernels):
 
 
 def test_main_library_names_the_block_library_as_a_dependency():
-    with open(os.path.join(os.path.dirname(BU.BLOCK_LIB), "libyolov3_hip.so"), "rb") as f:
+    with open(code_object.LIB, "rb") as f:
         data = f.read()
     assert b"libyolov3_hip_block.so" in data and b"$ORIGIN" in data
     assert b"conv_block_dw_kernel" not in data              # its device code is not in the main library

@@ -1,68 +1,32 @@
-"""CPU-side checks of the built library's device code (no GPU needed): the shared library carries gfx950 code objects
-only, every kernel's register / LDS budget is inside the CU's limits and no kernel spills registers to scratch
-memory.  Parses the clang offload bundles and the AMDGPU metadata notes of libyolov3_hip.so directly."""
+"""CPU-side checks of the built libraries' device code (no GPU needed), each made once for every library of
+``kernel_census.LIBRARIES``: gfx950 code objects only (tests/code_object.py reads them), every kernel's register / LDS budget
+inside the CU's limits, no kernel spills registers to scratch memory, the five libraries share no kernel name, and the census
+rules of tests/kernel_census.py on every library that has a fixture.  What is specific to one kernel family -- instance counts,
+exact key sets, tighter budgets -- is in that family's host test."""
+import functools
 import os
-import struct
 
-import msgpack
 import pytest
 
+import kernel_census as census
+from code_object import LIB, _code_objects
 from golden_util import ROOT
 
-LIB = os.path.join(ROOT, "pytorch-yolov3_amd", "lib", "libyolov3_hip.so")
-MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
+NAMES = sorted(census.LIBRARIES)
+WITH_FIXTURE = [n for n in NAMES if census.LIBRARIES[n].fixture]
+# 14 kernels of the main library (conv_halo_dw, two conv_halo_ws rings, detect_kernel among them) keep some SGPRs in VGPR lanes --
+# ``.sgpr_spill_count`` up to 87, no scratch memory --, as they did before this count was looked at; no other library does
+SGPR_SPILLS = ("main",)
 
 
-def _code_objects(data):
-    """(target triple, ELF bytes) of every device entry of every offload bundle in the file."""
-    pos = 0
-    while True:
-        i = data.find(MAGIC, pos)
-        if i < 0:
-            return
-        nent = struct.unpack_from("<Q", data, i + 24)[0]
-        off = i + 32
-        for _ in range(nent):
-            o, sz, tl = struct.unpack_from("<QQQ", data, off)
-            triple = data[off + 24:off + 24 + tl].decode()
-            off += 24 + tl
-            if sz and not triple.startswith("host"):
-                yield triple, data[i + o:i + o + sz]
-        pos = i + 24
-
-
-def _kernels(elf):
-    """amdhsa.kernels entries of one code object (NT_AMDGPU_METADATA note, msgpack)."""
-    shoff = struct.unpack_from("<Q", elf, 0x28)[0]
-    shentsize, shnum = struct.unpack_from("<HH", elf, 0x3A)
-    for k in range(shnum):
-        sh = elf[shoff + k * shentsize:shoff + (k + 1) * shentsize]
-        if struct.unpack_from("<I", sh, 4)[0] != 7:          # SHT_NOTE
-            continue
-        so, ss = struct.unpack_from("<QQ", sh, 0x18)
-        p = so
-        while p < so + ss:
-            namesz, descsz, ntype = struct.unpack_from("<III", elf, p)
-            d0 = p + 12 + ((namesz + 3) & ~3)
-            if ntype == 32 and elf[p + 12:p + 12 + namesz].startswith(b"AMDGPU"):
-                md = msgpack.unpackb(elf[d0:d0 + descsz], raw=False, strict_map_key=False)
-                for kern in md.get("amdhsa.kernels", []):
-                    yield kern
-            p = d0 + ((descsz + 3) & ~3)
+@functools.lru_cache(maxsize=None)
+def _kernels(name):
+    return census.kernels(name)           # (asserts: built, device code for gfx950 only)
 
 
 @pytest.fixture(scope="module")
 def kernels():
-    if not os.path.exists(LIB):
-        pytest.skip("library not built (python -c 'import __graft_entry__ as g; g.build()')")
-    data = open(LIB, "rb").read()
-    objs = list(_code_objects(data))
-    assert objs, "no device code in the library"
-    out = []
-    for triple, elf in objs:
-        assert "gfx950" in triple, triple                    # one target, no multi-arch fallbacks
-        out.extend(_kernels(elf))
-    return out
+    return _kernels("main")
 
 
 def test_library_has_the_hot_path_kernels(kernels):
@@ -73,13 +37,28 @@ def test_library_has_the_hot_path_kernels(kernels):
         assert needle in names, needle
 
 
-def test_no_kernel_spills_and_budgets_fit_a_cu(kernels):
-    for k in kernels:
-        name = k[".name"]
-        assert k[".private_segment_fixed_size"] == 0, (name, "uses scratch memory (register spills)")
-        assert k[".vgpr_count"] + k.get(".agpr_count", 0) <= 512, name
-        assert k[".group_segment_fixed_size"] <= 160 * 1024, name
-        assert k[".wavefront_size"] == 64, name
+@pytest.mark.parametrize("name", NAMES)
+def test_no_kernel_spills_and_budgets_fit_a_cu(name):
+    """no scratch, no spilled VGPR (nor SGPR, the main library aside), at most 512 VGPR + AGPR, at most 160 KiB of static LDS,
+    wave64"""
+    assert _kernels(name)
+    for k in _kernels(name):
+        sym = k[".name"]
+        assert k[".private_segment_fixed_size"] == 0, (sym, "uses scratch memory (register spills)")
+        assert k[".vgpr_spill_count"] == 0, sym
+        assert name in SGPR_SPILLS or k[".sgpr_spill_count"] == 0, sym
+        assert k[".vgpr_count"] + k.get(".agpr_count", 0) <= 512, sym
+        assert k[".group_segment_fixed_size"] <= 160 * 1024, sym
+        assert k[".wavefront_size"] == 64, sym
+
+
+def test_no_two_libraries_hold_a_kernel_of_the_same_name():
+    """each library's device code is its own: a kernel family that moved into a library of its own is in no other, so no census
+    (and not the device-code hash of the main library) sees another library's kernels"""
+    names = {n: {k[".name"] for k in _kernels(n)} for n in NAMES}
+    for i, a in enumerate(NAMES):
+        for b in NAMES[i + 1:]:
+            assert not names[a] & names[b], (a, b, sorted(names[a] & names[b]))
 
 
 def test_device_code_hash_does_not_depend_on_the_build_directory(tmp_path):
@@ -113,55 +92,93 @@ def test_device_code_hash_does_not_depend_on_the_build_directory(tmp_path):
     assert bench.device_code_sha256(objs[0]) != bench.device_code_sha256(LIB)
 
 
-# ---- the census of compiled instances (tests/kernel_census.py) ---------------------------------------------------------------
+# ---- the census of compiled instances (tests/kernel_census.py), per library that keeps one -------------------------------------
 
-def _census():
-    import kernel_census as census
-    if not os.path.exists(census.FIXTURE):
-        pytest.fail("tests/golden/kernel_instances.json is missing (tools/make_kernel_instances.py writes it on an MI355X)")
-    return census, census.load()
+def _census(name):
+    if not os.path.exists(census.fixture_path(name)):
+        pytest.fail("tests/golden/%s is missing (tools/make_kernel_instances.py --library %s writes it on an MI355X)" % (
+            census.LIBRARIES[name].fixture, name))
+    return census.load(name), {k[".name"] for k in _kernels(name)}
 
 
-def test_every_compiled_kernel_is_launched_by_a_footprint_case_or_provably_by_nothing(kernels):
+def _broken(name, fixture, library, *rules):
+    return "\n".join(m for m in census.failures(name, fixture, library) if any(census.WHAT[r] in m for r in rules))
+
+
+@pytest.mark.parametrize("name", WITH_FIXTURE)
+def test_every_compiled_kernel_is_launched_by_a_footprint_case_or_provably_by_nothing(name):
     """Coverage: every ``.name`` of the library's code objects is in the union of the fixture's ``footprint`` map -- a one-op
     test with the oracle gate, the strided / poisoned run and the byte-for-byte footprint check launched it on an MI355X --
-    or in ``kernel_census.UNREACHABLE`` with the chooser condition that excludes it.  Never both: no recorded GPU test
-    launches an UNREACHABLE symbol."""
-    census, fixture = _census()
-    library = {k[".name"] for k in kernels}
-    t = census.totals(fixture, library)
-    print("kernel census: %(symbols)d symbols, %(covered)d covered by footprint cases, %(unreachable)d unreachable" % t)
-    rep = census.report(fixture, library)
-    bad = [m for m in census.failures(fixture, library) if "footprint case" in m or "UNREACHABLE that" in m]
-    assert not rep["uncovered"] and not rep["unreachable_but_launched"], "\n".join(bad)
+    or among the library's ``unreachable`` symbols with the chooser condition that excludes it.  Never both: no recorded GPU
+    test launches an unreachable symbol."""
+    fixture, library = _census(name)
+    t = census.totals(name, fixture, library)
+    print("%s kernel census: %s" % (name, census.summary(name, fixture, library)))
+    rep = census.report(name, fixture, library)
+    assert not rep["uncovered"] and not rep["unreachable_but_launched"], _broken(name, fixture, library, "uncovered", "unreachable_but_launched")
     assert t["covered"] + t["unreachable"] == t["symbols"]
-    for sym, reason in census.UNREACHABLE.items():
+    for sym, reason in census.LIBRARIES[name].unreachable.items():
         assert ".hip:" in reason, "UNREACHABLE[%s] names no chooser line" % sym
 
 
-def test_census_names_no_kernel_the_library_lacks(kernels):
-    """Stale check: every symbol named in the fixture or in UNREACHABLE exists in the library (a removed or renamed instance
-    must leave the record too)."""
-    census, fixture = _census()
-    library = {k[".name"] for k in kernels}
-    assert not census.report(fixture, library)["stale"], "\n".join(m for m in census.failures(fixture, library) if "does not hold" in m)
-    assert set(fixture) == {"footprint", "contention"} and fixture["footprint"] and fixture["contention"]
+@pytest.mark.parametrize("name", WITH_FIXTURE)
+def test_census_names_no_kernel_the_library_lacks(name):
+    """Stale check: every symbol named in the fixture or as unreachable exists in the library (a removed or renamed instance
+    must leave the record too).  The fixture holds a footprint table and, where the library has run-ahead kernels, a contention
+    table, both filled; every symbol list is sorted, without repeats and not empty."""
+    fixture, library = _census(name)
+    assert not census.report(name, fixture, library)["stale"], _broken(name, fixture, library, "stale")
+    assert set(fixture) <= {"footprint", "contention"} and fixture["footprint"]
+    assert fixture.get("contention") or not census.LIBRARIES[name].run_ahead
     for table in fixture.values():
         for key, syms in table.items():
             assert syms == sorted(set(syms)) and syms, key
 
 
-def test_every_run_ahead_instance_runs_beside_the_copy_kernel(kernels):
-    """Contention: every instance of the register-destination run-ahead families -- conv1x1_dw_kernel with both HEAD values,
-    conv_dw48_kernel, conv_halo_dw_kernel: the kernels whose template parameter sets their wait counts -- is in the union of
-    the fixture's ``contention`` map, or UNREACHABLE."""
-    census, fixture = _census()
-    library = {k[".name"] for k in kernels}
-    t = census.totals(fixture, library)
-    print("kernel census: %(run_ahead)d run-ahead instances, %(under_contention)d under contention" % t)
-    assert t["run_ahead"] >= 2 * (9 + 5 + 14 + 3), t          # (both 16-bit types of the y3_ints lists as they stand)
-    assert not census.report(fixture, library)["not_under_contention"], "\n".join(
-        m for m in census.failures(fixture, library) if "contention case" in m)
+@pytest.mark.parametrize("name", WITH_FIXTURE)
+def test_every_run_ahead_instance_runs_beside_the_copy_kernel(name):
+    """Contention: every instance of the library's run-ahead families -- in the main library conv1x1_dw_kernel with both HEAD
+    values, conv_dw48_kernel, conv_halo_dw_kernel: the kernels whose template parameter sets their wait counts; in the block
+    library every kernel -- is in the union of the fixture's ``contention`` map, or unreachable."""
+    fixture, library = _census(name)
+    t = census.totals(name, fixture, library)
+    if name == "main":
+        assert t["run_ahead"] >= 2 * (9 + 5 + 14 + 3), t          # (both 16-bit types of the y3_ints lists as they stand)
+    if name == "block":
+        assert t["run_ahead"] == t["symbols"] > 0, t
+    assert not census.report(name, fixture, library)["not_under_contention"], _broken(name, fixture, library, "not_under_contention")
+
+
+def test_census_report_rules_on_hand_made_dictionaries(monkeypatch):
+    """each of the four rules fires alone; "every kernel is run-ahead" works; a fixture without a contention table reads as one
+    with an empty table"""
+    ahead, plain, dead, gone = "_Z9ra_kernelILi1EEvv", "_Z5plainv", "_Z4deadv", "_Z4gonev"
+    monkeypatch.setitem(census.LIBRARIES, "some", census.Library("some.so", None, ("ra_kernel",), {dead: "x.hip:1 never"}))
+    monkeypatch.setitem(census.LIBRARIES, "all", census.Library("all.so", None, census.EVERY_KERNEL, {}))
+    monkeypatch.setitem(census.LIBRARIES, "none", census.Library("none.so", None, (), {}))
+    library = {ahead, plain, dead}
+
+    def broken(name, footprint, contention, library=library):
+        fixture = {"footprint": footprint} if contention is None else {"footprint": footprint, "contention": contention}
+        rep = census.report(name, fixture, library)
+        assert set(rep) == set(census.WHAT)
+        assert len(census.failures(name, fixture, library)) == sum(1 for v in rep.values() if v)
+        return {k: v for k, v in rep.items() if v}
+    foot, cont = {"a": [ahead], "b": [plain]}, {"a": [ahead]}
+    assert broken("some", foot, cont) == {}
+    assert census.totals("some", {"footprint": foot, "contention": cont}, library) == {
+        "symbols": 3, "covered": 2, "unreachable": 1, "run_ahead": 1, "under_contention": 1}
+    assert broken("some", {"a": [ahead]}, cont) == {"uncovered": [plain]}
+    assert broken("some", {"a": [ahead], "b": [dead, plain]}, cont) == {"unreachable_but_launched": [dead]}
+    assert broken("some", dict(foot, c=[gone]), cont) == {"stale": [gone]}
+    assert broken("some", foot, cont, library - {dead}) == {"stale": [dead]}
+    assert broken("some", foot, {}) == broken("some", foot, None) == {"not_under_contention": [ahead]}
+    # every kernel run-ahead: the kernel no contention case launches is named, whatever template it is an instance of
+    assert broken("all", foot, cont, {ahead, plain}) == {"not_under_contention": [plain]}
+    assert broken("all", foot, foot, {ahead, plain}) == {}
+    # no run-ahead family: no contention table is needed, absent or empty
+    assert broken("none", foot, None, {ahead, plain}) == broken("none", foot, {}, {ahead, plain}) == {}
+    assert broken("none", {"a": [ahead]}, None, {ahead, plain}) == {"uncovered": [plain]}
 
 
 def test_launch_log_entry_points_and_names(kernels):

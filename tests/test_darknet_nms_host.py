@@ -298,11 +298,10 @@ def test_cli_parser_accepts_the_two_flags():
 
 # ---- the built device code ---------------------------------------------------------------------------------------------------
 def test_code_object_holds_the_new_kernels_without_spills_or_more_lds():
-    import test_code_object as T
-    if not os.path.exists(T.LIB):
+    import code_object
+    if not os.path.exists(code_object.LIB):
         pytest.skip("library not built")
-    data = open(T.LIB, "rb").read()
-    kern = [k for _, elf in T._code_objects(data) for k in T._kernels(elf) if "detect_kernel" in k[".name"]]
+    kern = [k for k in code_object.library_kernels() if "detect_kernel" in k[".name"]]
     by_name = {k[".name"]: k for k in kern}
     # detect_kernel<NMS_MODE, DK>: DK 0 = the reference's rule, 1 / 2 / 3 = Darknet's iou / greedynms / diounms
     base = {}

@@ -9,6 +9,7 @@ import torch
 from yolov3 import _hip
 
 import attention_util as AU
+import kernel_census as census
 import layer_patterns as L
 
 pytestmark = pytest.mark.gpu
@@ -177,4 +178,4 @@ def test_forms_cu_counts_and_graph_replay_give_the_same_bits(kind, dtype):
 def test_every_compiled_instance_is_launched_where_the_census_says(key):
     """one case per compiled instance of libyolov3_hip_attn.so on the strided, poisoned, guarded layout: right values, nothing
     written outside the output slice, and the launch log names exactly the symbol tests/golden/kernel_instances_attn.json records"""
-    assert AU.run_census_case(key) == AU.load_census()["footprint"][key]
+    census.assert_census(key, library="attn", launched=[AU.run_census_case(key)])

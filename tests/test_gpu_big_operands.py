@@ -26,6 +26,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import footprint_util as fu
+import kernel_census as census
 import test_gpu_footprint as G
 
 pytestmark = pytest.mark.gpu
@@ -80,14 +81,14 @@ def big_operands_run(row, dtype, log=False):
         pytest.skip("%s needs %.1f GiB of device memory, %.1f GiB are free" % (cid, need / 2.0 ** 30, free / 2.0 ** 30))
 
     # ---- the three base frames alone, dense between zero guards: the oracle gate, and what (a) compares with
-    del G.LAUNCHED[:], G.FRAGMENT_LAUNCHED[:]
+    del census.LAUNCHED[:], census.FRAGMENT_LAUNCHED[:]
     small = dict(case, B=3)
     dense, msg, names, ref, lay3 = G._run(small, dtype, "dense")
     assert names[0] == want, (names, want)
     assert msg is None, "small dense run: " + msg
     G._no_nan(dense, lay3)
     G._check_dense_against_oracle(small, dtype, dense, ref, lay3)
-    del G.LAUNCHED[:], G.FRAGMENT_LAUNCHED[:]
+    del census.LAUNCHED[:], census.FRAGMENT_LAUNCHED[:]
 
     # ---- the big run
     raw = torch.empty(lay0.total + fu.ALIGN, dtype=torch.uint8, device=dev)
@@ -110,7 +111,7 @@ def big_operands_run(row, dtype, log=False):
         before = alloc.clone()
         d_input = lay["input"].ptr(base) if lay.has("input") else None
         if log:
-            G._logged(lambda: H.check(lib.y3_plan_run(handle, d_input, None)))
+            census.logged(lambda: H.check(lib.y3_plan_run(handle, d_input, None)))
         else:
             H.check(lib.y3_plan_run(handle, d_input, None))
         torch.cuda.synchronize()

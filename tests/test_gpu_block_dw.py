@@ -2,7 +2,7 @@
 y3_options.fuse_block = 3, and 4 = wherever supported for the small maps here) against the two separate launches of the same
 plan under fuse_block = 0: same operands, same K order, same epilogue arithmetic -> ``torch.equal``.  Every case also asserts,
 through the library's launch log, that it launched the symbol tests/golden/kernel_instances_block.json records for it
-(tools/make_block_kernel_instances.py writes that file on an MI355X).
+(``kernel_census.assert_census``; tools/make_kernel_instances.py --library block writes that file on an MI355X).
 
 One case more goes against a float64 oracle at the one-ulp gate of tests/test_gpu_bf16.py, and one runs beside the
 memory-saturating copy kernel as tests/test_gpu_contention.py runs the other run-ahead families: a mis-counted wait shows there
@@ -18,20 +18,11 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import block_dw_util as BU  # noqa: E402
+import kernel_census as census  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 TDT = {"bf16": torch.bfloat16, "fp16": torch.float16}
-RECORD = None          # the census tool sets a dict: {key: symbols} is recorded instead of compared
-
-
-def _assert_launched(key, table, symbols):
-    if RECORD is not None:
-        RECORD[table][key] = symbols
-        return
-    want = BU.load_census()[table].get(key)
-    assert want is not None, "tests/golden/kernel_instances_block.json has no %s entry %r: run tools/make_block_kernel_instances.py" % (table, key)
-    assert symbols == want, (key, symbols, want)
 
 
 def _run(ops, t, shape, dtype, mode, log_key=None):
@@ -49,7 +40,7 @@ def _run(ops, t, shape, dtype, mode, log_key=None):
         lib.y3_plan_destroy(plan)
     if log_key:
         assert all("conv_block_dw_kernel" in s for s in log.symbols) and len(log.names) == 1, log.names
-        _assert_launched(log_key, "footprint", log.symbols)
+        census.assert_census(log_key, library="block", launched=[log.symbols])
     return out, name, grid
 
 
@@ -128,7 +119,6 @@ def test_block_dw_beside_a_copy_kernel(res, dtype):
     """76^2 x 16 frames under fuse_block = 3 (the shipped shape: one rectangle per CU) beside the copy kernel, exactly as
     tests/test_gpu_contention.py runs the other run-ahead families: quiet output against contended output, bit for bit.
     Both compiled instances run here (tests/test_block_dw_host.py holds the census to that)."""
-    import kernel_census as census
     import test_gpu_contention as TC
     from yolov3 import _hip
     lib = _hip.lib()
@@ -137,14 +127,8 @@ def test_block_dw_beside_a_copy_kernel(res, dtype):
     t, ops, _, _ = BU.random_pair(dev, dtype, 16, 76, 76, 256, 256, res, seed=7)
     out = torch.zeros((16, 76, 76, 256), dtype=TDT[dtype], device=dev)
     handle = BU.make_plan(ops, t["zero"], out, fuse_block=3)
-    key = "block_dw_%s-%s" % ("res" if res else "nores", dtype)
-    main_fixture, recording = census.FIXTURE, TC.RECORDING
-    census.FIXTURE, TC.RECORDING = BU.CENSUS_FIXTURE, RECORD is not None
     try:
         assert lib.y3_plan_op_kernel(handle, 0).decode() == "conv_block_dw_%s_x128" % BU.TAG[dtype]
-        TC._beside_a_copy(handle, out, key)
-        if RECORD is not None:
-            RECORD["contention"][key] = TC.LAUNCHED[key]
+        TC._beside_a_copy(handle, out, "block_dw_%s-%s" % ("res" if res else "nores", dtype), library="block")
     finally:
-        census.FIXTURE, TC.RECORDING = main_fixture, recording
         lib.y3_plan_destroy(handle)

@@ -11,11 +11,10 @@ kernel-level suites, on every row of tests/block_dw_cases.py in both 16-bit stor
   below 2^32 bytes one bf16 row, x and z each one frame below 2^32 bytes behind a 4 GiB pad (the kernel keeps 32-bit byte
                    offsets; the chooser diverts the pair one frame later: tests/test_block_dw_host.py).
 
-Every run asserts its launch set against tests/golden/kernel_instances_block.json (tools/make_block_kernel_instances.py), and
-the fragment-order copies -- made by y3_conv_make_fragment_weights inside the harness, which holds that call to its own operand --
-against the main census.  The epilogue pins of this kernel are tests/test_gpu_epilogue.py's, the network runs
+Every run asserts its launch set against tests/golden/kernel_instances_block.json (the "block" library of tests/kernel_census.py),
+and the fragment-order copies -- made by y3_conv_make_fragment_weights inside the harness, which holds that call to its own operand
+-- against the main census.  The epilogue pins of this kernel are tests/test_gpu_epilogue.py's, the network runs
 tests/test_gpu_block_dw_network.py's.  Need an MI355X: -m gpu."""
-import contextlib
 import os
 import sys
 
@@ -25,9 +24,9 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import block_dw_cases as BDC  # noqa: E402
-import block_dw_util as BU  # noqa: E402
 import exact_sums as XS  # noqa: E402
 import footprint_util as fu  # noqa: E402
+import kernel_census as census  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -35,28 +34,14 @@ MARKER = "(fused into the previous op)"
 IDS = ["%s-%s" % p for p in BDC.case_ids()]
 
 
-@contextlib.contextmanager
-def block_census():
-    """tests/kernel_census.py reads the block library's fixture (as test_block_dw_beside_a_copy_kernel switches it)"""
-    import kernel_census as census
-    main = census.FIXTURE
-    census.FIXTURE = BU.CENSUS_FIXTURE
-    try:
-        yield
-    finally:
-        census.FIXTURE = main
-
-
-def assert_census(F, key, fragment_calls):
+def assert_census(key, fragment_calls):
     """the logged plan runs launched the instance recorded for ``key`` in the block census and nothing else; the
     ``fragment_calls`` copies the harness made launched what the main census records for y3_conv_make_fragment_weights"""
-    assert F.LAUNCHED and all(len(s) == 1 and "conv_block_dw_kernel" in s[0] for s in F.LAUNCHED), F.LAUNCHED
-    with block_census():
-        F._assert_census(key)
-    assert len(F.FRAGMENT_LAUNCHED) == fragment_calls, F.FRAGMENT_LAUNCHED
-    F.LAUNCHED[:] = F.FRAGMENT_LAUNCHED
-    F._assert_census(F.FRAGMENT_KEY)
-    del F.FRAGMENT_LAUNCHED[:]
+    assert census.LAUNCHED and all(len(s) == 1 and "conv_block_dw_kernel" in s[0] for s in census.LAUNCHED), census.LAUNCHED
+    census.assert_census(key, library="block")
+    assert len(census.FRAGMENT_LAUNCHED) == fragment_calls, census.FRAGMENT_LAUNCHED
+    census.assert_census(census.FRAGMENT_KEY, launched=census.FRAGMENT_LAUNCHED[:])
+    del census.FRAGMENT_LAUNCHED[:]
 
 
 @pytest.mark.parametrize("cid", IDS)
@@ -67,7 +52,7 @@ def test_block_dw_touches_exactly_its_operands(cid):
     cname, dtype = cid.rsplit("-", 1)
     case = BDC.case_by_id(cname)
     want = [fu.family_name(case, dtype), MARKER]
-    del F.LAUNCHED[:], F.FRAGMENT_LAUNCHED[:]
+    del census.LAUNCHED[:], census.FRAGMENT_LAUNCHED[:]
     dense, msg, names, ref, lay = F._run(case, dtype, "dense")
     assert names == want, (names, want)
     assert msg is None, "dense run: " + msg
@@ -83,8 +68,8 @@ def test_block_dw_touches_exactly_its_operands(cid):
     assert strided.keys() == dense.keys() == {"output/0"}
     differ = int((strided["output/0"] != dense["output/0"]).sum())
     assert differ == 0, "%d bytes of the strided, poisoned run differ from the dense run" % differ
-    assert len(F.LAUNCHED) == 2
-    assert_census(F, BDC.footprint_key(cname, dtype), 4)
+    assert len(census.LAUNCHED) == 2
+    assert_census(BDC.footprint_key(cname, dtype), 4)
 
 
 @pytest.mark.parametrize("kind", BDC.PLANTS)
@@ -99,7 +84,7 @@ def test_block_dw_sum_is_exact_on_planted_integers(cid, kind):
     case = BDC.case_by_id(cname)
     p = XS.plant(case, dtype, kind)
     _, want = XS.reference(case, dtype, p)
-    del F.LAUNCHED[:], F.FRAGMENT_LAUNCHED[:]
+    del census.LAUNCHED[:], census.FRAGMENT_LAUNCHED[:]
     outs, msg, names, _, _ = F._run(case, dtype, "dense", plant=p)
     assert names == [fu.family_name(case, dtype), MARKER], names
     assert msg is None, msg
@@ -107,7 +92,7 @@ def test_block_dw_sum_is_exact_on_planted_integers(cid, kind):
     got = t.contiguous().view(fu.TORCH_DT[dtype]).reshape(t.shape[0], -1).float().numpy()
     assert got.shape == want.shape, (got.shape, want.shape)
     assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), XS.first_difference(got, want, case, dtype, p)
-    assert_census(F, BDC.exact_key(cname, dtype, kind), 2)
+    assert_census(BDC.exact_key(cname, dtype, kind), 2)
 
 
 def test_block_dw_one_frame_below_4_gib():
@@ -120,7 +105,6 @@ def test_block_dw_one_frame_below_4_gib():
     case = fu.big_case(row, "bf16")
     assert case["same_ld"] and case["B"] > 3000
     TB.big_operands_run(row, "bf16", log=True)
-    assert F.LAUNCHED and all(len(s) == 1 and "conv_block_dw_kernel" in s[0] for s in F.LAUNCHED), F.LAUNCHED
-    with block_census():
-        F._assert_census(BDC.big_key("bf16"))
-    del F.FRAGMENT_LAUNCHED[:]
+    assert census.LAUNCHED and all(len(s) == 1 and "conv_block_dw_kernel" in s[0] for s in census.LAUNCHED), census.LAUNCHED
+    census.assert_census(BDC.big_key("bf16"), library="block")
+    del census.FRAGMENT_LAUNCHED[:]

@@ -24,8 +24,9 @@ pytestmark = pytest.mark.gpu
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
+import kernel_census as census  # noqa: E402
+
 TDT = {"bf16": torch.bfloat16, "fp16": torch.float16}
-RECORDING = False      # the census tool sets it: record the launch sets, 0 contended rounds, no comparison with the fixture
 
 
 def _conv_op(dev, gen, dtype, B, h, cin, cout, k, stride, res):
@@ -59,28 +60,21 @@ def _conv_op(dev, gen, dtype, B, h, cin, cout, k, stride, res):
     return op, keep, out
 
 
-LAUNCHED = {}          # census key -> the sorted symbol set of the case's quiet run (tools/make_kernel_instances.py reads it)
-
-
-def _beside_a_copy(handle, out, key, rounds=20, launches=6, more=()):
+def _beside_a_copy(handle, out, key, rounds=20, launches=6, more=(), library="main"):
     """`out` (and the tensors in `more`) after launches beside the copy kernel == after a launch alone, and the quiet launch ran
-    the compiled instance(s) recorded as `key` (the log is on for that run only)."""
+    the compiled instance(s) the census of `library` records as `key` (the log is on for that run only).  While the census tool
+    records, the quiet run is all there is: no contended rounds."""
     from yolov3 import _hip
     lib = _hip.lib()
     dev = out.device
     with _hip.launch_log() as log:
         _hip.check(lib.y3_plan_run(handle, None, None))
     torch.cuda.synchronize()
-    LAUNCHED[key] = log.symbols
-    if not RECORDING:
-        import kernel_census as census
-        want = census.load()["contention"].get(key)
-        assert want is not None, "tests/golden/kernel_instances.json has no contention entry %r: run tools/make_kernel_instances.py" % key
-        assert log.symbols == want, (key, log.symbols, want)
+    census.assert_census(key, "contention", library, launched=[log.symbols])
     alone = out.clone()
     alone_more = [t.clone() for t in more]
     assert torch.isfinite(alone.float()).all() and float(alone.float().abs().max()) > 0
-    if RECORDING:
+    if census.is_recording():
         return
     out.zero_()
     for t in more:

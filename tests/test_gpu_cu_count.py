@@ -69,14 +69,14 @@ def _covered():
 def _assert_in_census(what):
     """every symbol launched since the last clear is one that a footprint case at the device's own count launches too: no other
     count reaches a compiled instance that the one-op suite leaves out"""
-    assert TF.LAUNCHED, what
-    got = set().union(*TF.LAUNCHED)
+    assert census.LAUNCHED, what
+    got = set().union(*census.LAUNCHED)
     names = census.demangle(got)
-    assert not got & set(census.UNREACHABLE), "%s launched what kernel_census.UNREACHABLE excludes: %s" % (
-        what, [names[s] for s in got & set(census.UNREACHABLE)])
+    unreachable = set(census.LIBRARIES["main"].unreachable)
+    assert not got & unreachable, "%s launched what kernel_census.UNREACHABLE excludes: %s" % (what, [names[s] for s in got & unreachable])
     assert got <= _covered(), "%s launched instances no footprint case covers:\n  %s" % (
         what, "\n  ".join(names[s] for s in sorted(got - _covered())))
-    del TF.LAUNCHED[:]
+    del census.LAUNCHED[:]
 
 
 @pytest.mark.parametrize("count", cu.GPU_COUNTS)
@@ -86,7 +86,7 @@ def test_one_op_row_under_another_cu_count(n, dtype, count):
     assert count <= _device_cus()
     case, opt, name = _row(n)
     own, own_names = _own(n, dtype)
-    del TF.LAUNCHED[:], TF.FRAGMENT_LAUNCHED[:]
+    del census.LAUNCHED[:], census.FRAGMENT_LAUNCHED[:]
     with _hip.device_cus(count):
         # the launch the plan records under this count, from a plan that only decides (fake addresses, every fragment-order copy given)
         step = cu.case_steps(case, dtype, opt, mode="dense")[0]
@@ -131,14 +131,13 @@ def test_one_op_row_under_another_cu_count(n, dtype, count):
 
 @pytest.mark.parametrize("created,run", [(20, 0), (0, 20), (1, 128), (32, 1)], ids=["20-own", "own-20", "1-128", "32-1"])
 @pytest.mark.parametrize("cid", cu.PERSISTENT_ROWS)
-def test_one_op_plan_keeps_the_count_it_was_created_with(cid, created, run, monkeypatch):
+def test_one_op_plan_keeps_the_count_it_was_created_with(cid, created, run):
     _hip.require_gpu()
     lib = _hip.lib()
     n = next(k for k, r in enumerate(cu.ONE_OP_ROWS) if r == (cid, None, {}))
     case, opt, name = _row(n)
     dtype = case["dtypes"][-1]
     own, own_names = _own(n, dtype)
-    logged = TF._logged
     seen = []
 
     def logged_under_the_other_count(call):
@@ -146,14 +145,13 @@ def test_one_op_plan_keeps_the_count_it_was_created_with(cid, created, run, monk
         _hip.check(lib.y3_set_tuning(b"device_cus", run))
         seen.append(run)
         try:
-            return logged(call)
+            return census.logged(call)
         finally:
             _hip.check(lib.y3_set_tuning(b"device_cus", created))
 
-    monkeypatch.setattr(TF, "_logged", logged_under_the_other_count)
-    del TF.LAUNCHED[:]
+    del census.LAUNCHED[:]
     with _hip.device_cus(created):
-        dense, msg, names, _, lay = TF._run(case, dtype, "strided")
+        dense, msg, names, _, lay = TF._run(case, dtype, "strided", logged=logged_under_the_other_count)
     assert seen == [run] and names == own_names
     assert msg is None, msg
     TF._no_nan(dense, lay)

@@ -102,12 +102,12 @@ def test_mixed_batch_in_one_launch_stays_inside_its_output(net, letterbox):
     torch.cuda.synchronize()
     before = alloc.clone()
     assert bool(torch.isnan(fu.read_slice(before, out, 0, torch.float32)).all())
-    import test_gpu_footprint as TF                      # (the launch census: tests/kernel_census.py)
-    del TF.LAUNCHED[:]
-    TF._logged(lambda: _hip.check(_hip.lib().y3_preprocess_darknet_f32(descs, len(frames), out.ptr(alloc.data_ptr()), net[0], net[1],
+    import kernel_census as census
+    del census.LAUNCHED[:]
+    census.logged(lambda: _hip.check(_hip.lib().y3_preprocess_darknet_f32(descs, len(frames), out.ptr(alloc.data_ptr()), net[0], net[1],
                                                                        1 if letterbox else 0, None)))
     torch.cuda.synchronize()
-    TF._assert_census("y3_preprocess_darknet_f32")
+    census.assert_census("y3_preprocess_darknet_f32")
     msg = fu.footprint_violations(before, alloc, lay)
     assert msg is None, msg
     got = fu.read_slice(alloc, out, 0, torch.float32).reshape(len(frames), 3, net[0], net[1]).cpu()

@@ -321,13 +321,13 @@ def _footprint_run(heads, bbox, rows_total, thresh, cap):
         v.d_head, v.h, v.w, v.ld, v.n_anchor, v.n_attr = lay["head%d" % k].ptr(base), h, w, lay["head%d" % k].ld, a, n
         v.row_offset, v.new_coords = hd["row_offset"], 0
     p = {o.name: o.ptr(base) for o in ops}
-    import test_gpu_footprint as TF                      # (the launch census: tests/kernel_census.py)
-    del TF.LAUNCHED[:]
-    TF._logged(lambda: _hip.check(lib.y3_expand_labels(views, len(heads), p["bbox"], batch, rows_total, ctypes.c_float(thresh), cap,
+    import kernel_census as census
+    del census.LAUNCHED[:]
+    census.logged(lambda: _hip.check(lib.y3_expand_labels(views, len(heads), p["bbox"], batch, rows_total, ctypes.c_float(thresh), cap,
                                                        p["workspace"], nws, p["vbbox"], p["vprob"], p["vcls"], p["vrow"], p["vcount"],
                                                        _hip.stream_ptr())))
     torch.cuda.synchronize()
-    TF._assert_census("y3_expand_labels")
+    census.assert_census("y3_expand_labels")
     msg = fu.footprint_violations(before, alloc, lay)
     assert msg is None, msg
     out = {name: fu.read_slice(alloc, lay[name], 0, dt).cpu().numpy()

@@ -351,9 +351,9 @@ def _block_run(bb, t, ops, mode, batch, h, census_key=None):
     finally:
         lib.y3_plan_destroy(plan)
     if census_key:
-        import test_gpu_block_dw as TD
+        import kernel_census as census
         assert len(log.symbols) == 1 and "conv_block_dw_kernel" in log.symbols[0], log.symbols
-        TD._assert_launched(census_key, "footprint", log.symbols)
+        census.assert_census(census_key, library="block", launched=[log.symbols])
     return out, name
 
 

@@ -48,6 +48,7 @@ def _stored(outs, key, odt):
 
 @pytest.mark.parametrize("cid", IDS)
 def test_conv_sum_is_exact_on_planted_integers(cid):
+    import kernel_census as census
     import test_gpu_footprint as F
     from yolov3 import _hip
     _hip.require_gpu()
@@ -58,7 +59,7 @@ def test_conv_sum_is_exact_on_planted_integers(cid):
     for kind in XS.plants_of(case):
         p = XS.plant(case, dtype, kind)
         _, want = XS.reference(case, dtype, p)
-        del F.LAUNCHED[:], F.FRAGMENT_LAUNCHED[:]
+        del census.LAUNCHED[:], census.FRAGMENT_LAUNCHED[:]
         outs, msg, names, _, _ = F._run(case, dtype, "dense", plant=p)
         assert names[0] == want_name, (kind, names, want_name)
         assert msg is None, "%s plant: %s" % (kind, msg)
@@ -76,4 +77,4 @@ def test_conv_sum_is_exact_on_planted_integers(cid):
         assert got.shape == want.shape, (got.shape, want.shape)
         diff = XS.first_difference(got, want, case, dtype, p)
         assert diff is None, "%s, %s plant (%s): %s" % (cid, kind, names[0], diff)
-    del F.LAUNCHED[:], F.FRAGMENT_LAUNCHED[:]
+    del census.LAUNCHED[:], census.FRAGMENT_LAUNCHED[:]

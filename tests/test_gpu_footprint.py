@@ -18,8 +18,8 @@ per-chunk (KMODE 1) and several-taps (KMODE 2) K-tilings, 5x5 and even kernels a
 
 Below the family name the library is compiled by instance: every run here is taken with the library's launch log, and the set
 of code-object symbols it launched must equal the record of tests/golden/kernel_instances.json for that case
-(tests/kernel_census.py; tools/make_kernel_instances.py writes the record, tests/test_code_object.py proves that it leaves no
-compiled kernel out).
+(tests/kernel_census.py, which keeps the launch log and ``assert_census``; tools/make_kernel_instances.py writes the record,
+tests/test_code_object.py proves that it leaves no compiled kernel out).
 
 Guards lie inside the allocation: a stray access is recorded, never a fault.  The reference has no counterpart of these
 layouts (the reference's yolov3/darknet.py:366-399 allocates a tensor per block).  Need an MI355X: -m gpu."""
@@ -34,6 +34,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import footprint_util as fu
+import kernel_census as census
 
 pytestmark = pytest.mark.gpu
 
@@ -160,48 +161,12 @@ def _make_data(case, dtype, lay, paths, plant=None):
     return data, ref
 
 
-# ------------------------------------------------------------------------------------------------ the launch census
-
-RECORD = None          # tools/make_kernel_instances.py sets it to {}: _assert_census then records instead of comparing
-FRAGMENT_LAUNCHED = []  # ... and of every y3_conv_make_fragment_weights call inside ``_run``
-LAUNCHED = []          # the sorted symbol set of every logged call since a test (or the census tool) last cleared it
-
-
-def _logged(call):
-    """``call()`` under the library's launch log; what it launched is appended to LAUNCHED"""
-    from yolov3 import _hip as H
-    with H.launch_log() as log:
-        out = call()
-    LAUNCHED.append(log.symbols)
-    return out
-
-
-def _assert_census(key, table="footprint"):
-    """every logged call since the last clear launched exactly the symbols recorded for ``key``; clears the list"""
-    import kernel_census as census
-    if RECORD is not None:
-        assert LAUNCHED and all(got == LAUNCHED[0] for got in LAUNCHED), (key, LAUNCHED)
-        assert RECORD.setdefault(key, LAUNCHED[0]) == LAUNCHED[0], key
-        del LAUNCHED[:]
-        return
-    want = census.load()[table].get(key)
-    assert want is not None, "tests/golden/kernel_instances.json has no %s entry %r: run tools/make_kernel_instances.py" % (table, key)
-    assert LAUNCHED, key
-    names = census.demangle(set(want).union(*LAUNCHED))
-    for got in LAUNCHED:
-        assert got == want, "%s launched\n  %s\nrecorded\n  %s" % (key, "\n  ".join(names[s] for s in got),
-                                                                 "\n  ".join(names[s] for s in want))
-    del LAUNCHED[:]
-
-
-FRAGMENT_KEY = "y3_conv_make_fragment_weights"
-
-
 # ------------------------------------------------------------------------------------------------ one run
 
-def _run(case, dtype, mode, u8_guard=0, opt_name=None, plant=None):
+def _run(case, dtype, mode, u8_guard=0, opt_name=None, plant=None, logged=census.logged):
     """(output tensors, footprint message or None, kernel names, float32 reference values, layout).  ``plant``: planted operands
-    for ``_make_data``; such a run also returns the scratch operands as it finds them (the float32 logits of an unfused head)"""
+    for ``_make_data``; such a run also returns the scratch operands as it finds them (the float32 logits of an unfused head).
+    ``logged``: what runs the plan, once it is created, in place of ``census.logged``"""
     from yolov3 import _hip as H
     lib = H.lib()
     dev = torch.device("cuda:0")
@@ -224,7 +189,7 @@ def _run(case, dtype, mode, u8_guard=0, opt_name=None, plant=None):
         with H.launch_log() as flog:
             H.check(lib.y3_conv_make_fragment_weights(ctypes.byref(ops[i]), ctypes.c_void_p(ops[i].d_weight_frag), None))
         torch.cuda.synchronize()
-        FRAGMENT_LAUNCHED.append(flog.symbols)
+        census.FRAGMENT_LAUNCHED.append(flog.symbols)
         lay[name].side = "scratch"
         msg = fu.footprint_violations(before, alloc, lay)
         lay[name].side = "in"
@@ -235,7 +200,7 @@ def _run(case, dtype, mode, u8_guard=0, opt_name=None, plant=None):
         names = [lib.y3_plan_op_kernel(handle, i).decode() for i in range(len(ops))]
         before = alloc.clone()
         d_input = lay["input"].ptr(base) if lay.has("input") else None
-        _logged(lambda: H.check(lib.y3_plan_run(handle, d_input, None)))
+        logged(lambda: H.check(lib.y3_plan_run(handle, d_input, None)))
         torch.cuda.synchronize()
     finally:
         lib.y3_plan_destroy(handle)
@@ -354,9 +319,9 @@ def _check_dense_against_oracle(case, dtype, outs, ref, lay):
         return
     if g == "head":
         # the gate the suite holds the fused head kernels to (tests/test_gpu_parity.py): the two separate kernels, bit for bit
-        held = list(LAUNCHED)
+        held = list(census.LAUNCHED)
         plain, msg, names, _, _ = _run(case, dtype, "dense", opt_name="head_unfused")
-        LAUNCHED[:] = held                                    # (the two separate kernels are not this case's launch set)
+        census.LAUNCHED[:] = held                                    # (the two separate kernels are not this case's launch set)
         assert msg is None, msg
         assert names[0].startswith("conv_igemm_") and names[1] == "yolo_decode_f32", names
         for key in ("bbox/0", "prob/0", "cls/0"):
@@ -400,7 +365,7 @@ def test_kernel_touches_exactly_its_operands(cid):
     cname, dtype = cid.rsplit("-", 1)
     case = fu.case_by_id(cname)
     want = fu.family_name(case, dtype)
-    del LAUNCHED[:], FRAGMENT_LAUNCHED[:]
+    del census.LAUNCHED[:], census.FRAGMENT_LAUNCHED[:]
     dense, msg, names, ref, lay = _run(case, dtype, "dense")
     assert names[0] == want, (names, want)
     assert msg is None, "dense run: " + msg
@@ -418,11 +383,11 @@ def test_kernel_touches_exactly_its_operands(cid):
             assert torch.equal(strided[key], dense[key]), "%s: %d bytes of the strided, poisoned run differ from the dense run" % (
                 key, int((strided[key] != dense[key]).sum()))
     # the dense run and every strided run launched exactly the compiled instance(s) recorded for this case
-    assert len(LAUNCHED) == (3 if u8 else 2)
-    _assert_census(cid)
-    if FRAGMENT_LAUNCHED:
-        LAUNCHED[:] = FRAGMENT_LAUNCHED
-        _assert_census(FRAGMENT_KEY)
+    assert len(census.LAUNCHED) == (3 if u8 else 2)
+    census.assert_census(cid)
+    if census.FRAGMENT_LAUNCHED:
+        census.LAUNCHED[:] = census.FRAGMENT_LAUNCHED
+        census.assert_census(census.FRAGMENT_KEY)
 
 
 # ------------------------------------------------------------------------------------------------ one K order
@@ -447,7 +412,7 @@ def test_implicit_gemm_versions_sum_in_one_k_order(cid, opts, dtype):
     _hip.require_gpu()
     base = fu.case_by_id(cid)
     first = None
-    del LAUNCHED[:]
+    del census.LAUNCHED[:]
     for opt in opts:
         if opt == "igemm3_64" and dtype == "float32":
             continue
@@ -483,7 +448,7 @@ def _guarded(bufs, call, poisoned):
     fu.fill(alloc, lay, data, poisoned=poisoned, u8_guard=0xFF if poisoned else 0)
     torch.cuda.synchronize()
     before = alloc.clone()
-    _logged(lambda: call({o.name: o.ptr(base) for o in ops}))
+    census.logged(lambda: call({o.name: o.ptr(base) for o in ops}))
     torch.cuda.synchronize()
     msg = fu.footprint_violations(before, alloc, lay)
     assert msg is None, ("poisoned guards: " if poisoned else "zero guards: ") + msg
@@ -504,7 +469,7 @@ def _unguarded(bufs, call):
             t[name] = torch.full((n * es,), 0x7F if side == "out" else 0xFF, dtype=torch.uint8, device=dev)
         assert t[name].numel() == n * es and t[name].data_ptr() % 16 == 0, name
     torch.cuda.synchronize()
-    _logged(lambda: call({name: v.data_ptr() for name, v in t.items()}))
+    census.logged(lambda: call({name: v.data_ptr() for name, v in t.items()}))
     torch.cuda.synchronize()
     return {name: t[name].reshape(1, -1).cpu() for name, side, _, _, _ in bufs if side == "out"}
 
@@ -512,15 +477,15 @@ def _unguarded(bufs, call):
 def _both(bufs, call, key):
     """outputs of the unguarded call, after the two guarded calls have been held to it byte for byte and all three to the
     launch set recorded as ``key``"""
-    del LAUNCHED[:]
+    del census.LAUNCHED[:]
     free = _unguarded(bufs, call)
     for what, poisoned in (("zero guards", False), ("poisoned guards", True)):
         got = _guarded(bufs, call, poisoned)
         for k in free:
             assert torch.equal(free[k], got[k]), "%s: %d bytes differ between the unguarded call and the call between %s" % (
                 k, int((free[k] != got[k]).sum()), what)
-    assert len(LAUNCHED) == 3
-    _assert_census(key)
+    assert len(census.LAUNCHED) == 3
+    census.assert_census(key)
     return free
 
 

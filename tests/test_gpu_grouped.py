@@ -29,7 +29,7 @@ import footprint_util as fu
 import grouped_cases as GC
 import grouped_ordered as GO
 import grouped_restate as GR
-import test_gpu_footprint as TF
+import kernel_census as census
 from golden_util import GOLDEN
 from test_gpu_bf16 import F32_BLOCK_TOL, MODES, _close_bf16
 
@@ -414,8 +414,8 @@ def test_footprint_and_census(instance, dtype):
         assert name == "conv_%s" % instance.replace("_", "_%s_" % TAG[dtype], 1), name
         assert _hip.plan_op_dims(handle, 0)[1] % 64 == 0
         before = alloc.clone()
-        del TF.LAUNCHED[:]
-        TF._logged(lambda: _hip.check(lib.y3_plan_run(handle, None, None)))
+        del census.LAUNCHED[:]
+        census.logged(lambda: _hip.check(lib.y3_plan_run(handle, None, None)))
         torch.cuda.synchronize()
     finally:
         lib.y3_plan_destroy(handle)
@@ -426,12 +426,5 @@ def test_footprint_and_census(instance, dtype):
     assert not bool(torch.isnan(got).any()), "%s %s: the NaN of the output slice survived (or a NaN operand was read)" % (instance, dtype)
     ho, wo = GC.out_hw(case)
     _gate(got.reshape(B, ho, wo, -1).permute(0, 3, 1, 2).contiguous(), want, dtype, "%s %s" % (instance, dtype))
-    # the launch log against the census of the grouped kernels' own library (tests/golden/kernel_instances_grouped.json), through
-    # the footprint tests' own comparison
-    import kernel_census as census
-    main_fixture = census.FIXTURE
-    census.FIXTURE = GC.CENSUS_FIXTURE
-    try:
-        TF._assert_census(census_key(instance, dtype))
-    finally:
-        census.FIXTURE = main_fixture
+    # the launch log against the census of the grouped kernels' own library (tests/golden/kernel_instances_grouped.json)
+    census.assert_census(census_key(instance, dtype), library="grouped")

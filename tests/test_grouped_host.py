@@ -506,34 +506,22 @@ def test_plan_creation_refuses_the_bad_ops():
 # ---------------------------------------------------------------------------------------------- the grouped library's device code
 
 def test_grouped_library_code_objects_and_census():
-    """tests/test_code_object.py's checks on libyolov3_hip_grouped.so, the dependency of libyolov3_hip.so that holds conv_dwise and
-    conv_grouped: gfx950 code only, no kernel spills to scratch, budgets inside a CU, blocks of whole waves; and the census: every
-    compiled instance is launched by a footprint case of tests/test_gpu_grouped.py (tests/golden/kernel_instances_grouped.json,
-    recorded on an MI355X by tools/make_grouped_kernel_instances.py), one key per instance and dtype, and no recorded symbol is
-    missing from the library.  The main library holds none of these kernels, so its own census is what it was."""
-    import json
-
-    import test_code_object as T
-    if not os.path.exists(GC.GROUPED_LIB):
-        pytest.fail("libyolov3_hip_grouped.so is not built (python -c 'import __graft_entry__ as g; g.build()')")
-    kernels = GC.library_kernels()
+    """libyolov3_hip_grouped.so, the dependency of libyolov3_hip.so that holds conv_dwise and conv_grouped: 15 instances, no LDS,
+    blocks of whole waves; and its census (tests/golden/kernel_instances_grouped.json, recorded on an MI355X by
+    tools/make_kernel_instances.py --library grouped): one key per instance and dtype.  What every library is held to -- gfx950
+    code only, no spills, budgets inside a CU, every compiled instance launched by a recorded footprint case, no recorded symbol
+    missing, no kernel shared with the main library -- is tests/test_code_object.py's."""
+    import kernel_census as census
+    kernels = census.kernels("grouped")          # (asserts: built, device code for gfx950 only)
     names = sorted(k[".name"] for k in kernels)
     assert len(names) == 15 and sum("conv_dwise_kernel" in n for n in names) == 9 and sum("conv_grouped_kernel" in n for n in names) == 6
     for k in kernels:
-        assert k[".private_segment_fixed_size"] == 0, (k[".name"], "uses scratch memory (register spills)")
-        assert k[".vgpr_count"] + k.get(".agpr_count", 0) <= 512 and k[".group_segment_fixed_size"] == 0, k[".name"]
-        assert k[".wavefront_size"] == 64 and k[".max_flat_workgroup_size"] % 64 == 0, k[".name"]
-    with open(GC.CENSUS_FIXTURE) as fh:
-        fixture = json.load(fh)
-    uncovered, stale = GC.census_report(fixture, names)
-    assert not uncovered and not stale, (uncovered, stale)
+        assert k[".group_segment_fixed_size"] == 0 and k[".max_flat_workgroup_size"] % 64 == 0, k[".name"]
+    fixture = census.load("grouped")
     assert sorted(fixture["footprint"]) == sorted("grouped_%s-%s" % (i, d) for i in (
         "dwise_k3s1", "dwise_k3s2", "dwise_kn", "grouped_oc1", "grouped_oc8") for d in GC.DTYPES)
     assert all(len(v) == 1 for v in fixture["footprint"].values())
     assert len({v[0] for v in fixture["footprint"].values()}) == 15        # one key per (kernel instance, dtype)
-    with open(T.LIB, "rb") as fh:
-        main = {k[".name"] for _, elf in T._code_objects(fh.read()) for k in T._kernels(elf)}
-    assert not main & set(names)
 
 
 # ---------------------------------------------------------------------------------------------- the kernel-level suites
@@ -543,12 +531,10 @@ def test_grouped_library_code_objects_and_census():
 def test_every_compiled_instance_has_an_epilogue_form_and_a_big_row():
     """no skip list: every (instance, dtype) of the grouped library's census has an epilogue form and, fp16 aside (it shares
     bf16's address code), a row past 4 GiB; an instance compiled later fails here until both suites hold it"""
-    import json
-
     import epilogue_cases as E
     import grouped_suites as GS
-    with open(GC.CENSUS_FIXTURE) as fh:
-        keys = sorted(json.load(fh)["footprint"])
+    import kernel_census as census
+    keys = sorted(census.load("grouped")["footprint"])
     assert len(keys) == 15
     pinned = {GS.census_key(f["instance"], d) for f in GS.EPILOGUE_FORMS.values() for d in E.DTYPES}
     big = {GS.census_key(i, d) for i in GS.BIG_ROWS for d in GS.BIG_DTYPES}

@@ -16,7 +16,8 @@ from yolov3 import _hip
 from yolov3.__main__ import build_parser, check_tiling, main
 from yolov3.tiles import check_merge, merge_detections
 
-import test_code_object as T
+import code_object
+import kernel_census as census
 import tile_merge_cases as C
 import tile_merge_restate as M
 from golden_util import ROOT
@@ -295,21 +296,8 @@ def test_command_line_refusals_come_before_anything_is_loaded(extra, words):
 
 
 # ---- the code object ----------------------------------------------------------------------------------------------------------------
-LIB_DIR = os.path.dirname(T.LIB)
-MERGE_LIB = os.path.join(LIB_DIR, "libyolov3_hip_tilemerge.so")
-
-
-def _lib_kernels(path):
-    if not os.path.exists(path):
-        pytest.fail("%s is not built (python -c 'import __graft_entry__ as g; g.build()')" % os.path.basename(path))
-    with open(path, "rb") as fh:
-        objs = list(T._code_objects(fh.read()))
-    assert objs and all("gfx950" in triple for triple, _ in objs)
-    return [k for _, elf in objs for k in T._kernels(elf)]
-
-
 def test_merge_library_holds_the_kernel_without_scratch_and_within_64_kib_of_lds():
-    kernels = _lib_kernels(MERGE_LIB)
+    kernels = census.kernels("tilemerge")          # (asserts: built, device code for gfx950 only)
     assert len(kernels) == 1 and "tile_merge_kernel" in kernels[0][".name"]
     k = kernels[0]
     assert k[".private_segment_fixed_size"] == 0, "scratch memory (register spills)"
@@ -319,8 +307,8 @@ def test_merge_library_holds_the_kernel_without_scratch_and_within_64_kib_of_lds
 
 
 def test_main_library_names_the_merge_library_and_does_not_hold_its_kernel():
-    with open(T.LIB, "rb") as fh:
+    with open(code_object.LIB, "rb") as fh:
         data = fh.read()
     assert b"libyolov3_hip_tilemerge.so" in data and b"$ORIGIN" in data
     assert b"tile_merge_kernel" not in data
-    assert not any("tile_merge" in k[".name"] for k in _lib_kernels(T.LIB))
+    assert not any("tile_merge" in k[".name"] for k in census.kernels("main"))
